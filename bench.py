@@ -15,6 +15,13 @@ sides; the max over ranks is reported.  ``busbw_gbps`` is the per-rank busBW = a
 busBW of all k ranks summed (k * busbw_gbps) for k >= 2.  At k = 1 busBW is 0 by definition, so
 ``value`` is the algBW of the single-rank RCCL all-reduce (BASELINE.md "k=1 reports algBW only").  Per-GPU message size is fixed
 as N grows ("weak" scaling).  Data is synthetic (exactly checked once before timing).
+
+A plain run does only what the headline needs: link probe + placement (they pick the subset), the
+communicator (at k >= 2 with its channel-count tuning pass), the exact check, W warm-up steps, the K
+timed steps and the JSON line.  ``--full`` adds the supplementary phases after the headline (K6 ring
+probe, size sweep, fp32 sum, hipGraph latency, worst-/default-subset A/B, RCCL log summary); their
+keys are null in a plain run's line.  ``--dump-outputs DIR`` writes the last timed step's result
+(:func:`dump_outputs`), so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -33,6 +40,12 @@ METRIC = "RCCL all-reduce bus GB/s on scheduler-chosen k-GPU subset, k=1/2/4/8"
 # them, and which count saturates the links depends on k, so it is measured on the node.
 TUNE_CANDIDATES = [(0, 0), (32, 128), (64, 128), (112, 128)]
 
+# --dump-outputs: a result of more than DUMP_BLOCKS * DUMP_BLOCK elements (16 MiB as float32) is sampled
+# in DUMP_BLOCKS contiguous blocks of DUMP_BLOCK elements at offsets drawn from a fixed seed
+DUMP_BLOCK = 1 << 16
+DUMP_BLOCKS = 64
+DUMP_SEED = 20240607
+
 
 def _free_port() -> int:
     with socket.socket() as s:
@@ -45,6 +58,17 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the supplementary phases (ring probe, size sweep, fp32 sum, graph "
+                         "latency, worst- and default-subset A/B, RCCL log summary), each steered by its own option below; "
+                         "without --full the run sets up, warms up, times the K steps and prints its line, and those "
+                         "options are ignored")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, rank 0 writes the result of the last timed all-reduce (every rank "
+                         "receives the same array) to DIR/allreduce_out.npy as float32: the whole array up to "
+                         f"{DUMP_BLOCKS * DUMP_BLOCK} elements, else a fixed seeded sample of {DUMP_BLOCKS} blocks of "
+                         f"{DUMP_BLOCK} elements (first and last block included); the first element index of every "
+                         "block goes to DIR/allreduce_out_blocks.npy (float64)")
     ap.add_argument("--size-mb", type=float, default=2048.0, help="per-GPU message size in MiB (default 2 GiB)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "fp32"])
     ap.add_argument("--backend", default="native", choices=["native", "torch", "cpu"],
@@ -308,6 +332,32 @@ def run_graph_latency(runner, sizes, env, tdev, barrier_kw, gpu_sync, ops: int =
     return {"ops_per_graph": ops, "rows": rows, "all_exact": all(r["wrong"] == 0 for r in rows)}
 
 
+def dump_blocks(count: int):
+    """``(first, n)`` element ranges that --dump-outputs keeps of a ``count``-element result: all of it
+    when it fits, else the first block, the last block and DUMP_BLOCKS - 2 distinct whole blocks between
+    them, drawn with a fixed seed (the same ranges for the same ``count`` in every run and build)."""
+    import random
+
+    if count <= DUMP_BLOCKS * DUMP_BLOCK:
+        return [(0, count)]
+    inner = random.Random(DUMP_SEED).sample(range(1, count // DUMP_BLOCK - 1), DUMP_BLOCKS - 2)
+    return [(0, DUMP_BLOCK)] + [(b * DUMP_BLOCK, DUMP_BLOCK) for b in sorted(inner)] + [(count - DUMP_BLOCK, DUMP_BLOCK)]
+
+
+def dump_outputs(runner, outdir: str) -> dict:
+    """Write the runner's last result (:func:`dump_blocks` of it, float32) and the blocks' first element
+    indices (float64) as .npy files under ``outdir``."""
+    import numpy as np
+
+    runner.synchronize()
+    blocks = dump_blocks(runner.count)
+    out = np.concatenate([runner.read_result(first, n) for first, n in blocks]).astype(np.float32, copy=False)
+    os.makedirs(outdir, exist_ok=True)
+    np.save(os.path.join(outdir, "allreduce_out.npy"), out)
+    np.save(os.path.join(outdir, "allreduce_out_blocks.npy"), np.array([first for first, _ in blocks], dtype=np.float64))
+    return {"dir": outdir, "elements": int(out.size), "of": int(runner.count), "blocks": len(blocks)}
+
+
 def parse_ctas(spec: str):
     if spec in ("auto", "tune", "default"):
         return None
@@ -447,7 +497,7 @@ def main(argv=None) -> int:
     wd_s = args.watchdog_s if args.watchdog_s is not None else (args.budget_s + 300.0 if args.budget_s > 0 else 0.0)
     watchdog = start_watchdog(wd_s, ph, int(os.environ.get("RANK", "0")), args.gpus, args)
     rccl_log = None
-    if args.backend != "cpu" and (args.rccl_log == "on" or (args.rccl_log == "auto" and args.gpus > 1)) \
+    if args.full and args.backend != "cpu" and (args.rccl_log == "on" or (args.rccl_log == "auto" and args.gpus > 1)) \
             and "NCCL_DEBUG" not in os.environ:
         from gpu_topology_on_k8s_amd.parallel.allreduce import rccl_log_env
 
@@ -492,7 +542,7 @@ def main(argv=None) -> int:
                 print(f"bench: link probe: {msg}", file=sys.stderr)
         choice = ph.run("place", choose_subset, env.world, backend=args.discovery,
                         visible=(args.cpu_visible or env.world) if cpu else None, topology=topo, via_k8s=args.via == "k8s")
-        want_ring = args.ring_probe == "on" or (args.ring_probe == "auto" and env.world > 1 and choice.probed)
+        want_ring = args.full and (args.ring_probe == "on" or (args.ring_probe == "auto" and env.world > 1 and choice.probed))
         if want_ring and not cpu and ph.allow("ring", 15.0):
             from gpu_topology_on_k8s_amd.ops.probe import ring_in_child
 
@@ -600,8 +650,12 @@ def main(argv=None) -> int:
         "algbw_gbps": round(algbw, 3), "busbw_gbps": round(busbw, 3), "scaling_comparable": env.world > 1,
     }
     step_s = ms_per_step / 1e3
+    dumped = None
+    if args.dump_outputs and env.rank == 0:  # before anything below re-prepares the runner's buffers
+        dumped = ph.run("dump", dump_outputs, runner, args.dump_outputs)
+    # everything from here to the JSON line is supplementary: it runs only with --full
     sweep = None
-    sizes = sweep_sizes(args.sweep, cpu=cpu)
+    sizes = sweep_sizes(args.sweep, cpu=cpu) if args.full else []
     if sizes and ph.allow("sweep", _sweep_cost(sizes, algbw), agree):
         try:  # supplementary: a failure here (e.g. no memory for 2 x 16 GiB) must not cost the headline
             sweep = ph.run("sweep", run_sweep, runner, sizes, env, tdev, barrier_kw, gpu_sync)
@@ -610,7 +664,7 @@ def main(argv=None) -> int:
             sweep = {"error": str(e)[:300]}
     other = None
     fp32_steps = max(1, min(args.steps, 20))
-    if args.fp32_check and runner.comm is not None and args.dtype != "fp32" \
+    if args.full and args.fp32_check and runner.comm is not None and args.dtype != "fp32" \
             and ph.allow("fp32", (fp32_steps + 2) * step_s + 1.0, agree):
         try:  # supplementary, like the sweep
             other = ph.run("fp32", run_other_dtype, runner, headline_bytes, "fp32", env, tdev, barrier_kw, gpu_sync, fp32_steps)
@@ -618,7 +672,7 @@ def main(argv=None) -> int:
             print(f"bench: fp32 all-reduce aborted on rank {env.rank}: {e}", file=sys.stderr)
             other = {"dtype": "fp32", "error": str(e)[:300]}
     graph = None
-    want_graph = args.graph == "on" or (args.graph == "auto" and env.world == 1)
+    want_graph = args.full and (args.graph == "on" or (args.graph == "auto" and env.world == 1))
     if want_graph and sizes and runner.comm is not None and not args.inplace and ph.allow("graph", 3.0, agree):
         try:  # supplementary, like the sweep
             graph = ph.run("graph", run_graph_latency, runner, [8, 4096, 65536, 1 << 20], env, tdev, barrier_kw, gpu_sync)
@@ -626,7 +680,7 @@ def main(argv=None) -> int:
             print(f"bench: graph latency aborted on rank {env.rank}: {e}", file=sys.stderr)
             graph = {"error": str(e)[:300]}
     worst_ab = None
-    want_ab = args.ab_worst == "on" or (args.ab_worst == "auto" and bool(choice.worst))
+    want_ab = args.full and (args.ab_worst == "on" or (args.ab_worst == "auto" and bool(choice.worst)))
     # a second communicator on other devices: the native RCCL comm (takes its device) or gloo on the CPU;
     # the torch backend's process group is bound to this rank's device
     if want_ab and choice.worst and (cpu or (choice.worst_hip and runner.comm is not None)) \
@@ -640,7 +694,7 @@ def main(argv=None) -> int:
             if not cpu:
                 torch.cuda.set_device(device)  # the second communicator switched this thread's device
     default_ab = None
-    want_default = args.ab_default == "on" or (args.ab_default == "auto" and bool(choice.default))
+    want_default = args.full and (args.ab_default == "on" or (args.ab_default == "auto" and bool(choice.default)))
     if want_default and choice.default and worst_ab and not worst_ab.get("error") and sorted(choice.default) == sorted(choice.worst or []):
         default_ab = dict(worst_ab, same_as="worst")  # the kubelet's choice is the worst subset: measured once
     elif want_default and choice.default and (cpu or (choice.default_hip and runner.comm is not None)) \
@@ -714,6 +768,8 @@ def main(argv=None) -> int:
             "phase_s": ph.report(),
             "skipped_phases": ph.skipped,
             "budget_s": args.budget_s,
+            "full": args.full,
+            "dumped_outputs": dumped,
             "cpuset_applied": [{k: b.get(k) for k in ("applied", "source", "cpus", "n", "reason")} for b in binds],
             "ctas_tuning": tuning,
             "link_probe": choice.extra.get("probe"),

@@ -122,7 +122,25 @@ class Comm {
     return st_.check(count_, t_, false);
   }
 
+  // Raw bytes of n elements of the last all-reduce's result from element `first` on (the receive
+  // buffer, or the send buffer after in-place calls), copied behind the work already on the stream:
+  // bench.py --dump-outputs samples the timed path's output through it.
+  py::bytes read_result(size_t first, size_t n, bool inplace) {
+    if (!count_ || !st_.send || !st_.recv) throw std::runtime_error("prepare() first");
+    if (first > count_ || n > count_ - first) throw std::out_of_range("read_result: range outside the prepared buffer");
+    std::string host(n * elem_, '\0');
+    if (n) {
+      py::gil_scoped_release nogil;
+      st_.set_device();
+      const char* src = static_cast<const char*>(inplace ? st_.send : st_.recv) + first * elem_;
+      RCCL_HIP_CHECK(hipMemcpyAsync(&host[0], src, n * elem_, hipMemcpyDeviceToHost, st_.stream));
+      RCCL_HIP_CHECK(hipStreamSynchronize(st_.stream));
+    }
+    return py::bytes(host);
+  }
+
   size_t bytes() const { return count_ * elem_; }
+  size_t count() const { return count_; }
   int rank() const { return st_.rank; }
   int nranks() const { return st_.nranks; }
   int device() const { return st_.device; }
@@ -209,7 +227,9 @@ PYBIND11_MODULE(_rccl, m) {
       .def("synchronize", &Comm::synchronize, py::call_guard<py::gil_scoped_release>())
       .def("check", &Comm::check, py::arg("inplace") = false, py::call_guard<py::gil_scoped_release>())
       .def("destroy", &Comm::destroy, py::call_guard<py::gil_scoped_release>())
+      .def("read_result", &Comm::read_result, py::arg("first"), py::arg("n"), py::arg("inplace") = false)
       .def_property_readonly("bytes", &Comm::bytes)
+      .def_property_readonly("count", &Comm::count)
       .def_property_readonly("rank", &Comm::rank)
       .def_property_readonly("nranks", &Comm::nranks)
       .def_property_readonly("device", &Comm::device)

@@ -393,6 +393,25 @@ class AllReduceRunner:
                 self.tensor.copy_(self.src)
             dist.all_reduce(self.tensor)
 
+    @property
+    def count(self) -> int:
+        """Elements of the prepared message."""
+        return int(self.comm.count) if self.comm is not None else int(self.tensor.numel())
+
+    def read_result(self, first: int, n: int):
+        """Elements ``[first, first + n)`` of the last step's result as a float32 numpy array (every
+        dtype the runner reduces converts to float32 exactly)."""
+        import numpy as np
+
+        if self.comm is None:
+            return self.tensor[first:first + n].float().cpu().numpy()
+        raw = self.comm.read_result(int(first), int(n), self.inplace)
+        if self.dtype == "fp32":
+            return np.frombuffer(raw, dtype=np.float32).copy()
+        if self.dtype == "fp16":
+            return np.frombuffer(raw, dtype=np.float16).astype(np.float32)
+        return (np.frombuffer(raw, dtype=np.uint16).astype(np.uint32) << 16).view(np.float32)  # bf16 = high half of fp32
+
     def synchronize(self) -> None:
         if self.comm is not None:
             self.comm.synchronize()

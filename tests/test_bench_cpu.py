@@ -21,7 +21,7 @@ def _bench(*args, timeout=300):
 
 
 def test_bench_two_ranks_gloo():
-    out = _bench("--gpus", "2", "--backend", "cpu", "--steps", "3", "--warmup", "1", "--size-mb", "1")
+    out = _bench("--gpus", "2", "--backend", "cpu", "--steps", "3", "--warmup", "1", "--size-mb", "1", "--full")
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config"):
         assert key in out
@@ -57,8 +57,23 @@ def test_bench_line_is_internally_consistent():
     assert ms * steps <= out["phase_s"]["headline"] * 1e3 + 0.5, out
 
 
-def test_bench_single_rank_cpu():
-    out = _bench("--backend", "cpu", "--steps", "2", "--warmup", "1", "--size-mb", "1", "--via", "direct")
+def test_bench_single_rank_cpu(tmp_path):
+    import numpy as np
+
+    out = _bench("--backend", "cpu", "--steps", "2", "--warmup", "1", "--size-mb", "1", "--via", "direct",
+                 "--dump-outputs", str(tmp_path / "dump"))
+    # a plain run: set-up, warm-up, the timed steps, the dump and the line; nothing supplementary
+    assert out["full"] is False and out["steps"] == 2 and out["ms_per_step"] > 0
+    assert set(out["phase_s"]) == {"place", "cpu_bind", "comm", "check", "warmup", "headline", "dump", "total"}, out["phase_s"]
+    assert out["skipped_phases"] == []
+    for key in ("size_sweep", "fp32_headline", "graph_latency", "ring_probe", "rccl", "worst_subset_ab", "default_subset_ab"):
+        assert out[key] is None, key
+    # the last timed step's result: 1 MiB of fp32 (gloo's dtype) fits whole, a one-rank sum of ones
+    assert sorted(p.name for p in (tmp_path / "dump").iterdir()) == ["allreduce_out.npy", "allreduce_out_blocks.npy"]
+    got = np.load(tmp_path / "dump" / "allreduce_out.npy")
+    assert got.dtype == np.float32 and got.shape == (1 << 18,) and (got == 1.0).all()
+    assert np.load(tmp_path / "dump" / "allreduce_out_blocks.npy").tolist() == [0.0]
+    assert out["dumped_outputs"]["elements"] == out["dumped_outputs"]["of"] == 1 << 18
     assert out["k8s_placement"] is None
     assert out["n_gpus"] == 1 and out["busbw_gbps"] == 0.0 and out["value"] == out["algbw_gbps"]
     # the k=1 point says it is a copy rate, not comparable to k>=2 aggregate busBW
@@ -115,6 +130,23 @@ def test_sweep_sizes():
     assert bench.sweep_sizes("1K:4K:2") == [1024, 2048, 4096]
 
 
+def test_dump_blocks():
+    """--dump-outputs keeps a result whole up to 64 blocks of 64 Ki elements; above that, the first and
+    last block and 62 distinct whole blocks between them, the same ones at every call."""
+    sys.path.insert(0, REPO)
+    import bench
+
+    blk, nb = bench.DUMP_BLOCK, bench.DUMP_BLOCKS
+    assert nb * blk * 4 <= 64 << 20  # float32 bytes of the largest dump
+    assert bench.dump_blocks(1) == [(0, 1)] and bench.dump_blocks(nb * blk) == [(0, nb * blk)]
+    for count in (nb * blk + 1, (1 << 30) + 5, 1 << 33):
+        b = bench.dump_blocks(count)
+        assert b == bench.dump_blocks(count) and len(b) == nb and all(n == blk for _, n in b)
+        firsts = [f for f, _ in b]
+        assert firsts[0] == 0 and firsts[-1] == count - blk and firsts == sorted(set(firsts))
+        assert all(f % blk == 0 for f in firsts[:-1]) and firsts[-2] + blk <= count
+
+
 def test_ingress_bound():
     import numpy as np
 
@@ -138,7 +170,7 @@ def test_bench_eight_ranks_gloo_dry_run():
     """The N=8 driver run, rehearsed on CPU: 8 ranks, an 8-device fake node placed through the full
     k8s flow (k = n: no worst subset), the store protocol with 8 ranks, max-over-ranks timing."""
     out = _bench("--gpus", "8", "--backend", "cpu", "--discovery", "fake", "--steps", "2", "--warmup", "1", "--size-mb", "1",
-                 "--sweep", "8:64K:64", timeout=900)
+                 "--sweep", "8:64K:64", "--full", timeout=900)
     assert out["n_gpus"] == 8 and out["config"]["parallelism"] == "dp8"
     assert sorted(out["config"]["subset"]) == list(range(8)) and out["config"]["worst_subset"] is None
     assert out["k8s_placement"]["assigned"] is True and len(out["k8s_placement"]["devices"]) == 8
@@ -157,7 +189,8 @@ def test_bench_eight_ranks_gloo_dry_run():
 def test_bench_tiny_budget_keeps_the_headline():
     """--budget-s far below any phase's cost: every supplementary phase is skipped by all ranks
     together, and the headline line still comes out, measured."""
-    out = _bench("--gpus", "2", "--backend", "cpu", "--steps", "2", "--warmup", "1", "--size-mb", "1", "--budget-s", "0.001")
+    out = _bench("--gpus", "2", "--backend", "cpu", "--steps", "2", "--warmup", "1", "--size-mb", "1", "--budget-s", "0.001",
+                 "--full")
     assert out["value"] > 0 and out["steps"] == 2 and out["phase_s"]["headline"] > 0
     skipped = {s["phase"] for s in out["skipped_phases"]}
     assert "sweep" in skipped and out["size_sweep"] is None
@@ -174,7 +207,7 @@ def test_bench_four_ranks_on_amdsmi_discovered_node():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "4", "--backend", "cpu", "--discovery", "amdsmi",
-                        "--steps", "2", "--warmup", "1", "--size-mb", "1", "--sweep", "off", "--cpu-visible", "8"],
+                        "--steps", "2", "--warmup", "1", "--size-mb", "1", "--sweep", "off", "--cpu-visible", "8", "--full"],
                        capture_output=True, text=True, timeout=600, cwd=REPO, env=env)
     assert p.returncode == 0, p.stderr[-4000:]
     out = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])

@@ -141,7 +141,7 @@ def test_ring_probe_bounded_by_its_links():
 @needs2
 def test_bench_two_gpus_native_exact_and_bounded():
     out = _run(["bench.py", "--gpus", "2", "--steps", "5", "--warmup", "2", "--size-mb", "256", "--sweep", "8:64M:64",
-                "--ctas", "default"])
+                "--ctas", "default", "--full"])
     assert out["n_gpus"] == 2 and out["value_kind"].startswith("aggregate busbw") and out["config"]["backend"] == "native"
     assert out["size_sweep"]["all_exact"]
     assert len(set(out["config"]["hip_devices"])) == 2
@@ -160,7 +160,7 @@ def test_bench_two_gpus_native_exact_and_bounded():
 @needs2
 def test_bench_two_gpus_graph_capture():
     out = _run(["bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--size-mb", "16", "--sweep", "8:4K:8",
-                "--graph", "on", "--ctas", "default", "--probe", "off"])
+                "--graph", "on", "--ctas", "default", "--probe", "off", "--full"])
     g = out["graph_latency"]
     assert g and g.get("all_exact"), g
 

@@ -220,6 +220,36 @@ def test_rccl_comm_api_single_rank():
     c.destroy()
 
 
+@pytest.mark.parametrize("dtype", ["bf16", "fp16", "fp32"])
+def test_rccl_runner_reads_back_the_result(dtype):
+    """What --dump-outputs samples: ranges of the last step's result come back as float32, equal to the
+    one-rank sum of the fill pattern (i % 7 + 1), from the first element to the last; a range past the
+    prepared message is refused, and so is a read after the buffers are gone."""
+    from gpu_topology_on_k8s_amd.parallel.allreduce import AllReduceRunner, DistEnv
+
+    class Store(dict):
+        set = dict.__setitem__
+
+    n = (1 << 20) + 3  # no multiple of the pattern's period or of the fill kernel's grid
+    r = AllReduceRunner(DistEnv(0, 1, 0, Store()), 0, n * (4 if dtype == "fp32" else 2), dtype, tag=f"/read-{dtype}")
+    try:
+        assert r.count == n
+        r.step()
+        r.synchronize()
+        for first, m in ((0, 4099), (n - 4099, 4099), (12345, 1), (n, 0), (0, n)):
+            got = r.read_result(first, m)
+            assert got.dtype == np.float32 and got.shape == (m,)
+            assert np.array_equal(got, ((np.arange(first, first + m) % 7) + 1).astype(np.float32))
+        for first, m in ((n, 1), (n - 1, 2), (n + 1, 0), (0, n + 1), (1, 2 ** 64 - 1)):
+            with pytest.raises((IndexError, OverflowError)):
+                r.comm.read_result(first, m)
+        comm = r.comm
+    finally:
+        r.close()
+    with pytest.raises(RuntimeError):
+        comm.read_result(0, 1)
+
+
 def test_rccl_comm_config_ctas():
     """ncclCommInitRankConfig path (minCTAs/maxCTAs) builds a working communicator."""
     from gpu_topology_on_k8s_amd._native import load
@@ -274,7 +304,8 @@ def test_rccl_cli_binary():
 
 
 def test_bench_py_single_gpu():
-    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "5", "--warmup", "2", "--size-mb", "64"],
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "5", "--warmup", "2", "--size-mb", "64",
+                        "--full"],
                        capture_output=True, text=True, timeout=600, cwd=REPO)
     assert p.returncode == 0, p.stderr[-4000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]
@@ -336,7 +367,7 @@ def test_bench_py_reports_rccl_log():
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if not k.startswith("NCCL_DEBUG")}
     p = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--size-mb", "16", "--sweep", "off",
-                        "--graph", "off", "--probe", "off", "--rccl-log", "on"], capture_output=True, text=True, timeout=600,
+                        "--graph", "off", "--probe", "off", "--rccl-log", "on", "--full"], capture_output=True, text=True, timeout=600,
                        cwd=repo, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])

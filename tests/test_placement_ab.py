@@ -72,7 +72,7 @@ def test_bench_dry_run_reports_three_subsets_with_terms(tmp_path, n, fixture):
     path = tmp_path / "topo.json"
     path.write_text(t.to_json())
     out = _bench("--gpus", str(n), "--backend", "cpu", "--steps", "2", "--warmup", "1", "--size-mb", "1", "--sweep", "off",
-                 "--cpu-visible", "8", "--topology-json", str(path))
+                 "--cpu-visible", "8", "--topology-json", str(path), "--full")
     pt = out["placement_terms"]
     assert {"chosen", "worst", "default", "vs_worst", "vs_default"} <= set(pt)
     assert pt["chosen"]["ids"] == out["config"]["subset"]

@@ -1,6 +1,6 @@
 #!/usr/bin/env bash
 # One gpurun call per invocation:  gpurun --timeout 1200 -- 'bash tools/gpu_suite.sh <mode> <outdir>'
-#   suite    pytest -m gpu, smoke(), headline bench (k=1)
+#   suite    pytest -m gpu, smoke(), headline bench (k=1) with its supplementary phases (--full)
 #   bench    headline bench only (the driver's command line)
 #   profile  rocprofv3 --kernel-trace --stats of the headline bench and of the link probe
 # Every GPU step has its own time limit; the first failing step ends the call (exit status kept).
@@ -23,7 +23,7 @@ case "$mode" in
   suite)
     step pytest_gpu 900 python -u -m pytest tests -m gpu -x -v -rP --timeout 300 --timeout-method thread
     step smoke 300 python -u -c 'import __graft_entry__ as g; g.smoke()'
-    step bench_k1 600 python -u bench.py --gpus 1 --steps 20 --warmup 5
+    step bench_k1 600 python -u bench.py --gpus 1 --steps 20 --warmup 5 --full
     ;;
   bench)
     step bench_k1 600 python -u bench.py --gpus 1 --steps 20 --warmup 5
