@@ -1,10 +1,12 @@
 // Standalone placement validator (no Python): run inside the pod on its allocated GPUs.
 //
 //   rccl_allreduce_bench [--devices 0,1,2,3] [--min 8] [--max 16G] [--factor 2] [--dtype bf16]
-//                        [--iters 20] [--warmup 5] [--inplace] [--no-check] [--json]
+//                        [--iters 20] [--warmup 5] [--inplace] [--no-check] [--json] [--self-copy on|off]
 //
 // Default device list: every visible device (the container only sees its GROUP, design.md:239,
 // via /dev/dri/renderD* mounts).  Prints an nccl-tests-style table or JSON lines.
+// On one device the out-of-place all-reduce is this repository's copy kernel (self_copy.h);
+// --self-copy off, or GTK_RCCL_SELF_COPY=0, sends it through ncclAllReduce as for k >= 2.
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -31,6 +33,7 @@ int main(int argc, char** argv) {
   int factor = 2, iters = 20, warmup = 5;
   std::string dtype = "bf16";
   bool inplace = false, check = true, json = false;
+  int self_copy = -1;  // -1: as GTK_RCCL_SELF_COPY says
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() -> std::string {
@@ -58,9 +61,16 @@ int main(int argc, char** argv) {
     else if (a == "--inplace") inplace = true;
     else if (a == "--no-check") check = false;
     else if (a == "--json") json = true;
-    else {
+    else if (a == "--self-copy") {
+      std::string v = next();
+      if (v != "on" && v != "off") {
+        fprintf(stderr, "--self-copy takes on or off\n");
+        return 2;
+      }
+      self_copy = v == "on";
+    } else {
       fprintf(stderr, "usage: %s [--devices a,b,..] [--min B] [--max B] [--factor F] [--dtype bf16|fp16|fp32] "
-                      "[--iters N] [--warmup N] [--inplace] [--no-check] [--json]\n", argv[0]);
+                      "[--iters N] [--warmup N] [--inplace] [--no-check] [--json] [--self-copy on|off]\n", argv[0]);
       return 2;
     }
   }
@@ -71,6 +81,7 @@ int main(int argc, char** argv) {
       for (int i = 0; i < n; ++i) devs.push_back(i);
     }
     LocalGroup g(devs);
+    if (self_copy >= 0) g.set_self_copy(self_copy != 0);
     if (!json) {
       printf("# rccl_allreduce_bench: k=%zu dtype=%s %s\n", devs.size(), dtype.c_str(), inplace ? "in-place" : "out-of-place");
       printf("%14s %14s %12s %12s %12s %8s\n", "size(B)", "count", "time(us)", "algbw(GB/s)", "busbw(GB/s)", "wrong");

@@ -8,6 +8,12 @@
 // ncclCommInitRank (one process per GPU), bf16/fp32 sum, algBW = bytes/t, busBW = algBW*2(k-1)/k
 // (nccl-tests convention), with an exact correctness check.
 //
+// One rank (k = 1): the sum is the rank's own contribution, so the out-of-place all-reduce is a copy
+// from `send` to `recv`.  RCCL passes it to the HIP runtime's copy; RankState::allreduce instead
+// launches this repository's gtk_self_copy_kernel (self_copy.h) for messages of kSelfCopyMinBytes and
+// more, and enqueues nothing in place.  GTK_RCCL_SELF_COPY=0, read once when a LocalGroup or Comm is
+// created, restores ncclAllReduce at every size; k >= 2 always is ncclAllReduce.
+//
 // Correctness data: rank r contributes (r+1)*((i%7)+1); every partial sum stays < 256 so bf16
 // represents it exactly and the reduced value must equal ((i%7)+1)*k(k+1)/2 bit-for-bit.
 #pragma once
@@ -16,10 +22,13 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
 #include <stdexcept>
 #include <string>
 #include <vector>
+
+#include "self_copy.h"
 
 #define RCCL_HIP_CHECK(expr)                                                                     \
   do {                                                                                           \
@@ -92,6 +101,7 @@ __global__ void gtk_check_kernel(const void* buf, size_t count, int dtype_code, 
 }
 
 inline int dtype_code(ncclDataType_t t) { return t == ncclBfloat16 ? 0 : (t == ncclFloat16 ? 1 : 2); }
+inline size_t elem_size(ncclDataType_t t) { return t == ncclFloat32 ? 4 : 2; }  // the types parse_dtype() yields
 
 // ---------------------------------------------------------------------------------- one rank
 // One communicator member on one device with persistent send/recv buffers.
@@ -102,8 +112,21 @@ struct RankState {
   void* send = nullptr;
   void* recv = nullptr;
   size_t cap_bytes = 0;
+  // the one-rank copy kernel (self_copy.h): on unless GTK_RCCL_SELF_COPY=0, for messages of at least
+  // self_copy_min bytes, grid cap from the CU count
+  bool self_copy = true;
+  size_t self_copy_min = kSelfCopyMinBytes;
+  int cus = 0, max_blocks = 0;
 
   void set_device() const { RCCL_HIP_CHECK(hipSetDevice(device)); }
+
+  // Once, when the owner (LocalGroup, Comm) has set `device`: the switch and the device's CU count.
+  void configure() {
+    const char* e = std::getenv("GTK_RCCL_SELF_COPY");
+    self_copy = !(e && std::strcmp(e, "0") == 0);
+    RCCL_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+    max_blocks = std::max(1, cus) * kSelfCopyBlocksPerCU;
+  }
 
   void ensure(size_t bytes) {
     set_device();
@@ -138,7 +161,22 @@ struct RankState {
     return bad;
   }
 
+  // One rank: the sum over the communicator is the rank's own contribution.  In place that is nothing
+  // at all, which is what RCCL enqueues there too; out of place it is a copy, done by our kernel on
+  // `stream` like the collective it stands in for, and capturable like it.  Messages under
+  // self_copy_min, where the runtime's copy is the faster one, k >= 2, or the switch off: RCCL.
   void allreduce(size_t count, ncclDataType_t t, bool inplace) {
+    if (nranks == 1 && self_copy) {
+      if (inplace) return;
+      const size_t bytes = count * elem_size(t);
+      if (bytes >= self_copy_min) {
+        if (!max_blocks) throw std::logic_error("RankState::configure() was not called");
+        hipLaunchKernelGGL(gtk_self_copy_kernel, dim3(self_copy_grid(bytes, max_blocks)), dim3(kSelfCopyBlock), 0, stream,
+                           send, recv, bytes);
+        RCCL_HIP_CHECK(hipGetLastError());
+        return;
+      }
+    }
     NCCL_CHECK(ncclAllReduce(send, inplace ? send : recv, count, t, ncclSum, comm, stream));
   }
 
@@ -178,6 +216,7 @@ class LocalGroup {
       ranks_[i].rank = (int)i;
       ranks_[i].nranks = (int)devs.size();
       ranks_[i].comm = comms[i];
+      ranks_[i].configure();
     }
   }
   ~LocalGroup() {
@@ -232,6 +271,9 @@ class LocalGroup {
   }
 
   size_t size() const { return ranks_.size(); }
+  void set_self_copy(bool on) {
+    for (auto& r : ranks_) r.self_copy = on;
+  }
 
  private:
   void launch_all(size_t count, ncclDataType_t t, bool inplace) {

@@ -5,7 +5,8 @@
 //                                     the ncclUniqueId, ships the 128 bytes through any store, every
 //                                     rank builds a Comm on its chosen device (ncclCommInitRank).
 // Comm.step() enqueues one out-of-place all-reduce on the Comm's stream and returns immediately so
-// a Python-side timing loop (bench.py) brackets exactly K of them with barrier + synchronize.
+// a Python-side timing loop (bench.py) brackets exactly K of them with barrier + synchronize.  On a
+// one-rank communicator that is the copy kernel of self_copy.h (Comm.self_copy, Comm.self_copy_min_bytes).
 // Comm.capture(n) records n back-to-back all-reduces into one hipGraph and Comm.replay() launches
 // it: small messages are launch-bound (a few µs of host enqueue per call), and a graph replays the
 // whole chain with one launch — the latency a graph-captured training step sees.
@@ -33,6 +34,7 @@ class Comm {
     st_.nranks = nranks;
     py::gil_scoped_release nogil;
     st_.set_device();
+    st_.configure();
     if (min_ctas > 0 || max_ctas > 0) {
       ncclConfig_t cfg = NCCL_CONFIG_INITIALIZER;
       if (min_ctas > 0) cfg.minCTAs = min_ctas;
@@ -146,6 +148,21 @@ class Comm {
   int device() const { return st_.device; }
   int min_ctas() const { return min_ctas_; }
   int max_ctas() const { return max_ctas_; }
+  // The one-rank copy kernel instead of ncclAllReduce (GTK_RCCL_SELF_COPY at construction).  A graph
+  // captured under the other setting is dropped: it would replay the path that was switched away from.
+  bool self_copy() const { return st_.self_copy; }
+  void set_self_copy(bool on) {
+    if (on != st_.self_copy) drop_graph();
+    st_.self_copy = on;
+  }
+  // Smallest message the kernel takes (kSelfCopyMinBytes by default; 0 sends every size to it).
+  size_t self_copy_min_bytes() const { return st_.self_copy_min; }
+  void set_self_copy_min_bytes(size_t bytes) {
+    if (bytes != st_.self_copy_min) drop_graph();
+    st_.self_copy_min = bytes;
+  }
+  int self_copy_cus() const { return st_.cus; }
+  int self_copy_max_blocks() const { return st_.max_blocks; }
   void destroy() {
     drop_graph();
     st_.release();
@@ -234,5 +251,12 @@ PYBIND11_MODULE(_rccl, m) {
       .def_property_readonly("nranks", &Comm::nranks)
       .def_property_readonly("device", &Comm::device)
       .def_property_readonly("min_ctas", &Comm::min_ctas)
-      .def_property_readonly("max_ctas", &Comm::max_ctas);
+      .def_property_readonly("max_ctas", &Comm::max_ctas)
+      .def_property("self_copy", &Comm::self_copy, &Comm::set_self_copy)
+      .def_property("self_copy_min_bytes", &Comm::self_copy_min_bytes, &Comm::set_self_copy_min_bytes)
+      .def_property_readonly("self_copy_cus", &Comm::self_copy_cus)
+      .def_property_readonly("self_copy_max_blocks", &Comm::self_copy_max_blocks);
+  m.attr("SELF_COPY_TILE_BYTES") = kSelfCopyTileBytes;
+  m.attr("SELF_COPY_BLOCKS_PER_CU") = kSelfCopyBlocksPerCU;
+  m.attr("SELF_COPY_MIN_BYTES") = kSelfCopyMinBytes;
 }

@@ -135,10 +135,10 @@ def targets() -> List[Target]:
                deps=[CSRC / "placement" / "engine.h"], pybind=False, shared=False),
         Target("_probe", [CSRC / "probe" / "probe.hip"], "hipcc", HERE / f"_probe{EXT}"),
         Target("_rccl", [CSRC / "rccl" / "rccl_module.hip"], "hipcc", HERE / f"_rccl{EXT}",
-               [f"-L{rocm_lib}", "-lrccl", f"-Wl,-rpath,{rocm_lib}"], deps=[CSRC / "rccl" / "rccl_core.h"]),
+               [f"-L{rocm_lib}", "-lrccl", f"-Wl,-rpath,{rocm_lib}"], deps=[CSRC / "rccl" / "rccl_core.h", CSRC / "rccl" / "self_copy.h"]),
         Target("rccl_allreduce_bench", [CSRC / "rccl" / "rccl_allreduce_bench.hip"], "hipcc",
                HERE / "bin" / "rccl_allreduce_bench", [f"-L{rocm_lib}", "-lrccl", f"-Wl,-rpath,{rocm_lib}"],
-               deps=[CSRC / "rccl" / "rccl_core.h"], pybind=False, shared=False),
+               deps=[CSRC / "rccl" / "rccl_core.h", CSRC / "rccl" / "self_copy.h"], pybind=False, shared=False),
         # container-side tier of a time-sliced share (Gaia vGPU): HBM cap + forced CU mask, preloaded into
         # the pod by Allocate (--share-guard); host-only C++, resolves the real HIP entry points at run time
         Target("vgpu_guard", [CSRC / "vgpu" / "vgpu_guard.cpp"], "gxx", HERE / "bin" / "libgtk_vgpu.so",

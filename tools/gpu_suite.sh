@@ -3,6 +3,7 @@
 #   suite    pytest -m gpu, smoke(), headline bench (k=1) with its supplementary phases (--full)
 #   bench    headline bench only (the driver's command line)
 #   profile  rocprofv3 --kernel-trace --stats of the headline bench and of the link probe
+#   k1copy   the k = 1 copy kernel: tests, A/B against RCCL's path, trace (profiles/k1_self_copy)
 # Every GPU step has its own time limit; the first failing step ends the call (exit status kept).
 set -uo pipefail
 mode=${1:-suite}
@@ -124,6 +125,14 @@ print(json.dumps({"tflops": round(float(w["tflops"]), 1), "hbm_copy_gbps": round
   shadow)
     # what 8-GPU DP communication costs the Llama-3-8B step: comm-shadow CTA sweep
     step shadow_sweep 1100 python -u bench/comm_shadow_sweep.py --ctas ${SHADOW_CTAS:-0,8,16,32,64} --busbw ${SHADOW_BUSBW:-350} --out "$out/shadow.jsonl" ${SHADOW_ZERO1:+--zero1}
+    ;;
+  k1copy)
+    # the one-rank all-reduce's own copy kernel: its tests, the A/B against RCCL's path at every size
+    # (the kernel at all of them), the routing as built at the small ones, and the headline's trace
+    step pytest_self_copy 300 python -u -m pytest tests/test_rccl_self_copy_gpu.py -x -v --timeout 200 --timeout-method thread
+    step allreduce_k1_ab 300 python -u bench/allreduce_k1_ab.py --sizes 65536,1M,16M,64M,128M,256M,512M,1G,2G,4G,8G,16G
+    step allreduce_k1_ab_routed 300 python -u bench/allreduce_k1_ab.py --cutoff build --sizes 8,4096,262144,2M,16M,128M
+    step prof_bench 600 rocprofv3 --kernel-trace --stats -d "$out/prof_bench" -o run -- python3 bench.py --steps 5 --warmup 2 --sweep off
     ;;
   *) echo "unknown mode $mode"; exit 2 ;;
 esac
