@@ -39,9 +39,11 @@
 #include <string>
 #include <vector>
 
+#include "../common/stream_copy.h"
+
 namespace py = pybind11;
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+using gtk::u32x4;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -55,10 +57,13 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
+// Equal to the all-reduce's kSelfCopy* (csrc/rccl/self_copy.h) today, but tuned on their own (these
+// on the LDS budget above, those on the 2 GiB headline): kept separate on purpose.
 constexpr int kBlock = 256;
 constexpr int kUnroll = 4;
 constexpr int kTileVec = kBlock * kUnroll;  // 16-byte vectors per block-iteration (16 KiB)
 constexpr int kBlocksPerCU = 8;
+static_assert(kBlock == gtk::kStreamBlock, "stream_copy.h indexes blocks of kStreamBlock threads");
 
 using gptr_t = const __attribute__((address_space(1))) void*;
 using lptr_t = __attribute__((address_space(3))) void*;
@@ -91,8 +96,7 @@ __device__ __forceinline__ void copy_lds_stream(const u32x4* __restrict__ src, u
         dst[off] = v;
     }
   }
-  // tail (< one tile): plain per-thread copy
-  for (size_t i = n_full + blk * kBlock + threadIdx.x; i < n_vec; i += nblk * kBlock) dst[i] = src[i];
+  gtk::stream_vec_tail(src, dst, n_vec, n_full, blk, nblk);
 }
 
 template <bool kNonTemporal>
@@ -134,37 +138,31 @@ __global__ __launch_bounds__(kBlock) void copy_reg_kernel(const u32x4* __restric
         dst[base + (size_t)u * kBlock + threadIdx.x] = r[u];
     }
   }
-  for (size_t i = n_full + (size_t)blockIdx.x * kBlock + threadIdx.x; i < n_vec; i += (size_t)gridDim.x * kBlock)
-    dst[i] = src[i];
+  gtk::stream_vec_tail(src, dst, n_vec, n_full, blockIdx.x, gridDim.x);
 }
 
-// Contiguous-chunk variant: block b streams its own 1/grid slice of the buffer (each workgroup walks
-// one DRAM region, instead of the whole grid sweeping one window together), U independent 16-B
-// loads in flight per lane, non-temporal loads and stores.
+// Contiguous-chunk variant: block b streams its own 1/grid slice of the buffer, U independent 16-B
+// loads in flight per lane, non-temporal loads and stores (the body the one-rank all-reduce uses).
 template <int U>
 __global__ __launch_bounds__(kBlock) void copy_chunk_kernel(const u32x4* __restrict__ src, u32x4* __restrict__ dst,
                                                             size_t n_vec) {
-  const size_t tile = (size_t)kBlock * U;
-  const size_t n_tiles = n_vec / tile;
-  const size_t per = (n_tiles + gridDim.x - 1) / gridDim.x;
-  const size_t t0 = (size_t)blockIdx.x * per;
-  const size_t t1 = std::min(n_tiles, t0 + per);
-  for (size_t t = t0; t < t1; ++t) {
-    const size_t base = t * tile + threadIdx.x;
-    u32x4 r[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) r[u] = __builtin_nontemporal_load(src + base + (size_t)u * kBlock);
-#pragma unroll
-    for (int u = 0; u < U; ++u) __builtin_nontemporal_store(r[u], dst + base + (size_t)u * kBlock);
-  }
-  for (size_t i = n_tiles * tile + (size_t)blockIdx.x * kBlock + threadIdx.x; i < n_vec; i += (size_t)gridDim.x * kBlock)
-    dst[i] = src[i];
+  const size_t first = gtk::stream_slices<U>(src, dst, n_vec, blockIdx.x, gridDim.x);
+  gtk::stream_vec_tail(src, dst, n_vec, first, blockIdx.x, gridDim.x);
 }
 
 __global__ __launch_bounds__(kBlock) void fill_pattern_kernel(unsigned int* __restrict__ p, size_t n_words,
                                                               unsigned int seed) {
   for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n_words; i += (size_t)gridDim.x * kBlock)
     p[i] = (unsigned int)(i * 2654435761u) ^ seed;
+}
+
+// Counts the words of p[0, n_words) that differ from what fill_pattern_kernel(seed) writes.
+__global__ __launch_bounds__(kBlock) void pattern_mismatch_kernel(const unsigned int* __restrict__ p, size_t n_words,
+                                                                  unsigned int seed, unsigned long long* bad) {
+  unsigned long long local = 0;
+  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n_words; i += (size_t)gridDim.x * kBlock)
+    local += (p[i] != ((unsigned int)(i * 2654435761u) ^ seed));
+  if (local) atomicAdd(bad, local);
 }
 
 // K4: MFMA warm-up.  Each wave keeps 4 independent 32x32 accumulators so back-to-back
@@ -286,6 +284,97 @@ void enable_peer(int from, int to) {
   (void)hipGetLastError();
 }
 
+void check_bytes_iters(size_t bytes, int iters = 1) {
+  if (bytes < 16 || bytes % 16) throw std::invalid_argument("bytes must be a positive multiple of 16");
+  if (iters < 1) throw std::invalid_argument("iters >= 1");
+}
+
+// Blocks of a gather launch on `dev`: a multiple of nsrc, so every source gets the same block count.
+// Members of a ring that share a device (`share` of them) split its CUs.
+int gather_grid(int dev, int blocks_per_cu, int nsrc, int share = 1) {
+  const int per = std::max(1, num_cus(dev) * std::max(1, blocks_per_cu) / (nsrc * share));
+  return per * nsrc;
+}
+
+// GB/s of `bytes` moved per iteration, `iters` iterations in `ms`.
+double gbps(double bytes, double ms, int iters) { return bytes / (ms / 1e3 / iters) / 1e9; }
+
+// A non-blocking stream of the current device with the two events that bracket a timed section.
+struct TimedStream {
+  int dev = 0;
+  hipStream_t s = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  TimedStream() {
+    try {
+      HIP_CHECK(hipGetDevice(&dev));
+      HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+      for (hipEvent_t* e : {&e0, &e1}) HIP_CHECK(hipEventCreate(e));
+    } catch (...) {
+      release();
+      throw;
+    }
+  }
+  ~TimedStream() { release(); }
+  TimedStream(const TimedStream&) = delete;
+  TimedStream& operator=(const TimedStream&) = delete;
+  void begin() { HIP_CHECK(hipEventRecord(e0, s)); }
+  void end() { HIP_CHECK(hipEventRecord(e1, s)); }
+  float ms() {  // of begin() .. end(), once the stream has reached end()
+    float t = 0.f;
+    HIP_CHECK(hipEventSynchronize(e1));
+    HIP_CHECK(hipEventElapsedTime(&t, e0, e1));
+    return t;
+  }
+  float end_ms() {
+    end();
+    return ms();
+  }
+
+ private:
+  void release() noexcept {
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    (void)hipSetDevice(dev);
+    if (s) (void)hipStreamSynchronize(s);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (s) (void)hipStreamDestroy(s);
+    (void)hipSetDevice(prev);
+  }
+};
+
+// Event-timed `iters` launches of `launch` on a fresh non-blocking stream (after `warmup` untimed).
+template <class F>
+float time_launches(F launch, int iters, int warmup) {
+  TimedStream t;
+  for (int i = 0; i < warmup; ++i) launch(t.s);
+  HIP_CHECK(hipGetLastError());
+  t.begin();
+  for (int i = 0; i < iters; ++i) launch(t.s);
+  HIP_CHECK(hipGetLastError());
+  return t.end_ms();
+}
+
+void fill_pattern(int dev, void* p, size_t bytes, unsigned int seed) {
+  DeviceGuard g(dev);
+  hipLaunchKernelGGL(fill_pattern_kernel, dim3(num_cus(dev) * 4), dim3(kBlock), 0, 0, (unsigned int*)p, bytes / 4, seed);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipDeviceSynchronize());
+}
+
+// Does p[0, n_words), memory of `dev`, hold pattern(seed) in every word?  One pass on the device.
+bool holds_pattern(int dev, const void* p, size_t n_words, unsigned int seed) {
+  DeviceGuard g(dev);
+  DevBuf bad(dev, sizeof(unsigned long long));
+  HIP_CHECK(hipMemset(bad.p, 0, sizeof(unsigned long long)));
+  hipLaunchKernelGGL(pattern_mismatch_kernel, dim3(num_cus(dev) * kBlocksPerCU), dim3(kBlock), 0, 0,
+                     (const unsigned int*)p, n_words, seed, (unsigned long long*)bad.p);
+  HIP_CHECK(hipGetLastError());
+  unsigned long long n = 0;
+  HIP_CHECK(hipMemcpy(&n, bad.p, sizeof(n), hipMemcpyDeviceToHost));
+  return n == 0;
+}
+
 void launch_copy(const std::string& kind, bool nt, const void* src, void* dst, size_t n_vec, int grid, hipStream_t s) {
   auto* S = reinterpret_cast<const u32x4*>(src);
   auto* D = reinterpret_cast<u32x4*>(dst);
@@ -312,22 +401,6 @@ void launch_copy(const std::string& kind, bool nt, const void* src, void* dst, s
   HIP_CHECK(hipGetLastError());
 }
 
-// Verify a few windows of dst against the host-side pattern.
-bool verify_pattern(const DevBuf& dst, size_t n_words, unsigned int seed) {
-  const size_t win = std::min<size_t>(n_words, 1 << 16);
-  std::vector<size_t> starts = {0, n_words / 2 - std::min(n_words / 2, win / 2), n_words - win};
-  std::vector<unsigned int> h(win);
-  DeviceGuard g(dst.dev);
-  for (size_t st : starts) {
-    HIP_CHECK(hipMemcpy(h.data(), (const unsigned int*)dst.p + st, win * 4, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < win; ++i) {
-      unsigned int want = (unsigned int)((st + i) * 2654435761u) ^ seed;
-      if (h[i] != want) return false;
-    }
-  }
-  return true;
-}
-
 struct CopyResult {
   int src, dst, exec, iters, grid;
   size_t bytes;
@@ -338,9 +411,8 @@ struct CopyResult {
 
 CopyResult copy_bw_impl(int src_dev, int dst_dev, int exec_dev, size_t bytes, int iters, int warmup,
                         const std::string& kind, bool nontemporal, int blocks_per_cu) {
-  if (bytes < 16 || bytes % 16) throw std::invalid_argument("bytes must be a positive multiple of 16");
+  check_bytes_iters(bytes, iters);
   if (exec_dev != src_dev && exec_dev != dst_dev) throw std::invalid_argument("exec_dev must be src or dst");
-  if (iters < 1) throw std::invalid_argument("iters >= 1");
   int ndev = 0;
   HIP_CHECK(hipGetDeviceCount(&ndev));
   for (int d : {src_dev, dst_dev})
@@ -350,43 +422,17 @@ CopyResult copy_bw_impl(int src_dev, int dst_dev, int exec_dev, size_t bytes, in
   DevBuf src(src_dev, bytes), dst(dst_dev, bytes);
   const size_t n_vec = bytes / 16;
   const unsigned int seed = 0x9e3779b9u ^ (unsigned)(src_dev * 131 + dst_dev);
-  {
-    DeviceGuard g(src_dev);
-    hipLaunchKernelGGL(fill_pattern_kernel, dim3(num_cus(src_dev) * 4), dim3(kBlock), 0, 0, (unsigned int*)src.p,
-                       bytes / 4, seed);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipDeviceSynchronize());
-  }
-  DeviceGuard g(exec_dev);
-  hipStream_t s;
-  HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  fill_pattern(src_dev, src.p, bytes, seed);
   const int grid = num_cus(exec_dev) * std::max(1, blocks_per_cu);
-  hipEvent_t e0, e1;
-  HIP_CHECK(hipEventCreate(&e0));
-  HIP_CHECK(hipEventCreate(&e1));
   float ms = 0.f;
-  try {
-    for (int i = 0; i < warmup; ++i) launch_copy(kind, nontemporal, src.p, dst.p, n_vec, grid, s);
-    HIP_CHECK(hipEventRecord(e0, s));
-    for (int i = 0; i < iters; ++i) launch_copy(kind, nontemporal, src.p, dst.p, n_vec, grid, s);
-    HIP_CHECK(hipEventRecord(e1, s));
-    HIP_CHECK(hipEventSynchronize(e1));
-    HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-  } catch (...) {
-    (void)hipStreamSynchronize(s);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    (void)hipStreamDestroy(s);
-    throw;
+  {
+    DeviceGuard g(exec_dev);
+    ms = time_launches([&](hipStream_t s) { launch_copy(kind, nontemporal, src.p, dst.p, n_vec, grid, s); }, iters, warmup);
   }
-  HIP_CHECK(hipEventDestroy(e0));
-  HIP_CHECK(hipEventDestroy(e1));
-  HIP_CHECK(hipStreamDestroy(s));
-  const bool ok = verify_pattern(dst, bytes / 4, seed);
-  const double sec = ms / 1e3 / iters;
+  const bool ok = holds_pattern(dst_dev, dst.p, bytes / 4, seed);
   // gbps = bytes copied per second (one direction over the link; for a self copy HBM moves 2x)
   return CopyResult{src_dev, dst_dev, exec_dev, iters, grid, bytes, kind, nontemporal, ok, (double)ms / iters,
-                    (double)bytes / sec / 1e9};
+                    gbps((double)bytes, ms, iters)};
 }
 
 // K5: aggregate ingress of `dst_dev` reading `bytes` from every device in `srcs` concurrently.
@@ -394,15 +440,15 @@ CopyResult copy_bw_impl(int src_dev, int dst_dev, int exec_dev, size_t bytes, in
 // the kernel's segment indexing; on a node the sources are the peers.
 py::dict gather_bw(int dst_dev, const std::vector<int>& srcs, size_t bytes, int iters, int warmup, int blocks_per_cu) {
   if (srcs.empty() || srcs.size() > (size_t)kMaxSrc) throw std::invalid_argument("1..16 source devices");
-  if (bytes < 16 || bytes % 16) throw std::invalid_argument("bytes must be a positive multiple of 16");
-  if (iters < 1) throw std::invalid_argument("iters >= 1");
+  check_bytes_iters(bytes, iters);
   int ndev = 0;
   HIP_CHECK(hipGetDeviceCount(&ndev));
   if (dst_dev < 0 || dst_dev >= ndev) throw std::invalid_argument("device index out of range");
   for (int d : srcs) {
     if (d < 0 || d >= ndev) throw std::invalid_argument("source device index out of range");
   }
-  double ms_total = 0.0;
+  auto seed_of = [](int dev) { return 0x51ed27u ^ (unsigned)(dev * 977); };
+  float ms = 0.f;
   bool ok = true;
   const int nsrc = (int)srcs.size();
   {
@@ -412,60 +458,26 @@ py::dict gather_bw(int dst_dev, const std::vector<int>& srcs, size_t bytes, int 
     SrcSet set{};
     for (int i = 0; i < nsrc; ++i) {
       src_bufs.emplace_back(new DevBuf(srcs[i], bytes));
-      DeviceGuard g(srcs[i]);
-      hipLaunchKernelGGL(fill_pattern_kernel, dim3(num_cus(srcs[i]) * 4), dim3(kBlock), 0, 0,
-                         (unsigned int*)src_bufs.back()->p, bytes / 4, 0x51ed27u ^ (unsigned)(srcs[i] * 977));
-      HIP_CHECK(hipGetLastError());
-      HIP_CHECK(hipDeviceSynchronize());
+      fill_pattern(srcs[i], src_bufs.back()->p, bytes, seed_of(srcs[i]));
       set.p[i] = reinterpret_cast<const u32x4*>(src_bufs.back()->p);
     }
     DevBuf dst(dst_dev, bytes * (size_t)nsrc);
     DeviceGuard g(dst_dev);
-    hipStream_t st;
-    HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    const int per = std::max(1, num_cus(dst_dev) * std::max(1, blocks_per_cu) / nsrc);
-    const int grid = per * nsrc;  // a multiple of nsrc: every source gets the same block count
-    hipEvent_t e0, e1;
-    HIP_CHECK(hipEventCreate(&e0));
-    HIP_CHECK(hipEventCreate(&e1));
-    for (int i = 0; i < warmup; ++i)
-      hipLaunchKernelGGL(gather_lds_kernel, dim3(grid), dim3(kBlock), 0, st, set, nsrc, (u32x4*)dst.p, bytes / 16);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(e0, st));
-    for (int i = 0; i < iters; ++i)
-      hipLaunchKernelGGL(gather_lds_kernel, dim3(grid), dim3(kBlock), 0, st, set, nsrc, (u32x4*)dst.p, bytes / 16);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(e1, st));
-    HIP_CHECK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    ms_total = ms;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    (void)hipStreamDestroy(st);
-    // verify every segment against its source's pattern (windows, as for the pairwise probe)
-    const size_t words = bytes / 4, win = std::min<size_t>(words, 1 << 14);
-    std::vector<unsigned int> h(win);
-    for (int i = 0; i < nsrc && ok; ++i) {
-      const unsigned int seed = 0x51ed27u ^ (unsigned)(srcs[i] * 977);
-      for (size_t st0 : {(size_t)0, words - win}) {
-        HIP_CHECK(hipMemcpy(h.data(), (const unsigned int*)dst.p + (size_t)i * words + st0, win * 4, hipMemcpyDeviceToHost));
-        for (size_t k = 0; k < win; ++k)
-          if (h[k] != ((unsigned int)((st0 + k) * 2654435761u) ^ seed)) {
-            ok = false;
-            break;
-          }
-      }
-    }
+    const int grid = gather_grid(dst_dev, blocks_per_cu, nsrc);
+    ms = time_launches([&](hipStream_t s) {
+      hipLaunchKernelGGL(gather_lds_kernel, dim3(grid), dim3(kBlock), 0, s, set, nsrc, (u32x4*)dst.p, bytes / 16);
+    }, iters, warmup);
+    // every segment holds its source's pattern
+    for (int i = 0; i < nsrc && ok; ++i)
+      ok = holds_pattern(dst_dev, (const char*)dst.p + (size_t)i * bytes, bytes / 4, seed_of(srcs[i]));
   }
-  const double sec = ms_total / 1e3 / iters;
   py::dict r;
   r["dst"] = dst_dev;
   r["srcs"] = srcs;
   r["bytes_per_src"] = bytes;
   r["iters"] = iters;
-  r["ms_per_iter"] = ms_total / iters;
-  r["gbps"] = (double)bytes * nsrc / sec / 1e9;
+  r["ms_per_iter"] = (double)ms / iters;
+  r["gbps"] = gbps((double)bytes * nsrc, ms, iters);
   r["ok"] = ok;
   return r;
 }
@@ -483,8 +495,7 @@ py::dict ring_bw(const std::vector<int>& devs, const std::vector<std::vector<int
   const int k = (int)devs.size();
   if (k < 2 || k > kMaxSrc + 1) throw std::invalid_argument("2..17 ring members");
   if ((int)peers.size() != k) throw std::invalid_argument("one peer list per member");
-  if (bytes < 16 || bytes % 16) throw std::invalid_argument("bytes must be a positive multiple of 16");
-  if (iters < 1) throw std::invalid_argument("iters >= 1");
+  check_bytes_iters(bytes, iters);
   int ndev = 0;
   HIP_CHECK(hipGetDeviceCount(&ndev));
   for (int d : devs)
@@ -506,33 +517,25 @@ py::dict ring_bw(const std::vector<int>& devs, const std::vector<std::vector<int
     for (int m = 0; m < k; ++m) {
       src.emplace_back(new DevBuf(devs[m], bytes));
       inbox.emplace_back(new DevBuf(devs[m], bytes * peers[m].size()));
-      DeviceGuard g(devs[m]);
-      hipLaunchKernelGGL(fill_pattern_kernel, dim3(num_cus(devs[m]) * 4), dim3(kBlock), 0, 0, (unsigned int*)src[m]->p,
-                         bytes / 4, seed_of(m));
-      HIP_CHECK(hipGetLastError());
-      HIP_CHECK(hipDeviceSynchronize());
+      fill_pattern(devs[m], src[m]->p, bytes, seed_of(m));
     }
     std::vector<SrcSet> sets(k);
     std::vector<int> grid(k);
-    std::vector<hipStream_t> st(k, nullptr);
-    std::vector<hipEvent_t> e0(k, nullptr), e1(k, nullptr);
+    std::vector<std::unique_ptr<TimedStream>> ts;
     for (int m = 0; m < k; ++m) {
       const int ns = (int)peers[m].size();
       for (int i = 0; i < ns; ++i) sets[m].p[i] = reinterpret_cast<const u32x4*>(src[peers[m][i]]->p);
       // members sharing a device split its CUs, so the self-test does not oversubscribe one GPU
       int share = 0;
       for (int d : devs) share += (d == devs[m]);
-      const int per = std::max(1, num_cus(devs[m]) * std::max(1, blocks_per_cu) / (ns * share));
-      grid[m] = per * ns;
+      grid[m] = gather_grid(devs[m], blocks_per_cu, ns, share);
       DeviceGuard g(devs[m]);
-      HIP_CHECK(hipStreamCreateWithFlags(&st[m], hipStreamNonBlocking));
-      HIP_CHECK(hipEventCreate(&e0[m]));
-      HIP_CHECK(hipEventCreate(&e1[m]));
+      ts.emplace_back(new TimedStream());
     }
     auto launch_round = [&]() {
       for (int m = 0; m < k; ++m) {
         DeviceGuard g(devs[m]);
-        hipLaunchKernelGGL(gather_lds_kernel, dim3(grid[m]), dim3(kBlock), 0, st[m], sets[m], (int)peers[m].size(),
+        hipLaunchKernelGGL(gather_lds_kernel, dim3(grid[m]), dim3(kBlock), 0, ts[m]->s, sets[m], (int)peers[m].size(),
                            (u32x4*)inbox[m]->p, bytes / 16);
         HIP_CHECK(hipGetLastError());
       }
@@ -540,7 +543,7 @@ py::dict ring_bw(const std::vector<int>& devs, const std::vector<std::vector<int
     auto sync_all = [&]() {
       for (int m = 0; m < k; ++m) {
         DeviceGuard g(devs[m]);
-        HIP_CHECK(hipStreamSynchronize(st[m]));
+        HIP_CHECK(hipStreamSynchronize(ts[m]->s));
       }
     };
     for (int i = 0; i < warmup; ++i) launch_round();
@@ -548,41 +551,24 @@ py::dict ring_bw(const std::vector<int>& devs, const std::vector<std::vector<int
     auto t0 = std::chrono::steady_clock::now();
     for (int m = 0; m < k; ++m) {
       DeviceGuard g(devs[m]);
-      HIP_CHECK(hipEventRecord(e0[m], st[m]));
+      ts[m]->begin();
     }
     for (int i = 0; i < iters; ++i) launch_round();
     for (int m = 0; m < k; ++m) {
       DeviceGuard g(devs[m]);
-      HIP_CHECK(hipEventRecord(e1[m], st[m]));
+      ts[m]->end();
     }
     sync_all();
     wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     for (int m = 0; m < k; ++m) {
       DeviceGuard g(devs[m]);
-      float ms = 0.f;
-      HIP_CHECK(hipEventElapsedTime(&ms, e0[m], e1[m]));
-      ms_member[m] = ms;
-      (void)hipEventDestroy(e0[m]);
-      (void)hipEventDestroy(e1[m]);
-      (void)hipStreamDestroy(st[m]);
+      ms_member[m] = ts[m]->ms();
     }
-    // every inbox segment holds its peer's pattern (head and tail windows)
-    const size_t words = bytes / 4, win = std::min<size_t>(words, 1 << 14);
-    std::vector<unsigned int> h(win);
-    for (int m = 0; m < k && ok; ++m) {
-      DeviceGuard g(devs[m]);
-      for (size_t i = 0; i < peers[m].size() && ok; ++i) {
-        const unsigned int seed = seed_of(peers[m][i]);
-        for (size_t st0 : {(size_t)0, words - win}) {
-          HIP_CHECK(hipMemcpy(h.data(), (const unsigned int*)inbox[m]->p + i * words + st0, win * 4, hipMemcpyDeviceToHost));
-          for (size_t w = 0; w < win; ++w)
-            if (h[w] != ((unsigned int)((st0 + w) * 2654435761u) ^ seed)) {
-              ok = false;
-              break;
-            }
-        }
-      }
-    }
+    ts.clear();
+    // every inbox segment holds its peer's pattern
+    for (int m = 0; m < k && ok; ++m)
+      for (size_t i = 0; i < peers[m].size() && ok; ++i)
+        ok = holds_pattern(devs[m], (const char*)inbox[m]->p + i * bytes, bytes / 4, seed_of(peers[m][i]));
   }
   py::dict r;
   std::vector<double> gbps(k);
@@ -629,6 +615,7 @@ py::dict copy_bw(int src_dev, int dst_dev, int exec_dev, size_t bytes, int iters
   return to_dict(c);
 }
 
+// On the null stream, which every other stream of the device waits for: lifts the whole device's clocks.
 py::dict mfma_warmup(int dev, double target_ms, int iters_per_launch, bool random_operands) {
   py::gil_scoped_release nogil_outer;
   DeviceGuard g(dev);
@@ -637,12 +624,10 @@ py::dict mfma_warmup(int dev, double target_ms, int iters_per_launch, bool rando
   const int grid = num_cus(dev) * 4;  // 16 waves per CU = 4 per SIMD
   DevBuf out(dev, (size_t)grid * kBlock * sizeof(float));
   hipEvent_t e0, e1;
-  HIP_CHECK(hipEventCreate(&e0));
-  HIP_CHECK(hipEventCreate(&e1));
+  for (hipEvent_t* e : {&e0, &e1}) HIP_CHECK(hipEventCreate(e));
   int launches = 0;
   float total_ms = 0.f;
   auto t0 = std::chrono::steady_clock::now();
-  HIP_CHECK(hipEventRecord(e0, 0));
   do {
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, 0, (float*)out.p, iters_per_launch);
     HIP_CHECK(hipGetLastError());
@@ -758,11 +743,9 @@ py::dict xcc_census(int dev, int blocks) {
 class IpcBuffer {
  public:
   IpcBuffer(int dev, size_t bytes, unsigned int seed) : buf_(dev, bytes), seed_(seed) {
-    if (bytes < 16 || bytes % 16) throw std::invalid_argument("bytes must be a positive multiple of 16");
+    check_bytes_iters(bytes);
+    fill_pattern(dev, buf_.p, bytes, seed);
     DeviceGuard g(dev);
-    hipLaunchKernelGGL(fill_pattern_kernel, dim3(num_cus(dev) * 4), dim3(kBlock), 0, 0, (unsigned int*)buf_.p, bytes / 4, seed);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipDeviceSynchronize());
     HIP_CHECK(hipIpcGetMemHandle(&h_, buf_.p));
   }
   py::bytes handle() const { return py::bytes(reinterpret_cast<const char*>(&h_), sizeof(h_)); }
@@ -771,7 +754,7 @@ class IpcBuffer {
   // After a peer wrote into this buffer through its mapping (K2 over IPC): does it hold pattern(seed)?
   bool holds(unsigned int seed) const {
     py::gil_scoped_release nogil;
-    return verify_pattern(buf_, buf_.bytes / 4, seed);
+    return holds_pattern(buf_.dev, buf_.p, buf_.bytes / 4, seed);
   }
 
  private:
@@ -802,45 +785,19 @@ struct IpcMappings {
   IpcMappings& operator=(const IpcMappings&) = delete;
 };
 
-// Event-timed `iters` launches of `launch` on a fresh non-blocking stream (after `warmup` untimed).
-template <class F>
-float time_launches(F launch, int iters, int warmup) {
-  hipStream_t s;
-  HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  hipEvent_t e0, e1;
-  HIP_CHECK(hipEventCreate(&e0));
-  HIP_CHECK(hipEventCreate(&e1));
-  for (int i = 0; i < warmup; ++i) launch(s);
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipEventRecord(e0, s));
-  for (int i = 0; i < iters; ++i) launch(s);
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipEventRecord(e1, s));
-  HIP_CHECK(hipEventSynchronize(e1));
-  float ms = 0.f;
-  HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  (void)hipStreamDestroy(s);
-  return ms;
-}
-
 // K2 over IPC: the writer's kernel pushes a local patterned buffer into another process's buffer
 // through the imported mapping (remote stores, the direction RCCL's P2P write protocol uses).  The
 // owner checks the result (IpcBuffer.holds), since only it knows the write has landed in its memory.
 py::dict ipc_write_bw(const py::bytes& handle, int dev, size_t bytes, unsigned int seed, int iters, int warmup,
                       int blocks_per_cu) {
-  if (bytes < 16 || bytes % 16) throw std::invalid_argument("bytes must be a positive multiple of 16");
-  if (iters < 1) throw std::invalid_argument("iters >= 1");
+  check_bytes_iters(bytes, iters);
   IpcMappings map({handle}, dev);
   float ms = 0.f;
   {
     py::gil_scoped_release nogil;
     DeviceGuard g(dev);
     DevBuf src(dev, bytes);
-    hipLaunchKernelGGL(fill_pattern_kernel, dim3(num_cus(dev) * 4), dim3(kBlock), 0, 0, (unsigned int*)src.p, bytes / 4, seed);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipDeviceSynchronize());
+    fill_pattern(dev, src.p, bytes, seed);
     const int grid = num_cus(dev) * std::max(1, blocks_per_cu);
     ms = time_launches([&](hipStream_t s) { launch_copy("lds", true, src.p, map.p[0], bytes / 16, grid, s); }, iters, warmup);
   }
@@ -849,7 +806,7 @@ py::dict ipc_write_bw(const py::bytes& handle, int dev, size_t bytes, unsigned i
   d["bytes"] = bytes;
   d["iters"] = iters;
   d["ms_per_iter"] = ms / iters;
-  d["gbps"] = (double)bytes / (ms / 1e3 / iters) / 1e9;
+  d["gbps"] = gbps((double)bytes, ms, iters);
   return d;
 }
 
@@ -860,8 +817,7 @@ py::dict ipc_gather_bw(const std::vector<py::bytes>& handles, int dev, size_t by
   const int nsrc = (int)handles.size();
   if (nsrc < 1 || nsrc > kMaxSrc) throw std::invalid_argument("1..16 handles");
   if (seeds.size() != handles.size()) throw std::invalid_argument("one seed per handle");
-  if (bytes < 16 || bytes % 16) throw std::invalid_argument("bytes must be a positive multiple of 16");
-  if (iters < 1) throw std::invalid_argument("iters >= 1");
+  check_bytes_iters(bytes, iters);
   IpcMappings map(handles, dev);
   float ms = 0.f;
   bool ok = true;
@@ -871,22 +827,12 @@ py::dict ipc_gather_bw(const std::vector<py::bytes>& handles, int dev, size_t by
     SrcSet set{};
     for (int i = 0; i < nsrc; ++i) set.p[i] = reinterpret_cast<const u32x4*>(map.p[i]);
     DevBuf inbox(dev, bytes * (size_t)nsrc);
-    const int per = std::max(1, num_cus(dev) * std::max(1, blocks_per_cu) / nsrc);
-    const int grid = per * nsrc;  // every source gets the same block count
+    const int grid = gather_grid(dev, blocks_per_cu, nsrc);
     ms = time_launches([&](hipStream_t s) {
       hipLaunchKernelGGL(gather_lds_kernel, dim3(grid), dim3(kBlock), 0, s, set, nsrc, (u32x4*)inbox.p, bytes / 16);
     }, iters, warmup);
-    const size_t words = bytes / 4, win = std::min<size_t>(words, 1 << 14);
-    std::vector<unsigned int> h(win);
     for (int i = 0; i < nsrc && ok; ++i)
-      for (size_t st0 : {(size_t)0, words / 2 - std::min(words / 2, win / 2), words - win}) {
-        HIP_CHECK(hipMemcpy(h.data(), (const unsigned int*)inbox.p + (size_t)i * words + st0, win * 4, hipMemcpyDeviceToHost));
-        for (size_t w = 0; w < win; ++w)
-          if (h[w] != ((unsigned int)((st0 + w) * 2654435761u) ^ seeds[i])) {
-            ok = false;
-            break;
-          }
-      }
+      ok = holds_pattern(dev, (const char*)inbox.p + (size_t)i * bytes, bytes / 4, seeds[i]);
   }
   py::dict d;
   d["dev"] = dev;
@@ -894,51 +840,31 @@ py::dict ipc_gather_bw(const std::vector<py::bytes>& handles, int dev, size_t by
   d["bytes_per_segment"] = bytes;
   d["iters"] = iters;
   d["ms_per_iter"] = ms / iters;
-  d["gbps"] = (double)bytes * nsrc / (ms / 1e3 / iters) / 1e9;
+  d["gbps"] = gbps((double)bytes * nsrc, ms, iters);
   d["ok"] = ok;
   return d;
 }
 
 py::dict ipc_read_bw(const py::bytes& handle, int dev, size_t bytes, unsigned int seed, int iters, int warmup,
                      int blocks_per_cu) {
-  const std::string raw = handle;
-  if (raw.size() != sizeof(hipIpcMemHandle_t)) throw std::invalid_argument("not a hipIpcMemHandle_t");
-  if (bytes < 16 || bytes % 16) throw std::invalid_argument("bytes must be a positive multiple of 16");
-  if (iters < 1) throw std::invalid_argument("iters >= 1");
-  hipIpcMemHandle_t h;
-  std::memcpy(&h, raw.data(), sizeof(h));
-  DeviceGuard g(dev);
-  void* src = nullptr;
-  HIP_CHECK(hipIpcOpenMemHandle(&src, h, hipIpcMemLazyEnablePeerAccess));
-  struct Closer {
-    void* p;
-    ~Closer() { (void)hipIpcCloseMemHandle(p); }
-  } closer{src};
-  DevBuf dst(dev, bytes);
-  const size_t n_vec = bytes / 16;
-  const int grid = num_cus(dev) * std::max(1, blocks_per_cu);
-  hipStream_t s;
-  HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  hipEvent_t e0, e1;
-  HIP_CHECK(hipEventCreate(&e0));
-  HIP_CHECK(hipEventCreate(&e1));
-  for (int i = 0; i < warmup; ++i) launch_copy("lds", true, src, dst.p, n_vec, grid, s);
-  HIP_CHECK(hipEventRecord(e0, s));
-  for (int i = 0; i < iters; ++i) launch_copy("lds", true, src, dst.p, n_vec, grid, s);
-  HIP_CHECK(hipEventRecord(e1, s));
-  HIP_CHECK(hipEventSynchronize(e1));
+  check_bytes_iters(bytes, iters);
+  IpcMappings map({handle}, dev);
   float ms = 0.f;
-  HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-  HIP_CHECK(hipEventDestroy(e0));
-  HIP_CHECK(hipEventDestroy(e1));
-  HIP_CHECK(hipStreamDestroy(s));
-  const bool ok = verify_pattern(dst, bytes / 4, seed);
+  bool ok = true;
+  {
+    py::gil_scoped_release nogil;
+    DeviceGuard g(dev);
+    DevBuf dst(dev, bytes);
+    const int grid = num_cus(dev) * std::max(1, blocks_per_cu);
+    ms = time_launches([&](hipStream_t s) { launch_copy("lds", true, map.p[0], dst.p, bytes / 16, grid, s); }, iters, warmup);
+    ok = holds_pattern(dev, dst.p, bytes / 4, seed);
+  }
   py::dict d;
   d["dev"] = dev;
   d["bytes"] = bytes;
   d["iters"] = iters;
   d["ms_per_iter"] = ms / iters;
-  d["gbps"] = (double)bytes / (ms / 1e3 / iters) / 1e9;
+  d["gbps"] = gbps((double)bytes, ms, iters);
   d["ok"] = ok;
   return d;
 }

@@ -22,15 +22,18 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "../common/stream_copy.h"
+
 namespace gtk {
 
-typedef unsigned int sc_u32x4 __attribute__((ext_vector_type(4)));
-
+// Equal to the probe's kBlock / kUnroll / kBlocksPerCU today, but tuned on their own (these on the
+// 2 GiB headline, the probe's on its LDS budget): kept separate on purpose.
 constexpr int kSelfCopyBlock = 256;
 constexpr int kSelfCopyUnroll = 4;
 constexpr int kSelfCopyBlocksPerCU = 8;
 constexpr size_t kSelfCopyTileVec = (size_t)kSelfCopyBlock * kSelfCopyUnroll;  // 16-byte vectors per tile
-constexpr size_t kSelfCopyTileBytes = kSelfCopyTileVec * sizeof(sc_u32x4);     // 16 KiB
+constexpr size_t kSelfCopyTileBytes = kSelfCopyTileVec * sizeof(u32x4);        // 16 KiB
+static_assert(kSelfCopyBlock == kStreamBlock, "stream_copy.h indexes blocks of kStreamBlock threads");
 
 // Messages below this many bytes stay with ncclAllReduce (RankState::self_copy_min's default).
 // Measured from Comm.step() with bench/allreduce_k1_ab.py, GB/s copied, median of 5 alternating runs,
@@ -46,28 +49,14 @@ constexpr size_t kSelfCopyMinBytes = (size_t)256 << 20;
 // `src` and `dst` are 16-byte aligned and do not overlap; `bytes` is a multiple of 2.
 __global__ __launch_bounds__(kSelfCopyBlock) void gtk_self_copy_kernel(const void* __restrict__ src_,
                                                                         void* __restrict__ dst_, size_t bytes) {
-  const sc_u32x4* __restrict__ src = static_cast<const sc_u32x4*>(src_);
-  sc_u32x4* __restrict__ dst = static_cast<sc_u32x4*>(dst_);
-  const size_t n_vec = bytes / sizeof(sc_u32x4);
-  const size_t n_tiles = n_vec / kSelfCopyTileVec;
-  const size_t per = (n_tiles + gridDim.x - 1) / gridDim.x;
-  const size_t t0 = (size_t)blockIdx.x * per;
-  const size_t t1 = std::min(n_tiles, t0 + per);
-  for (size_t t = t0; t < t1; ++t) {
-    const size_t base = t * kSelfCopyTileVec + threadIdx.x;
-    sc_u32x4 r[kSelfCopyUnroll];
-#pragma unroll
-    for (int u = 0; u < kSelfCopyUnroll; ++u) r[u] = __builtin_nontemporal_load(src + base + (size_t)u * kSelfCopyBlock);
-#pragma unroll
-    for (int u = 0; u < kSelfCopyUnroll; ++u) __builtin_nontemporal_store(r[u], dst + base + (size_t)u * kSelfCopyBlock);
-  }
-  // under one tile of whole vectors
-  for (size_t i = n_tiles * kSelfCopyTileVec + (size_t)blockIdx.x * kSelfCopyBlock + threadIdx.x; i < n_vec;
-       i += (size_t)gridDim.x * kSelfCopyBlock)
-    dst[i] = src[i];
+  const u32x4* __restrict__ src = static_cast<const u32x4*>(src_);
+  u32x4* __restrict__ dst = static_cast<u32x4*>(dst_);
+  const size_t n_vec = bytes / sizeof(u32x4);
+  const size_t first = stream_slices<kSelfCopyUnroll>(src, dst, n_vec, blockIdx.x, gridDim.x);
+  stream_vec_tail(src, dst, n_vec, first, blockIdx.x, gridDim.x);
   // under one vector, in 2-byte units
   if (blockIdx.x == 0) {
-    const size_t done = n_vec * sizeof(sc_u32x4);
+    const size_t done = n_vec * sizeof(u32x4);
     const size_t units = (bytes - done) / sizeof(uint16_t);
     if (threadIdx.x < units) {
       const uint16_t* s = reinterpret_cast<const uint16_t*>(static_cast<const char*>(src_) + done);

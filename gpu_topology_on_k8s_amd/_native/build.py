@@ -119,6 +119,7 @@ class Target:
 
 def targets() -> List[Target]:
     rocm_lib = str(ROCM / "lib")
+    stream_copy = CSRC / "common" / "stream_copy.h"  # the copy body the probe and the one-rank all-reduce share
     return [
         Target("_topo", [CSRC / "topo" / "topo_reader.cpp"], "gxx", HERE / f"_topo{EXT}", ["-ldl"]),
         # host-only sanitizer build of the sysfs reader; run by tests/test_topo_reader_asan.py
@@ -133,12 +134,13 @@ def targets() -> List[Target]:
         Target("engine_selftest", [CSRC / "placement" / "engine.cpp", CSRC / "placement" / "engine_selftest.cpp"], "gxx",
                HERE / "bin" / "engine_selftest", ["-g", "-O1", "-fsanitize=address,undefined", "-fno-omit-frame-pointer"],
                deps=[CSRC / "placement" / "engine.h"], pybind=False, shared=False),
-        Target("_probe", [CSRC / "probe" / "probe.hip"], "hipcc", HERE / f"_probe{EXT}"),
+        Target("_probe", [CSRC / "probe" / "probe.hip"], "hipcc", HERE / f"_probe{EXT}", deps=[stream_copy]),
         Target("_rccl", [CSRC / "rccl" / "rccl_module.hip"], "hipcc", HERE / f"_rccl{EXT}",
-               [f"-L{rocm_lib}", "-lrccl", f"-Wl,-rpath,{rocm_lib}"], deps=[CSRC / "rccl" / "rccl_core.h", CSRC / "rccl" / "self_copy.h"]),
+               [f"-L{rocm_lib}", "-lrccl", f"-Wl,-rpath,{rocm_lib}"],
+               deps=[CSRC / "rccl" / "rccl_core.h", CSRC / "rccl" / "self_copy.h", stream_copy]),
         Target("rccl_allreduce_bench", [CSRC / "rccl" / "rccl_allreduce_bench.hip"], "hipcc",
                HERE / "bin" / "rccl_allreduce_bench", [f"-L{rocm_lib}", "-lrccl", f"-Wl,-rpath,{rocm_lib}"],
-               deps=[CSRC / "rccl" / "rccl_core.h", CSRC / "rccl" / "self_copy.h"], pybind=False, shared=False),
+               deps=[CSRC / "rccl" / "rccl_core.h", CSRC / "rccl" / "self_copy.h", stream_copy], pybind=False, shared=False),
         # container-side tier of a time-sliced share (Gaia vGPU): HBM cap + forced CU mask, preloaded into
         # the pod by Allocate (--share-guard); host-only C++, resolves the real HIP entry points at run time
         Target("vgpu_guard", [CSRC / "vgpu" / "vgpu_guard.cpp"], "gxx", HERE / "bin" / "libgtk_vgpu.so",

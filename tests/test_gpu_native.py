@@ -72,6 +72,33 @@ def test_copy_odd_size_tail(probe_mod):
     assert r["ok"], r
 
 
+# (kind, nontemporal, 16-byte vectors per lane and tile)
+COPY_KINDS = [("lds", False, 4), ("lds", True, 4), ("reg", False, 4), ("reg", True, 4), ("chunk4", True, 4),
+              ("chunk", True, 8)]
+
+
+@pytest.mark.parametrize("kind,nontemporal,unroll", COPY_KINDS)
+def test_copy_kinds_at_boundary_shapes(probe_mod, kind, nontemporal, unroll):
+    """Every copy kernel at one block per CU, on the sizes at which its slicing can go wrong: no whole
+    tile (the vector tail alone), fewer tiles than blocks (most blocks get an empty slice), and more
+    than one tile per block with a ragged last slice.  ``ok`` checks every word of the destination."""
+    from gpu_topology_on_k8s_amd.ops.probe import copy_bw
+
+    tile = 256 * unroll * 16
+    grid = probe_mod.device_props(0)["cus"]
+    tail = 16 * 37
+    for nbytes in (tail, 3 * tile + tail, (2 * grid + 5) * tile + tail):
+        r = copy_bw(0, 0, nbytes, iters=1, warmup_iters=0, kind=kind, nontemporal=nontemporal, blocks_per_cu=1)
+        assert r["ok"], r
+        assert r["bytes"] == nbytes and r["grid"] == grid, r
+
+
+def test_pattern_verifier_is_not_vacuous(probe_mod):
+    b = probe_mod.IpcBuffer(0, (1 << 20) + 16, seed=0x5EED)
+    assert b.holds(0x5EED)
+    assert not b.holds(0x5EED ^ 1)
+
+
 def test_gather_kernel_segments(probe_mod):
     """K5 gather: three source buffers streamed by one launch land in their own dst segments (the
     sources are local here; on a node they are the peers, same kernel); odd size exercises tails."""
