@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Producer-written transposes vs a separate transpose pass, at the Llama-3-8B b4 x 4096 shapes
 (event-timed medians, interleaved):
-  swiglu forward   T 16384, F 14336: swiglu_fwd (+ transpose) vs swiglu_fwd_t (64x64) vs swiglu_fwd_t128
+  swiglu forward   T 16384, F 14336: swiglu_fwd (+ transpose) vs swiglu_fwd_t with 64x64 and 64x128 tiles
   xent backward    T 16384, V 128256: xent_bwd_inplace (+ transpose) vs xent_bwd_t
   RoPE backward    B 4, H 32, Hkv 8, S 4096: rope_split_bwd (+ transpose) vs rope_split_bwd_t
   attention fwd    B 4, H 32, Hkv 8, S 4096: attn_fwd (+ transpose of O) vs attn_fwd_t
@@ -39,8 +39,8 @@ def main():
     out["swiglu_fwd_ms"] = timed({
         "fwd": lambda: hip.swiglu_fwd(gu),
         "fwd+transpose": lambda: hip.transpose_bf16(hip.swiglu_fwd(gu)),
-        "fwd_t64": lambda: hip.swiglu_fwd_t(gu),
-        "fwd_t128": lambda: hip.swiglu_fwd_t128(gu),
+        "fwd_t64": lambda: hip.swiglu_fwd_t(gu, tile=64),
+        "fwd_t128": lambda: hip.swiglu_fwd_t(gu, tile=128),
     })
     del gu
     torch.cuda.empty_cache()

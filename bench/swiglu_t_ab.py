@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Interleaved A/B of the SwiGLU backward-with-transpose kernels at the Llama-3-8B shape
-(T 16384, F 14336): 64 x 64 tiles (swiglu_bwd_t) vs 64 x 128 (swiglu_bwd_t128); event-timed medians."""
+(T 16384, F 14336): swiglu_bwd_t with 64 x 64 tiles (tile=64) vs 64 x 128 (tile=128); event-timed medians."""
 import json
 import os
 import sys
@@ -16,7 +16,7 @@ def main():
     gu = torch.randn(T, 2 * F, device="cuda", dtype=torch.bfloat16)
     dh = torch.randn(T, F, device="cuda", dtype=torch.bfloat16)
     hip = fused.hip()
-    fns = {"t64": hip.swiglu_bwd_t, "t128": hip.swiglu_bwd_t128}
+    fns = {"t64": lambda d, g: hip.swiglu_bwd_t(d, g, tile=64), "t128": lambda d, g: hip.swiglu_bwd_t(d, g, tile=128)}
     for f in fns.values():
         f(dh, gu)
     times = {n: [] for n in fns}

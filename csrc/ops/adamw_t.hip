@@ -9,28 +9,20 @@
 //   adamw_tiles_kernel   one 64 x 256 tile of one projection matrix per loop trip (grid-stride over
 //                        every matrix's tiles: the persistent grid ends when the tile index passes the
 //                        total, so every wave exits).  The update walks 1 KiB row segments like the
-//                        flat kernel, stages the new bf16 rows in an XOR-swizzled LDS tile, and writes
-//                        8 consecutive rows of one column of W^T per 16-B store (conflict-free).
+//                        flat kernel, stages the new bf16 rows in the LDS tile of tile_t.h, and writes
+//                        W^T from it.
 //   adamw_ranges_kernel  the parameters that are not transposed (embedding, norms): blockIdx.y picks a
 //                        range, grid-stride over its 16-B vectors.
 // Both apply exactly adamw_body's arithmetic (csrc/ops/fused_ops.hip), in the same per-element order,
 // so the master/m/v/W bits equal the flat kernel's.  DEV = the graph-capturable form: bias
 // corrections and the clipping factor are derived on the device (adamw_dev_kernel's contract).
-#include <hip/hip_runtime.h>
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
-
-#include <cstdint>
 #include <vector>
+
+#include "tile_t.h"
 
 namespace gtk_adamw {
 
-typedef unsigned short u16;
-typedef u16 u16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float bf2f(u16 v) { return __uint_as_float((uint32_t)v << 16); }
-__device__ __forceinline__ u16 f2bf(float f) { return __builtin_bit_cast(u16, (__bf16)f); }
+using namespace gtk;
 
 struct Hyper {
   float lr, b1, b2, eps, wd, gs, bc1, bc2;
@@ -184,12 +176,9 @@ __global__ __launch_bounds__(256) void adamw_tiles_kernel(float* __restrict__ ma
                                                           const Mat* __restrict__ mats, int nmats, int64_t total_tiles,
                                                           const float* __restrict__ hp, const float* __restrict__ part, int nparts,
                                                           const float* __restrict__ tptr) {
-  // [row][16-B vector]: vector v of row r at slot v ^ ((r >> 3) & 7) -- the XOR touches the low 3 bits
-  // only, so a row's 32 vectors stay a permutation of its own 512 B
-  __shared__ u16x8 tile[kTR][kTC / 8];
+  __shared__ TileT<kTC / 8> tile;
   const Hyper h = hyper<DEV>(hp, part, nparts, tptr);
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const u16* lds = reinterpret_cast<const u16*>(&tile[0][0]);
+  const int t = threadIdx.x;
   for (int64_t ti = blockIdx.x; ti < total_tiles; ti += gridDim.x) {
     int lo = 0, hi = nmats - 1;  // last matrix whose tile_base <= ti (block-uniform)
     while (lo < hi) {
@@ -205,8 +194,7 @@ __global__ __launch_bounds__(256) void adamw_tiles_kernel(float* __restrict__ ma
 #pragma unroll 4
       for (int pass = 0; pass < kTR / 8; ++pass) {
         const int r = 8 * pass + (t >> 5), vv = t & 31;
-        const u16x8 wo = adam8(master, m, v, g, w, (size_t)(mt.off + (r0 + r) * mt.C + c0 + 8 * vv), h);
-        tile[r][vv ^ ((r >> 3) & 7)] = wo;
+        tile.put(r, vv, adam8(master, m, v, g, w, (size_t)(mt.off + (r0 + r) * mt.C + c0 + 8 * vv), h));
       }
     } else {  // kAhead passes' loads in flight before their stores
 #pragma unroll 1
@@ -220,25 +208,12 @@ __global__ __launch_bounds__(256) void adamw_tiles_kernel(float* __restrict__ ma
 #pragma unroll
         for (int u = 0; u < kAhead; ++u) {
           const int r = 8 * (p0 + u) + (t >> 5), vv = t & 31;
-          tile[r][vv ^ ((r >> 3) & 7)] = adam8_store(master, m, v, w, (size_t)(mt.off + (r0 + r) * mt.C + c0 + 8 * vv), in[u], h);
+          tile.put(r, vv, adam8_store(master, m, v, w, (size_t)(mt.off + (r0 + r) * mt.C + c0 + 8 * vv), in[u], h));
         }
       }
     }
     __syncthreads();
-    // transposed write: per instruction a wave takes one 16-B column vector vc (8 columns) x the 8
-    // row groups p, lanes (p, column & 7): the row groups sit on 8 different slots, the 8 columns in
-    // one slot's 4 dwords -- 32 banks, no conflicts; each output row gets 8 x 16 B = 128 B
-    const int p = lane >> 3, cl = lane & 7;
-#pragma unroll 4
-    for (int i = 0; i < kTC / 32; ++i) {
-      const int vc = 4 * i + wv;
-      const int c = 8 * vc + cl;
-      const int slot = vc ^ p;
-      u16x8 o;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] = lds[((8 * p + j) * (kTC / 8) + slot) * 8 + cl];
-      *reinterpret_cast<u16x8*>(wt + mt.toff + (c0 + c) * mt.R + r0 + 8 * p) = o;
-    }
+    tile.store_t(wt + mt.toff, (size_t)mt.R, (size_t)c0, (size_t)r0);  // W^T: 256 output rows x 128 B
     __syncthreads();  // the tile is free for the next trip
   }
 }
@@ -271,7 +246,7 @@ void launch(at::Tensor& master, at::Tensor& m, at::Tensor& v, const G* gp, at::T
     np = (int)part->numel();
   }
   const float* tp = dev ? t->data_ptr<float>() : nullptr;
-  hipStream_t s = at::hip::getCurrentHIPStream().stream();
+  hipStream_t s = cur_stream();
   auto* mp = master.data_ptr<float>();
   auto* mmp = m.data_ptr<float>();
   auto* vp = v.data_ptr<float>();

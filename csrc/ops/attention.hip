@@ -28,23 +28,19 @@
 //   * dQ: forward-shaped (query on the lane), dQ^T += K^T.dS^T accumulated in registers.
 // Earlier generations (forward v1 with one LDS buffer, backward v1 with fp32 dQ atomics, backward v2
 // with synchronous slice staging) were measured, retired, and live in git history before round 2.
-#include <hip/hip_runtime.h>
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
-
 #include <cmath>
-#include <cstdint>
+
+#include "bf16.h"
 
 namespace gtk_attn {
 
-typedef unsigned short u16;
-typedef u16 u16x8 __attribute__((ext_vector_type(8)));
+using namespace gtk;
+
 typedef u16 u16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int D = 128;
 constexpr int BQ = 128;  // forward: queries per workgroup
@@ -53,9 +49,6 @@ constexpr int KB = 128;  // backward: keys per workgroup
 constexpr int QT = 32;   // backward: queries per slice
 
 #define LDS_AS __attribute__((address_space(3)))
-
-__device__ __forceinline__ float bf2f(u16 v) { return __uint_as_float((uint32_t)v << 16); }
-__device__ __forceinline__ u16 f2bf(float f) { return __builtin_bit_cast(u16, (__bf16)f); }
 
 // byte offset of 16-B chunk `ch` of row `row` in a [rows][128 x bf16] swizzled image
 __device__ __forceinline__ int swz(int row, int ch) { return row * 256 + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
@@ -769,10 +762,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq2n_kernel(const u16* __rest
 }
 
 // ==================================================================================== host
-hipStream_t cur_stream() { return at::hip::getCurrentHIPStream().stream(); }
-const u16* bp(const at::Tensor& t) { return reinterpret_cast<const u16*>(t.data_ptr()); }
-u16* bpm(at::Tensor& t) { return reinterpret_cast<u16*>(t.data_ptr()); }
-
 void check_qkv(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v) {
   for (const at::Tensor* x : {&q, &k, &v})
     TORCH_CHECK(x->is_cuda() && x->scalar_type() == at::kBFloat16 && x->is_contiguous() && x->dim() == 4,

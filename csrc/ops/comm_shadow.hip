@@ -16,16 +16,11 @@
 // Timing: wall_clock64() is the 100 MHz constant clock (s_memrealtime), so the pacing does not drift
 // with the shader clock.  Every workgroup exits once its last chunk's deadline has passed: the loop is
 // bounded by `chunks` and the deadline is finite, so the grid always drains.
-#include <hip/hip_runtime.h>
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
-
-#include <cstdint>
+#include "bf16.h"
 
 namespace gtk_shadow {
 
-typedef unsigned short u16;
-typedef u16 u16x8 __attribute__((ext_vector_type(8)));
+using namespace gtk;
 
 __global__ __launch_bounds__(256) void comm_shadow_kernel(const u16x8* __restrict__ src, u16x8* __restrict__ dst,
                                                           int64_t vec_per_chunk, int chunks, int64_t ticks_per_chunk) {
@@ -49,7 +44,7 @@ void comm_shadow(const at::Tensor& src, at::Tensor& dst, int64_t bytes, int64_t 
   const int chunks = 16;
   const int64_t vec_per_chunk = bytes / 16 / ctas / chunks;
   const int64_t ticks = (int64_t)(micros * 100.0 / chunks);  // 100 MHz wall clock
-  hipLaunchKernelGGL(comm_shadow_kernel, dim3((unsigned)ctas), dim3(256), 0, at::hip::getCurrentHIPStream().stream(),
+  hipLaunchKernelGGL(comm_shadow_kernel, dim3((unsigned)ctas), dim3(256), 0, cur_stream(),
                      reinterpret_cast<const u16x8*>(src.data_ptr()), reinterpret_cast<u16x8*>(dst.data_ptr()), vec_per_chunk,
                      chunks, ticks);
 }

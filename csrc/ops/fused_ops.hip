@@ -17,21 +17,15 @@
 //   adamw_step_dev /            the graph-capturable pair: step count, bias corrections and the
 //   sq_norm_parts               clipping factor live on the device (2 launches per optimizer step)
 //   mnist_synth                 the MNIST workload's synthetic batch, one launch, device-indexed
+//   rope_split_bwd_t, swiglu_fwd_t / _bwd_t, xent_bwd_t
+//                               the same arithmetic bodies as the flat kernels, and the output's
+//                               transpose written from an LDS tile (tile_t.h) for the NT-layout GEMMs
 // All math in fp32, bf16 storage.  Wave size 64 everywhere (gfx950).
-#include <hip/hip_runtime.h>
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
-
-#include <cstdint>
+#include "tile_t.h"
 
 namespace {
 
-typedef unsigned short u16;
-typedef u16 u16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float bf2f(u16 v) { return __uint_as_float((uint32_t)v << 16); }
-__device__ __forceinline__ u16 f2bf(float f) { return __builtin_bit_cast(u16, (__bf16)f); }
+using namespace gtk;
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -44,14 +38,8 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
-hipStream_t cur_stream() { return at::hip::getCurrentHIPStream().stream(); }
-
-#define CHECK_BF16(t) TORCH_CHECK((t).is_cuda() && (t).scalar_type() == at::kBFloat16 && (t).is_contiguous(), #t " must be a contiguous bf16 GPU tensor")
 #define CHECK_GRAD(t) TORCH_CHECK((t).is_cuda() && ((t).scalar_type() == at::kBFloat16 || (t).scalar_type() == at::kFloat) && (t).is_contiguous(), #t " must be a contiguous bf16 or fp32 GPU tensor")
 #define CHECK_F32(t) TORCH_CHECK((t).is_cuda() && (t).scalar_type() == at::kFloat && (t).is_contiguous(), #t " must be a contiguous fp32 GPU tensor")
-
-const u16* bp(const at::Tensor& t) { return reinterpret_cast<const u16*>(t.data_ptr()); }
-u16* bpm(at::Tensor& t) { return reinterpret_cast<u16*>(t.data_ptr()); }
 
 // =============================================================================== RMSNorm
 // One wave per row; lane l owns vectors c = i*64 + l (8 bf16 each).  NV = ceil(D / 512).
@@ -363,6 +351,25 @@ std::vector<at::Tensor> rmsnorm_bwd_impl(const at::Tensor& dy, const at::Tensor&
 //   out[i] = x[i]*cos - x[i+Dh/2]*sin ; out[i+Dh/2] = x[i+Dh/2]*cos + x[i]*sin
 // cos/sin tables: fp32 [S_max, Dh/2].  One thread = 8 consecutive pairs of one (token, head).
 // Backward (inverse=true) maps dq/dk/dv back to dqkv with the transposed rotation (sin -> -sin).
+
+// 8 pairs (lo[j], hi[j]) = (x[i0 + j], x[half + i0 + j]) of one head at position pos, rotated
+template <bool kInverse>
+__device__ __forceinline__ void rope_rotate8(const float* __restrict__ cosb, const float* __restrict__ sinb, size_t pos,
+                                             int half, int i0, u16x8 lo, u16x8 hi, u16x8& olo, u16x8& ohi) {
+  const float* cr = cosb + pos * half + i0;
+  const float* sr = sinb + pos * half + i0;
+  f32x4 c0 = *reinterpret_cast<const f32x4*>(cr), c1 = *reinterpret_cast<const f32x4*>(cr + 4);
+  f32x4 s0 = *reinterpret_cast<const f32x4*>(sr), s1 = *reinterpret_cast<const f32x4*>(sr + 4);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float c = j < 4 ? c0[j] : c1[j - 4];
+    const float sn = (j < 4 ? s0[j] : s1[j - 4]) * (kInverse ? -1.f : 1.f);
+    const float a = bf2f(lo[j]), bb = bf2f(hi[j]);
+    olo[j] = f2bf(a * c - bb * sn);
+    ohi[j] = f2bf(bb * c + a * sn);
+  }
+}
+
 template <bool kInverse>
 __global__ __launch_bounds__(256) void rope_split_kernel(u16* __restrict__ qkv, u16* __restrict__ q, u16* __restrict__ k,
                                                          u16* __restrict__ v, const float* __restrict__ cosb,
@@ -397,19 +404,8 @@ __global__ __launch_bounds__(256) void rope_split_kernel(u16* __restrict__ qkv, 
       *reinterpret_cast<u16x8*>(ta + half + i0) = hi;
       continue;
     }
-    const float* cr = cosb + (size_t)(s + pos_offset) * half + i0;
-    const float* sr = sinb + (size_t)(s + pos_offset) * half + i0;
-    f32x4 c0 = *reinterpret_cast<const f32x4*>(cr), c1 = *reinterpret_cast<const f32x4*>(cr + 4);
-    f32x4 s0 = *reinterpret_cast<const f32x4*>(sr), s1 = *reinterpret_cast<const f32x4*>(sr + 4);
     u16x8 olo, ohi;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float c = j < 4 ? c0[j] : c1[j - 4];
-      const float sn = (j < 4 ? s0[j] : s1[j - 4]) * (kInverse ? -1.f : 1.f);
-      const float a = bf2f(lo[j]), bb = bf2f(hi[j]);
-      olo[j] = f2bf(a * c - bb * sn);
-      ohi[j] = f2bf(bb * c + a * sn);
-    }
+    rope_rotate8<kInverse>(cosb, sinb, (size_t)(s + pos_offset), half, i0, lo, hi, olo, ohi);
     *reinterpret_cast<u16x8*>(ta + i0) = olo;
     *reinterpret_cast<u16x8*>(ta + half + i0) = ohi;
   }
@@ -456,17 +452,16 @@ at::Tensor rope_split_bwd(const at::Tensor& dq, const at::Tensor& dk, const at::
 // RoPE backward with a transposed copy: dqkv^T [(H+2Hkv)*128, B*S] is the A operand of the QKV
 // weight-gradient GEMM in NT layout, written from the LDS tile instead of by a transpose pass that
 // re-reads dqkv.  One 256-thread block = 64 tokens x one head (head dim 128): a thread takes 8
-// rotation pairs (lo = x[8v..8v+7], hi = x[64+8v..]) of one token, the tile is staged in LDS with the
-// swiglu_bwd_t128 swizzle and written as 128-B segments of the transposed rows.  Same expressions as
-// rope_split_kernel<true> (bit-identical dqkv).  S multiple of 64.
+// rotation pairs (lo = x[8v..8v+7], hi = x[64+8v..]) of one token and puts both vectors in the 64 x 128
+// tile (tile_t.h).  S multiple of 64.
 __global__ __launch_bounds__(256) void rope_bwd_t_kernel(u16* __restrict__ dqkv, u16* __restrict__ dqkvT,
                                                          const u16* __restrict__ q, const u16* __restrict__ k,
                                                          const u16* __restrict__ v, const float* __restrict__ cosb,
                                                          const float* __restrict__ sinb, int B, int S, int H, int Hkv,
                                                          int pos_offset) {
   constexpr int Dh = 128, half = 64;
-  __shared__ u16x8 tile[64][16];
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  __shared__ TileT<16> tile;
+  const int t = threadIdx.x;
   const int hh = blockIdx.x, heads = H + 2 * Hkv;
   const size_t tok0 = (size_t)blockIdx.y * 64;  // never crosses a sequence (S % 64 == 0)
   const int b = (int)(tok0 / S), s0 = (int)(tok0 % S);
@@ -475,7 +470,7 @@ __global__ __launch_bounds__(256) void rope_bwd_t_kernel(u16* __restrict__ dqkv,
   else if (hh < H + Hkv) src = k + (((size_t)b * Hkv + (hh - H)) * S + s0) * Dh;
   else src = v + (((size_t)b * Hkv + (hh - H - Hkv)) * S + s0) * Dh;
   const int vi = t & 7;
-  u16x8 lol[2], hil[2];  // both passes' loads first (as swiglu_bwd_t128_kernel)
+  u16x8 lol[2], hil[2];  // both passes' loads first (see swiglu_bwd_t_kernel)
 #pragma unroll
   for (int pass = 0; pass < 2; ++pass) {
     const u16* fa = src + (size_t)((t >> 3) + 32 * pass) * Dh;
@@ -493,39 +488,16 @@ __global__ __launch_bounds__(256) void rope_bwd_t_kernel(u16* __restrict__ dqkv,
       olo = lo;
       ohi = hi;
     } else {
-      const int sp = s0 + r;
-      const float* cr = cosb + (size_t)(sp + pos_offset) * half + i0;
-      const float* sr = sinb + (size_t)(sp + pos_offset) * half + i0;
-      f32x4 c0 = *reinterpret_cast<const f32x4*>(cr), c1 = *reinterpret_cast<const f32x4*>(cr + 4);
-      f32x4 sn0 = *reinterpret_cast<const f32x4*>(sr), sn1 = *reinterpret_cast<const f32x4*>(sr + 4);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float c = j < 4 ? c0[j] : c1[j - 4];
-        const float sn = (j < 4 ? sn0[j] : sn1[j - 4]) * -1.f;
-        const float a = bf2f(lo[j]), bb = bf2f(hi[j]);
-        olo[j] = f2bf(a * c - bb * sn);
-        ohi[j] = f2bf(bb * c + a * sn);
-      }
+      rope_rotate8<true>(cosb, sinb, (size_t)(s0 + r + pos_offset), half, i0, lo, hi, olo, ohi);
     }
     u16* ta = dqkv + (tok0 + r) * (size_t)heads * Dh + (size_t)hh * Dh;
     *reinterpret_cast<u16x8*>(ta + i0) = olo;
     *reinterpret_cast<u16x8*>(ta + half + i0) = ohi;
-    tile[r][vi ^ ((r >> 3) & 7)] = olo;
-    tile[r][(8 + vi) ^ ((r >> 3) & 7)] = ohi;
+    tile.put(r, vi, olo);
+    tile.put(r, 8 + vi, ohi);
   }
   __syncthreads();
-  const size_t BS = (size_t)B * S;
-  const int p = lane >> 3, cl = lane & 7;
-  const u16* lds = reinterpret_cast<const u16*>(&tile[0][0]);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int vc = 4 * i + wv;
-    const int c = 8 * vc + cl;
-    u16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = lds[((8 * p + j) * 16 + (vc ^ p)) * 8 + cl];
-    *reinterpret_cast<u16x8*>(dqkvT + ((size_t)hh * Dh + c) * BS + tok0 + 8 * p) = o;
-  }
+  tile.store_t(dqkvT, (size_t)B * S, (size_t)hh * Dh, tok0);
 }
 
 // rope_split_bwd that also returns dqkv^T [(H+2Hkv)*Dh, B*S]; head dim 128, S multiple of 64
@@ -553,6 +525,28 @@ std::vector<at::Tensor> rope_split_bwd_t(const at::Tensor& dq, const at::Tensor&
 
 // =============================================================================== SwiGLU
 // gu: [T, 2F] = [gate | up]; h = silu(g) * u : [T, F]
+__device__ __forceinline__ u16x8 swiglu_fwd8(u16x8 g, u16x8 u) {
+  u16x8 o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float gf = bf2f(g[j]);
+    o[j] = f2bf(gf / (1.f + __expf(-gf)) * bf2f(u[j]));
+  }
+  return o;
+}
+
+// d[gate], d[up] of 8 elements from dh = d
+__device__ __forceinline__ void swiglu_bwd8(u16x8 g, u16x8 u, u16x8 d, u16x8& og, u16x8& ou) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float gf = bf2f(g[j]), uf = bf2f(u[j]), df = bf2f(d[j]);
+    const float sg = 1.f / (1.f + __expf(-gf));
+    const float silu = gf * sg;
+    ou[j] = f2bf(df * silu);
+    og[j] = f2bf(df * uf * sg * (1.f + gf * (1.f - sg)));
+  }
+}
+
 __global__ __launch_bounds__(256) void swiglu_fwd_kernel(const u16* __restrict__ gu, u16* __restrict__ h, size_t T, int F) {
   const int fv = F >> 3;
   const size_t total = T * fv;
@@ -561,13 +555,7 @@ __global__ __launch_bounds__(256) void swiglu_fwd_kernel(const u16* __restrict__
     const int c = (int)(i % fv);
     const u16x8 g = reinterpret_cast<const u16x8*>(gu + t * 2 * F)[c];
     const u16x8 u = reinterpret_cast<const u16x8*>(gu + t * 2 * F + F)[c];
-    u16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float gf = bf2f(g[j]);
-      o[j] = f2bf(gf / (1.f + __expf(-gf)) * bf2f(u[j]));
-    }
-    reinterpret_cast<u16x8*>(h + t * F)[c] = o;
+    reinterpret_cast<u16x8*>(h + t * F)[c] = swiglu_fwd8(g, u);
   }
 }
 
@@ -582,246 +570,117 @@ __global__ __launch_bounds__(256) void swiglu_bwd_kernel(const u16* __restrict__
     const u16x8 u = reinterpret_cast<const u16x8*>(gu + t * 2 * F + F)[c];
     const u16x8 d = reinterpret_cast<const u16x8*>(dh + t * F)[c];
     u16x8 og, ou;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float gf = bf2f(g[j]), uf = bf2f(u[j]), df = bf2f(d[j]);
-      const float sg = 1.f / (1.f + __expf(-gf));
-      const float silu = gf * sg;
-      ou[j] = f2bf(df * silu);
-      og[j] = f2bf(df * uf * sg * (1.f + gf * (1.f - sg)));
-    }
+    swiglu_bwd8(g, u, d, og, ou);
     reinterpret_cast<u16x8*>(dgu + t * 2 * F)[c] = og;
     reinterpret_cast<u16x8*>(dgu + t * 2 * F + F)[c] = ou;
   }
 }
 
-// Backward with a second, transposed copy of the gradient: dguT [2F, T] is the A operand of the
-// w13 weight-gradient GEMM in NT layout (dW13 = dguT . hT^T), written here from the LDS tile instead
-// of by a separate transpose pass (saves re-reading the 2*T*F gradient).  One 256-thread block =
-// 64 tokens x 64 features: each thread computes 2 x 8 features of the gate AND up halves, stores
-// them row-major, stages both tiles in LDS (XOR-swizzled exactly like csrc/ops/transpose.hip) and
-// writes 2 x 8 tokens of a transposed row per tile.  T and F must be multiples of 64.
-__global__ __launch_bounds__(256) void swiglu_bwd_t_kernel(const u16* __restrict__ dh, const u16* __restrict__ gu,
-                                                           u16* __restrict__ dgu, u16* __restrict__ dguT, int T, int F) {
-  __shared__ u16x8 tile[2][64][8];  // [gate | up][token][feature vector]
-  const int t = threadIdx.x;
-  const size_t r0 = (size_t)blockIdx.y * 64, c0 = (size_t)blockIdx.x * 64;
-  const size_t F2 = 2 * (size_t)F;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int r = (t >> 3) + 32 * i, v = t & 7;
-    const size_t row = r0 + r;
-    const u16x8 g = *reinterpret_cast<const u16x8*>(gu + row * F2 + c0 + 8 * v);
-    const u16x8 u = *reinterpret_cast<const u16x8*>(gu + row * F2 + F + c0 + 8 * v);
-    const u16x8 d = *reinterpret_cast<const u16x8*>(dh + row * F + c0 + 8 * v);
-    u16x8 og, ou;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float gf = bf2f(g[j]), uf = bf2f(u[j]), df = bf2f(d[j]);
-      const float sg = 1.f / (1.f + __expf(-gf));
-      const float silu = gf * sg;  // same expression order as swiglu_bwd_kernel: identical rounding
-      ou[j] = f2bf(df * silu);
-      og[j] = f2bf(df * uf * sg * (1.f + gf * (1.f - sg)));
-    }
-    *reinterpret_cast<u16x8*>(dgu + row * F2 + c0 + 8 * v) = og;
-    *reinterpret_cast<u16x8*>(dgu + row * F2 + F + c0 + 8 * v) = ou;
-    tile[0][r][v ^ ((r >> 3) & 7)] = og;
-    tile[1][r][v ^ ((r >> 3) & 7)] = ou;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const u16* lds = reinterpret_cast<const u16*>(&tile[h][0][0]);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int idx = t + 256 * i;
-      const int c = idx >> 3, p = idx & 7;
-      const int pv = (c >> 3) ^ p;
-      u16x8 o;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] = lds[(8 * p + j) * 64 + pv * 8 + (c & 7)];
-      *reinterpret_cast<u16x8*>(dguT + ((size_t)h * F + c0 + c) * T + r0 + 8 * p) = o;
-    }
-  }
-}
-
-// Forward with a transposed copy of the output: hT [F, T] is the B operand of the w2 weight-gradient
-// GEMM in NT layout, written from the LDS tile here (Llama(transpose_x="forward")) instead of by a
-// transpose pass over the 2*T*F-byte output in the backward.  Same tiling and swizzle as
-// swiglu_bwd_t_kernel, same expression as swiglu_fwd_kernel (identical h bits).  T, F multiples of 64.
+// Forward and backward with a second, transposed copy of the output, written from the LDS tile of
+// tile_t.h instead of by a transpose pass that re-reads the output:
+//   hT   [F, T]   the B operand of the w2 weight-gradient GEMM in NT layout (Llama(transpose_x="forward"))
+//   dguT [2F, T]  the A operand of the w13 weight-gradient GEMM (dW13 = dguT . hT^T)
+// One 256-thread block = 64 tokens x 8 NV features, NV = 16 (256-B row segments) or 8 (128-B ones: ran
+// the backward at 4.96 TB/s in the Llama step, 7 % behind NV = 16, profiles/r04_llama; kept for F that
+// only 64 divides).  Thread t takes vector t % NV of rows t / NV + (256 / NV) i.  All loads of the
+// tile are issued first: the compiler otherwise issued one pass's loads and waited for them before
+// the next pass (48 B per lane in flight, 5.2 TB/s in the backward).  T multiple of 64, F of 8 NV.
+template <int NV>
 __global__ __launch_bounds__(256) void swiglu_fwd_t_kernel(const u16* __restrict__ gu, u16* __restrict__ h,
                                                            u16* __restrict__ hT, int T, int F) {
-  __shared__ u16x8 tile[64][8];
-  const int t = threadIdx.x;
-  const size_t r0 = (size_t)blockIdx.y * 64, c0 = (size_t)blockIdx.x * 64;
+  constexpr int kPass = NV / 4, kRows = 256 / NV;
+  __shared__ TileT<NV> tile;
+  const int t = threadIdx.x, v = t % NV;
+  const size_t r0 = (size_t)blockIdx.y * 64, c0 = (size_t)blockIdx.x * (8 * NV);
   const size_t F2 = 2 * (size_t)F;
+  u16x8 gl[kPass], ul[kPass];
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int r = (t >> 3) + 32 * i, v = t & 7;
-    const size_t row = r0 + r;
-    const u16x8 g = *reinterpret_cast<const u16x8*>(gu + row * F2 + c0 + 8 * v);
-    const u16x8 u = *reinterpret_cast<const u16x8*>(gu + row * F2 + F + c0 + 8 * v);
-    u16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float gf = bf2f(g[j]);
-      o[j] = f2bf(gf / (1.f + __expf(-gf)) * bf2f(u[j]));
-    }
-    *reinterpret_cast<u16x8*>(h + row * F + c0 + 8 * v) = o;
-    tile[r][v ^ ((r >> 3) & 7)] = o;
-  }
-  __syncthreads();
-  const u16* lds = reinterpret_cast<const u16*>(&tile[0][0]);
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int idx = t + 256 * i;
-    const int c = idx >> 3, p = idx & 7;
-    const int pv = (c >> 3) ^ p;
-    u16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = lds[(8 * p + j) * 64 + pv * 8 + (c & 7)];
-    *reinterpret_cast<u16x8*>(hT + (c0 + c) * T + r0 + 8 * p) = o;
-  }
-}
-
-std::vector<at::Tensor> swiglu_fwd_t(const at::Tensor& gu) {
-  CHECK_BF16(gu);
-  TORCH_CHECK(gu.dim() == 2, "swiglu_fwd_t: gu must be [T, 2F]");
-  const int64_t T = gu.size(0), F = gu.size(1) / 2;
-  TORCH_CHECK(T % 64 == 0 && F % 64 == 0 && T / 64 <= 65535, "swiglu_fwd_t: T and F must be multiples of 64");
-  auto h = at::empty({T, F}, gu.options());
-  auto hT = at::empty({F, T}, gu.options());
-  if (T && F) hipLaunchKernelGGL(swiglu_fwd_t_kernel, dim3((unsigned)(F / 64), (unsigned)(T / 64)), dim3(256), 0, cur_stream(), bp(gu),
-                           bpm(h), bpm(hT), (int)T, (int)F);
-  return {h, hT};
-}
-
-// swiglu_fwd_t with 64-token x 128-feature tiles (the swiglu_bwd_t128 layout): 256-B row segments of
-// gate / up / h, 128-B segments of the transposed rows, conflict-free transposed LDS reads.  Same
-// expression as swiglu_fwd_kernel (identical h bits).  T multiple of 64, F multiple of 128.
-__global__ __launch_bounds__(256) void swiglu_fwd_t128_kernel(const u16* __restrict__ gu, u16* __restrict__ h,
-                                                              u16* __restrict__ hT, int T, int F) {
-  __shared__ u16x8 tile[64][16];  // [token][feature vector, swizzled]
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const size_t r0 = (size_t)blockIdx.y * 64, c0 = (size_t)blockIdx.x * 128;
-  const size_t F2 = 2 * (size_t)F;
-  u16x8 gl[4], ul[4];  // all 8 loads of the tile first (as swiglu_bwd_t128_kernel)
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const size_t row = r0 + (t >> 4) + 16 * i;
-    const int v = t & 15;
+  for (int i = 0; i < kPass; ++i) {
+    const size_t row = r0 + t / NV + kRows * i;
     gl[i] = *reinterpret_cast<const u16x8*>(gu + row * F2 + c0 + 8 * v);
     ul[i] = *reinterpret_cast<const u16x8*>(gu + row * F2 + F + c0 + 8 * v);
   }
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int r = (t >> 4) + 16 * i, v = t & 15;
-    const size_t row = r0 + r;
-    const u16x8 g = gl[i], u = ul[i];
-    u16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float gf = bf2f(g[j]);
-      o[j] = f2bf(gf / (1.f + __expf(-gf)) * bf2f(u[j]));
-    }
-    *reinterpret_cast<u16x8*>(h + row * F + c0 + 8 * v) = o;
-    tile[r][v ^ ((r >> 3) & 7)] = o;
+  for (int i = 0; i < kPass; ++i) {
+    const int r = t / NV + kRows * i;
+    const u16x8 o = swiglu_fwd8(gl[i], ul[i]);
+    *reinterpret_cast<u16x8*>(h + (r0 + r) * F + c0 + 8 * v) = o;
+    tile.put(r, v, o);
   }
   __syncthreads();
-  const int p = lane >> 3, cl = lane & 7;
-  const u16* lds = reinterpret_cast<const u16*>(&tile[0][0]);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int vc = 4 * i + wv;
-    const int c = 8 * vc + cl;
-    u16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = lds[((8 * p + j) * 16 + (vc ^ p)) * 8 + cl];
-    *reinterpret_cast<u16x8*>(hT + (c0 + c) * T + r0 + 8 * p) = o;
-  }
+  tile.store_t(hT, (size_t)T, c0, r0);
 }
 
-std::vector<at::Tensor> swiglu_fwd_t128(const at::Tensor& gu) {
-  CHECK_BF16(gu);
-  TORCH_CHECK(gu.dim() == 2, "swiglu_fwd_t128: gu must be [T, 2F]");
-  const int64_t T = gu.size(0), F = gu.size(1) / 2;
-  TORCH_CHECK(T % 64 == 0 && F % 128 == 0 && T / 64 <= 65535, "swiglu_fwd_t128: T multiple of 64, F of 128");
-  auto h = at::empty({T, F}, gu.options());
-  auto hT = at::empty({F, T}, gu.options());
-  if (T && F) hipLaunchKernelGGL(swiglu_fwd_t128_kernel, dim3((unsigned)(F / 128), (unsigned)(T / 64)), dim3(256), 0, cur_stream(),
-                           bp(gu), bpm(h), bpm(hT), (int)T, (int)F);
-  return {h, hT};
-}
-
-// swiglu_bwd_t with 64-token x 128-feature tiles: 256-B row segments of dh / gate / up (the 64 x 64
-// tile reads 128-B segments and ran at 4.96 TB/s in the Llama step, profiles/r04_llama) and 128-B
-// segments of the transposed rows.  Lanes of one transposed-store instruction take one 16-B column
-// vector x 8 row groups (the swizzle puts the row groups on 8 slots): conflict-free.  Same arithmetic
-// as swiglu_bwd_kernel (bit-identical).  T multiple of 64, F multiple of 128.
-__global__ __launch_bounds__(256) void swiglu_bwd_t128_kernel(const u16* __restrict__ dh, const u16* __restrict__ gu,
-                                                              u16* __restrict__ dgu, u16* __restrict__ dguT, int T, int F) {
-  __shared__ u16x8 tile[2][64][16];  // [gate | up][token][feature vector, swizzled]
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const size_t r0 = (size_t)blockIdx.y * 64, c0 = (size_t)blockIdx.x * 128;
+template <int NV>
+__global__ __launch_bounds__(256) void swiglu_bwd_t_kernel(const u16* __restrict__ dh, const u16* __restrict__ gu,
+                                                           u16* __restrict__ dgu, u16* __restrict__ dguT, int T, int F) {
+  constexpr int kPass = NV / 4, kRows = 256 / NV;
+  __shared__ TileT<NV> tile[2];  // [gate | up]
+  const int t = threadIdx.x, v = t % NV;
+  const size_t r0 = (size_t)blockIdx.y * 64, c0 = (size_t)blockIdx.x * (8 * NV);
   const size_t F2 = 2 * (size_t)F;
-  // all 12 loads of the tile first (the compiler otherwise issued one pass's 3 loads and waited for
-  // them before the next pass: 48 B per lane in flight, 5.2 TB/s)
-  u16x8 gl[4], ul[4], dl[4];
+  u16x8 gl[kPass], ul[kPass], dl[kPass];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const size_t row = r0 + (t >> 4) + 16 * i;
-    const int v = t & 15;
+  for (int i = 0; i < kPass; ++i) {
+    const size_t row = r0 + t / NV + kRows * i;
     gl[i] = *reinterpret_cast<const u16x8*>(gu + row * F2 + c0 + 8 * v);
     ul[i] = *reinterpret_cast<const u16x8*>(gu + row * F2 + F + c0 + 8 * v);
     dl[i] = *reinterpret_cast<const u16x8*>(dh + row * F + c0 + 8 * v);
   }
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int r = (t >> 4) + 16 * i, v = t & 15;
-    const size_t row = r0 + r;
-    const u16x8 g = gl[i], u = ul[i], d = dl[i];
+  for (int i = 0; i < kPass; ++i) {
+    const int r = t / NV + kRows * i;
     u16x8 og, ou;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float gf = bf2f(g[j]), uf = bf2f(u[j]), df = bf2f(d[j]);
-      const float sg = 1.f / (1.f + __expf(-gf));
-      const float silu = gf * sg;
-      ou[j] = f2bf(df * silu);
-      og[j] = f2bf(df * uf * sg * (1.f + gf * (1.f - sg)));
-    }
-    *reinterpret_cast<u16x8*>(dgu + row * F2 + c0 + 8 * v) = og;
-    *reinterpret_cast<u16x8*>(dgu + row * F2 + F + c0 + 8 * v) = ou;
-    tile[0][r][v ^ ((r >> 3) & 7)] = og;
-    tile[1][r][v ^ ((r >> 3) & 7)] = ou;
+    swiglu_bwd8(gl[i], ul[i], dl[i], og, ou);
+    *reinterpret_cast<u16x8*>(dgu + (r0 + r) * F2 + c0 + 8 * v) = og;
+    *reinterpret_cast<u16x8*>(dgu + (r0 + r) * F2 + F + c0 + 8 * v) = ou;
+    tile[0].put(r, v, og);
+    tile[1].put(r, v, ou);
   }
   __syncthreads();
-  const int p = lane >> 3, cl = lane & 7;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const u16* lds = reinterpret_cast<const u16*>(&tile[h][0][0]);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int vc = 4 * i + wv;
-      const int c = 8 * vc + cl;
-      u16x8 o;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] = lds[((8 * p + j) * 16 + (vc ^ p)) * 8 + cl];
-      *reinterpret_cast<u16x8*>(dguT + ((size_t)h * F + c0 + c) * T + r0 + 8 * p) = o;
-    }
-  }
+  tile[0].store_t(dguT, (size_t)T, c0, r0);
+  tile[1].store_t(dguT, (size_t)T, F + c0, r0);
 }
 
-std::vector<at::Tensor> swiglu_bwd_t128(const at::Tensor& dh, const at::Tensor& gu) {
+// the tile width in features for [T, F]: `tile` = 64 or 128 as given, 0 = the widest that divides F
+int swiglu_tile(const char* who, int64_t T, int64_t F, int64_t tile) {
+  TORCH_CHECK(tile == 0 || tile == 64 || tile == 128, who, ": tile must be 0, 64 or 128");
+  if (tile == 0) tile = F % 128 == 0 ? 128 : 64;
+  TORCH_CHECK(T % 64 == 0 && F % tile == 0 && T / 64 <= 65535, who, ": T must be a multiple of 64 and F of the tile width ", tile);
+  return (int)tile;
+}
+
+// -> (h [T, F], h^T [F, T])
+std::vector<at::Tensor> swiglu_fwd_t(const at::Tensor& gu, int64_t tile) {
+  CHECK_BF16(gu);
+  TORCH_CHECK(gu.dim() == 2, "swiglu_fwd_t: gu must be [T, 2F]");
+  const int64_t T = gu.size(0), F = gu.size(1) / 2;
+  const int w = swiglu_tile("swiglu_fwd_t", T, F, tile);
+  auto h = at::empty({T, F}, gu.options());
+  auto hT = at::empty({F, T}, gu.options());
+  if (T && F) {
+    const dim3 grid((unsigned)(F / w), (unsigned)(T / 64));
+    auto* kernel = w == 128 ? swiglu_fwd_t_kernel<16> : swiglu_fwd_t_kernel<8>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, cur_stream(), bp(gu), bpm(h), bpm(hT), (int)T, (int)F);
+  }
+  return {h, hT};
+}
+
+// -> (dgu [T, 2F], dgu^T [2F, T])
+std::vector<at::Tensor> swiglu_bwd_t(const at::Tensor& dh, const at::Tensor& gu, int64_t tile) {
   CHECK_BF16(dh);
   CHECK_BF16(gu);
-  TORCH_CHECK(gu.dim() == 2, "swiglu_bwd_t128: gu must be [T, 2F]");
+  TORCH_CHECK(gu.dim() == 2, "swiglu_bwd_t: gu must be [T, 2F]");
   const int64_t T = gu.size(0), F = gu.size(1) / 2;
-  TORCH_CHECK(dh.numel() == T * F, "swiglu_bwd_t128: shape mismatch");
-  TORCH_CHECK(T % 64 == 0 && F % 128 == 0 && T / 64 <= 65535, "swiglu_bwd_t128: T multiple of 64, F of 128");
+  TORCH_CHECK(dh.numel() == T * F, "swiglu_bwd_t: shape mismatch");
+  const int w = swiglu_tile("swiglu_bwd_t", T, F, tile);
   auto dgu = at::empty_like(gu);
   auto dguT = at::empty({2 * F, T}, gu.options());
-  if (T && F) hipLaunchKernelGGL(swiglu_bwd_t128_kernel, dim3((unsigned)(F / 128), (unsigned)(T / 64)), dim3(256), 0, cur_stream(),
-                           bp(dh), bp(gu), bpm(dgu), bpm(dguT), (int)T, (int)F);
+  if (T && F) {
+    const dim3 grid((unsigned)(F / w), (unsigned)(T / 64));
+    auto* kernel = w == 128 ? swiglu_bwd_t_kernel<16> : swiglu_bwd_t_kernel<8>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, cur_stream(), bp(dh), bp(gu), bpm(dgu), bpm(dguT), (int)T, (int)F);
+  }
   return {dgu, dguT};
 }
 
@@ -847,20 +706,6 @@ at::Tensor swiglu_bwd(const at::Tensor& dh, const at::Tensor& gu) {
   auto dgu = at::empty_like(gu);
   if (T) hipLaunchKernelGGL(swiglu_bwd_kernel, dim3(grid_for(T * (F / 8))), dim3(256), 0, cur_stream(), bp(dh), bp(gu), bpm(dgu), T, F);
   return dgu;
-}
-
-std::vector<at::Tensor> swiglu_bwd_t(const at::Tensor& dh, const at::Tensor& gu) {
-  CHECK_BF16(dh);
-  CHECK_BF16(gu);
-  TORCH_CHECK(gu.dim() == 2, "swiglu_bwd_t: gu must be [T, 2F]");
-  const int64_t T = gu.size(0), F = gu.size(1) / 2;
-  TORCH_CHECK(dh.numel() == T * F, "swiglu_bwd_t: shape mismatch");
-  TORCH_CHECK(T % 64 == 0 && F % 64 == 0 && T / 64 <= 65535, "swiglu_bwd_t: T and F must be multiples of 64");
-  auto dgu = at::empty_like(gu);
-  auto dguT = at::empty({2 * F, T}, gu.options());
-  if (T && F) hipLaunchKernelGGL(swiglu_bwd_t_kernel, dim3((unsigned)(F / 64), (unsigned)(T / 64)), dim3(256), 0, cur_stream(), bp(dh),
-                           bp(gu), bpm(dgu), bpm(dguT), (int)T, (int)F);
-  return {dgu, dguT};
 }
 
 // =============================================================================== cross-entropy
@@ -911,6 +756,17 @@ __global__ __launch_bounds__(256) void xent_fwd_kernel(const u16* __restrict__ l
 }
 
 // dlogits = (softmax - onehot) * scale, written over the logits (scale = dL/dloss_mean per valid row)
+// 8 logits of columns col0 .. col0+7 of a row with log-sum-exp l, label y and scale sc (0: ignored row)
+__device__ __forceinline__ u16x8 xent_grad8(u16x8 x, int64_t col0, float l, int64_t y, float sc) {
+  u16x8 o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float p = __expf(bf2f(x[j]) - l);
+    o[j] = f2bf((p - (col0 + j == y ? 1.f : 0.f)) * sc);
+  }
+  return o;
+}
+
 __global__ __launch_bounds__(256) void xent_bwd_kernel(u16* __restrict__ logits, const int64_t* __restrict__ labels,
                                                        const float* __restrict__ lse, const float* __restrict__ gscale,
                                                        int V, int64_t ignore_index) {
@@ -921,32 +777,21 @@ __global__ __launch_bounds__(256) void xent_bwd_kernel(u16* __restrict__ logits,
   const float sc = ignored ? 0.f : gscale[0];
   u16x8* lr = reinterpret_cast<u16x8*>(logits + (size_t)row * V);
   const int nvec = V >> 3;
-  for (int c = threadIdx.x; c < nvec; c += 256) {
-    const u16x8 x = lr[c];
-    u16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int col = c * 8 + j;
-      const float p = __expf(bf2f(x[j]) - l);
-      o[j] = f2bf((p - (col == y ? 1.f : 0.f)) * sc);
-    }
-    lr[c] = o;
-  }
+  for (int c = threadIdx.x; c < nvec; c += 256) lr[c] = xent_grad8(lr[c], (int64_t)c * 8, l, y, sc);
 }
 
 // xent_bwd with a transposed copy: dlogits^T [V, T] is the A operand of the lm_head weight-gradient
 // GEMM in NT layout, written from the LDS tile instead of by a transpose pass that re-reads the
 // 4.2 GB gradient (Llama-3-8B, T 16384).  One 256-thread block = 64 rows x 128 vocabulary columns:
-// 256-B row segments in, 128-B transposed segments out (the swiglu_bwd_t128 tile).  Same expression
-// as xent_bwd_kernel (bit-identical dlogits).  T multiple of 64, V multiple of 128.
+// 256-B row segments in, 128-B transposed segments out (tile_t.h).  T multiple of 64, V multiple of 128.
 __global__ __launch_bounds__(256) void xent_bwd_t_kernel(u16* __restrict__ logits, u16* __restrict__ dlT,
                                                          const int64_t* __restrict__ labels, const float* __restrict__ lse,
                                                          const float* __restrict__ gscale, int T, int V, int64_t ignore_index) {
-  __shared__ u16x8 tile[64][16];
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  __shared__ TileT<16> tile;
+  const int t = threadIdx.x;
   const size_t r0 = (size_t)blockIdx.y * 64, c0 = (size_t)blockIdx.x * 128;
   const float g = gscale[0];
-  u16x8 xl[4];  // the tile's 4 loads first (as swiglu_bwd_t128_kernel)
+  u16x8 xl[4];  // the tile's 4 loads first (see swiglu_bwd_t_kernel)
 #pragma unroll
   for (int i = 0; i < 4; ++i) xl[i] = *reinterpret_cast<const u16x8*>(logits + (r0 + (t >> 4) + 16 * i) * V + c0 + 8 * (t & 15));
 #pragma unroll
@@ -957,30 +802,12 @@ __global__ __launch_bounds__(256) void xent_bwd_t_kernel(u16* __restrict__ logit
     const bool ignored = (y == ignore_index || y < 0 || y >= V);
     const float l = lse[row];
     const float sc = ignored ? 0.f : g;
-    u16x8* src = reinterpret_cast<u16x8*>(logits + row * V + c0 + 8 * v);
-    const u16x8 x = xl[i];
-    u16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int64_t col = (int64_t)c0 + 8 * v + j;
-      const float p = __expf(bf2f(x[j]) - l);
-      o[j] = f2bf((p - (col == y ? 1.f : 0.f)) * sc);
-    }
-    *src = o;
-    tile[r][v ^ ((r >> 3) & 7)] = o;
+    const u16x8 o = xent_grad8(xl[i], (int64_t)c0 + 8 * v, l, y, sc);
+    *reinterpret_cast<u16x8*>(logits + row * V + c0 + 8 * v) = o;
+    tile.put(r, v, o);
   }
   __syncthreads();
-  const int p = lane >> 3, cl = lane & 7;
-  const u16* lds = reinterpret_cast<const u16*>(&tile[0][0]);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int vc = 4 * i + wv;
-    const int c = 8 * vc + cl;
-    u16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = lds[((8 * p + j) * 16 + (vc ^ p)) * 8 + cl];
-    *reinterpret_cast<u16x8*>(dlT + (c0 + c) * T + r0 + 8 * p) = o;
-  }
+  tile.store_t(dlT, (size_t)T, c0, r0);
 }
 
 std::vector<at::Tensor> xent_fwd(const at::Tensor& logits, const at::Tensor& labels, int64_t ignore_index) {
@@ -1412,10 +1239,10 @@ PYBIND11_MODULE(_fused, m) {
   m.def("rope_split_bwd", &rope_split_bwd);
   m.def("swiglu_fwd", &swiglu_fwd);
   m.def("swiglu_bwd", &swiglu_bwd);
-  m.def("swiglu_bwd_t128", &swiglu_bwd_t128, "swiglu_bwd_t with 64 x 128 tiles (bit-identical)");
-  m.def("swiglu_fwd_t128", &swiglu_fwd_t128, "swiglu_fwd_t with 64 x 128 tiles; T multiple of 64, F of 128");
-  m.def("swiglu_fwd_t", &swiglu_fwd_t, "swiglu forward -> (h [T, F], h^T [F, T]); T, F multiples of 64");
-  m.def("swiglu_bwd_t", &swiglu_bwd_t, "swiglu backward -> (dgu [T, 2F], dgu^T [2F, T]); T, F multiples of 64");
+  m.def("swiglu_fwd_t", &swiglu_fwd_t, "swiglu forward -> (h [T, F], h^T [F, T]); T multiple of 64, F of the tile width (64 or 128; 0 = auto)",
+        py::arg("gu"), py::arg("tile") = 0);
+  m.def("swiglu_bwd_t", &swiglu_bwd_t, "swiglu backward -> (dgu [T, 2F], dgu^T [2F, T]); T multiple of 64, F of the tile width (64 or 128; 0 = auto)",
+        py::arg("dh"), py::arg("gu"), py::arg("tile") = 0);
   m.def("xent_fwd", &xent_fwd);
   m.def("rope_split_bwd_t", &rope_split_bwd_t, "rope_split_bwd that also returns dqkv^T; head dim 128, S multiple of 64");
   m.def("xent_bwd_inplace", &xent_bwd_inplace);

@@ -22,19 +22,14 @@
 // conv1.w [32][3][3] (+ bias [32]); conv2.w [64][3][3][32] (co, ky, kx, ci) (+ bias [64]).
 // MFMA: v_mfma_f32_16x16x32_bf16 — lane l holds A[l&15][8(l>>4)+j], B[8(l>>4)+j][l&15], and
 // C/D col = l&15, row = 4(l>>4) + reg (cdna_hip_programming.md "Fragment layout").
-#include <hip/hip_runtime.h>
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
-
-#include <cstdint>
+#include "bf16.h"
 
 namespace gtk_mnist {
 namespace {
 
-typedef unsigned short u16;
-typedef u16 u16x8 __attribute__((ext_vector_type(8)));
+using namespace gtk;
+
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 #define LDS_AS __attribute__((address_space(3)))
@@ -47,8 +42,6 @@ constexpr int NW2 = C2 * KW2;             // 18432 conv2 weights
 constexpr int P2 = NW2 + C2;              // conv2 partial row: weights + bias
 constexpr int P1 = C1 * 10;               // conv1 partial row: [ci][9 taps + bias]
 
-__device__ __forceinline__ float bf2f(u16 v) { return __uint_as_float((uint32_t)v << 16); }
-__device__ __forceinline__ u16 f2bf(float f) { return __builtin_bit_cast(u16, (__bf16)f); }
 __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
@@ -75,10 +68,6 @@ __device__ __forceinline__ uint32_t mix32(uint32_t x) {
   return x;
 }
 __device__ __forceinline__ uint32_t hash3(uint32_t a, uint32_t b, uint32_t c) { return mix32(a ^ mix32(b ^ mix32(c))); }
-
-hipStream_t cur_stream() { return at::hip::getCurrentHIPStream().stream(); }
-const u16* bp(const at::Tensor& t) { return reinterpret_cast<const u16*>(t.data_ptr()); }
-u16* bpm(at::Tensor& t) { return reinterpret_cast<u16*>(t.data_ptr()); }
 
 // ------------------------------------------------------------------------------- conv1 forward
 __global__ __launch_bounds__(256) void conv1_fwd_kernel(const u16* __restrict__ x, const u16* __restrict__ w1,
@@ -596,8 +585,6 @@ __global__ __launch_bounds__(256) void xent10_bwd_kernel(const float* __restrict
     gb[threadIdx.x] = f2bf(t);
   }
 }
-
-#define CHECK_BF16(t) TORCH_CHECK((t).is_cuda() && (t).scalar_type() == at::kBFloat16 && (t).is_contiguous(), #t " must be a contiguous bf16 GPU tensor")
 
 void check_w(const at::Tensor& w1, const at::Tensor& b1, const at::Tensor& w2, const at::Tensor& b2) {
   CHECK_BF16(w1);

@@ -7,50 +7,28 @@
 // pays only when it runs near HBM speed; torch's strided copy runs at ~0.25 TB/s on [16384, 128256]
 // (8.5 ms), so the workload uses this kernel instead.
 //
-// Tile 64x64 bf16 per 256-thread block (4 wave64):
-//   load : thread t reads 16 B (8 columns) of rows t/8 and t/8+32 -> 8 lanes cover one 128-B row
-//          segment, a wave 8 rows;
-//   LDS  : [64 rows][8 vectors of 16 B], vector v of row r stored at v ^ ((r>>3)&7) (XOR swizzle);
-//   store: thread t gathers 8 consecutive rows r = 8p..8p+7 of one column c (8 ds_read_u16), packs
-//          them into 16 B and writes out[c][8p..8p+7].  In one instruction a wave's lanes take 8
-//          columns x 8 row-groups; the swizzle puts the 8 row-groups on 8 different 16-B slots, so
-//          the 64 lanes touch 32 distinct banks (lane pairs share a dword): no conflicts.
-// R and C must be multiples of 64; multiples of 128 (all Llama-3 dims) take the 128x128 kernel below.
-// Other shapes take torch's copy.
-#include <hip/hip_runtime.h>
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
-
-#include <cstdint>
+// R and C must be multiples of 64; multiples of 128 (all Llama-3 dims) take the 128x128 kernel below,
+// the rest the 64x64 tile of tile_t.h.  Other shapes take torch's copy.
+#include "tile_t.h"
 
 namespace gtk_xpose {
 
-typedef unsigned short u16;
-typedef u16 u16x8 __attribute__((ext_vector_type(8)));
+using namespace gtk;
 
 constexpr int kTile = 64;
 
+// thread t reads 16 B (8 columns) of rows t/8 and t/8+32: 8 lanes cover one 128-B row segment
 __global__ __launch_bounds__(256) void transpose_bf16_kernel(const u16* __restrict__ x, u16* __restrict__ y, int R, int C) {
-  __shared__ u16x8 tile[kTile][8];
+  __shared__ TileT<8> tile;
   const int t = threadIdx.x;
   const size_t r0 = (size_t)blockIdx.y * kTile, c0 = (size_t)blockIdx.x * kTile;
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int r = (t >> 3) + 32 * i, v = t & 7;
-    tile[r][v ^ ((r >> 3) & 7)] = *reinterpret_cast<const u16x8*>(x + (r0 + r) * C + c0 + 8 * v);
+    tile.put(r, v, *reinterpret_cast<const u16x8*>(x + (r0 + r) * C + c0 + 8 * v));
   }
   __syncthreads();
-  const u16* lds = reinterpret_cast<const u16*>(&tile[0][0]);
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int idx = t + 256 * i;
-    const int c = idx >> 3, p = idx & 7;
-    const int pv = (c >> 3) ^ p;  // ((r >> 3) & 7) == p for every r in 8p..8p+7
-    u16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = lds[(8 * p + j) * 64 + pv * 8 + (c & 7)];
-    *reinterpret_cast<u16x8*>(y + (c0 + c) * R + r0 + 8 * p) = o;
-  }
+  tile.store_t(y, R, c0, r0);
 }
 
 // 128x128 tile per 256-thread block (the path for every Llama-3 shape: all dims are multiples of
@@ -106,12 +84,12 @@ void transpose_bf16_out(const at::Tensor& x, at::Tensor& y) {
   if (R == 0 || C == 0) return;
   if (R % kBig == 0 && C % kBig == 0) {
     hipLaunchKernelGGL(transpose128_bf16_kernel, dim3((unsigned)(C / kBig), (unsigned)(R / kBig)), dim3(256), 0,
-                       at::hip::getCurrentHIPStream().stream(), reinterpret_cast<const u16*>(x.data_ptr()),
+                       cur_stream(), reinterpret_cast<const u16*>(x.data_ptr()),
                        reinterpret_cast<u16*>(y.data_ptr()), (int)R, (int)C);
     return;
   }
   hipLaunchKernelGGL(transpose_bf16_kernel, dim3((unsigned)(C / kTile), (unsigned)(R / kTile)), dim3(256), 0,
-                     at::hip::getCurrentHIPStream().stream(), reinterpret_cast<const u16*>(x.data_ptr()),
+                     cur_stream(), reinterpret_cast<const u16*>(x.data_ptr()),
                      reinterpret_cast<u16*>(y.data_ptr()), (int)R, (int)C);
 }
 

@@ -202,13 +202,10 @@ def swiglu_bwd_ref(dh: torch.Tensor, gu: torch.Tensor) -> torch.Tensor:
 
 def swiglu_bwd_t(dh: torch.Tensor, gu: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """SwiGLU backward returning ``(dgu [T, 2F], dgu^T [2F, T])``: the HIP kernel writes the transposed
-    copy from its LDS tile (T, F multiples of 64); elsewhere the reference plus a transpose."""
-    if gu.is_cuda and gu.dim() == 2 and gu.size(0) % 64 == 0 and (gu.size(1) // 2) % 128 == 0:
-        # 64 x 128 tiles: 7 % faster than 64 x 64 at the Llama-3-8B shape (profiles/r04_llama)
-        return tuple(hip().swiglu_bwd_t128(dh.contiguous(), gu.contiguous()))
+    copy from its LDS tile (T, F multiples of 64; the kernel picks its tile width); elsewhere the
+    reference plus a transpose."""
     if gu.is_cuda and gu.dim() == 2 and gu.size(0) % 64 == 0 and (gu.size(1) // 2) % 64 == 0:
-        dgu, dgu_t = hip().swiglu_bwd_t(dh.contiguous(), gu.contiguous())
-        return dgu, dgu_t
+        return tuple(hip().swiglu_bwd_t(dh.contiguous(), gu.contiguous()))
     dgu = hip().swiglu_bwd(dh.contiguous(), gu.contiguous()) if gu.is_cuda else swiglu_bwd_ref(dh, gu)
     return dgu, transpose(dgu)
 
@@ -216,8 +213,6 @@ def swiglu_bwd_t(dh: torch.Tensor, gu: torch.Tensor) -> Tuple[torch.Tensor, torc
 def swiglu_fwd_t(gu: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """SwiGLU forward returning ``(h [T, F], h^T [F, T])`` (no autograd): the HIP kernel writes the
     transposed copy from its LDS tile; elsewhere the reference plus a transpose."""
-    if gu.is_cuda and gu.dim() == 2 and gu.size(0) % 64 == 0 and (gu.size(1) // 2) % 128 == 0:
-        return tuple(hip().swiglu_fwd_t128(gu.contiguous()))
     if gu.is_cuda and gu.dim() == 2 and gu.size(0) % 64 == 0 and (gu.size(1) // 2) % 64 == 0:
         return tuple(hip().swiglu_fwd_t(gu.contiguous()))
     h = hip().swiglu_fwd(gu.contiguous()) if gu.is_cuda else swiglu_ref(gu)

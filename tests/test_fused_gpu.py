@@ -249,9 +249,8 @@ def test_transpose_kernel_exact(hip, R, C):
 def test_swiglu_bwd_t_matches_bwd_and_transpose(hip, T, F):
     gu = torch.randn(T, 2 * F, device="cuda", dtype=torch.bfloat16)
     dh = torch.randn(T, F, device="cuda", dtype=torch.bfloat16)
-    dgu, dgu_t = hip.swiglu_bwd_t(dh, gu)
-    ref = hip.swiglu_bwd(dh, gu)  # same math; allow a rare 1-ulp difference from FMA contraction
-    assert (dgu.float() - ref.float()).abs().max().item() <= 1e-2 * ref.float().abs().max().item()
+    dgu, dgu_t = hip.swiglu_bwd_t(dh, gu, tile=64)
+    assert torch.equal(dgu, hip.swiglu_bwd(dh, gu))  # one arithmetic body (swiglu_bwd8) in both kernels
     assert _rel(dgu, fused_swiglu_bwd_ref(dh, gu)) < 1e-2
     assert dgu_t.shape == (2 * F, T) and torch.equal(dgu_t, dgu.t().contiguous())
 
@@ -259,17 +258,58 @@ def test_swiglu_bwd_t_matches_bwd_and_transpose(hip, T, F):
 @pytest.mark.parametrize("T,F", [(64, 64), (256, 512), (16384 // 8, 14336 // 8)])
 def test_swiglu_fwd_t_matches_fwd_and_transpose(hip, T, F):
     gu = torch.randn(T, 2 * F, device="cuda", dtype=torch.bfloat16)
-    h, ht = hip.swiglu_fwd_t(gu)
+    h, ht = hip.swiglu_fwd_t(gu, tile=64)
     ref = hip.swiglu_fwd(gu)
     assert torch.equal(h, ref) and torch.equal(ht, ref.t().contiguous())
+
+
+@pytest.fixture(scope="module")
+def swiglu_flat(hip):
+    """(gu, dh, flat forward, flat backward) per F at T = 128, computed once and left unchanged."""
+    out = {}
+    for F in (192, 256):
+        g = torch.Generator(device="cuda").manual_seed(F)
+        gu = torch.randn(128, 2 * F, device="cuda", dtype=torch.bfloat16, generator=g)
+        dh = torch.randn(128, F, device="cuda", dtype=torch.bfloat16, generator=g)
+        out[F] = (gu, dh, hip.swiglu_fwd(gu), hip.swiglu_bwd(dh, gu))
+    return out
+
+
+def test_swiglu_t_tile_widths_agree_with_each_other_and_the_flat_kernels(hip, swiglu_flat):
+    gu, dh, h_ref, dgu_ref = swiglu_flat[256]
+    for tile in (64, 128):
+        h, ht = hip.swiglu_fwd_t(gu, tile=tile)
+        assert torch.equal(h, h_ref) and torch.equal(ht, h_ref.t().contiguous()), tile
+        dgu, dgut = hip.swiglu_bwd_t(dh, gu, tile=tile)
+        assert torch.equal(dgu, dgu_ref) and torch.equal(dgut, dgu_ref.t().contiguous()), tile
+
+
+def test_swiglu_t_explicit_tile_must_divide_f(hip, swiglu_flat):
+    gu, dh, _, _ = swiglu_flat[192]
+    with pytest.raises(RuntimeError, match="tile width 128"):
+        hip.swiglu_fwd_t(gu, tile=128)
+    with pytest.raises(RuntimeError, match="tile width 128"):
+        hip.swiglu_bwd_t(dh, gu, tile=128)
+    with pytest.raises(RuntimeError, match="tile must be 0, 64 or 128"):
+        hip.swiglu_fwd_t(gu, tile=32)
+
+
+@pytest.mark.parametrize("F", [192, 256])
+def test_swiglu_t_auto_tile_matches_the_flat_kernels(hip, swiglu_flat, F):
+    """tile=0 (the default): the widest tile that divides F -- 64 at F = 192, 128 at F = 256."""
+    gu, dh, h_ref, dgu_ref = swiglu_flat[F]
+    h, ht = hip.swiglu_fwd_t(gu)
+    assert torch.equal(h, h_ref) and torch.equal(ht, h_ref.t().contiguous())
+    dgu, dgut = hip.swiglu_bwd_t(dh, gu, tile=0)
+    assert torch.equal(dgu, dgu_ref) and torch.equal(dgut, dgu_ref.t().contiguous())
 
 
 @pytest.mark.parametrize("T,F", [(64, 128), (256, 512), (16384 // 8, 14336 // 8)])
 def test_swiglu_bwd_t128_is_bit_identical(hip, T, F):
     gu = torch.randn(T, 2 * F, device="cuda", dtype=torch.bfloat16)
     dh = torch.randn(T, F, device="cuda", dtype=torch.bfloat16)
-    a, at = hip.swiglu_bwd_t(dh, gu)
-    b, bt = hip.swiglu_bwd_t128(dh, gu)
+    a, at = hip.swiglu_bwd_t(dh, gu, tile=64)
+    b, bt = hip.swiglu_bwd_t(dh, gu, tile=128)
     assert torch.equal(a, b) and torch.equal(at, bt)
 
 
@@ -473,11 +513,14 @@ def test_training_with_the_default_rccl_cta_cap_initialises_its_communicator():
 
 @pytest.mark.parametrize("T,F", [(64, 128), (256, 512), (16384 // 8, 14336 // 8)])
 def test_swiglu_fwd_t128_is_bit_identical(hip, T, F):
-    """64 x 128-tile forward-with-transpose: h equals swiglu_fwd's bits, h^T its transpose."""
+    """64 x 128-tile forward-with-transpose: h equals swiglu_fwd's bits, h^T its transpose, and the
+    64 x 64 tile gives the same pair."""
     gu = torch.randn(T, 2 * F, device="cuda", dtype=torch.bfloat16)
-    h, ht = hip.swiglu_fwd_t128(gu)
+    h, ht = hip.swiglu_fwd_t(gu, tile=128)
     ref = hip.swiglu_fwd(gu)
     assert torch.equal(h, ref) and torch.equal(ht, ref.t().contiguous())
+    a, at = hip.swiglu_fwd_t(gu, tile=64)
+    assert torch.equal(a, h) and torch.equal(at, ht)
 
 
 @pytest.mark.parametrize("T,V", [(64, 128), (256, 1024), (512, 128256)])
