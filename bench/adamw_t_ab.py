@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """AdamW-T tile kernel look-ahead A/B at the Llama-3-8B parameter layout: 1, 2 or 4 eight-row passes'
-loads issued before their stores (csrc/ops/adamw_t.hip kAhead), interleaved, event-timed medians."""
+loads issued before their stores (csrc/ops/adamw.hip kAhead), interleaved, event-timed medians."""
 import json
 import os
 import sys

@@ -1,4 +1,4 @@
-// Fused elementwise / normalisation / loss / optimizer kernels for the Llama-3 DP validation
+// Fused elementwise / normalisation / loss kernels for the Llama-3 DP validation
 // workload (BASELINE config 5: "Llama-3-8B DP all-reduce training on the allocated set").
 //
 // The reference has no model code; these kernels exist because the validation
@@ -12,10 +12,6 @@
 //   swiglu_fwd / swiglu_bwd     gate|up GEMM output [T, 2F] -> silu(g)*u, and its gradient
 //   xent_fwd / xent_bwd         fused log-softmax cross-entropy over V=128256, gradient written
 //                               in place over the bf16 logits (saves a T x V fp32 tensor)
-//   adamw_step / sq_norm        one flat-buffer AdamW over bf16 params + fp32 master/m/v, and the
-//                               global gradient-norm reduction for clipping
-//   adamw_step_dev /            the graph-capturable pair: step count, bias corrections and the
-//   sq_norm_parts               clipping factor live on the device (2 launches per optimizer step)
 //   mnist_synth                 the MNIST workload's synthetic batch, one launch, device-indexed
 //   rope_split_bwd_t, swiglu_fwd_t / _bwd_t, xent_bwd_t
 //                               the same arithmetic bodies as the flat kernels, and the output's
@@ -26,20 +22,6 @@
 namespace {
 
 using namespace gtk;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return v;
-}
-
-#define CHECK_GRAD(t) TORCH_CHECK((t).is_cuda() && ((t).scalar_type() == at::kBFloat16 || (t).scalar_type() == at::kFloat) && (t).is_contiguous(), #t " must be a contiguous bf16 or fp32 GPU tensor")
-#define CHECK_F32(t) TORCH_CHECK((t).is_cuda() && (t).scalar_type() == at::kFloat && (t).is_contiguous(), #t " must be a contiguous fp32 GPU tensor")
 
 // =============================================================================== RMSNorm
 // One wave per row; lane l owns vectors c = i*64 + l (8 bf16 each).  NV = ceil(D / 512).
@@ -409,11 +391,6 @@ __global__ __launch_bounds__(256) void rope_split_kernel(u16* __restrict__ qkv, 
     *reinterpret_cast<u16x8*>(ta + i0) = olo;
     *reinterpret_cast<u16x8*>(ta + half + i0) = ohi;
   }
-}
-
-int grid_for(size_t work, int per_block = 256) {
-  size_t g = (work + per_block - 1) / per_block;
-  return (int)std::max<size_t>(1, std::min<size_t>(g, 256 * 16));  // >> 256 CUs, grid-stride beyond
 }
 
 std::vector<at::Tensor> rope_split_fwd(const at::Tensor& qkv, const at::Tensor& cosb, const at::Tensor& sinb, int64_t B,
@@ -900,177 +877,6 @@ void embed_bwd_into(const at::Tensor& sorted, const at::Tensor& perm, const at::
                        perm.data_ptr<int64_t>(), bp(dx), bpm(out), (int)T, (int)dx.size(1), out.size(0));
 }
 
-// =============================================================================== optimizer
-// Flat-buffer AdamW (decoupled weight decay).  8 elements per thread per iteration: two 16-B loads
-// each of master/m/v, one 16-B load of the bf16 gradient; writes master/m/v and the bf16 weight.
-// hp: device fp32 [lr, beta1, beta2, eps, weight_decay, grad_scale, bias_c1, bias_c2] so a captured
-// graph replays with updated hyper-parameters.
-// 8 gradient elements of vector i as fp32: the bf16 gradient buffer, or the fp32 buffer a DP
-// all-reduce in fp32 leaves (parallel/dp.py grad_reduce="fp32")
-__device__ __forceinline__ void load_g8(const u16* __restrict__ g, size_t i, float (&out)[8]) {
-  const u16x8 gv = reinterpret_cast<const u16x8*>(g)[i];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) out[j] = bf2f(gv[j]);
-}
-__device__ __forceinline__ void load_g8(const float* __restrict__ g, size_t i, float (&out)[8]) {
-  const f32x4 a = reinterpret_cast<const f32x4*>(g)[2 * i], b = reinterpret_cast<const f32x4*>(g)[2 * i + 1];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) out[j] = a[j], out[j + 4] = b[j];
-}
-
-template <typename G>
-__device__ __forceinline__ void adamw_body(float* __restrict__ master, float* __restrict__ m, float* __restrict__ v,
-                                           const G* __restrict__ g, u16* __restrict__ w, size_t n, float lr, float b1,
-                                           float b2, float eps, float wd, float gs, float bc1, float bc2) {
-  const size_t nv = n >> 3;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nv; i += (size_t)gridDim.x * 256) {
-    f32x4 p0 = reinterpret_cast<f32x4*>(master)[2 * i], p1 = reinterpret_cast<f32x4*>(master)[2 * i + 1];
-    f32x4 m0 = reinterpret_cast<f32x4*>(m)[2 * i], m1 = reinterpret_cast<f32x4*>(m)[2 * i + 1];
-    f32x4 v0 = reinterpret_cast<f32x4*>(v)[2 * i], v1 = reinterpret_cast<f32x4*>(v)[2 * i + 1];
-    float gf[8];
-    load_g8(g, i, gf);
-    u16x8 wo;
-    float p[8], mm[8], vv[8];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      p[j] = p0[j], p[j + 4] = p1[j];
-      mm[j] = m0[j], mm[j + 4] = m1[j];
-      vv[j] = v0[j], vv[j + 4] = v1[j];
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float gr = gf[j] * gs;
-      mm[j] = b1 * mm[j] + (1.f - b1) * gr;
-      vv[j] = b2 * vv[j] + (1.f - b2) * gr * gr;
-      const float upd = (mm[j] / bc1) / (sqrtf(vv[j] / bc2) + eps);
-      p[j] = p[j] - lr * (upd + wd * p[j]);
-      wo[j] = f2bf(p[j]);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      p0[j] = p[j], p1[j] = p[j + 4];
-      m0[j] = mm[j], m1[j] = mm[j + 4];
-      v0[j] = vv[j], v1[j] = vv[j + 4];
-    }
-    reinterpret_cast<f32x4*>(master)[2 * i] = p0;
-    reinterpret_cast<f32x4*>(master)[2 * i + 1] = p1;
-    reinterpret_cast<f32x4*>(m)[2 * i] = m0;
-    reinterpret_cast<f32x4*>(m)[2 * i + 1] = m1;
-    reinterpret_cast<f32x4*>(v)[2 * i] = v0;
-    reinterpret_cast<f32x4*>(v)[2 * i + 1] = v1;
-    reinterpret_cast<u16x8*>(w)[i] = wo;
-  }
-}
-
-template <typename G>
-__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ master, float* __restrict__ m, float* __restrict__ v,
-                                                    const G* __restrict__ g, u16* __restrict__ w, const float* __restrict__ hp,
-                                                    size_t n) {
-  adamw_body(master, m, v, g, w, n, hp[0], hp[1], hp[2], hp[3], hp[4], hp[5], hp[6], hp[7]);
-}
-
-// Graph-mode AdamW: everything the host used to compute per step is derived on the device, so one
-// captured launch replays correctly forever (``FlatAdamW(capturable=True)``).
-//   hp   = [lr, beta1, beta2, eps, weight_decay, grad_scale, clip_norm (<= 0: off), -]
-//   part = sqnorm partials of the gradient (``sq_norm_parts``); every block reduces them itself
-//   t    = optimizer step count AFTER this step (``sq_norm_parts`` advanced it in stream order)
-// Bias corrections 1 - beta^t and the clipping factor min(1, clip / ||g * grad_scale||) follow.
-template <typename G>
-__global__ __launch_bounds__(256) void adamw_dev_kernel(float* __restrict__ master, float* __restrict__ m, float* __restrict__ v,
-                                                        const G* __restrict__ g, u16* __restrict__ w, const float* __restrict__ hp,
-                                                        const float* __restrict__ part, int nparts, const float* __restrict__ tptr,
-                                                        size_t n) {
-  __shared__ float red[4];
-  const float lr = hp[0], b1 = hp[1], b2 = hp[2], eps = hp[3], wd = hp[4], gscale = hp[5], clip = hp[6];
-  float gs = gscale;
-  if (nparts > 0 && clip > 0.f) {
-    float s = 0.f;
-    for (int i = threadIdx.x; i < nparts; i += 256) s += part[i];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    const float norm = sqrtf(red[0] + red[1] + red[2] + red[3]) * gscale;
-    gs = gscale * fminf(1.f, clip / (norm + 1e-6f));
-  }
-  const float t = tptr[0];
-  adamw_body(master, m, v, g, w, n, lr, b1, b2, eps, wd, gs, 1.f - powf(b1, t), 1.f - powf(b2, t));
-}
-
-// sum of squares of a bf16 buffer -> per-block partials (fp32)
-template <typename G>
-__global__ __launch_bounds__(256) void sqnorm_kernel(const G* __restrict__ g, float* __restrict__ part, size_t n) {
-  __shared__ float red[4];
-  // each thread's grid-stride vectors are loaded four at a time (four 16-B loads in flight per lane;
-  // one at a time ran the 16 GB bf16 gradient at 5.3 TB/s) but summed in the same order into one
-  // accumulator: the partials keep their bits (the clip factor, and with it the training trajectory,
-  // is sensitive to the norm's last bits -- profiles/r04_norm)
-  float s = 0.f;
-  const size_t nv = n >> 3, stride = (size_t)gridDim.x * 256;
-  size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  for (; i + 3 * stride < nv; i += 4 * stride) {
-    float x[4][8];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) load_g8(g, i + u * stride, x[u]);
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) s += x[u][j] * x[u][j];
-  }
-  for (; i < nv; i += stride) {
-    float x[8];
-    load_g8(g, i, x);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s += x[j] * x[j];
-  }
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-
-void adamw_step(at::Tensor& master, at::Tensor& m, at::Tensor& v, const at::Tensor& g, at::Tensor& w, const at::Tensor& hp) {
-  CHECK_F32(master);
-  CHECK_F32(m);
-  CHECK_F32(v);
-  CHECK_GRAD(g);
-  CHECK_BF16(w);
-  CHECK_F32(hp);
-  const size_t n = master.numel();
-  TORCH_CHECK(n % 8 == 0 && (size_t)m.numel() == n && (size_t)v.numel() == n && (size_t)g.numel() == n && (size_t)w.numel() == n,
-              "adamw: flat buffers must have equal sizes, a multiple of 8");
-  TORCH_CHECK(hp.numel() >= 8, "adamw: hp needs 8 entries");
-  if (!n) return;
-  if (g.scalar_type() == at::kFloat)
-    hipLaunchKernelGGL(adamw_kernel<float>, dim3(grid_for(n / 8)), dim3(256), 0, cur_stream(), master.data_ptr<float>(),
-                       m.data_ptr<float>(), v.data_ptr<float>(), g.data_ptr<float>(), bpm(w), hp.data_ptr<float>(), n);
-  else
-    hipLaunchKernelGGL(adamw_kernel<u16>, dim3(grid_for(n / 8)), dim3(256), 0, cur_stream(), master.data_ptr<float>(),
-                       m.data_ptr<float>(), v.data_ptr<float>(), bp(g), bpm(w), hp.data_ptr<float>(), n);
-}
-
-// sqnorm + (optionally) the step counter: block 0 / thread 0 adds 1 to ``tick`` — nothing else in
-// this kernel reads it; the AdamW kernel after it in stream order does.
-template <typename G>
-__global__ __launch_bounds__(256) void sqnorm_tick_kernel(const G* __restrict__ g, float* __restrict__ part, size_t n,
-                                                          float* __restrict__ tick) {
-  __shared__ float red[4];
-  float s = 0.f;
-  const size_t nv = n >> 3;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nv; i += (size_t)gridDim.x * 256) {
-    float x[8];
-    load_g8(g, i, x);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s += x[j] * x[j];
-  }
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    part[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-    if (tick != nullptr && blockIdx.x == 0) tick[0] = tick[0] + 1.f;
-  }
-}
-
 // ============================================================================ synthetic MNIST
 // One block per image: label = hash(seed, step, image) % classes, pixel = (prototype[label] +
 // noise * N(0,1) - mean) / std in bf16, N(0,1) by Box-Muller from a counter-based hash of
@@ -1123,69 +929,6 @@ std::vector<at::Tensor> mnist_synth(const at::Tensor& proto, int64_t batch, cons
   return {x, y};
 }
 
-at::Tensor sq_norm_parts(const at::Tensor& g, c10::optional<at::Tensor> tick) {
-  CHECK_GRAD(g);
-  const size_t n = g.numel();
-  TORCH_CHECK(n % 8 == 0, "sq_norm_parts: size must be a multiple of 8");
-  float* tk = nullptr;
-  if (tick.has_value()) {
-    CHECK_F32(*tick);
-    tk = tick->data_ptr<float>();
-  }
-  const int grid = (int)std::max<size_t>(1, std::min<size_t>((n / 8 + 255) / 256, 1024));
-  auto part = at::empty({grid}, g.options().dtype(at::kFloat));  // every slot written
-  if (g.scalar_type() == at::kFloat)
-    hipLaunchKernelGGL(sqnorm_tick_kernel<float>, dim3(grid), dim3(256), 0, cur_stream(), g.data_ptr<float>(), part.data_ptr<float>(), n,
-                       tk);
-  else
-    hipLaunchKernelGGL(sqnorm_tick_kernel<u16>, dim3(grid), dim3(256), 0, cur_stream(), bp(g), part.data_ptr<float>(), n, tk);
-  return part;
-}
-
-void adamw_step_dev(at::Tensor& master, at::Tensor& m, at::Tensor& v, const at::Tensor& g, at::Tensor& w, const at::Tensor& hp,
-                    c10::optional<at::Tensor> part, const at::Tensor& t) {
-  CHECK_F32(master);
-  CHECK_F32(m);
-  CHECK_F32(v);
-  CHECK_GRAD(g);
-  CHECK_BF16(w);
-  CHECK_F32(hp);
-  CHECK_F32(t);
-  const size_t n = master.numel();
-  TORCH_CHECK(n % 8 == 0 && (size_t)m.numel() == n && (size_t)v.numel() == n && (size_t)g.numel() == n && (size_t)w.numel() == n,
-              "adamw: flat buffers must have equal sizes, a multiple of 8");
-  TORCH_CHECK(hp.numel() >= 7, "adamw_step_dev: hp needs 7 entries");
-  const float* pp = nullptr;
-  int np = 0;
-  if (part.has_value()) {
-    CHECK_F32(*part);
-    pp = part->data_ptr<float>();
-    np = (int)part->numel();
-  }
-  if (!n) return;
-  if (g.scalar_type() == at::kFloat)
-    hipLaunchKernelGGL(adamw_dev_kernel<float>, dim3(grid_for(n / 8)), dim3(256), 0, cur_stream(), master.data_ptr<float>(),
-                       m.data_ptr<float>(), v.data_ptr<float>(), g.data_ptr<float>(), bpm(w), hp.data_ptr<float>(), pp, np,
-                       t.data_ptr<float>(), n);
-  else
-    hipLaunchKernelGGL(adamw_dev_kernel<u16>, dim3(grid_for(n / 8)), dim3(256), 0, cur_stream(), master.data_ptr<float>(),
-                       m.data_ptr<float>(), v.data_ptr<float>(), bp(g), bpm(w), hp.data_ptr<float>(), pp, np,
-                       t.data_ptr<float>(), n);
-}
-
-at::Tensor sq_norm(const at::Tensor& g) {
-  CHECK_GRAD(g);
-  const size_t n = g.numel();
-  TORCH_CHECK(n % 8 == 0, "sq_norm: size must be a multiple of 8");
-  const int grid = 1024;
-  auto part = at::zeros({grid}, g.options().dtype(at::kFloat));
-  if (n && g.scalar_type() == at::kFloat)
-    hipLaunchKernelGGL(sqnorm_kernel<float>, dim3(grid), dim3(256), 0, cur_stream(), g.data_ptr<float>(), part.data_ptr<float>(), n);
-  else if (n)
-    hipLaunchKernelGGL(sqnorm_kernel<u16>, dim3(grid), dim3(256), 0, cur_stream(), bp(g), part.data_ptr<float>(), n);
-  return part.sum();
-}
-
 }  // namespace
 
 namespace gtk_mnist {  // csrc/ops/mnist_conv.hip
@@ -1217,7 +960,12 @@ namespace gtk_shadow {  // csrc/ops/comm_shadow.hip
 void comm_shadow(const at::Tensor& src, at::Tensor& dst, int64_t bytes, int64_t ctas, double micros);
 }  // namespace gtk_shadow
 
-namespace gtk_adamw {  // csrc/ops/adamw_t.hip
+namespace gtk_adamw {  // csrc/ops/adamw.hip
+void adamw_step(at::Tensor& master, at::Tensor& m, at::Tensor& v, const at::Tensor& g, at::Tensor& w, const at::Tensor& hp);
+void adamw_step_dev(at::Tensor& master, at::Tensor& m, at::Tensor& v, const at::Tensor& g, at::Tensor& w, const at::Tensor& hp,
+                    c10::optional<at::Tensor> part, const at::Tensor& t);
+at::Tensor sq_norm(const at::Tensor& g);
+at::Tensor sq_norm_parts(const at::Tensor& g, c10::optional<at::Tensor> tick);
 void adamw_step_t(at::Tensor& master, at::Tensor& m, at::Tensor& v, const at::Tensor& g, at::Tensor& w, at::Tensor& wt,
                   const at::Tensor& hp, const at::Tensor& mats, int64_t total_tiles, const at::Tensor& ranges,
                   int64_t max_range, c10::optional<at::Tensor> part, c10::optional<at::Tensor> t, int64_t ahead);
@@ -1247,10 +995,10 @@ PYBIND11_MODULE(_fused, m) {
   m.def("rope_split_bwd_t", &rope_split_bwd_t, "rope_split_bwd that also returns dqkv^T; head dim 128, S multiple of 64");
   m.def("xent_bwd_inplace", &xent_bwd_inplace);
   m.def("xent_bwd_t", &xent_bwd_t, "xent_bwd_inplace that also returns dlogits^T [V, T]; T multiple of 64, V of 128");
-  m.def("adamw_step", &adamw_step);
-  m.def("sq_norm", &sq_norm);
-  m.def("sq_norm_parts", &sq_norm_parts, "sum-of-squares partials of a bf16 buffer; optionally advance a step counter");
-  m.def("adamw_step_dev", &adamw_step_dev, "AdamW with device-side bias correction and clipping (graph-capturable)");
+  m.def("adamw_step", &gtk_adamw::adamw_step);
+  m.def("sq_norm", &gtk_adamw::sq_norm);
+  m.def("sq_norm_parts", &gtk_adamw::sq_norm_parts, "sum-of-squares partials of a bf16 buffer; optionally advance a step counter");
+  m.def("adamw_step_dev", &gtk_adamw::adamw_step_dev, "AdamW with device-side bias correction and clipping (graph-capturable)");
   m.def("mnist_synth", &mnist_synth, "synthetic MNIST batch on the device, indexed by a device step counter");
   m.def("mnist_conv1_fwd", &gtk_mnist::conv1_fwd, "MNIST conv1 + ReLU, NHWC bf16");
   m.def("mnist_conv2_pool_fwd", &gtk_mnist::conv2_pool_fwd, "MNIST conv2 + ReLU + 2x2 max-pool + dropout (MFMA)");

@@ -107,12 +107,7 @@ class FlatAdamW:
         b1, b2 = self.betas
         gs = torch.tensor(grad_scale, dtype=torch.float32, device=self.hp.device)
         if self.clip_norm is not None:
-            for g in ([] if sq is not None else self._views(gbuf)):
-                part = fused.hip().sq_norm(g) if g.is_cuda else g.float().pow(2).sum()
-                sq = part if sq is None else sq + part
-            if self.sharded and dist.is_initialized() and dist.get_world_size(self.group) > 1:
-                dist.all_reduce(sq, group=self.group)
-            norm = sq.sqrt() * grad_scale
+            norm = self._clip_sq(sq, gbuf).sqrt() * grad_scale
             gs = gs * torch.clamp(self.clip_norm / (norm + 1e-6), max=1.0)
         vals = torch.tensor([self.lr, b1, b2, self.eps, self.wd, 0.0, 1 - b1 ** self.t, 1 - b2 ** self.t], dtype=torch.float32)
         self.hp.copy_(vals, non_blocking=True)
@@ -123,6 +118,11 @@ class FlatAdamW:
                                      mats, tiles, ranges, maxr, None, None, self.adamw_ahead)
             self.flat.mark_t_valid()
             return
+        self._step_shards(gbuf)
+
+    def _step_shards(self, gbuf: torch.Tensor) -> None:
+        """The host-form update with ``self.hp`` on every shard (the whole buffer without shards);
+        W^T goes stale."""
         self._invalidate_t()
         o = 0
         for (s, e), g, d in zip(self.shards, self._views(gbuf), self._views(self.flat.data)):
@@ -135,6 +135,8 @@ class FlatAdamW:
             o += n
 
     def _clip_sq(self, sq: Optional[torch.Tensor], gbuf: torch.Tensor) -> torch.Tensor:
+        """The sum of squared gradients over every rank's shards (``sq``: this rank's, when the
+        caller has it)."""
         for g in ([] if sq is not None else self._views(gbuf)):
             part = fused.hip().sq_norm(g) if g.is_cuda else g.float().pow(2).sum()
             sq = part if sq is None else sq + part
@@ -179,16 +181,7 @@ class FlatAdamW:
             self.hp[5:6].copy_((torch.clamp(self.clip_norm / (norm + 1e-6), max=1.0) * grad_scale).reshape(1))
         else:
             self.hp[5:6].fill_(grad_scale)
-        self._invalidate_t()
-        o = 0
-        for (s, e), g, d in zip(self.shards, self._views(gbuf), self._views(self.flat.data)):
-            n = e - s
-            st = (self.master[o:o + n], self.m[o:o + n], self.v[o:o + n])
-            if d.is_cuda:
-                fused.hip().adamw_step(*st, g, d, self.hp)
-            else:
-                self._step_ref(*st, g, d)
-            o += n
+        self._step_shards(gbuf)
 
     def _invalidate_t(self) -> None:
         if hasattr(self.flat, "invalidate_t"):

@@ -176,11 +176,13 @@ def test_cross_entropy_autograd_mean(hip):
     assert _rel(a.grad, b.grad) < 1e-2
 
 
-@pytest.mark.parametrize("gdtype", [torch.bfloat16, torch.float32])
-def test_adamw_and_sqnorm(hip, gdtype):
-    """bf16 gradients, and the fp32 sum a DP reduction in fp32 leaves (parallel/dp.py grad_reduce)."""
+_ADAMW_KEYS = ("master", "m", "v", "g", "w")
+
+
+def _flat_adamw_against_torch(hip, n, gdtype):
+    """One ``adamw_step`` of n elements against the op-by-op fp32 torch reference; returns the
+    inputs and the kernel's outputs."""
     torch.manual_seed(5)
-    n = 1 << 20
     master = torch.randn(n, device="cuda")
     m = torch.randn(n, device="cuda").abs() * 0.01
     v = torch.randn(n, device="cuda").abs() * 0.001
@@ -193,6 +195,7 @@ def test_adamw_and_sqnorm(hip, gdtype):
     rm.mul_(b1).add_(gg, alpha=1 - b1)
     rv.mul_(b2).addcmul_(gg, gg, value=1 - b2)
     rp -= lr * ((rm / (1 - b1 ** t)) / ((rv / (1 - b2 ** t)).sqrt() + eps) + wd * rp)
+    before = {k: x.clone() for k, x in zip(_ADAMW_KEYS, (master, m, v, g, w))}
     hip.adamw_step(master, m, v, g, w, hp)
     assert torch.allclose(m, rm, atol=1e-6, rtol=1e-5) and torch.allclose(v, rv, atol=1e-7, rtol=1e-5)
     assert torch.allclose(master, rp, atol=1e-6, rtol=1e-5)
@@ -203,8 +206,88 @@ def test_adamw_and_sqnorm(hip, gdtype):
         assert torch.equal(w, rp.to(torch.bfloat16))
     else:
         assert (w.float() - rp.to(torch.bfloat16).float()).abs().max() <= 2 ** -7 * rp.abs().max()
+    return before, dict(zip(_ADAMW_KEYS, (master, m, v, g, w))), hp
+
+
+@pytest.mark.parametrize("gdtype", [torch.bfloat16, torch.float32])
+def test_adamw_and_sqnorm(hip, gdtype):
+    """bf16 gradients, and the fp32 sum a DP reduction in fp32 leaves (parallel/dp.py grad_reduce)."""
+    before, _, _ = _flat_adamw_against_torch(hip, 1 << 20, gdtype)
+    g = before["g"]
     sq = hip.sq_norm(g)
     assert math.isclose(sq.item(), g.float().pow(2).sum().item(), rel_tol=1e-4)
+
+
+@pytest.mark.parametrize("gdtype", [torch.bfloat16, torch.float32])
+@pytest.mark.parametrize("n", [8, 8 * 257])
+def test_adamw_flat_and_single_range_at_the_smallest_sizes(hip, n, gdtype):
+    """One vector, and one vector past a block: the flat kernel against the torch reference, and
+    ``adamw_step_t`` with no matrix and the single range [0, n] bit for bit against the flat kernel."""
+    before, flat, hp = _flat_adamw_against_torch(hip, n, gdtype)
+    got = {k: x.clone() for k, x in before.items()}
+    mats = torch.zeros(0, 5, dtype=torch.int64, device="cuda")
+    ranges = torch.tensor([[0, n]], dtype=torch.int64, device="cuda")
+    wt = torch.zeros(8, dtype=torch.bfloat16, device="cuda")
+    hip.adamw_step_t(got["master"], got["m"], got["v"], got["g"], got["w"], wt, hp, mats, 0, ranges, n, None, None, 2)
+    for k in _ADAMW_KEYS:
+        assert torch.equal(got[k], flat[k]), k
+    assert not wt.any()
+
+
+@pytest.mark.parametrize("case", ["clip", "clip_off_in_hp", "no_partials"])
+@pytest.mark.parametrize("gdtype", [torch.bfloat16, torch.float32])
+@pytest.mark.parametrize("n", [8 * 257, 1 << 18])
+def test_adamw_step_dev_matches_host_form_with_python_hyperparameters(hip, n, gdtype, case):
+    """The device-side derivation (clip factor from the partials, 1 - beta^t) against the host form
+    fed the same quantities computed in float64.  Integer gradients in [-3, 3]: their sum of squares
+    is exact in fp32, so the two differ only by the fp32 sqrtf / powf / division roundings of the
+    scalars (the tolerance of test_gpu_mnist.test_fused_dev_optimizer_matches_host_optimizer)."""
+    torch.manual_seed(11)
+    g = torch.randint(-3, 4, (n,), device="cuda").to(gdtype)
+    master = torch.randn(n, device="cuda")
+    st = dict(zip(_ADAMW_KEYS, (master, torch.randn(n, device="cuda").abs() * 0.01, torch.randn(n, device="cuda").abs() * 0.001,
+                                g, master.to(torch.bfloat16))))
+    ref = {k: x.clone() for k, x in st.items()}
+    lr, b1, b2, eps, wd, gs, t, clip = 1e-3, 0.9, 0.95, 1e-8, 0.1, 0.5, 3, 1.0
+    part = None if case == "no_partials" else hip.sq_norm_parts(g, None)
+    hp_dev = torch.tensor([lr, b1, b2, eps, wd, gs, -1.0 if case == "clip_off_in_hp" else clip, 0.0], device="cuda")
+    hip.adamw_step_dev(st["master"], st["m"], st["v"], st["g"], st["w"], hp_dev, part, torch.tensor([float(t)], device="cuda"))
+    gs_ref = gs
+    if case == "clip":
+        norm = math.sqrt(g.double().pow(2).sum().item()) * gs
+        assert norm > 10 * clip  # the clip is active
+        gs_ref = gs * min(1.0, clip / (norm + 1e-6))
+    hp = torch.tensor([lr, b1, b2, eps, wd, gs_ref, 1 - b1 ** t, 1 - b2 ** t], dtype=torch.float64).float().cuda()
+    hip.adamw_step(ref["master"], ref["m"], ref["v"], ref["g"], ref["w"], hp)
+    for k in ("master", "m", "v"):
+        assert torch.allclose(st[k], ref[k], rtol=1e-4, atol=1e-6), k
+    assert torch.equal(st["w"], st["master"].to(torch.bfloat16))
+
+
+@pytest.fixture(scope="module")
+def ternary():
+    """Values from {-1, 0, 1} (every sum of squares an exact integer below 2^24) at a size where the
+    1024-block grid runs the four-in-flight loop, the tail loop and a ragged last stride."""
+    n = 8 * (5 * 262144 + 777)
+    x = torch.randint(-1, 2, (n,), device="cuda", generator=torch.Generator("cuda").manual_seed(13))
+    return x, {k: int(x[:k].ne(0).sum().item()) for k in (8, 8 * 257, n)}
+
+
+@pytest.mark.parametrize("gdtype", [torch.bfloat16, torch.float32])
+def test_sum_of_squares_is_exact(hip, ternary, gdtype):
+    x, count = ternary
+    n = x.numel()
+    g = x.to(gdtype)
+    assert hip.sq_norm(g).item() == count[n]
+    parts = hip.sq_norm_parts(g, None)
+    assert parts.shape == (1024,) and parts.dtype == torch.float32 and parts.sum().item() == count[n]
+    for k, blocks in ((8, 1), (8 * 257, 2)):
+        p = hip.sq_norm_parts(g[:k], None)
+        assert p.shape == (blocks,) and p.sum().item() == count[k]
+    tick = torch.tensor([6.0], device="cuda")
+    assert torch.equal(hip.sq_norm_parts(g, tick), parts)
+    assert tick.item() == 7.0
+    assert hip.sq_norm(g[:0]).item() == 0.0
 
 
 def test_sharded_flat_adamw_matches_full_on_gpu():
@@ -365,7 +448,7 @@ def test_smoke_step_and_training_gpu():
 
 
 
-def _adamw_t_case(seed=7):
+def _adamw_t_case(gdtype, seed=7):
     """A flat buffer of 3 matrices (64-multiples) and 2 vectors with alignment gaps, as FlatParams lays
     it out, plus its adamw_step_t plan."""
     from gpu_topology_on_k8s_amd.models.llama import FlatParams
@@ -376,16 +459,18 @@ def _adamw_t_case(seed=7):
     torch.manual_seed(seed)
     n = flat.numel
     st = {"master": torch.randn(n, device="cuda"), "m": torch.randn(n, device="cuda").abs() * 0.01,
-          "v": torch.randn(n, device="cuda").abs() * 0.001, "g": torch.randn(n, device="cuda", dtype=torch.bfloat16)}
+          "v": torch.randn(n, device="cuda").abs() * 0.001, "g": torch.randn(n, device="cuda", dtype=gdtype)}
     st["w"] = st["master"].to(torch.bfloat16)
     return flat, st
 
 
+@pytest.mark.parametrize("gdtype", [torch.bfloat16, torch.float32])
 @pytest.mark.parametrize("dev,ahead", [(False, 1), (False, 2), (False, 4), (True, 1)])
-def test_adamw_step_t_matches_flat_kernel_and_writes_wt(hip, dev, ahead):
+def test_adamw_step_t_matches_flat_kernel_and_writes_wt(hip, dev, ahead, gdtype):
     """The tile kernel applies the flat kernel's arithmetic bit for bit (master, m, v, W) and writes
-    W^T of every planned matrix; the ranges kernel covers the rest (VERDICT r3 next #3)."""
-    flat, st = _adamw_t_case()
+    W^T of every planned matrix; the ranges kernel covers the rest.  Both
+    gradient types: bf16, and the fp32 sum of ``--grad-reduce fp32``."""
+    flat, st = _adamw_t_case(gdtype)
     mats, tiles, ranges, maxr = flat.adamw_plan()
     assert tiles == 3 * 1 + 1 * 2 + 4 * 3 and ranges.shape[0] >= 2
     ref = {k: v.clone() for k, v in st.items()}

@@ -56,7 +56,7 @@ def test_dq_spills_only_a_few_bytes(stats):
     assert q["Occupancy"] == 2 and q["ScratchSize"] <= 64, q  # 48 B in the diagonal-tile code (profiles/r05_attn7)
 
 
-@pytest.mark.parametrize("src", ["fused_ops.hip", "adamw_t.hip", "transpose.hip"])
+@pytest.mark.parametrize("src", ["fused_ops.hip", "adamw.hip", "transpose.hip"])
 def test_memory_bound_kernels_do_not_spill(tmp_path, src):
     """Every kernel of the Llama step's memory-bound sources is spill-free; the one exception is the
     RMSNorm backward instance for rows of 4097-8192 elements (NV = 16, not used by the Llama-3-8B /
