@@ -296,6 +296,7 @@ std::vector<at::Tensor> rmsnorm_bwd_impl(const at::Tensor& dy, const at::Tensor&
   CHECK_BF16(w);
   CHECK_F32(rstd);
   const int D = (int)x.size(-1);
+  TORCH_CHECK(D % 8 == 0 && D <= 8192 && w.numel() == D, "rmsnorm_bwd: D must be a multiple of 8, <= 8192, and match w");
   const int M = (int)(x.numel() / D);
   TORCH_CHECK(dy.numel() == x.numel() && rstd.numel() == M, "rmsnorm_bwd: shape mismatch");
   auto dx = at::empty_like(x);
@@ -399,6 +400,7 @@ std::vector<at::Tensor> rope_split_fwd(const at::Tensor& qkv, const at::Tensor& 
   CHECK_F32(cosb);
   CHECK_F32(sinb);
   TORCH_CHECK(Dh % 16 == 0, "head dim must be a multiple of 16");
+  TORCH_CHECK(pos_offset >= 0, "rope_split_fwd: pos_offset must not be negative");
   TORCH_CHECK(qkv.numel() == B * S * (H + 2 * Hkv) * Dh, "qkv shape mismatch");
   TORCH_CHECK(cosb.size(-1) == Dh / 2 && cosb.size(0) >= S + pos_offset && sinb.sizes() == cosb.sizes(), "rope table shape");
   auto opt = qkv.options();
@@ -416,7 +418,14 @@ at::Tensor rope_split_bwd(const at::Tensor& dq, const at::Tensor& dk, const at::
   CHECK_BF16(dq);
   CHECK_BF16(dk);
   CHECK_BF16(dv);
+  CHECK_F32(cosb);
+  CHECK_F32(sinb);
+  TORCH_CHECK(dq.dim() == 4 && dk.dim() == 4, "rope_split_bwd: dq, dk, dv must be [B, heads, S, Dh]");
   const int64_t B = dq.size(0), H = dq.size(1), S = dq.size(2), Dh = dq.size(3), Hkv = dk.size(1);
+  TORCH_CHECK(Dh % 16 == 0, "head dim must be a multiple of 16");
+  TORCH_CHECK(pos_offset >= 0, "rope_split_bwd: pos_offset must not be negative");
+  TORCH_CHECK(dk.sizes() == dv.sizes() && dk.size(0) == B && dk.size(2) == S && dk.size(3) == Dh, "rope_split_bwd: shapes");
+  TORCH_CHECK(cosb.size(-1) == Dh / 2 && cosb.size(0) >= S + pos_offset && sinb.sizes() == cosb.sizes(), "rope table shape");
   auto dqkv = at::empty({B * S, (H + 2 * Hkv) * Dh}, dq.options());
   const size_t work = (size_t)B * S * (H + 2 * Hkv) * (Dh / 16);
   if (work)
@@ -487,6 +496,7 @@ std::vector<at::Tensor> rope_split_bwd_t(const at::Tensor& dq, const at::Tensor&
   CHECK_F32(sinb);
   const int64_t B = dq.size(0), H = dq.size(1), S = dq.size(2), Dh = dq.size(3), Hkv = dk.size(1);
   TORCH_CHECK(Dh == 128 && S % 64 == 0, "rope_split_bwd_t: head dim 128 and S multiple of 64");
+  TORCH_CHECK(pos_offset >= 0, "rope_split_bwd_t: pos_offset must not be negative");
   TORCH_CHECK(dk.sizes() == dv.sizes() && dk.size(0) == B && dk.size(2) == S && dk.size(3) == Dh, "rope_split_bwd_t: shapes");
   TORCH_CHECK(cosb.size(-1) == Dh / 2 && cosb.size(0) >= S + pos_offset && sinb.sizes() == cosb.sizes(), "rope table shape");
   TORCH_CHECK(B * S / 64 <= 65535, "rope_split_bwd_t: too many tokens for the grid");
@@ -677,6 +687,7 @@ at::Tensor swiglu_fwd(const at::Tensor& gu) {
 at::Tensor swiglu_bwd(const at::Tensor& dh, const at::Tensor& gu) {
   CHECK_BF16(dh);
   CHECK_BF16(gu);
+  TORCH_CHECK(gu.size(-1) % 16 == 0, "swiglu_bwd: 2F must be a multiple of 16");
   const int F = (int)(gu.size(-1) / 2);
   const size_t T = gu.numel() / (2 * F);
   TORCH_CHECK((size_t)dh.numel() == T * F, "swiglu_bwd: shape mismatch");
@@ -806,8 +817,13 @@ void xent_bwd_inplace(at::Tensor& logits, const at::Tensor& labels, const at::Te
   CHECK_BF16(logits);
   CHECK_F32(lse);
   CHECK_F32(gscale);
-  const int V = (int)logits.size(-1);
-  const int64_t T = logits.numel() / V;
+  TORCH_CHECK(logits.dim() == 2, "xent_bwd_inplace: logits must be [T, V]");
+  TORCH_CHECK(labels.is_cuda() && labels.scalar_type() == at::kLong && labels.is_contiguous(), "labels must be int64 GPU");
+  const int V = (int)logits.size(1);
+  const int64_t T = logits.size(0);
+  TORCH_CHECK(V % 8 == 0, "vocab must be a multiple of 8");
+  TORCH_CHECK(labels.numel() == T && lse.numel() == T, "xent_bwd_inplace: labels/lse must have T entries");
+  TORCH_CHECK(gscale.numel() >= 1, "xent_bwd_inplace: gscale must hold the scale");
   if (T) hipLaunchKernelGGL(xent_bwd_kernel, dim3((unsigned)T), dim3(256), 0, cur_stream(), bpm(logits), labels.data_ptr<int64_t>(),
                             lse.data_ptr<float>(), gscale.data_ptr<float>(), V, ignore_index);
 }
@@ -822,6 +838,7 @@ at::Tensor xent_bwd_t(at::Tensor& logits, const at::Tensor& labels, const at::Te
   TORCH_CHECK(labels.is_cuda() && labels.scalar_type() == at::kLong && labels.is_contiguous(), "labels must be int64 GPU");
   const int64_t T = logits.size(0), V = logits.size(1);
   TORCH_CHECK(labels.numel() == T && lse.numel() == T, "xent_bwd_t: labels/lse must have T entries");
+  TORCH_CHECK(gscale.numel() >= 1, "xent_bwd_t: gscale must hold the scale");
   TORCH_CHECK(T % 64 == 0 && V % 128 == 0 && T / 64 <= 65535, "xent_bwd_t: T multiple of 64, V of 128");
   auto dlT = at::empty({V, T}, logits.options());
   if (T && V)
