@@ -771,12 +771,20 @@ void check_qkv(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v) {
   TORCH_CHECK(q.size(1) % k.size(1) == 0, "attention: q heads must be a multiple of kv heads");
   TORCH_CHECK(q.size(2) % BQ == 0, "attention: sequence length must be a multiple of 128");
   TORCH_CHECK(q.size(1) * q.size(2) * D * 2 < (int64_t(1) << 31), "attention: per-batch q/dO bytes must fit the 32-bit buffer offsets");
+  TORCH_CHECK(k.device() == q.device() && v.device() == q.device(), "attention: q/k/v must be on one device");
+}
+
+// the forward takes its running max on raw scores and scales afterwards: only right for c > 0
+void check_scale(double scale) {
+  TORCH_CHECK(std::isfinite(scale) && scale > 0 && std::isfinite((float)scale) && (float)scale > 0.f,
+              "attention: scale must be finite and greater than 0");
 }
 
 // forward (fwd2); with_t: also O^T [H*D, B*S] (the o-projection's NT-layout x^T) from the epilogue
 std::vector<at::Tensor> attn_fwd_impl(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, double scale,
                                       bool with_t) {
   check_qkv(q, k, v);
+  check_scale(scale);
   const int B = q.size(0), H = q.size(1), S = q.size(2), Hkv = k.size(1);
   auto o = at::empty({B, S, H, D}, q.options());
   auto lse = at::empty({B, H, S}, q.options().dtype(at::kFloat));
@@ -802,11 +810,15 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k, const
 std::vector<at::Tensor> attn_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                                  const at::Tensor& out, const at::Tensor& lse, double scale) {
   check_qkv(q, k, v);
+  check_scale(scale);
   const int B = q.size(0), H = q.size(1), S = q.size(2), Hkv = k.size(1);
-  TORCH_CHECK(dout.is_contiguous() && out.is_contiguous() && dout.numel() == q.numel() && out.numel() == q.numel(),
-              "attention bwd: dout/out must be contiguous [B, S, H, D]");
-  TORCH_CHECK(lse.is_contiguous() && lse.scalar_type() == at::kFloat && lse.numel() == (int64_t)B * H * S,
-              "attention bwd: lse must be fp32 [B, H, S]");
+  for (const at::Tensor* x : {&dout, &out})
+    TORCH_CHECK(x->is_cuda() && x->device() == q.device() && x->scalar_type() == at::kBFloat16 && x->is_contiguous() &&
+                    x->dim() == 4 && x->size(0) == B && x->size(1) == S && x->size(2) == H && x->size(3) == D,
+                "attention bwd: dout/out must be contiguous bf16 [B, S, H, D] GPU tensors on q's device");
+  TORCH_CHECK(lse.is_cuda() && lse.device() == q.device() && lse.is_contiguous() && lse.scalar_type() == at::kFloat &&
+                  lse.dim() == 3 && lse.size(0) == B && lse.size(1) == H && lse.size(2) == S,
+              "attention bwd: lse must be a contiguous fp32 [B, H, S] GPU tensor on q's device");
   auto fopt = q.options().dtype(at::kFloat);
   auto delta = at::empty({B, H, S}, fopt), nls = at::empty({B, H, S}, fopt), ndl = at::empty({B, H, S}, fopt);
   auto dq = at::empty_like(q), dk = at::empty_like(k), dv = at::empty_like(v);
