@@ -1,0 +1,160 @@
+// K7: all-reduce (sum) over peer pointers, device side.  A fragment of csrc/probe/probe.hip, included
+// there at file scope once SrcSet / kMaxSrc (K5) are defined in its unnamed namespace, which the
+// code below joins.  Device code only, in the style of csrc/common/stream_copy.h: blocks of
+// gtk::kStreamBlock threads, 64-bit indices, 16-byte vectors.
+//
+// Every member's buffers are padded with zeros to a whole number of vectors by the host driver, so
+// no kernel sees a scalar tail.  The sum of one element is fp32, taken in member order
+// ((x0 + x1) + x2) + ... with no tree and no reassociation, and rounded once: every member computes
+// the same bits, and a sequential CPU sum reproduces them (ops/peer_ref.py).
+//
+// No kernel here waits for another running kernel: the all-reduce's cross-member ordering is stream
+// events between launches (the host driver in probe.hip), visibility rests on kernel boundaries.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "../common/stream_copy.h"
+
+namespace {
+
+// fp32 lanes of one 16-byte vector: 4 of float, 8 of bf16 (raw u16; element 2j is the low half of word j).
+template <typename T>
+constexpr int kPeerLanes = 16 / (int)sizeof(T);
+
+__device__ __forceinline__ void peer_widen(const u32x4& v, float (&f)[4]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) f[j] = __uint_as_float(v[j]);
+}
+__device__ __forceinline__ void peer_widen(const u32x4& v, float (&f)[8]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    f[2 * j] = __uint_as_float(v[j] << 16);
+    f[2 * j + 1] = __uint_as_float(v[j] & 0xffff0000u);
+  }
+}
+__device__ __forceinline__ u32x4 peer_narrow(const float (&f)[4]) {
+  u32x4 v;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) v[j] = __float_as_uint(f[j]);
+  return v;
+}
+__device__ __forceinline__ unsigned int peer_bf16_bits(float x) {  // round to nearest even
+  return (unsigned int)__builtin_bit_cast(unsigned short, (__bf16)x);
+}
+__device__ __forceinline__ u32x4 peer_narrow(const float (&f)[8]) {
+  u32x4 v;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) v[j] = peer_bf16_bits(f[2 * j]) | (peer_bf16_bits(f[2 * j + 1]) << 16);
+  return v;
+}
+
+// U vectors per lane, `stride` apart from `i`: the k x U loads (member-major, all in flight before the
+// first add), then per position the sum in member order, one rounding and one 16-byte store.  KB is
+// the member bucket the registers are sized for (k <= KB): r[] is indexed by constants only.
+template <typename T, int KB, int U>
+__device__ __forceinline__ void peer_reduce_vecs(const SrcSet& srcs, int k, u32x4* __restrict__ dst, size_t i,
+                                                 size_t stride) {
+  u32x4 r[KB][U];
+#pragma unroll
+  for (int m = 0; m < KB; ++m)
+    if (m < k) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) r[m][u] = __builtin_nontemporal_load(srcs.p[m] + i + (size_t)u * stride);
+    }
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    float acc[kPeerLanes<T>];
+    peer_widen(r[0][u], acc);
+#pragma unroll
+    for (int m = 1; m < KB; ++m)
+      if (m < k) {
+        float x[kPeerLanes<T>];
+        peer_widen(r[m][u], x);
+#pragma unroll
+        for (int j = 0; j < kPeerLanes<T>; ++j) acc[j] = acc[j] + x[j];
+      }
+    __builtin_nontemporal_store(peer_narrow(acc), dst + i + (size_t)u * stride);
+  }
+}
+
+// dst[v0, v1) = sum over members m < k of srcs.p[m][v0, v1), T = float or bf16 as raw u16.  Whole
+// tiles (kStreamBlock x U vectors) are cut into one contiguous run per block, as gtk::stream_slices
+// does; what is left of the range, under one tile, goes one vector per lane over the whole grid.
+template <typename T, int KB, int U>
+__global__ __launch_bounds__(gtk::kStreamBlock) void peer_reduce_kernel(SrcSet srcs, int k, size_t v0, size_t v1,
+                                                                        u32x4* __restrict__ dst) {
+  const size_t tile = (size_t)gtk::kStreamBlock * U;
+  const size_t n_tiles = (v1 - v0) / tile;
+  const size_t per = (n_tiles + gridDim.x - 1) / gridDim.x;
+  const size_t t0 = (size_t)blockIdx.x * per;
+  const size_t t1 = std::min(n_tiles, t0 + per);
+  for (size_t t = t0; t < t1; ++t)
+    peer_reduce_vecs<T, KB, U>(srcs, k, dst, v0 + t * tile + threadIdx.x, gtk::kStreamBlock);
+  for (size_t i = v0 + n_tiles * tile + (size_t)blockIdx.x * gtk::kStreamBlock + threadIdx.x; i < v1;
+       i += (size_t)gridDim.x * gtk::kStreamBlock)
+    peer_reduce_vecs<T, KB, 1>(srcs, k, dst, i, 0);
+}
+
+// Slice i of an all-gather: `count` vectors from vector `first` of p[i], to the same offset of dst.
+struct SliceSet {
+  const u32x4* p[kMaxSrc];
+  size_t first[kMaxSrc];
+  size_t count[kMaxSrc];
+};
+
+// Block b serves slice b % nsrc with gridDim / nsrc blocks (the grid is a multiple of nsrc), as the
+// K5 gather does; slices differ in length and may be empty.
+__global__ __launch_bounds__(gtk::kStreamBlock) void peer_allgather_kernel(SliceSet sl, int nsrc,
+                                                                           u32x4* __restrict__ dst) {
+  const int s = blockIdx.x % nsrc;
+  const size_t blk = blockIdx.x / nsrc, nblk = gridDim.x / nsrc;
+  const u32x4* src = sl.p[s] + sl.first[s];
+  u32x4* out = dst + sl.first[s];
+  const size_t first = gtk::stream_slices<4>(src, out, sl.count[s], blk, nblk);
+  gtk::stream_vec_tail(src, out, sl.count[s], first, blk, nblk);
+}
+
+// Test inputs: element i of the member with seed `seed` is a small integer in [-8, 7], so a sum over
+// up to 16 members lies in [-128, 112] and is exact in bf16 as in fp32.
+__device__ __forceinline__ int peer_pattern(size_t i, unsigned int seed) {
+  return (int)((((unsigned int)i * 2654435761u + seed * 40503u) >> 16) & 15u) - 8;
+}
+__device__ __forceinline__ void peer_put(float* p, float x) { *p = x; }
+__device__ __forceinline__ void peer_put(uint16_t* p, float x) { *p = (uint16_t)(__float_as_uint(x) >> 16); }
+__device__ __forceinline__ float peer_get(const float* p) { return *p; }
+__device__ __forceinline__ float peer_get(const uint16_t* p) { return __uint_as_float((unsigned int)*p << 16); }
+
+// p[0, count) = pattern(seed); p[count, padded) = 0.
+template <typename T>
+__global__ __launch_bounds__(gtk::kStreamBlock) void peer_fill_kernel(T* __restrict__ p, size_t count, size_t padded,
+                                                                      unsigned int seed) {
+  for (size_t i = (size_t)blockIdx.x * gtk::kStreamBlock + threadIdx.x; i < padded;
+       i += (size_t)gridDim.x * gtk::kStreamBlock)
+    peer_put(p + i, i < count ? (float)peer_pattern(i, seed) : 0.f);
+}
+
+struct SeedSet {
+  unsigned int s[kMaxSrc];
+};
+
+// Counts the elements of p[0, count) that differ from the sum of the k members' patterns, and the
+// padding elements p[count, padded) that are not zero.
+template <typename T>
+__global__ __launch_bounds__(gtk::kStreamBlock) void peer_check_kernel(const T* __restrict__ p, size_t count,
+                                                                       size_t padded, SeedSet seeds, int k,
+                                                                       unsigned long long* bad) {
+  unsigned long long local = 0;
+  for (size_t i = (size_t)blockIdx.x * gtk::kStreamBlock + threadIdx.x; i < padded;
+       i += (size_t)gridDim.x * gtk::kStreamBlock) {
+    int want = 0;
+    if (i < count)
+      for (int m = 0; m < k; ++m) want += peer_pattern(i, seeds.s[m]);
+    local += (peer_get(p + i) != (float)want);
+  }
+  if (local) atomicAdd(bad, local);
+}
+
+}  // namespace

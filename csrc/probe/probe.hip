@@ -16,6 +16,9 @@
 //                  (ingress and egress of every GPU loaded together, as under a ring all-reduce):
 //                  the slowest member's ingress is the bound a ring all-reduce's busBW is measured
 //                  against.
+//   K7 allreduce : the sum of every member's buffer, in every member's output, by kernels over peer
+//                  pointers (peer_allreduce.h): a fixed summation order, so the result is exact
+//                  against a CPU sum; the repository's own collective, next to RCCL's.
 //   IPC read     : the K1 kernel on a buffer another process exported with hipIpcGetMemHandle (the
 //                  mapping RCCL's P2P transport gives a rank of its peers' buffers).
 // The copy kernel exists in two staging forms (LDS-DMA and plain register staging) so the
@@ -27,6 +30,7 @@
 // with a grid-stride loop: >>256 workgroups fills all 8 XCDs; a streaming copy has no reuse so no
 // XCD remap is needed (each byte is touched once).
 #include <hip/hip_runtime.h>
+#include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
@@ -120,6 +124,10 @@ __global__ __launch_bounds__(kBlock) void gather_lds_kernel(SrcSet srcs, int nsr
   const int s = blockIdx.x % nsrc;
   copy_lds_stream<true>(srcs.p[s], dst + (size_t)s * n_vec, n_vec, lds, blockIdx.x / nsrc, gridDim.x / nsrc);
 }
+
+}  // namespace
+#include "peer_allreduce.h"  // K7 kernels, over SrcSet / kMaxSrc above
+namespace {
 
 // Register-staged variant of the same stream (kUnroll independent 16-B loads in flight per lane).
 template <bool kNonTemporal>
@@ -589,6 +597,319 @@ py::dict ring_bw(const std::vector<int>& devs, const std::vector<std::vector<int
   return r;
 }
 
+// K7 peer all-reduce: the sum of k members' buffers, left in every member's `out`, by this
+// repository's own kernels over peer pointers (peer_allreduce.h): no RCCL.  One process, one stream
+// per member as in K6, and members may repeat a device, so a 1-GPU box runs the k-member indexing
+// and ordering.  The sum is taken in member order in fp32 and rounded once, so every member's result
+// is bit-identical and equals a sequential CPU sum (ops/peer_ref.py).
+//   oneshot: member m reduces every member's whole `in` into its own `out`; k x N read per member,
+//            one launch, no dependency between members.
+//   twoshot: phase 1, member m reduces slice m of every `in` into slice m of its `out`; phase 2, it
+//            copies slice p from out[p] for every p != m.  Ingress per member 2(k-1)/k x N.
+// Members are ordered by stream events alone (no kernel waits for a running kernel): e1[m] follows
+// m's phase 1 and every member's phase 2 waits for all of them; e2[m] follows m's phase 2 and every
+// member's next phase 1 waits for all of them, since phase 2 of p reads the slice m then overwrites.
+struct PeerSlice {
+  size_t first, count;  // in 16-byte vectors
+};
+
+// Slice s of k: vectors [s*per, min(n_vec, (s+1)*per)), per = ceil(n_vec / k); trailing ones may be empty.
+std::vector<PeerSlice> peer_slices(size_t n_vec, int k) {
+  const size_t per = (n_vec + k - 1) / k;
+  std::vector<PeerSlice> out(k);
+  for (int s = 0; s < k; ++s) {
+    const size_t a = std::min(n_vec, (size_t)s * per), b = std::min(n_vec, (size_t)(s + 1) * per);
+    out[s] = PeerSlice{a, b - a};
+  }
+  return out;
+}
+
+// Member buckets of peer_reduce_kernel: k x U loads of 16 bytes per lane stay within 64 VGPRs.
+template <typename T>
+void launch_peer_reduce(const SrcSet& set, int k, size_t v0, size_t v1, u32x4* dst, int grid, hipStream_t s) {
+  const dim3 g(grid), b(kBlock);
+  if (k <= 2)
+    peer_reduce_kernel<T, 2, 4><<<g, b, 0, s>>>(set, k, v0, v1, dst);
+  else if (k <= 4)
+    peer_reduce_kernel<T, 4, 4><<<g, b, 0, s>>>(set, k, v0, v1, dst);
+  else if (k <= 8)
+    peer_reduce_kernel<T, 8, 2><<<g, b, 0, s>>>(set, k, v0, v1, dst);
+  else
+    peer_reduce_kernel<T, 16, 1><<<g, b, 0, s>>>(set, k, v0, v1, dst);
+  HIP_CHECK(hipGetLastError());
+}
+
+struct PeerAllreduce {
+  static constexpr size_t kMaxCount = (size_t)64 << 20;  // elements, through the array entry point
+
+  std::vector<int> devs;
+  int k = 0, nsets = 1;
+  bool bf16 = true, twoshot = false;
+  size_t count = 0, elem = 2, n_vec = 0;
+  std::vector<std::unique_ptr<DevBuf>> in[2], out;  // in[set][m]: rounds alternate between the sets
+  SrcSet srcs[2]{};
+  std::vector<PeerSlice> plan;
+  std::vector<SliceSet> gather;  // member m's phase 2: slice p of out[p], every p != m
+  std::vector<int> reduce_grid, gather_grid_;
+  std::vector<std::unique_ptr<TimedStream>> ts;
+  std::vector<hipEvent_t> e1, e2;
+  size_t rounds_done = 0;
+
+  static void check_args(const std::vector<int>& devs, size_t count, const std::string& dtype, const std::string& algo) {
+    if (devs.size() < 2 || devs.size() > (size_t)kMaxSrc) throw std::invalid_argument("2..16 members");
+    int ndev = 0;
+    HIP_CHECK(hipGetDeviceCount(&ndev));
+    for (int d : devs)
+      if (d < 0 || d >= ndev) throw std::invalid_argument("device index out of range");
+    if (count < 1) throw std::invalid_argument("count >= 1");
+    if (dtype != "bf16" && dtype != "fp32") throw std::invalid_argument("dtype must be bf16|fp32");
+    if (algo != "oneshot" && algo != "twoshot") throw std::invalid_argument("algo must be oneshot|twoshot");
+  }
+
+  PeerAllreduce(const std::vector<int>& devs_, size_t count_, const std::string& dtype, const std::string& algo,
+                int nsets_, int blocks_per_cu)
+      : devs(devs_), k((int)devs_.size()), nsets(nsets_), bf16(dtype == "bf16"), twoshot(algo == "twoshot"),
+        count(count_), elem(dtype == "bf16" ? 2 : 4), n_vec((count_ * (dtype == "bf16" ? 2 : 4) + 15) / 16),
+        plan(peer_slices(n_vec, k)), gather(k), reduce_grid(k), gather_grid_(k), e1(k, nullptr), e2(k, nullptr) {
+    for (int m = 0; m < k; ++m)
+      for (int p = 0; p < k; ++p) enable_peer(devs[m], devs[p]);
+    for (int m = 0; m < k; ++m) {
+      for (int s = 0; s < nsets; ++s) {
+        in[s].emplace_back(new DevBuf(devs[m], n_vec * 16));
+        srcs[s].p[m] = reinterpret_cast<const u32x4*>(in[s][m]->p);
+      }
+      out.emplace_back(new DevBuf(devs[m], n_vec * 16));
+    }
+    try {
+      for (int m = 0; m < k; ++m) {
+        int share = 0;  // members sharing a device split its CUs, as in K6
+        for (int d : devs) share += (d == devs[m]);
+        const size_t mine = twoshot ? plan[m].count : n_vec;  // no more blocks than vectors to reduce
+        const size_t cap = std::max(1, num_cus(devs[m]) * std::max(1, blocks_per_cu) / share);
+        reduce_grid[m] = (int)std::max<size_t>(1, std::min(cap, (mine + kBlock - 1) / kBlock));
+        gather_grid_[m] = gather_grid(devs[m], blocks_per_cu, k - 1, share);
+        int i = 0;
+        for (int p = 0; p < k; ++p) {
+          if (p == m) continue;
+          gather[m].p[i] = reinterpret_cast<const u32x4*>(out[p]->p);
+          gather[m].first[i] = plan[p].first;
+          gather[m].count[i] = plan[p].count;
+          ++i;
+        }
+        DeviceGuard g(devs[m]);
+        ts.emplace_back(new TimedStream());
+        HIP_CHECK(hipEventCreateWithFlags(&e1[m], hipEventDisableTiming));
+        HIP_CHECK(hipEventCreateWithFlags(&e2[m], hipEventDisableTiming));
+      }
+    } catch (...) {
+      release();
+      throw;
+    }
+  }
+  ~PeerAllreduce() { release(); }
+  PeerAllreduce(const PeerAllreduce&) = delete;
+  PeerAllreduce& operator=(const PeerAllreduce&) = delete;
+
+  size_t padded() const { return n_vec * 16 / elem; }  // elements of a buffer, zero padding included
+
+  void reduce(int m, int set, size_t v0, size_t v1) {
+    if (v0 == v1) return;
+    auto* dst = reinterpret_cast<u32x4*>(out[m]->p);
+    if (bf16)
+      launch_peer_reduce<uint16_t>(srcs[set], k, v0, v1, dst, reduce_grid[m], ts[m]->s);
+    else
+      launch_peer_reduce<float>(srcs[set], k, v0, v1, dst, reduce_grid[m], ts[m]->s);
+  }
+
+  // One all-reduce of input set `set`, enqueued on every member's stream.  Every e1 / e2 is recorded
+  // before any stream is made to wait for it (a wait for an event never recorded is no wait).
+  void round(int set) {
+    for (int m = 0; m < k; ++m) {
+      DeviceGuard g(devs[m]);
+      if (!twoshot) {
+        reduce(m, set, 0, n_vec);
+        continue;
+      }
+      if (rounds_done)
+        for (int p = 0; p < k; ++p)
+          if (p != m) HIP_CHECK(hipStreamWaitEvent(ts[m]->s, e2[p], 0));
+      reduce(m, set, plan[m].first, plan[m].first + plan[m].count);
+      HIP_CHECK(hipEventRecord(e1[m], ts[m]->s));
+    }
+    for (int m = 0; twoshot && m < k; ++m) {
+      DeviceGuard g(devs[m]);
+      for (int p = 0; p < k; ++p)
+        if (p != m) HIP_CHECK(hipStreamWaitEvent(ts[m]->s, e1[p], 0));
+      peer_allgather_kernel<<<dim3(gather_grid_[m]), dim3(kBlock), 0, ts[m]->s>>>(gather[m], k - 1, (u32x4*)out[m]->p);
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipEventRecord(e2[m], ts[m]->s));
+    }
+    ++rounds_done;
+  }
+
+  void sync_all() {
+    for (int m = 0; m < k; ++m) {
+      DeviceGuard g(devs[m]);
+      HIP_CHECK(hipStreamSynchronize(ts[m]->s));
+    }
+  }
+
+  // in[set][m] = pattern(seed_of(set, m)), padding zero.
+  static unsigned int seed_of(int set, int m) { return 0x243f6a88u ^ (unsigned)(set * 0x9e3779b9u) ^ (unsigned)(m * 7919 + 1); }
+  void fill(int set) {
+    for (int m = 0; m < k; ++m) {
+      DeviceGuard g(devs[m]);
+      const dim3 grid(num_cus(devs[m]) * 4), block(kBlock);
+      if (bf16)
+        peer_fill_kernel<uint16_t><<<grid, block>>>((uint16_t*)in[set][m]->p, count, padded(), seed_of(set, m));
+      else
+        peer_fill_kernel<float><<<grid, block>>>((float*)in[set][m]->p, count, padded(), seed_of(set, m));
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipDeviceSynchronize());
+    }
+  }
+
+  // Elements of every member's `out` (padding included) that are not the sum of set `set`'s patterns.
+  unsigned long long wrong(int set) {
+    SeedSet seeds{};
+    for (int m = 0; m < k; ++m) seeds.s[m] = seed_of(set, m);
+    unsigned long long total = 0;
+    for (int m = 0; m < k; ++m) {
+      DeviceGuard g(devs[m]);
+      DevBuf bad(devs[m], sizeof(unsigned long long));
+      HIP_CHECK(hipMemset(bad.p, 0, sizeof(unsigned long long)));
+      const dim3 grid(num_cus(devs[m]) * kBlocksPerCU), block(kBlock);
+      if (bf16)
+        peer_check_kernel<uint16_t><<<grid, block>>>((const uint16_t*)out[m]->p, count, padded(), seeds, k,
+                                                     (unsigned long long*)bad.p);
+      else
+        peer_check_kernel<float><<<grid, block>>>((const float*)out[m]->p, count, padded(), seeds, k,
+                                                  (unsigned long long*)bad.p);
+      HIP_CHECK(hipGetLastError());
+      unsigned long long n = 0;
+      HIP_CHECK(hipMemcpy(&n, bad.p, sizeof(n), hipMemcpyDeviceToHost));
+      total += n;
+    }
+    return total;
+  }
+
+ private:
+  void release() noexcept {
+    ts.clear();  // synchronises every stream first
+    for (int m = 0; m < k; ++m) {
+      int prev = 0;
+      (void)hipGetDevice(&prev);
+      (void)hipSetDevice(devs[m]);
+      if (e1[m]) (void)hipEventDestroy(e1[m]);
+      if (e2[m]) (void)hipEventDestroy(e2[m]);
+      e1[m] = e2[m] = nullptr;
+      (void)hipSetDevice(prev);
+    }
+  }
+};
+
+py::dict peer_allreduce(const std::vector<int>& devs, size_t count, const std::string& dtype, const std::string& algo,
+                        int iters, int warmup, int blocks_per_cu) {
+  PeerAllreduce::check_args(devs, count, dtype, algo);
+  if (iters < 1 || warmup < 0) throw std::invalid_argument("iters >= 1, warmup >= 0");
+  const int k = (int)devs.size();
+  std::vector<double> ms_member(k, 0.0);
+  double wall_ms = 0.0;
+  unsigned long long wrong = 0;
+  size_t bytes = 0;
+  {
+    py::gil_scoped_release nogil;
+    // with more than one round, consecutive rounds alternate between two input sets and the check uses
+    // the last round's: a round that ran ahead of the one before it leaves a mix of the two sums
+    const int total = warmup + iters;
+    PeerAllreduce ar(devs, count, dtype, algo, total >= 2 ? 2 : 1, blocks_per_cu);
+    bytes = count * ar.elem;
+    for (int s = 0; s < ar.nsets; ++s) ar.fill(s);
+    int r = 0;
+    for (; r < warmup; ++r) ar.round(r % ar.nsets);
+    ar.sync_all();
+    auto t0 = std::chrono::steady_clock::now();
+    for (int m = 0; m < k; ++m) {
+      DeviceGuard g(devs[m]);
+      ar.ts[m]->begin();
+    }
+    for (; r < total; ++r) ar.round(r % ar.nsets);
+    for (int m = 0; m < k; ++m) {
+      DeviceGuard g(devs[m]);
+      ar.ts[m]->end();
+    }
+    ar.sync_all();
+    wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    for (int m = 0; m < k; ++m) {
+      DeviceGuard g(devs[m]);
+      ms_member[m] = ar.ts[m]->ms();
+    }
+    wrong = ar.wrong((total - 1) % ar.nsets);
+  }
+  const double time_us = *std::max_element(ms_member.begin(), ms_member.end()) * 1e3 / iters;
+  py::dict r;
+  r["devs"] = devs;
+  r["dtype"] = dtype;
+  r["algo"] = algo;
+  r["iters"] = iters;
+  r["bytes"] = bytes;
+  r["count"] = count;
+  r["time_us"] = time_us;
+  r["algbw_gbps"] = (double)bytes / (time_us * 1e-6) / 1e9;
+  r["busbw_gbps"] = (double)bytes / (time_us * 1e-6) / 1e9 * (2.0 * (k - 1) / k);
+  r["ms_member"] = ms_member;
+  r["wall_ms"] = wall_ms;
+  r["wrong"] = wrong;
+  r["ok"] = wrong == 0;
+  return r;
+}
+
+// The same all-reduce on the caller's data: k one-dimensional arrays of equal length (uint16 bit
+// patterns for bf16, float32 for fp32) in, the k members' results out, after `rounds` all-reduces of
+// the same inputs.
+py::list peer_allreduce_arrays(const std::vector<int>& devs, const std::vector<py::array>& inputs, const std::string& dtype,
+                               const std::string& algo, int rounds) {
+  if (inputs.size() != devs.size()) throw std::invalid_argument("one input array per member");
+  const size_t count = inputs.empty() ? 0 : (size_t)inputs[0].size();
+  PeerAllreduce::check_args(devs, count, dtype, algo);
+  if (count > PeerAllreduce::kMaxCount) throw std::invalid_argument("count <= 64 Mi elements");
+  if (rounds < 1) throw std::invalid_argument("rounds >= 1");
+  const py::dtype want = dtype == "bf16" ? py::dtype::of<uint16_t>() : py::dtype::of<float>();
+  const int k = (int)devs.size();
+  std::vector<py::array> src, dst;
+  for (const py::array& a : inputs) {
+    if (a.ndim() != 1 || (size_t)a.size() != count || !a.dtype().is(want))
+      throw std::invalid_argument("inputs: one-dimensional arrays of one length, uint16 (bf16) or float32 (fp32)");
+    src.push_back(py::array::ensure(a, py::array::c_style));
+    dst.push_back(py::array(want, std::vector<py::ssize_t>{(py::ssize_t)count}));
+  }
+  std::vector<const void*> from(k);
+  std::vector<void*> to(k);
+  for (int m = 0; m < k; ++m) {
+    from[m] = src[m].data();
+    to[m] = dst[m].mutable_data();
+  }
+  {
+    py::gil_scoped_release nogil;
+    PeerAllreduce ar(devs, count, dtype, algo, 1, kBlocksPerCU);
+    for (int m = 0; m < k; ++m) {
+      DeviceGuard g(devs[m]);
+      HIP_CHECK(hipMemset(ar.in[0][m]->p, 0, ar.n_vec * 16));
+      HIP_CHECK(hipMemcpy(ar.in[0][m]->p, from[m], count * ar.elem, hipMemcpyHostToDevice));
+      HIP_CHECK(hipDeviceSynchronize());
+    }
+    for (int r = 0; r < rounds; ++r) ar.round(0);
+    ar.sync_all();
+    for (int m = 0; m < k; ++m) {
+      DeviceGuard g(devs[m]);
+      HIP_CHECK(hipMemcpy(to[m], ar.out[m]->p, count * ar.elem, hipMemcpyDeviceToHost));
+    }
+  }
+  py::list r;
+  for (py::array& a : dst) r.append(a);
+  return r;
+}
+
 py::dict to_dict(const CopyResult& c) {
   py::dict r;
   r["src"] = c.src;
@@ -883,6 +1204,12 @@ PYBIND11_MODULE(_probe, m) {
         py::arg("iters") = 3, py::arg("warmup") = 1, py::arg("blocks_per_cu") = kBlocksPerCU);
   m.def("ring_bw", &ring_bw, py::arg("devs"), py::arg("peers"), py::arg("bytes") = (size_t)64 << 20, py::arg("iters") = 3,
         py::arg("warmup") = 1, py::arg("blocks_per_cu") = kBlocksPerCU);
+  m.def("peer_allreduce", &peer_allreduce, py::arg("devs"), py::arg("count"), py::arg("dtype") = "bf16",
+        py::arg("algo") = "twoshot", py::arg("iters") = 3, py::arg("warmup") = 1, py::arg("blocks_per_cu") = kBlocksPerCU,
+        "K7: timed all-reduce (sum) of device-made inputs over peer pointers; every member's result checked");
+  m.def("peer_allreduce_arrays", &peer_allreduce_arrays, py::arg("devs"), py::arg("inputs"), py::arg("dtype") = "bf16",
+        py::arg("algo") = "twoshot", py::arg("rounds") = 1,
+        "K7 on the caller's arrays (uint16 bit patterns for bf16, float32 for fp32): the k members' results");
   m.def("mfma_warmup", &mfma_warmup, py::arg("dev"), py::arg("target_ms") = 50.0, py::arg("iters_per_launch") = 4096,
         py::arg("random_operands") = false);
   m.def("probe_matrix", &probe_matrix, py::arg("devs"), py::arg("bytes") = (size_t)256 << 20, py::arg("iters") = 5,

@@ -7,7 +7,8 @@
   config    emit the scheduler config: ``scheduler`` (KubeSchedulerConfiguration), ``policy``
             (the reference's legacy Policy JSON, design.md:92-113) or ``manifests`` (deploy YAML)
   validate  RCCL all-reduce over the allocated devices (GTK_GPU_GROUP or --devices): the
-            placement validator of SURVEY.md §3.5 (flow step 8)
+            placement validator of SURVEY.md §3.5 (flow step 8); --backend peer runs the K7 peer
+            all-reduce of csrc/probe instead, which needs no RCCL
   sim       run a small in-process cluster and print the scheduling decisions
   doctor    node / pod readiness checks (device nodes, discovery, extensions, IPC mode, CPU affinity,
             a pod's GROUP, cpuset and share guard), one JSON line each; --gpu adds HIP checks
@@ -389,17 +390,41 @@ def cmd_validate(a) -> int:
     if a.resolve_only:
         print(json.dumps({"hip_devices": devs}))
         return 0
-    rccl = load("_rccl")
-    sizes = rccl.size_sweep(a.min_bytes, a.max_bytes, a.factor)
-    pts = rccl.local_sweep(devs, sizes, a.dtype, a.iters, a.warmup, False, True)
+    extra = {}
+    if a.backend == "peer":  # K7, this repository's own kernels: _rccl (and librccl) are never loaded
+        from .ops.probe import peer_sweep
+
+        if a.dtype not in ("bf16", "fp32"):
+            raise SystemExit("--backend peer sums bf16 or fp32")
+        if not 2 <= len(devs) <= 16:
+            raise SystemExit(f"--backend peer takes 2 to 16 members, got {devs} (a device may repeat: --devices 0,0)")
+        keys = ("bytes", "count", "time_us", "algbw_gbps", "busbw_gbps", "wrong")
+        pts = [{**{k: p[k] for k in keys}, "backend": "peer", "algo": p["algo"]}
+               for p in peer_sweep(devs, _size_sweep(a.min_bytes, a.max_bytes, a.factor), a.dtype, a.algo, a.iters, a.warmup)]
+        extra = {"backend": "peer", "algo": a.algo}
+    else:
+        rccl = load("_rccl")
+        sizes = rccl.size_sweep(a.min_bytes, a.max_bytes, a.factor)
+        pts = rccl.local_sweep(devs, sizes, a.dtype, a.iters, a.warmup, False, True)
     wrong = sum(p["wrong"] for p in pts)
     peak = max(pts, key=lambda p: p["busbw_gbps"] if len(devs) > 1 else p["algbw_gbps"])
     for p in pts:
         print(json.dumps({"k": len(devs), "devices": devs, **p}))
     print(json.dumps({"summary": True, "k": len(devs), "devices": devs, "wrong": wrong, "peak_bytes": peak["bytes"],
                       "peak_algbw_gbps": round(peak["algbw_gbps"], 2), "peak_busbw_gbps": round(peak["busbw_gbps"], 2),
-                      "cpuset_applied": {k: cpu_rep.get(k) for k in ("applied", "source", "cpus", "n", "reason")}}))
+                      "cpuset_applied": {k: cpu_rep.get(k) for k in ("applied", "source", "cpus", "n", "reason")}, **extra}))
     return 1 if wrong else 0
+
+
+def _size_sweep(min_bytes: int, max_bytes: int, factor: int) -> List[int]:
+    """The sizes ``_rccl.size_sweep`` gives: ``min_bytes`` (at least 4) times powers of ``factor`` (at
+    least 2) up to ``max_bytes``."""
+    factor = max(2, factor)
+    out, b = [], max(min_bytes, 4)
+    while b <= max_bytes:
+        out.append(b)
+        b *= factor
+    return out
 
 
 def cmd_sim(a) -> int:
@@ -522,6 +547,9 @@ def main(argv=None) -> int:
     p.add_argument("--iters", type=int, default=20)
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--cpu-bind", default="env", choices=["env", "off"], help="pin to GTK_CPUSET (the pod's cores) or not")
+    p.add_argument("--backend", default="rccl", choices=["rccl", "peer"],
+                   help="rccl: librccl's all-reduce; peer: this repository's K7 kernels over peer pointers (no RCCL; bf16|fp32)")
+    p.add_argument("--algo", default="both", choices=["oneshot", "twoshot", "both"], help="--backend peer: K7 algorithm(s)")
     p.set_defaults(fn=cmd_validate)
     p = sub.add_parser("doctor", help="node / pod readiness checks (JSON lines); exit 1 on any failure")
     p.add_argument("--discovery", default="auto", choices=["auto", "amdsmi", "sysfs", "fake"])

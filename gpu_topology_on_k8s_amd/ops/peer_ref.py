@@ -1,0 +1,47 @@
+"""CPU reference of the K7 peer all-reduce (``csrc/probe/peer_allreduce.h``), pure numpy.
+
+The kernels sum every element in fp32 in member order, ``((x0 + x1) + x2) + ...``, and round once,
+so a sequential numpy sum reproduces their result bit for bit; :func:`peer_slices` is the driver's
+slice plan of the two-shot algorithm.
+"""
+from __future__ import annotations
+
+from typing import List, Sequence, Tuple
+
+import numpy as np
+
+__all__ = ["peer_slices", "bf16_round", "bf16_to_f32", "allreduce_ref"]
+
+
+def peer_slices(n_vec: int, k: int) -> List[Tuple[int, int]]:
+    """``[first, end)`` in 16-byte vectors of each of ``k`` members' slice of ``n_vec`` vectors:
+    ``per = ceil(n_vec / k)`` vectors each, the last one ragged, trailing ones possibly empty."""
+    if k < 1 or n_vec < 0:
+        raise ValueError("k >= 1 and n_vec >= 0")
+    per = -(-n_vec // k)
+    return [(min(n_vec, s * per), min(n_vec, (s + 1) * per)) for s in range(k)]
+
+
+def bf16_round(x: np.ndarray) -> np.ndarray:
+    """bf16 bit patterns (uint16) of finite float32 ``x``, round to nearest even on the bit pattern."""
+    b = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
+    return ((b + (np.uint32(0x7FFF) + ((b >> np.uint32(16)) & np.uint32(1)))) >> np.uint32(16)).astype(np.uint16)
+
+
+def bf16_to_f32(bits: np.ndarray) -> np.ndarray:
+    """float32 values of bf16 bit patterns (uint16)."""
+    return (np.ascontiguousarray(bits, dtype=np.uint16).astype(np.uint32) << np.uint32(16)).view(np.float32)
+
+
+def allreduce_ref(inputs: Sequence[np.ndarray], dtype: str) -> np.ndarray:
+    """What every member holds after the all-reduce of ``inputs`` (finite values; uint16 bit patterns
+    for ``bf16``, float32 for ``fp32``): a sequential fp32 sum in member order, rounded once."""
+    if dtype not in ("bf16", "fp32"):
+        raise ValueError(f"dtype must be bf16|fp32, got {dtype!r}")
+    if not inputs:
+        raise ValueError("no inputs")
+    wide = [bf16_to_f32(a) if dtype == "bf16" else np.ascontiguousarray(a, dtype=np.float32) for a in inputs]
+    acc = wide[0].copy()
+    for x in wide[1:]:
+        acc = (acc + x).astype(np.float32)
+    return bf16_round(acc) if dtype == "bf16" else acc

@@ -27,7 +27,7 @@ log = logging.getLogger(__name__)
 
 __all__ = ["device_count", "device_props", "warmup", "copy_bw", "gather_bw", "measure_matrix", "measure_ingress",
            "probe_topology", "probe_in_child", "ingress_bound", "ring_peers", "ring_bw", "measure_ring", "ring_in_child",
-           "PROBE_PRESETS"]
+           "peer_allreduce", "peer_allreduce_arrays", "peer_sweep", "PEER_ALGOS", "PROBE_PRESETS"]
 
 #: bytes per transfer / timed iterations / repeats of every pair (the link's median is published, its
 #: spread decides which links are noise-equivalent: ops/checks.py band_links); sizes exceed the 256 MiB
@@ -126,6 +126,47 @@ def ring_in_child(devs: Sequence[int], preset: str = "quick", timeout: float = 1
     if p.returncode != 0 or not lines:
         return None, f"ring probe exited {p.returncode}: {(p.stderr or p.stdout).strip()[-400:]}"
     return json.loads(lines[-1]), "ok"
+
+
+#: K7 algorithms.  Neither is preferred by size: where two-shot overtakes one-shot on xGMI has not been
+#: measured, so ``peer_sweep(..., algo="both")`` reports it per size instead of assuming a cutoff.
+PEER_ALGOS = ("oneshot", "twoshot")
+
+
+def peer_allreduce(devs: Sequence[int], count: int, dtype: str = "bf16", algo: str = "twoshot", iters: int = 3,
+                   warmup_iters: int = 1, blocks_per_cu: int = 8) -> Dict[str, object]:
+    """K7: all-reduce (sum) of ``count`` elements over the members ``devs`` (HIP ordinals, which may
+    repeat) by this repository's own peer kernels, timed like ``_rccl.local_sweep`` (``algbw_gbps``,
+    ``busbw_gbps`` = algBW x 2(k-1)/k) and checked on every member (``wrong``, ``ok``)."""
+    return dict(_p().peer_allreduce([int(d) for d in devs], int(count), dtype, algo, int(iters), int(warmup_iters),
+                                    int(blocks_per_cu)))
+
+
+def peer_allreduce_arrays(devs: Sequence[int], inputs: Sequence[np.ndarray], dtype: str = "bf16", algo: str = "twoshot",
+                          rounds: int = 1) -> List[np.ndarray]:
+    """K7 on the caller's data: one array per member (uint16 bit patterns for ``bf16``, float32 for
+    ``fp32``) in, every member's result out; ``ops.peer_ref.allreduce_ref`` gives the same bits."""
+    return list(_p().peer_allreduce_arrays([int(d) for d in devs], list(inputs), dtype, algo, int(rounds)))
+
+
+def peer_sweep(devs: Sequence[int], sizes: Sequence[int], dtype: str = "bf16", algo: str = "both", iters: int = 3,
+               warmup_iters: int = 1) -> List[Dict[str, object]]:
+    """K7 at every size (bytes) under ``algo`` (``oneshot``, ``twoshot`` or ``both``): one dict per size
+    and algorithm, in size order, with ``fastest`` marking the quicker algorithm of each size."""
+    if algo != "both" and algo not in PEER_ALGOS:
+        raise ValueError(f"algo must be oneshot|twoshot|both, got {algo!r}")
+    elem = {"bf16": 2, "fp32": 4}.get(dtype)
+    if elem is None:
+        raise ValueError(f"dtype must be bf16|fp32, got {dtype!r}")
+    out: List[Dict[str, object]] = []
+    for nbytes in sizes:
+        pts = [peer_allreduce(devs, max(1, int(nbytes) // elem), dtype, a, iters, warmup_iters)
+               for a in (PEER_ALGOS if algo == "both" else (algo,))]
+        best = min(pts, key=lambda p: p["time_us"])
+        for p in pts:
+            p["fastest"] = p is best
+        out.extend(pts)
+    return out
 
 
 def _device_map(topo: Topology, dmap: Optional[DeviceMap]) -> DeviceMap:
