@@ -19,6 +19,8 @@
 //   K7 allreduce : the sum of every member's buffer, in every member's output, by kernels over peer
 //                  pointers (peer_allreduce.h): a fixed summation order, so the result is exact
 //                  against a CPU sum; the repository's own collective, next to RCCL's.
+//   K8 latency   : one wave follows a chain of dependent loads through a buffer of another device
+//                  (chase_latency.h): nanoseconds per access over the link, next to K1's GB/s.
 //   IPC read     : the K1 kernel on a buffer another process exported with hipIpcGetMemHandle (the
 //                  mapping RCCL's P2P transport gives a rank of its peers' buffers).
 // The copy kernel exists in two staging forms (LDS-DMA and plain register staging) so the
@@ -127,6 +129,7 @@ __global__ __launch_bounds__(kBlock) void gather_lds_kernel(SrcSet srcs, int nsr
 
 }  // namespace
 #include "peer_allreduce.h"  // K7 kernels, over SrcSet / kMaxSrc above
+#include "chase_latency.h"   // K8 kernels and the chain's closed form
 namespace {
 
 // Register-staged variant of the same stream (kUnroll independent 16-B loads in flight per lane).
@@ -910,6 +913,184 @@ py::list peer_allreduce_arrays(const std::vector<int>& devs, const std::vector<p
   return r;
 }
 
+// K8 link latency: one wave on `exec_dev` follows a chain of dependent loads (chase_latency.h) that
+// lives in the memory of the chain's device, the orientation of copy_bw in read mode: the number for
+// (src, exec) sits where K1's GB/s for (src, dst) sits.  Time is taken inside the kernel (wall clock
+// around the loop), so launch and completion overheads are outside it; the hipEvent time of the same
+// launch is reported next to it.  Lane l starts (l * n) / chains hops from node 0, so lanes are spread
+// evenly over the cycle, and launch j + 1 continues where launch j ended: no line is visited twice
+// until hops x launches reaches n / chains.  After every launch the host compares every lane's
+// position with the chain's closed form.
+//   evict   : before the first launch a 512 MiB scratch buffer of the owning device is streamed with
+//             fill_pattern, so the 256 MiB Infinity Cache does not hold freshly written chain lines.
+//   !evict  : one untimed lap over all n nodes first (up to 64 lanes, each its own n / lanes stretch),
+//             so that a small working set is resident before it is timed.
+struct ChaseResult {
+  std::vector<double> kernel_ns, event_ms;  // per timed launch
+  std::vector<unsigned int> end;            // node index per lane after the last launch
+  bool ok = true;
+  int rate_khz = 0;
+};
+
+class ChaseChain {
+ public:
+  static constexpr size_t kMaxBytes = (size_t)4 << 30;
+  static constexpr size_t kEvictBytes = (size_t)512 << 20;
+  static constexpr int kMaxHops = 1 << 18, kMaxLaunches = 64;
+
+  static void check_chain(size_t ws_bytes, size_t stride) {
+    auto pow2 = [](size_t x) { return x != 0 && (x & (x - 1)) == 0; };
+    if (!pow2(stride) || stride < 4) throw std::invalid_argument("stride: a power of two >= 4");
+    if (!pow2(ws_bytes) || ws_bytes > kMaxBytes) throw std::invalid_argument("ws_bytes: a power of two <= 4 GiB");
+    if (ws_bytes / stride < 2) throw std::invalid_argument("ws_bytes / stride: at least 2 nodes");
+  }
+  static void check_run(int hops, int chains, int iters, int warmup) {
+    if (chains < 1 || chains > kChaseMaxChains) throw std::invalid_argument("1 <= chains <= 64");
+    if (hops < 1 || hops > kMaxHops) throw std::invalid_argument("1 <= hops <= 2^18");
+    if (warmup < 0 || iters + warmup > kMaxLaunches) throw std::invalid_argument("warmup >= 0, iters + warmup <= 64");
+    check_bytes_iters(kEvictBytes, iters);
+  }
+  static void check_dev(int dev) {
+    int ndev = 0;
+    HIP_CHECK(hipGetDeviceCount(&ndev));
+    if (dev < 0 || dev >= ndev) throw std::invalid_argument("device index out of range");
+  }
+
+  // Allocates the chain on `dev` and writes it there, once for every run() that follows.
+  ChaseChain(int dev, size_t ws_bytes, size_t stride) : dev_(dev), ws_(ws_bytes), stride_(stride) {
+    check_chain(ws_bytes, stride);
+    check_dev(dev);
+    n_ = ws_bytes / stride;
+    while (((size_t)1 << log2_stride_) < stride) ++log2_stride_;
+    py::gil_scoped_release nogil;
+    buf_.reset(new DevBuf(dev, ws_bytes));
+    DeviceGuard g(dev);
+    const int grid = (int)std::min<size_t>((size_t)num_cus(dev) * 4, (n_ + kBlock - 1) / kBlock);
+    chase_fill_kernel<<<dim3(grid), dim3(kBlock)>>>((unsigned char*)buf_->p, n_, log2_stride_);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+  }
+  ChaseChain(const ChaseChain&) = delete;
+  ChaseChain& operator=(const ChaseChain&) = delete;
+
+  ChaseResult run(int exec_dev, int hops, int chains, int iters, int warmup, bool evict) {
+    check_run(hops, chains, iters, warmup);
+    check_dev(exec_dev);
+    enable_peer(exec_dev, dev_);
+    if (evict) {
+      if (!scratch_) scratch_.reset(new DevBuf(dev_, kEvictBytes));
+      fill_pattern(dev_, scratch_->p, kEvictBytes, 0xe71c7u);
+    }
+    ChaseResult r;
+    DeviceGuard g(exec_dev);
+    HIP_CHECK(hipDeviceGetAttribute(&r.rate_khz, hipDeviceAttributeWallClockRate, exec_dev));
+    if (r.rate_khz <= 0) throw std::runtime_error("hipDeviceAttributeWallClockRate is not positive");
+    DevBuf pos(exec_dev, kChaseMaxChains * sizeof(unsigned int)), ticks(exec_dev, sizeof(unsigned long long));
+    TimedStream t;
+    const unsigned int off_mask = (unsigned int)(n_ - 1) << log2_stride_;
+    std::vector<unsigned int> host(kChaseMaxChains, 0u);
+    // every lane's node index, to the device as byte offsets and back
+    auto put = [&](const std::vector<unsigned int>& nodes) {
+      for (size_t l = 0; l < nodes.size(); ++l) host[l] = nodes[l] << log2_stride_;
+      HIP_CHECK(hipMemcpyAsync(pos.p, host.data(), host.size() * sizeof(unsigned int), hipMemcpyHostToDevice, t.s));
+      HIP_CHECK(hipStreamSynchronize(t.s));
+    };
+    auto starts = [&](int lanes) {
+      std::vector<unsigned int> s(lanes);
+      for (int l = 0; l < lanes; ++l) s[l] = chain_skip(0u, (unsigned long long)l * n_ / lanes, n_);
+      return s;
+    };
+    auto launch = [&](int lanes, int h) {
+      chase_kernel<<<dim3(1), dim3(64), 0, t.s>>>((const unsigned char*)buf_->p, off_mask, (unsigned int*)pos.p, lanes, h,
+                                                  (unsigned long long*)ticks.p);
+      HIP_CHECK(hipGetLastError());
+    };
+    if (!evict) {
+      const int lanes = (int)std::min<size_t>(kChaseMaxChains, n_);
+      put(starts(lanes));
+      for (size_t left = n_ / lanes; left;) {
+        const int h = (int)std::min<size_t>(left, kMaxHops);
+        launch(lanes, h);
+        HIP_CHECK(hipStreamSynchronize(t.s));
+        left -= h;
+      }
+    }
+    std::vector<unsigned int> want = starts(chains);
+    put(want);
+    const ChainMap step = chain_power((unsigned long long)hops);
+    for (int j = 0; j < warmup + iters; ++j) {
+      t.begin();
+      launch(chains, hops);
+      const float ms = t.end_ms();
+      unsigned long long tk = 0;
+      HIP_CHECK(hipMemcpyAsync(&tk, ticks.p, sizeof(tk), hipMemcpyDeviceToHost, t.s));
+      HIP_CHECK(hipMemcpyAsync(host.data(), pos.p, host.size() * sizeof(unsigned int), hipMemcpyDeviceToHost, t.s));
+      HIP_CHECK(hipStreamSynchronize(t.s));
+      for (int l = 0; l < chains; ++l) {
+        want[l] = step(want[l]) & (unsigned int)(n_ - 1);
+        r.ok = r.ok && host[l] == (want[l] << log2_stride_);
+      }
+      if (j >= warmup) {
+        r.kernel_ns.push_back((double)tk * 1e6 / r.rate_khz);
+        r.event_ms.push_back((double)ms);
+      }
+    }
+    r.end.resize(chains);
+    for (int l = 0; l < chains; ++l) r.end[l] = host[l] >> log2_stride_;
+    return r;
+  }
+
+  py::dict run_py(int exec_dev, int hops, int chains, int iters, int warmup, bool evict) {
+    ChaseResult c;
+    {
+      py::gil_scoped_release nogil;
+      c = run(exec_dev, hops, chains, iters, warmup, evict);
+    }
+    std::vector<double> per(c.kernel_ns);
+    for (double& x : per) x /= hops;
+    std::vector<double> sorted(per);
+    std::sort(sorted.begin(), sorted.end());
+    const size_t m = sorted.size();
+    py::dict r;
+    r["src"] = dev_;
+    r["exec"] = exec_dev;
+    r["ns_per_hop"] = m % 2 ? sorted[m / 2] : 0.5 * (sorted[m / 2 - 1] + sorted[m / 2]);
+    r["ns_min"] = sorted.front();
+    r["ns_max"] = sorted.back();
+    r["ns_launches"] = per;
+    r["kernel_ns"] = c.kernel_ns;
+    r["event_ms"] = c.event_ms;
+    r["end"] = c.end;
+    r["ok"] = c.ok;
+    r["n_nodes"] = n_;
+    r["hops"] = hops;
+    r["chains"] = chains;
+    r["iters"] = iters;
+    r["stride"] = stride_;
+    r["ws_bytes"] = ws_;
+    r["evicted"] = evict;
+    r["clock_khz"] = c.rate_khz;
+    return r;
+  }
+
+ private:
+  int dev_;
+  size_t ws_, stride_, n_ = 0;
+  unsigned int log2_stride_ = 0;
+  std::unique_ptr<DevBuf> buf_, scratch_;
+};
+
+py::dict chase_latency(int src_dev, int exec_dev, size_t ws_bytes, size_t stride, int hops, int chains, int iters, int warmup,
+                       bool evict) {
+  // every argument is checked before the chain is allocated or anything is launched
+  ChaseChain::check_chain(ws_bytes, stride);
+  ChaseChain::check_run(hops, chains, iters, warmup);
+  ChaseChain::check_dev(src_dev);
+  ChaseChain::check_dev(exec_dev);
+  ChaseChain chain(src_dev, ws_bytes, stride);
+  return chain.run_py(exec_dev, hops, chains, iters, warmup, evict);
+}
+
 py::dict to_dict(const CopyResult& c) {
   py::dict r;
   r["src"] = c.src;
@@ -1210,6 +1391,14 @@ PYBIND11_MODULE(_probe, m) {
   m.def("peer_allreduce_arrays", &peer_allreduce_arrays, py::arg("devs"), py::arg("inputs"), py::arg("dtype") = "bf16",
         py::arg("algo") = "twoshot", py::arg("rounds") = 1,
         "K7 on the caller's arrays (uint16 bit patterns for bf16, float32 for fp32): the k members' results");
+  m.def("chase_latency", &chase_latency, py::arg("src_dev"), py::arg("exec_dev"), py::arg("ws_bytes") = (size_t)1 << 30,
+        py::arg("stride") = (size_t)128, py::arg("hops") = 4096, py::arg("chains") = 1, py::arg("iters") = 5,
+        py::arg("warmup") = 1, py::arg("evict") = true,
+        "K8: ns per dependent load of exec_dev through a chain in src_dev's memory; every launch's end is checked");
+  py::class_<ChaseChain>(m, "ChaseChain", "K8: a chain written once on its device, for run() from several devices")
+      .def(py::init<int, size_t, size_t>(), py::arg("dev"), py::arg("ws_bytes") = (size_t)1 << 30, py::arg("stride") = (size_t)128)
+      .def("run", &ChaseChain::run_py, py::arg("exec_dev"), py::arg("hops") = 4096, py::arg("chains") = 1, py::arg("iters") = 5,
+           py::arg("warmup") = 1, py::arg("evict") = true);
   m.def("mfma_warmup", &mfma_warmup, py::arg("dev"), py::arg("target_ms") = 50.0, py::arg("iters_per_launch") = 4096,
         py::arg("random_operands") = false);
   m.def("probe_matrix", &probe_matrix, py::arg("devs"), py::arg("bytes") = (size_t)256 << 20, py::arg("iters") = 5,

@@ -8,7 +8,7 @@ Targets (all land in ``gpu_topology_on_k8s_amd/_native/``):
   bin/topo_selftest         ASan/UBSan host build of the sysfs reader, fed corrupted trees
   _placement  C++  (g++)    branch-and-bound placement engine
   bin/engine_selftest       ASan/UBSan host build of the engine checked against brute force
-  _probe      HIP  (hipcc)  gfx950 link/HBM probe kernels + MFMA warm-up + peer all-reduce (K7)
+  _probe      HIP  (hipcc)  gfx950 link/HBM probe kernels + MFMA warm-up + peer all-reduce (K7) + latency chase (K8)
   _rccl       HIP  (hipcc)  RCCL all-reduce validator (librccl)
   _fused      HIP  (hipcc)  PyTorch custom ops for the Llama-3 workload (torch headers)
   bin/rccl_allreduce_bench  standalone validator binary
@@ -135,7 +135,7 @@ def targets() -> List[Target]:
                HERE / "bin" / "engine_selftest", ["-g", "-O1", "-fsanitize=address,undefined", "-fno-omit-frame-pointer"],
                deps=[CSRC / "placement" / "engine.h"], pybind=False, shared=False),
         Target("_probe", [CSRC / "probe" / "probe.hip"], "hipcc", HERE / f"_probe{EXT}",
-               deps=[stream_copy, CSRC / "probe" / "peer_allreduce.h"]),
+               deps=[stream_copy, CSRC / "probe" / "peer_allreduce.h", CSRC / "probe" / "chase_latency.h"]),
         Target("_rccl", [CSRC / "rccl" / "rccl_module.hip"], "hipcc", HERE / f"_rccl{EXT}",
                [f"-L{rocm_lib}", "-lrccl", f"-Wl,-rpath,{rocm_lib}"],
                deps=[CSRC / "rccl" / "rccl_core.h", CSRC / "rccl" / "self_copy.h", stream_copy]),

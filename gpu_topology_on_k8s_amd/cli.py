@@ -3,6 +3,7 @@
   topo      discover the node (amdsmi / sysfs / fake) and print the matrix, JSON or annotations
   probe     run the HIP link probe (MFMA warm-up + LDS-staged copies) and print GB/s / cost
   ring      K6: every member of a subset pulls from its peers at once; the busBW ceiling of a ring
+  latency   K8: ns per dependent load of one device from another's memory (pointer chase over the link)
   select    run the placement core on a topology (file, discovery or fake) for k devices
   config    emit the scheduler config: ``scheduler`` (KubeSchedulerConfiguration), ``policy``
             (the reference's legacy Policy JSON, design.md:92-113) or ``manifests`` (deploy YAML)
@@ -94,6 +95,13 @@ def cmd_probe(a) -> int:
         from .ops.probe import measure_ingress
 
         measure_ingress(t, t.probe.get("devices", list(range(t.n))), preset=a.preset)
+        if a.out:  # again before the latency stage
+            with open(a.out, "w") as f:
+                f.write(t.to_json())
+    if a.latency:
+        from .ops.probe import measure_latency
+
+        measure_latency(t, t.probe.get("devices", list(range(t.n))), preset=a.preset)
         if a.out:
             with open(a.out, "w") as f:
                 f.write(t.to_json())
@@ -113,6 +121,34 @@ def cmd_ring(a) -> int:
         return 2
     print(json.dumps(measure_ring(devs, preset=a.preset, patterns=[p for p in a.patterns.split(",") if p])))
     return 0
+
+
+def cmd_latency(a) -> int:
+    """K8: nanoseconds per dependent load of HIP ordinal ``--dst`` from the memory of ``--src``; one
+    JSON line.  Exits 2 on bad arguments (before the native module is loaded) and 1 when a lane did
+    not end where the chain's closed form puts it."""
+    def pow2(x: int) -> bool:
+        return x > 0 and x & (x - 1) == 0
+
+    bad = [msg for cond, msg in (
+        (not pow2(a.stride) or a.stride < 4, "--stride must be a power of two >= 4"),
+        (not pow2(a.ws) or a.ws > 4 << 30, "--ws must be a power of two <= 4 GiB"),
+        (pow2(a.stride) and pow2(a.ws) and a.ws // a.stride < 2, "--ws / --stride must give at least 2 nodes"),
+        (not 1 <= a.chains <= 64, "--chains must be 1..64"),
+        (not 1 <= a.hops <= 1 << 18, "--hops must be 1..262144"),
+        (a.iters < 1 or a.warmup < 0 or a.iters + a.warmup > 64, "--iters >= 1, --warmup >= 0, together <= 64"),
+        (a.src < 0 or a.dst < 0, "--src and --dst are HIP ordinals"),
+    ) if cond]
+    if bad:
+        print("gtk latency: " + "; ".join(bad), file=sys.stderr)
+        return 2
+    from .ops.probe import chase_latency
+
+    r = chase_latency(a.src, a.dst, a.ws, a.stride, a.hops, a.chains, a.iters, a.warmup, evict=not a.no_evict)
+    for k in ("ns_per_hop", "ns_min", "ns_max"):
+        r[k] = round(float(r[k]), 2)
+    print(json.dumps(r))
+    return 0 if r["ok"] else 1
 
 
 def cmd_ipc(a) -> int:
@@ -461,8 +497,22 @@ def main(argv=None) -> int:
     p.add_argument("--preset", default="quick", choices=["quick", "full"])
     p.add_argument("--mode", default="read", choices=["read", "write"])
     p.add_argument("--ingress", action="store_true", help="also measure each GPU's all-peer ingress (K5 gather)")
+    p.add_argument("--latency", action="store_true",
+                   help="also measure every link's dependent-load latency (K8 chase), after --ingress; data only, no cost")
     p.add_argument("--out", default="")
     p.set_defaults(fn=cmd_probe)
+    p = sub.add_parser("latency", help="K8: ns per dependent load of --dst from the memory of --src (pointer chase)")
+    p.add_argument("--src", type=int, required=True, help="HIP ordinal that owns the chain")
+    p.add_argument("--dst", type=int, required=True, help="HIP ordinal that walks it")
+    p.add_argument("--ws", type=int, default=1 << 30, help="working set in bytes, a power of two <= 4 GiB")
+    p.add_argument("--stride", type=int, default=128, help="bytes between nodes, a power of two >= 4")
+    p.add_argument("--hops", type=int, default=4096, help="dependent loads per launch (1..262144)")
+    p.add_argument("--chains", type=int, default=1, help="independent chains, one lane each (1..64)")
+    p.add_argument("--iters", type=int, default=5)
+    p.add_argument("--warmup", type=int, default=1)
+    p.add_argument("--no-evict", action="store_true",
+                   help="walk one untimed lap first instead of streaming 512 MiB over the caches (warm small sets)")
+    p.set_defaults(fn=cmd_latency)
     p = sub.add_parser("ring", help="K6: concurrent ring-pattern probe of a device subset (busBW ceiling)")
     p.add_argument("--devices", default="", help="HIP ordinals (skips GROUP resolution)")
     p.add_argument("--group", default="", help="node-local device indices (default: $GTK_GPU_GROUP)")

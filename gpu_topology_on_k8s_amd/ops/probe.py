@@ -6,6 +6,10 @@ Seeds the link-cost matrix at node start (BASELINE.json north_star; SURVEY.md §
 
 With one visible GPU only the diagonal (K3 HBM self-copy) is measurable; off-diagonal entries are
 left unmeasured (nan) and the cost model falls back to the discovered link class.
+
+Next to the bandwidth, :func:`measure_latency` (K8, a dependent-load chase) stores what one access over
+each link costs in ``topo.probe["latency_us"]``.  It is data only: no exchange rate between latency
+and bandwidth has been measured, so the cost matrix does not read it.
 """
 from __future__ import annotations
 
@@ -27,7 +31,8 @@ log = logging.getLogger(__name__)
 
 __all__ = ["device_count", "device_props", "warmup", "copy_bw", "gather_bw", "measure_matrix", "measure_ingress",
            "probe_topology", "probe_in_child", "ingress_bound", "ring_peers", "ring_bw", "measure_ring", "ring_in_child",
-           "peer_allreduce", "peer_allreduce_arrays", "peer_sweep", "PEER_ALGOS", "PROBE_PRESETS"]
+           "peer_allreduce", "peer_allreduce_arrays", "peer_sweep", "PEER_ALGOS", "PROBE_PRESETS",
+           "chase_latency", "measure_latency", "LATENCY_PRESETS"]
 
 #: bytes per transfer / timed iterations / repeats of every pair (the link's median is published, its
 #: spread decides which links are noise-equivalent: ops/checks.py band_links); sizes exceed the 256 MiB
@@ -167,6 +172,67 @@ def peer_sweep(devs: Sequence[int], sizes: Sequence[int], dtype: str = "bf16", a
             p["fastest"] = p is best
         out.extend(pts)
     return out
+
+
+#: K8: working set and stride of the chain, dependent loads per launch and timed launches of every pair.
+#: 1 GiB is four times the 256 MiB Infinity Cache and the chain is evicted before it is walked, so the
+#: published number is a miss all the way to the owner's HBM (plus the TLB misses of a random 1 GiB walk).
+LATENCY_PRESETS: Dict[str, Dict[str, int]] = {
+    "quick": {"ws_bytes": 1 << 30, "stride": 128, "hops": 4096, "iters": 5, "warmup": 1},
+    "full": {"ws_bytes": 1 << 30, "stride": 128, "hops": 16384, "iters": 5, "warmup": 1},
+}
+
+
+def chase_latency(src: int, dst: int, ws_bytes: int = 1 << 30, stride: int = 128, hops: int = 4096, chains: int = 1,
+                  iters: int = 5, warmup_iters: int = 1, evict: bool = True) -> Dict[str, object]:
+    """K8: one wave on ``dst`` follows ``chains`` chains of ``hops`` dependent loads per launch through
+    a buffer of ``ws_bytes`` in the memory of ``src`` (HIP ordinals; the orientation of :func:`copy_bw`
+    in read mode).  ``ns_per_hop`` is the median over the ``iters`` timed launches of the in-kernel
+    wall-clock time per load, ``ns_min`` / ``ns_max`` their range, ``event_ms`` the hipEvent time of the
+    same launches; ``ok`` says that every lane stood where ``ops.chase_ref.chain_skip`` puts it after
+    every launch.  ``evict`` streams 512 MiB on ``src`` first (a cold chain); without it one untimed lap
+    makes a small working set resident."""
+    return dict(_p().chase_latency(int(src), int(dst), int(ws_bytes), int(stride), int(hops), int(chains), int(iters),
+                                   int(warmup_iters), bool(evict)))
+
+
+def measure_latency(topo: Topology, devs: Sequence[int], preset: str = "quick", dmap: Optional[DeviceMap] = None,
+                    by_package: bool = True) -> List[List[Optional[float]]]:
+    """K8 over the pairs the bandwidth probe walks (:func:`_probe_pairs`): ``latency_us[i][j]`` is the
+    time of one dependent load of device ``j`` from the memory of device ``i`` in microseconds, where
+    ``bw_gbps[i, j]`` sits; the diagonal is the device's own HBM-miss latency; pairs without peer access
+    and devices this process cannot reach stay ``None``.  Every owner's chain is written once and read
+    by each of its readers.  Stored with ``latency_meta`` in ``topo.probe``, next to what is already
+    there.  Published as data only: the cost matrix and the measured bandwidth are not touched."""
+    cfg = LATENCY_PRESETS[preset]
+    m = _device_map(topo, dmap)
+    devs = [d for d in devs if d in m.hip_of_index]
+    t0 = time.time()
+    lat = np.full((topo.n, topo.n), np.nan)
+    pairs, rep = _probe_pairs(topo, devs, by_package)
+    readers_of: Dict[int, List[int]] = {}
+    for i, j in pairs:
+        if i == j or bool(_p().can_access_peer(m.hip(j), m.hip(i))):
+            readers_of.setdefault(i, []).append(j)
+    for i, readers in readers_of.items():
+        chain = _p().ChaseChain(m.hip(i), cfg["ws_bytes"], cfg["stride"])
+        for j in readers:
+            r = dict(chain.run(m.hip(j), cfg["hops"], 1, cfg["iters"], cfg["warmup"], True))
+            if not r["ok"]:
+                raise RuntimeError(f"latency probe verification failed for {i}->{j}")
+            lat[i, j] = float(r["ns_per_hop"]) / 1e3
+        del chain  # the owner's 1 GiB chain and its scratch buffer, before the next owner's are allocated
+    if rep is not None:  # partitioned node: every XCP pair takes its packages' measurement
+        for i in devs:
+            for j in devs:
+                if np.isnan(lat[i, j]):
+                    a, b = rep[(i, j)]
+                    lat[i, j] = lat[a, b]
+    rows = [[None if not np.isfinite(v) else round(float(v), 4) for v in row] for row in lat]
+    meta = {"hops": cfg["hops"], "stride": cfg["stride"], "ws": cfg["ws_bytes"], "iters": cfg["iters"], "preset": preset,
+            "pairs_measured": sum(len(v) for v in readers_of.values()), "seconds": round(time.time() - t0, 3)}
+    topo.probe = dict(topo.probe, latency_us=rows, latency_meta=meta)
+    return rows
 
 
 def _device_map(topo: Topology, dmap: Optional[DeviceMap]) -> DeviceMap:
@@ -355,14 +421,15 @@ def probe_topology(topo: Topology, preset: str = "quick", devs: Optional[List[in
 
 
 def probe_in_child(preset: str = "quick", backend: str = "auto", timeout: float = 150.0,
-                   ingress: bool = True, cancel=None) -> Tuple[Optional[Topology], str]:
+                   ingress: bool = True, cancel=None, latency: bool = False) -> Tuple[Optional[Topology], str]:
     """Discovery + K4 warm-up + K1 p2p read of every visible ordered pair (+ K5 ingress) in a CHILD
     process (``gtk probe --out``), returned as a probed :class:`Topology`.
 
     Long-lived callers (the device-plugin DaemonSet, rank 0 of the bench) must not keep HIP contexts
     and probe buffers on every GPU of the node: the child takes them and exits, and a failure there
     (fault, timeout) cannot take the caller down.  The pairwise matrix is written before the ingress
-    stage runs, so an ingress failure still returns it.  ``cancel`` (a ``threading.Event``): once set,
+    stage runs, so an ingress failure still returns it; ``latency`` adds the K8 stage after it
+    (:func:`measure_latency`), under the same rule.  ``cancel`` (a ``threading.Event``): once set,
     the child is killed and reaped — its GPU memory and queues are gone when this returns — and the
     result is ``(None, "cancelled")`` (the device plugin yields its links to an arriving pod this
     way).  Returns ``(Topology | None, message)``."""
@@ -371,6 +438,8 @@ def probe_in_child(preset: str = "quick", backend: str = "auto", timeout: float 
     cmd = [sys.executable, "-m", "gpu_topology_on_k8s_amd", "probe", "--preset", preset, "--discovery", backend, "--out", path]
     if ingress:
         cmd.append("--ingress")
+    if latency:  # K8 stage, after the ingress stage: the child writes --out before it, too
+        cmd.append("--latency")
     root = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     try:
         p = subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=root)
@@ -394,7 +463,10 @@ def probe_in_child(preset: str = "quick", backend: str = "auto", timeout: float 
             text = f.read()
         if not text:
             return None, err
-        return Topology.from_json(text), ("ok" if p.returncode == 0 else "pairwise only; ingress stage failed: " + err)
+        return Topology.from_json(text), (
+            "ok" if p.returncode == 0 else
+            ("what the stages before the failing one wrote; ingress or latency stage failed: " if latency else
+             "pairwise only; ingress stage failed: ") + err)
     except (OSError, ValueError, KeyError) as e:
         return None, f"probe output unreadable: {e}"
     finally:

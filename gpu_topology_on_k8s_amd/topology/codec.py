@@ -8,7 +8,8 @@ matrices, so a real CPX node could fail to publish at all.  Version 2:
 * device fields are columns, and a column whose values are all equal is one scalar;
 * every matrix is ``"<dtype>:<base64(zlib(bytes))>"`` — link classes and hops as u8, amdsmi weights
   as u32, measured GB/s as f16 (GB/s up to 65504 at 0.05 % resolution, far below run-to-run probe
-  noise), amdsmi max-bandwidth as u32;
+  noise), amdsmi max-bandwidth as u32; the probe's own n x n rows (``raw_gbps``, ``spread`` and K8's
+  ``latency_us``) as f16 too, each only when the probe holds it;
 * ``cost`` is omitted whenever it is what :meth:`Topology.recompute_cost` derives from the other
   fields, which is every probed node.  Measured bandwidth is quantised to f16 *in the model*
   (:meth:`Topology.set_measured_bw`) so the device plugin and the extender derive bit-identical
@@ -31,6 +32,9 @@ __all__ = ["encode_v2", "decode_v2", "pack_matrix", "unpack_matrix"]
 
 _DT = {"u8": np.uint8, "u16": np.uint16, "u32": np.uint32, "i32": np.int32, "f16": np.float16, "f32": np.float32,
        "f64": np.float64}
+
+#: n x n matrices of ``Topology.probe`` (rows of floats, None where unmeasured) that travel as f16 in ``m``
+_PROBE_MATRICES = ("raw_gbps", "spread", "latency_us")
 
 
 def pack_matrix(a: np.ndarray, dtype: str) -> str:
@@ -81,7 +85,9 @@ def encode_v2(topo) -> Dict[str, Any]:
     if topo.ref_class is not None:
         m["ref_class"] = pack_matrix(topo.ref_class, "u8")
     probe = dict(topo.probe or {})
-    for key in ("raw_gbps", "spread"):  # the probe's per-link medians and repeat spreads (ops/checks.py banding)
+    # the probe's per-link medians and repeat spreads (ops/checks.py banding), and K8's per-link latency in
+    # microseconds (f16: 0.05 % resolution, far below the spread between launches); absent ones add no key
+    for key in _PROBE_MATRICES:
         v = probe.pop(key, None)
         if v is not None:
             a = np.array([[np.nan if x is None else float(x) for x in row] for row in v], dtype=np.float64)
@@ -129,7 +135,7 @@ def decode_v2(d: Dict[str, Any]):
         return unpack_matrix(m[key], n) if key in m else None
 
     probe = dict(d.get("probe") or {})
-    for key in ("raw_gbps", "spread"):
+    for key in _PROBE_MATRICES:
         a = mat(key)
         if a is not None:
             probe[key] = [[None if not math.isfinite(x) else float(x) for x in row] for row in a.tolist()]

@@ -20,7 +20,8 @@ sys.path.insert(0, str(REPO))
 
 def kernel_stats(src: str, target: str = "_fused", out: str = "/tmp/gtk_isa.s") -> dict:
     """{kernel symbol: {NumVgprs, NumAgprs, TotalNumSgprs, ScratchSize, LDSByteSize, Occupancy, mfma,
-    ds_read, accvgpr_read, accvgpr_write, accvgpr_mov, s_waitcnt, scratch, total}} of one source."""
+    ds_read, accvgpr_read, accvgpr_write, accvgpr_mov, s_waitcnt, scratch, global_load, s_load, total}} of
+    one source."""
     from gpu_topology_on_k8s_amd._native import build
 
     t = next(x for x in build.targets() if x.name == target)
@@ -42,7 +43,7 @@ def kernel_stats(src: str, target: str = "_fused", out: str = "/tmp/gtk_isa.s") 
                and not ln.strip().endswith(":")]
         for k, pre in (("mfma", "v_mfma"), ("ds_read", "ds_read"), ("accvgpr_read", "v_accvgpr_read"),
                        ("accvgpr_write", "v_accvgpr_write"), ("accvgpr_mov", "v_accvgpr_mov"), ("s_waitcnt", "s_waitcnt"),
-                       ("scratch", "scratch_")):
+                       ("scratch", "scratch_"), ("global_load", "global_load"), ("s_load", "s_load")):
             meta[k] = sum(1 for i in ins if i.startswith(pre))
         meta["total"] = len(ins)
         res[name] = meta
