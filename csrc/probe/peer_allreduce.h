@@ -5,8 +5,10 @@
 //
 // Every member's buffers are padded with zeros to a whole number of vectors by the host driver, so
 // no kernel sees a scalar tail.  The sum of one element is fp32, taken in member order
-// ((x0 + x1) + x2) + ... with no tree and no reassociation, and rounded once: every member computes
-// the same bits, and a sequential CPU sum reproduces them (ops/peer_ref.py).
+// ((x0 + x1) + x2) + ... with no tree and no reassociation, multiplied once by the call's scale (1 for
+// a sum, 1/k for a mean) and rounded once: every member computes the same bits, and a sequential CPU
+// sum reproduces them (ops/peer_ref.py).  The output may be wider than the input: bf16 read over the
+// link, fp32 written, which halves the link traffic of reducing a widened copy.
 //
 // No kernel here waits for another running kernel: the all-reduce's cross-member ordering is stream
 // events between launches (the host driver in probe.hip), visibility rests on kernel boundaries.
@@ -51,12 +53,35 @@ __device__ __forceinline__ u32x4 peer_narrow(const float (&f)[8]) {
   return v;
 }
 
+// One position's result: `scale` applied to the fp32 sum, then a bf16 output rounds once and stores one
+// vector at `o`; an fp32 output of bf16 inputs (the wide form) stores two, at 2 * o and 2 * o + 1, so its
+// offsets and slice bounds are twice the input's.  scale == 1.0f changes no bit of the sum.
+template <typename TO, int L>
+__device__ __forceinline__ void peer_store(float (&acc)[L], float scale, u32x4* __restrict__ dst, size_t o) {
+#pragma unroll
+  for (int j = 0; j < L; ++j) acc[j] = acc[j] * scale;
+  if constexpr (L == kPeerLanes<TO>) {
+    __builtin_nontemporal_store(peer_narrow(acc), dst + o);
+  } else {
+    static_assert(L == 8 && kPeerLanes<TO> == 4, "the wide form is bf16 in, fp32 out");
+    u32x4 lo, hi;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      lo[j] = __float_as_uint(acc[j]);
+      hi[j] = __float_as_uint(acc[4 + j]);
+    }
+    __builtin_nontemporal_store(lo, dst + 2 * o);
+    __builtin_nontemporal_store(hi, dst + 2 * o + 1);
+  }
+}
+
 // U vectors per lane, `stride` apart from `i`: the k x U loads (member-major, all in flight before the
-// first add), then per position the sum in member order, one rounding and one 16-byte store.  KB is
-// the member bucket the registers are sized for (k <= KB): r[] is indexed by constants only.
-template <typename T, int KB, int U>
+// first add), then per position the sum in member order, one multiply by `scale`, one rounding and the
+// store.  TI / TO are the input and output element types.  KB is the member bucket the registers are
+// sized for (k <= KB): r[] is indexed by constants only.
+template <typename TI, typename TO, int KB, int U>
 __device__ __forceinline__ void peer_reduce_vecs(const SrcSet& srcs, int k, u32x4* __restrict__ dst, size_t i,
-                                                 size_t stride) {
+                                                 size_t stride, float scale) {
   u32x4 r[KB][U];
 #pragma unroll
   for (int m = 0; m < KB; ++m)
@@ -66,36 +91,37 @@ __device__ __forceinline__ void peer_reduce_vecs(const SrcSet& srcs, int k, u32x
     }
 #pragma unroll
   for (int u = 0; u < U; ++u) {
-    float acc[kPeerLanes<T>];
+    float acc[kPeerLanes<TI>];
     peer_widen(r[0][u], acc);
 #pragma unroll
     for (int m = 1; m < KB; ++m)
       if (m < k) {
-        float x[kPeerLanes<T>];
+        float x[kPeerLanes<TI>];
         peer_widen(r[m][u], x);
 #pragma unroll
-        for (int j = 0; j < kPeerLanes<T>; ++j) acc[j] = acc[j] + x[j];
+        for (int j = 0; j < kPeerLanes<TI>; ++j) acc[j] = acc[j] + x[j];
       }
-    __builtin_nontemporal_store(peer_narrow(acc), dst + i + (size_t)u * stride);
+    peer_store<TO>(acc, scale, dst, i + (size_t)u * stride);
   }
 }
 
-// dst[v0, v1) = sum over members m < k of srcs.p[m][v0, v1), T = float or bf16 as raw u16.  Whole
+// dst[v0, v1) = scale * sum over members m < k of srcs.p[m][v0, v1), vectors of the input type TI
+// (float, or bf16 as raw u16); the wide form (bf16 in, float out) writes dst[2 * v0, 2 * v1).  Whole
 // tiles (kStreamBlock x U vectors) are cut into one contiguous run per block, as gtk::stream_slices
 // does; what is left of the range, under one tile, goes one vector per lane over the whole grid.
-template <typename T, int KB, int U>
+template <typename TI, typename TO, int KB, int U>
 __global__ __launch_bounds__(gtk::kStreamBlock) void peer_reduce_kernel(SrcSet srcs, int k, size_t v0, size_t v1,
-                                                                        u32x4* __restrict__ dst) {
+                                                                        u32x4* __restrict__ dst, float scale) {
   const size_t tile = (size_t)gtk::kStreamBlock * U;
   const size_t n_tiles = (v1 - v0) / tile;
   const size_t per = (n_tiles + gridDim.x - 1) / gridDim.x;
   const size_t t0 = (size_t)blockIdx.x * per;
   const size_t t1 = std::min(n_tiles, t0 + per);
   for (size_t t = t0; t < t1; ++t)
-    peer_reduce_vecs<T, KB, U>(srcs, k, dst, v0 + t * tile + threadIdx.x, gtk::kStreamBlock);
+    peer_reduce_vecs<TI, TO, KB, U>(srcs, k, dst, v0 + t * tile + threadIdx.x, gtk::kStreamBlock, scale);
   for (size_t i = v0 + n_tiles * tile + (size_t)blockIdx.x * gtk::kStreamBlock + threadIdx.x; i < v1;
        i += (size_t)gridDim.x * gtk::kStreamBlock)
-    peer_reduce_vecs<T, KB, 1>(srcs, k, dst, i, 0);
+    peer_reduce_vecs<TI, TO, KB, 1>(srcs, k, dst, i, 0, scale);
 }
 
 // Slice i of an all-gather: `count` vectors from vector `first` of p[i], to the same offset of dst.

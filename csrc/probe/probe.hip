@@ -41,6 +41,7 @@
 #include <cstdint>
 #include <cstring>
 #include <memory>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -628,18 +629,45 @@ std::vector<PeerSlice> peer_slices(size_t n_vec, int k) {
 }
 
 // Member buckets of peer_reduce_kernel: k x U loads of 16 bytes per lane stay within 64 VGPRs.
-template <typename T>
-void launch_peer_reduce(const SrcSet& set, int k, size_t v0, size_t v1, u32x4* dst, int grid, hipStream_t s) {
+// The wide form (bf16 in, fp32 out) holds the same loads and eight accumulators, so it keeps the same U.
+template <typename TI, typename TO>
+void launch_peer_reduce(const SrcSet& set, int k, size_t v0, size_t v1, u32x4* dst, float scale, int grid, hipStream_t s) {
   const dim3 g(grid), b(kBlock);
   if (k <= 2)
-    peer_reduce_kernel<T, 2, 4><<<g, b, 0, s>>>(set, k, v0, v1, dst);
+    peer_reduce_kernel<TI, TO, 2, 4><<<g, b, 0, s>>>(set, k, v0, v1, dst, scale);
   else if (k <= 4)
-    peer_reduce_kernel<T, 4, 4><<<g, b, 0, s>>>(set, k, v0, v1, dst);
+    peer_reduce_kernel<TI, TO, 4, 4><<<g, b, 0, s>>>(set, k, v0, v1, dst, scale);
   else if (k <= 8)
-    peer_reduce_kernel<T, 8, 2><<<g, b, 0, s>>>(set, k, v0, v1, dst);
+    peer_reduce_kernel<TI, TO, 8, 2><<<g, b, 0, s>>>(set, k, v0, v1, dst, scale);
   else
-    peer_reduce_kernel<T, 16, 1><<<g, b, 0, s>>>(set, k, v0, v1, dst);
+    peer_reduce_kernel<TI, TO, 16, 1><<<g, b, 0, s>>>(set, k, v0, v1, dst, scale);
   HIP_CHECK(hipGetLastError());
+}
+
+// The element types of a reduce: bf16 -> bf16, fp32 -> fp32 and the wide bf16 -> fp32.
+struct PeerTypes {
+  bool in_bf16 = true, out_bf16 = true;
+  size_t in_elem() const { return in_bf16 ? 2 : 4; }
+  size_t out_elem() const { return out_bf16 ? 2 : 4; }
+  size_t ratio() const { return out_elem() / in_elem(); }  // output vectors per input vector
+};
+
+PeerTypes peer_types(const std::string& dtype, const std::string& out_dtype) {
+  if (dtype != "bf16" && dtype != "fp32") throw std::invalid_argument("dtype must be bf16|fp32");
+  const std::string& o = out_dtype.empty() ? dtype : out_dtype;
+  if (o != "bf16" && o != "fp32") throw std::invalid_argument("out_dtype must be bf16|fp32");
+  if (dtype == "fp32" && o == "bf16") throw std::invalid_argument("fp32 inputs reduce to fp32 only");
+  return PeerTypes{dtype == "bf16", o == "bf16"};
+}
+
+void launch_peer_reduce(PeerTypes t, const SrcSet& set, int k, size_t v0, size_t v1, u32x4* dst, float scale, int grid,
+                        hipStream_t s) {
+  if (!t.in_bf16)
+    launch_peer_reduce<float, float>(set, k, v0, v1, dst, scale, grid, s);
+  else if (t.out_bf16)
+    launch_peer_reduce<uint16_t, uint16_t>(set, k, v0, v1, dst, scale, grid, s);
+  else
+    launch_peer_reduce<uint16_t, float>(set, k, v0, v1, dst, scale, grid, s);
 }
 
 struct PeerAllreduce {
@@ -648,6 +676,8 @@ struct PeerAllreduce {
   std::vector<int> devs;
   int k = 0, nsets = 1;
   bool bf16 = true, twoshot = false;
+  PeerTypes types;
+  float scale = 1.0f;
   size_t count = 0, elem = 2, n_vec = 0;
   std::vector<std::unique_ptr<DevBuf>> in[2], out;  // in[set][m]: rounds alternate between the sets
   SrcSet srcs[2]{};
@@ -670,9 +700,9 @@ struct PeerAllreduce {
   }
 
   PeerAllreduce(const std::vector<int>& devs_, size_t count_, const std::string& dtype, const std::string& algo,
-                int nsets_, int blocks_per_cu)
+                int nsets_, int blocks_per_cu, const std::string& out_dtype = "", float scale_ = 1.0f)
       : devs(devs_), k((int)devs_.size()), nsets(nsets_), bf16(dtype == "bf16"), twoshot(algo == "twoshot"),
-        count(count_), elem(dtype == "bf16" ? 2 : 4), n_vec((count_ * (dtype == "bf16" ? 2 : 4) + 15) / 16),
+        types(peer_types(dtype, out_dtype)), scale(scale_), count(count_), elem(dtype == "bf16" ? 2 : 4), n_vec((count_ * (dtype == "bf16" ? 2 : 4) + 15) / 16),
         plan(peer_slices(n_vec, k)), gather(k), reduce_grid(k), gather_grid_(k), e1(k, nullptr), e2(k, nullptr) {
     for (int m = 0; m < k; ++m)
       for (int p = 0; p < k; ++p) enable_peer(devs[m], devs[p]);
@@ -681,7 +711,7 @@ struct PeerAllreduce {
         in[s].emplace_back(new DevBuf(devs[m], n_vec * 16));
         srcs[s].p[m] = reinterpret_cast<const u32x4*>(in[s][m]->p);
       }
-      out.emplace_back(new DevBuf(devs[m], n_vec * 16));
+      out.emplace_back(new DevBuf(devs[m], n_vec * 16 * types.ratio()));
     }
     try {
       for (int m = 0; m < k; ++m) {
@@ -695,8 +725,8 @@ struct PeerAllreduce {
         for (int p = 0; p < k; ++p) {
           if (p == m) continue;
           gather[m].p[i] = reinterpret_cast<const u32x4*>(out[p]->p);
-          gather[m].first[i] = plan[p].first;
-          gather[m].count[i] = plan[p].count;
+          gather[m].first[i] = plan[p].first * types.ratio();  // slices of the output type
+          gather[m].count[i] = plan[p].count * types.ratio();
           ++i;
         }
         DeviceGuard g(devs[m]);
@@ -717,11 +747,7 @@ struct PeerAllreduce {
 
   void reduce(int m, int set, size_t v0, size_t v1) {
     if (v0 == v1) return;
-    auto* dst = reinterpret_cast<u32x4*>(out[m]->p);
-    if (bf16)
-      launch_peer_reduce<uint16_t>(srcs[set], k, v0, v1, dst, reduce_grid[m], ts[m]->s);
-    else
-      launch_peer_reduce<float>(srcs[set], k, v0, v1, dst, reduce_grid[m], ts[m]->s);
+    launch_peer_reduce(types, srcs[set], k, v0, v1, reinterpret_cast<u32x4*>(out[m]->p), scale, reduce_grid[m], ts[m]->s);
   }
 
   // One all-reduce of input set `set`, enqueued on every member's stream.  Every e1 / e2 is recorded
@@ -869,22 +895,24 @@ py::dict peer_allreduce(const std::vector<int>& devs, size_t count, const std::s
 
 // The same all-reduce on the caller's data: k one-dimensional arrays of equal length (uint16 bit
 // patterns for bf16, float32 for fp32) in, the k members' results out, after `rounds` all-reduces of
-// the same inputs.
+// the same inputs.  `out_dtype` (none: the inputs') and `scale` select the wide and the scaled reduce.
 py::list peer_allreduce_arrays(const std::vector<int>& devs, const std::vector<py::array>& inputs, const std::string& dtype,
-                               const std::string& algo, int rounds) {
+                               const std::string& algo, int rounds, const std::optional<std::string>& out_dtype, float scale) {
   if (inputs.size() != devs.size()) throw std::invalid_argument("one input array per member");
   const size_t count = inputs.empty() ? 0 : (size_t)inputs[0].size();
   PeerAllreduce::check_args(devs, count, dtype, algo);
   if (count > PeerAllreduce::kMaxCount) throw std::invalid_argument("count <= 64 Mi elements");
   if (rounds < 1) throw std::invalid_argument("rounds >= 1");
+  const PeerTypes types = peer_types(dtype, out_dtype.value_or(""));
   const py::dtype want = dtype == "bf16" ? py::dtype::of<uint16_t>() : py::dtype::of<float>();
+  const py::dtype give = types.out_bf16 ? py::dtype::of<uint16_t>() : py::dtype::of<float>();
   const int k = (int)devs.size();
   std::vector<py::array> src, dst;
   for (const py::array& a : inputs) {
     if (a.ndim() != 1 || (size_t)a.size() != count || !a.dtype().is(want))
       throw std::invalid_argument("inputs: one-dimensional arrays of one length, uint16 (bf16) or float32 (fp32)");
     src.push_back(py::array::ensure(a, py::array::c_style));
-    dst.push_back(py::array(want, std::vector<py::ssize_t>{(py::ssize_t)count}));
+    dst.push_back(py::array(give, std::vector<py::ssize_t>{(py::ssize_t)count}));
   }
   std::vector<const void*> from(k);
   std::vector<void*> to(k);
@@ -894,7 +922,7 @@ py::list peer_allreduce_arrays(const std::vector<int>& devs, const std::vector<p
   }
   {
     py::gil_scoped_release nogil;
-    PeerAllreduce ar(devs, count, dtype, algo, 1, kBlocksPerCU);
+    PeerAllreduce ar(devs, count, dtype, algo, 1, kBlocksPerCU, out_dtype.value_or(""), scale);
     for (int m = 0; m < k; ++m) {
       DeviceGuard g(devs[m]);
       HIP_CHECK(hipMemset(ar.in[0][m]->p, 0, ar.n_vec * 16));
@@ -905,7 +933,7 @@ py::list peer_allreduce_arrays(const std::vector<int>& devs, const std::vector<p
     ar.sync_all();
     for (int m = 0; m < k; ++m) {
       DeviceGuard g(devs[m]);
-      HIP_CHECK(hipMemcpy(to[m], ar.out[m]->p, count * ar.elem, hipMemcpyDeviceToHost));
+      HIP_CHECK(hipMemcpy(to[m], ar.out[m]->p, count * types.out_elem(), hipMemcpyDeviceToHost));
     }
   }
   py::list r;
@@ -1389,8 +1417,9 @@ PYBIND11_MODULE(_probe, m) {
         py::arg("algo") = "twoshot", py::arg("iters") = 3, py::arg("warmup") = 1, py::arg("blocks_per_cu") = kBlocksPerCU,
         "K7: timed all-reduce (sum) of device-made inputs over peer pointers; every member's result checked");
   m.def("peer_allreduce_arrays", &peer_allreduce_arrays, py::arg("devs"), py::arg("inputs"), py::arg("dtype") = "bf16",
-        py::arg("algo") = "twoshot", py::arg("rounds") = 1,
-        "K7 on the caller's arrays (uint16 bit patterns for bf16, float32 for fp32): the k members' results");
+        py::arg("algo") = "twoshot", py::arg("rounds") = 1, py::arg("out_dtype") = py::none(), py::arg("scale") = 1.0f,
+        "K7 on the caller's arrays (uint16 bit patterns for bf16, float32 for fp32): the k members' results, "
+        "scale x sum, in out_dtype (none: dtype; fp32 of bf16 inputs is the wide reduce)");
   m.def("chase_latency", &chase_latency, py::arg("src_dev"), py::arg("exec_dev"), py::arg("ws_bytes") = (size_t)1 << 30,
         py::arg("stride") = (size_t)128, py::arg("hops") = 4096, py::arg("chains") = 1, py::arg("iters") = 5,
         py::arg("warmup") = 1, py::arg("evict") = true,

@@ -1,16 +1,16 @@
 """CPU reference of the K7 peer all-reduce (``csrc/probe/peer_allreduce.h``), pure numpy.
 
-The kernels sum every element in fp32 in member order, ``((x0 + x1) + x2) + ...``, and round once,
-so a sequential numpy sum reproduces their result bit for bit; :func:`peer_slices` is the driver's
+The kernels sum every element in fp32 in member order, ``((x0 + x1) + x2) + ...``, multiply once by
+the call's scale and round once, so a sequential numpy sum reproduces their result bit for bit; :func:`peer_slices` is the driver's
 slice plan of the two-shot algorithm.
 """
 from __future__ import annotations
 
-from typing import List, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-__all__ = ["peer_slices", "bf16_round", "bf16_to_f32", "allreduce_ref"]
+__all__ = ["peer_slices", "bf16_round", "bf16_to_f32", "allreduce_ref", "reduce_scatter_ref"]
 
 
 def peer_slices(n_vec: int, k: int) -> List[Tuple[int, int]]:
@@ -33,15 +33,39 @@ def bf16_to_f32(bits: np.ndarray) -> np.ndarray:
     return (np.ascontiguousarray(bits, dtype=np.uint16).astype(np.uint32) << np.uint32(16)).view(np.float32)
 
 
-def allreduce_ref(inputs: Sequence[np.ndarray], dtype: str) -> np.ndarray:
-    """What every member holds after the all-reduce of ``inputs`` (finite values; uint16 bit patterns
-    for ``bf16``, float32 for ``fp32``): a sequential fp32 sum in member order, rounded once."""
+def _types(dtype: str, out_dtype: Optional[str]) -> str:
     if dtype not in ("bf16", "fp32"):
         raise ValueError(f"dtype must be bf16|fp32, got {dtype!r}")
+    out = dtype if out_dtype is None else out_dtype
+    if out not in ("bf16", "fp32"):
+        raise ValueError(f"out_dtype must be bf16|fp32, got {out!r}")
+    if dtype == "fp32" and out == "bf16":
+        raise ValueError("fp32 inputs reduce to fp32 only")
+    return out
+
+
+def allreduce_ref(inputs: Sequence[np.ndarray], dtype: str, out_dtype: Optional[str] = None, scale: float = 1.0) -> np.ndarray:
+    """What every member holds after the all-reduce of ``inputs`` (finite values; uint16 bit patterns
+    for ``bf16``, float32 for ``fp32``): a sequential fp32 sum in member order, one fp32 multiply by
+    ``scale`` (rounded to fp32 first, as the kernel's argument is), then one rounding to ``out_dtype``
+    (none: ``dtype``; ``fp32`` of ``bf16`` inputs keeps the fp32 sum)."""
+    out = _types(dtype, out_dtype)
     if not inputs:
         raise ValueError("no inputs")
     wide = [bf16_to_f32(a) if dtype == "bf16" else np.ascontiguousarray(a, dtype=np.float32) for a in inputs]
     acc = wide[0].copy()
     for x in wide[1:]:
         acc = (acc + x).astype(np.float32)
-    return bf16_round(acc) if dtype == "bf16" else acc
+    acc = (acc * np.float32(scale)).astype(np.float32)
+    return bf16_round(acc) if out == "bf16" else acc
+
+
+def reduce_scatter_ref(inputs: Sequence[np.ndarray], dtype: str, out_dtype: Optional[str] = None,
+                       scale: float = 1.0) -> List[np.ndarray]:
+    """Rank r's piece of the reduce-scatter of ``inputs``: the elements of slice r of :func:`peer_slices`
+    over the input's vectors (the last piece ends at the count, trailing pieces may be empty).  The
+    pieces concatenate to :func:`allreduce_ref`."""
+    full = allreduce_ref(inputs, dtype, out_dtype, scale)
+    per = 8 if dtype == "bf16" else 4
+    count = int(full.shape[0])
+    return [full[min(count, a * per):min(count, b * per)] for a, b in peer_slices(-(-count // per), len(inputs))]

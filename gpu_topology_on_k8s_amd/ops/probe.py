@@ -148,10 +148,13 @@ def peer_allreduce(devs: Sequence[int], count: int, dtype: str = "bf16", algo: s
 
 
 def peer_allreduce_arrays(devs: Sequence[int], inputs: Sequence[np.ndarray], dtype: str = "bf16", algo: str = "twoshot",
-                          rounds: int = 1) -> List[np.ndarray]:
+                          rounds: int = 1, out_dtype: Optional[str] = None, scale: float = 1.0) -> List[np.ndarray]:
     """K7 on the caller's data: one array per member (uint16 bit patterns for ``bf16``, float32 for
-    ``fp32``) in, every member's result out; ``ops.peer_ref.allreduce_ref`` gives the same bits."""
-    return list(_p().peer_allreduce_arrays([int(d) for d in devs], list(inputs), dtype, algo, int(rounds)))
+    ``fp32``) in, every member's result out; ``ops.peer_ref.allreduce_ref`` gives the same bits.
+    ``out_dtype="fp32"`` of ``bf16`` inputs is the wide reduce (bf16 read, fp32 summed and written);
+    ``scale`` multiplies the fp32 sum once before the one rounding (``1 / k`` for a mean)."""
+    return list(_p().peer_allreduce_arrays([int(d) for d in devs], list(inputs), dtype, algo, int(rounds), out_dtype,
+                                           float(scale)))
 
 
 def peer_sweep(devs: Sequence[int], sizes: Sequence[int], dtype: str = "bf16", algo: str = "both", iters: int = 3,
