@@ -1,0 +1,121 @@
+#!/usr/bin/env python3
+"""The peer communicator's thread-rank all_reduce next to the in-process driver's, as one JSON document:
+
+    python bench/peer_comm_bench.py [--members 0,0,0,0] [--sizes-mib 1,4,16,64,256] [--dtype bf16]
+                                    [--iters 20] [--warmup 2] [--out FILE] [--md FILE]
+
+Both run the same K7 kernels on the same members at the same count, in one process:
+  * thread ranks (``PeerComm(backend="device")``, one thread per member): host time per ``all_reduce``
+    call, each ending in a stream synchronise, the slowest rank's; and the part of it spent inside the
+    call's two host barriers;
+  * the in-process driver (``ops.probe.peer_allreduce``): one call enqueues every member's launches,
+    ordered by stream events; event-timed per round.
+Per size and algorithm the two are measured alternately, ``--reps`` times each, and the quicker
+repetition of each is reported.  Their ratio is the price of host-synchronous ordering: two store round
+trips and two (two-shot: three) stream synchronisations per call.  Members that repeat a device give
+HBM rates of that one GPU, not xGMI rates.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from gpu_topology_on_k8s_amd.ops import probe  # noqa: E402
+from gpu_topology_on_k8s_amd.ops.peer_ref import allreduce_ref  # noqa: E402
+from gpu_topology_on_k8s_amd.parallel import peer_comm as pc  # noqa: E402
+
+ELEM = {"bf16": 2, "fp32": 4}
+
+
+def measure(devs, sizes, dtype, iters, warmup, reps):
+    k, elem = len(devs), ELEM[dtype]
+    counts = [max(1, n // elem) for n in sizes]
+    once = pc._Once()
+    driver = {}  # (count, algo, rep) -> the driver's result, measured by rank 0 while the other ranks wait
+
+    def body(comm):
+        rows = []
+        for count in counts:
+            xs = once.get(("in", count), lambda: [pc.case_input(0, 0, p, count, dtype) for p in range(k)], lambda o: o[1] == count)
+            ref = once.get(("ref", count), lambda: allreduce_ref(xs, dtype), lambda o: o[1] == count)
+            comm.write(xs[comm.rank])
+            for algo in pc.ALGOS:
+                for rep in range(reps):
+                    secs, in_barriers = pc.timed_all_reduce(comm, count, dtype, algo, iters, warmup)
+                    wrong = int(np.count_nonzero(pc._bits(comm.read(0, count, dtype)) != pc._bits(ref))) if rep == 0 else 0
+                    rows.append((count, algo, rep, secs, in_barriers, wrong))
+                    comm.barrier()  # every rank's stream is idle: the driver has the device to itself
+                    if comm.rank == 0:
+                        driver[(count, algo, rep)] = probe.peer_allreduce(devs, count, dtype, algo, iters, warmup)
+                    comm.barrier()
+        return rows
+
+    cap = -(-max(counts) * elem // 16) * 16
+    res = pc.run_thread_ranks(devs, body, cap, timeout_s=300.0, join_s=3000.0)
+    out = []
+    for count in counts:
+        row = {"bytes": count * elem, "count": count}
+        for algo in pc.ALGOS:
+            mine = [[r for r in rank_rows if r[:2] == (count, algo)] for rank_rows in res]
+            t_reps = [max(rows[rep][3] for rows in mine) * 1e6 for rep in range(reps)]  # the slowest rank of each repetition
+            best = min(range(reps), key=lambda i: t_reps[i])
+            d_reps = [driver[(count, algo, rep)] for rep in range(reps)]
+            d = min(d_reps, key=lambda r: r["time_us"])
+            thread_us = t_reps[best]
+            row[algo] = {
+                "thread_time_us": thread_us, "thread_barrier_us": sum(rows[best][4] for rows in mine) / k * 1e6,
+                "thread_algbw_gbps": count * elem / (thread_us * 1e-6) / 1e9, "thread_time_us_reps": t_reps,
+                "thread_wrong": sum(r[5] for rows in mine for r in rows),
+                "driver_time_us": d["time_us"], "driver_algbw_gbps": d["algbw_gbps"], "driver_time_us_reps": [r["time_us"] for r in d_reps],
+                "driver_wrong": sum(int(r["wrong"]) for r in d_reps), "thread_over_driver": thread_us / d["time_us"]}
+        out.append(row)
+        print(json.dumps(row), file=sys.stderr, flush=True)
+    return {"members": list(devs), "k": k, "distinct_devices": len(set(devs)) == k, "dtype": dtype, "iters": iters, "warmup": warmup,
+            "reps": reps, "sizes": out}
+
+
+def markdown(res) -> str:
+    out = [f"### members {res['members']} (k = {res['k']}), {res['dtype']}, {res['iters']} timed calls, best of {res['reps']} alternated repetitions", "",
+           "| N per member | algorithm | thread ranks us / call | of it in barriers | thread algBW | driver us / round | driver algBW | thread / driver |",
+           "|---|---|---|---|---|---|---|---|"]
+    for r in res["sizes"]:
+        for algo in pc.ALGOS:
+            a = r[algo]
+            out.append(f"| {r['bytes'] / 2**20:.1f} MiB | {algo} | {a['thread_time_us']:.1f} | {a['thread_barrier_us']:.1f} | {a['thread_algbw_gbps']:.1f} "
+                       f"| {a['driver_time_us']:.1f} | {a['driver_algbw_gbps']:.1f} | {a['thread_over_driver']:.2f} |")
+    out.append("")
+    return "\n".join(out)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--members", action="append", default=[], help="HIP ordinals, comma-separated; may be given more than once")
+    ap.add_argument("--sizes-mib", default="1,4,16,64,256")
+    ap.add_argument("--dtype", default="bf16", choices=sorted(ELEM))
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--reps", type=int, default=2, help="alternated repetitions of each measurement")
+    ap.add_argument("--out", default="", help="also write the JSON document here")
+    ap.add_argument("--md", default="", help="also write the tables as Markdown here")
+    a = ap.parse_args()
+    groups = [[int(x) for x in m.split(",")] for m in (a.members or ["0,0,0,0"])]
+    sizes = [int(float(x) * (1 << 20)) for x in a.sizes_mib.split(",")]
+    probe.warmup(groups[0][0], 100.0)
+    doc = {"device": probe.device_props(groups[0][0])["name"], "rates": "GB/s (1e9 bytes/s)",
+           "runs": [measure(g, sizes, a.dtype, a.iters, a.warmup, max(1, a.reps)) for g in groups]}
+    text = json.dumps(doc)
+    print(text)
+    for path, body in ((a.out, text + "\n"), (a.md, "\n".join(markdown(r) for r in doc["runs"]))):
+        if path:
+            os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+            with open(path, "w") as f:
+                f.write(body)
+    return 1 if any(r[al][w] for run in doc["runs"] for r in run["sizes"] for al in pc.ALGOS for w in ("thread_wrong", "driver_wrong")) else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

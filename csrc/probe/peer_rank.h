@@ -1,0 +1,296 @@
+// One rank's device state for the peer communicator (parallel/peer_comm.py, backend="device").  A
+// fragment of csrc/probe/probe.hip, included there at file scope after the K7 driver like
+// peer_allreduce.h; the code below joins its unnamed namespace.  Host code only: it launches the K7
+// kernels of peer_allreduce.h through launch_peer_reduce and adds no kernel and no instantiation.
+//
+// A rank owns a window (inputs, `capacity` bytes), an out (results, twice that: the wide form writes
+// two vectors per input vector) and one non-blocking stream on its device.  Ranks are threads of one
+// process, so a peer's buffer is reached through its plain device address and, across devices,
+// hipDeviceEnablePeerAccess: no IPC call.  A PeerRank is used by one thread.  Nothing here waits on
+// the GPU for another rank: no event is shared between ranks and no kernel spins, so ordering between
+// ranks is the caller's (synchronize(), then a host barrier).  Every HIP call is made with the GIL
+// released, since a rank blocked in hipStreamSynchronize must not keep another from its barrier.
+#pragma once
+#include <mutex>
+
+namespace {
+
+// Allocation, free and peer enabling of every rank, one at a time.
+std::mutex& peer_rank_mutex() {
+  static std::mutex m;
+  return m;
+}
+
+class PeerRank {
+ public:
+  PeerRank(int dev, int rank, int world, size_t capacity_bytes, int blocks_per_cu)
+      : dev_(dev), rank_(rank), world_(world), cap_(capacity_bytes), blocks_per_cu_(std::max(1, blocks_per_cu)) {
+    if (world < 2 || world > kMaxSrc) throw std::invalid_argument("2..16 ranks");
+    if (rank < 0 || rank >= world) throw std::invalid_argument("rank out of range");
+    if (capacity_bytes < 16 || capacity_bytes % 16) throw std::invalid_argument("capacity_bytes must be a positive multiple of 16");
+    py::gil_scoped_release nogil;
+    int ndev = 0;
+    HIP_CHECK(hipGetDeviceCount(&ndev));
+    if (dev < 0 || dev >= ndev) throw std::invalid_argument("device index out of range");
+    cus_ = num_cus(dev);
+    try {
+      {
+        std::lock_guard<std::mutex> lock(peer_rank_mutex());
+        window_.reset(new DevBuf(dev, cap_));
+        out_.reset(new DevBuf(dev, 2 * cap_));
+      }
+      DeviceGuard g(dev);
+      HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+      HIP_CHECK(hipMemsetAsync(window_->p, 0, cap_, stream_));
+      HIP_CHECK(hipMemsetAsync(out_->p, 0, 2 * cap_, stream_));
+      HIP_CHECK(hipStreamSynchronize(stream_));
+    } catch (...) {
+      release_locked();
+      throw;
+    }
+  }
+  ~PeerRank() {
+    if (released_) return;
+    if (Py_IsInitialized() && PyGILState_Check()) {
+      py::gil_scoped_release nogil;
+      release_locked();
+    } else {
+      release_locked();
+    }
+  }
+  PeerRank(const PeerRank&) = delete;
+  PeerRank& operator=(const PeerRank&) = delete;
+
+  uintptr_t window_ptr() const { return reinterpret_cast<uintptr_t>(live().window_->p); }
+  uintptr_t out_ptr() const { return reinterpret_cast<uintptr_t>(live().out_->p); }
+  size_t capacity_bytes() const { return cap_; }
+  size_t launches() const { return launches_; }
+  bool released() const { return released_; }
+
+  // Every rank's device and buffer addresses, this rank's own included (and checked to be its own).
+  // A peer's address must be the base of a device allocation of this process on the device it names,
+  // at least as large as this rank's buffers: the kernels index a peer's buffer as they index their own.
+  void open_peers(const std::vector<int>& devices, const std::vector<uintptr_t>& windows, const std::vector<uintptr_t>& outs) {
+    live();
+    const size_t k = (size_t)world_;
+    if (devices.size() != k || windows.size() != k || outs.size() != k) throw std::invalid_argument("one device, window and out per rank");
+    if (devices[rank_] != dev_ || windows[rank_] != window_ptr() || outs[rank_] != out_ptr())
+      throw std::invalid_argument("this rank's own entry is not its device and buffers");
+    int ndev = 0;
+    HIP_CHECK(hipGetDeviceCount(&ndev));
+    for (size_t p = 0; p < k; ++p) {
+      if (devices[p] < 0 || devices[p] >= ndev) throw std::invalid_argument("device index out of range");
+      check_allocation(windows[p], devices[p], cap_);
+      check_allocation(outs[p], devices[p], 2 * cap_);
+    }
+    {
+      std::lock_guard<std::mutex> lock(peer_rank_mutex());
+      for (size_t p = 0; p < k; ++p) enable_peer(dev_, devices[p]);
+    }
+    share_ = 0;  // ranks sharing this device split its CUs, as the members of PeerAllreduce do
+    for (int d : devices) share_ += (d == dev_);
+    for (size_t p = 0; p < k; ++p) {
+      windows_.p[p] = reinterpret_cast<const u32x4*>(windows[p]);
+      outs_[p] = reinterpret_cast<const u32x4*>(outs[p]);
+    }
+    open_ = true;
+  }
+
+  void close_peers() {
+    windows_ = SrcSet{};
+    for (auto& o : outs_) o = nullptr;
+    open_ = false;
+  }
+
+  // out[v0, v1) of this rank = scale x the sum over ranks of window[v0, v1), vectors of the input type
+  // (the wide form writes out[2 * v0, 2 * v1)).
+  void reduce(size_t v0, size_t v1, const std::string& in_dtype, const std::string& out_dtype, float scale) {
+    const PeerTypes t = peer_types(in_dtype, out_dtype);
+    need_peers();
+    if (v0 > v1 || v1 > cap_ / 16) throw std::invalid_argument("reduce: vectors past the end of the window");
+    if (v1 * t.ratio() > 2 * cap_ / 16) throw std::invalid_argument("reduce: vectors past the end of out");
+    if (v0 == v1) return;
+    const size_t cap = std::max(1, cus_ * blocks_per_cu_ / share_);
+    const int grid = (int)std::max<size_t>(1, std::min(cap, (v1 - v0 + kBlock - 1) / kBlock));
+    DeviceGuard g(dev_);
+    launch_peer_reduce(t, windows_, world_, v0, v1, reinterpret_cast<u32x4*>(out_->p), scale, grid, stream_);
+    ++launches_;
+  }
+
+  // Phase 2 of a two-shot: vectors [a, b) of out of rank p, to the same vectors of this rank's out, for
+  // every p but this rank.  One launch; slices may be empty.
+  void gather(const std::vector<std::pair<size_t, size_t>>& slices) {
+    need_peers();
+    if (slices.size() != (size_t)world_) throw std::invalid_argument("gather: one slice per rank");
+    SliceSet sl{};
+    int i = 0;
+    for (int p = 0; p < world_; ++p) {
+      const size_t a = slices[p].first, b = slices[p].second;
+      if (a > b || b > 2 * cap_ / 16) throw std::invalid_argument("gather: slice past the end of out");
+      if (p == rank_) continue;
+      sl.p[i] = outs_[p];
+      sl.first[i] = a;
+      sl.count[i] = b - a;
+      ++i;
+    }
+    launch_gather(sl, world_ - 1);
+  }
+
+  // All-gather: vectors [p * n_vec, (p + 1) * n_vec) of rank p's window to the same vectors of this
+  // rank's out, for every p, this rank included.  One launch.
+  void gather_windows(size_t n_vec) {
+    need_peers();
+    if (n_vec > cap_ / 16 / (size_t)world_) throw std::invalid_argument("gather_windows: slices past the end of the window");
+    SliceSet sl{};
+    for (int p = 0; p < world_; ++p) {
+      sl.p[p] = windows_.p[p];
+      sl.first[p] = (size_t)p * n_vec;
+      sl.count[p] = n_vec;
+    }
+    launch_gather(sl, world_);
+  }
+
+  // Host bytes into the window from `first_byte` on, the rest of the last 16-byte vector zeroed (the
+  // kernels assume zero padding).  On the rank's stream; returns once the host bytes have been read.
+  void write_host(const void* src, size_t nbytes, size_t first_byte) {
+    live();
+    const size_t padded = (nbytes + 15) / 16 * 16;
+    if (first_byte % 16 || first_byte > cap_ || padded > cap_ - first_byte)
+      throw std::invalid_argument("write_host: past the end of the window, or first_byte is no multiple of 16");
+    if (!nbytes) return;
+    DeviceGuard g(dev_);
+    char* dst = static_cast<char*>(window_->p) + first_byte;
+    HIP_CHECK(hipMemcpyAsync(dst, src, nbytes, hipMemcpyHostToDevice, stream_));
+    if (padded > nbytes) HIP_CHECK(hipMemsetAsync(dst + nbytes, 0, padded - nbytes, stream_));
+    HIP_CHECK(hipStreamSynchronize(stream_));
+  }
+
+  // Bytes [first_byte, first_byte + nbytes) of out to `dst`, after everything on the stream.
+  void read_host(void* dst, size_t first_byte, size_t nbytes) {
+    live();
+    if (first_byte > 2 * cap_ || nbytes > 2 * cap_ - first_byte) throw std::invalid_argument("read_host: past the end of out");
+    DeviceGuard g(dev_);
+    if (nbytes) HIP_CHECK(hipMemcpyAsync(dst, static_cast<const char*>(out_->p) + first_byte, nbytes, hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipStreamSynchronize(stream_));
+  }
+
+  void synchronize() {
+    live();
+    DeviceGuard g(dev_);
+    HIP_CHECK(hipStreamSynchronize(stream_));
+  }
+
+  // Synchronises, destroys the stream, frees both buffers.  Idempotent.  The caller must know that no
+  // peer still reads this rank's buffers.
+  void release() { release_locked(); }
+
+ private:
+  const PeerRank& live() const {
+    if (released_) throw std::runtime_error("the PeerRank is released");
+    return *this;
+  }
+  void need_peers() const {
+    live();
+    if (!open_) throw std::runtime_error("open_peers first");
+  }
+
+  static void check_allocation(uintptr_t addr, int dev, size_t bytes) {
+    void* p = reinterpret_cast<void*>(addr);
+    hipPointerAttribute_t attr{};
+    hipError_t e = addr ? hipPointerGetAttributes(&attr, p) : hipErrorInvalidValue;
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      throw std::invalid_argument("open_peers: an address is no device allocation of this process");
+    }
+    if (attr.type != hipMemoryTypeDevice || attr.device != dev)
+      throw std::invalid_argument("open_peers: an address is not device memory of the device it is given with");
+    void* base = nullptr;
+    size_t size = 0;
+    HIP_CHECK(hipMemGetAddressRange(reinterpret_cast<hipDeviceptr_t*>(&base), &size, reinterpret_cast<hipDeviceptr_t>(p)));
+    if (base != p || size < bytes) throw std::invalid_argument("open_peers: an allocation is smaller than this rank's buffers");
+  }
+
+  void launch_gather(const SliceSet& sl, int nsrc) {
+    const int grid = gather_grid(dev_, blocks_per_cu_, nsrc, share_);
+    DeviceGuard g(dev_);
+    peer_allgather_kernel<<<dim3(grid), dim3(kBlock), 0, stream_>>>(sl, nsrc, reinterpret_cast<u32x4*>(out_->p));
+    HIP_CHECK(hipGetLastError());
+    ++launches_;
+  }
+
+  void release_locked() noexcept {
+    if (released_) return;
+    released_ = true;
+    close_peers();
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    (void)hipSetDevice(dev_);
+    if (stream_) {
+      (void)hipStreamSynchronize(stream_);
+      (void)hipStreamDestroy(stream_);
+      stream_ = nullptr;
+    }
+    (void)hipSetDevice(prev);
+    std::lock_guard<std::mutex> lock(peer_rank_mutex());
+    window_.reset();
+    out_.reset();
+  }
+
+  int dev_, rank_, world_;
+  size_t cap_;
+  int blocks_per_cu_, cus_ = 1, share_ = 1;
+  std::unique_ptr<DevBuf> window_, out_;
+  hipStream_t stream_ = nullptr;
+  SrcSet windows_{};
+  const u32x4* outs_[kMaxSrc] = {};
+  bool open_ = false, released_ = false;
+  size_t launches_ = 0;
+};
+
+void bind_peer_rank(py::module_& m) {
+  using nogil = py::call_guard<py::gil_scoped_release>;
+  py::class_<PeerRank>(m, "PeerRank",
+                       "one rank of the peer communicator's device backend: a window, an out and a stream on one device, "
+                       "the K7 kernels launched over the peers' addresses; used by one thread")
+      .def(py::init<int, int, int, size_t, int>(), py::arg("dev"), py::arg("rank"), py::arg("world"), py::arg("capacity_bytes"),
+           py::arg("blocks_per_cu") = kBlocksPerCU)
+      .def("window_ptr", &PeerRank::window_ptr)
+      .def("out_ptr", &PeerRank::out_ptr)
+      .def("open_peers", &PeerRank::open_peers, py::arg("devices"), py::arg("windows"), py::arg("outs"), nogil())
+      .def("close_peers", &PeerRank::close_peers, nogil())
+      .def("reduce", &PeerRank::reduce, py::arg("v0"), py::arg("v1"), py::arg("in_dtype"), py::arg("out_dtype"), py::arg("scale") = 1.0f,
+           nogil())
+      .def("gather", &PeerRank::gather, py::arg("slices"), nogil())
+      .def("gather_windows", &PeerRank::gather_windows, py::arg("n_vec"), nogil())
+      .def("write_host",
+           [](PeerRank& r, const py::buffer& b, size_t first_byte) {
+             const py::buffer_info info = b.request();
+             if (!PyBuffer_IsContiguous(info.view(), 'C')) throw std::invalid_argument("write_host: a contiguous buffer");
+             const void* p = info.ptr;
+             const size_t n = (size_t)info.size * (size_t)info.itemsize;
+             py::gil_scoped_release nogil;
+             r.write_host(p, n, first_byte);
+           },
+           py::arg("bytes_like"), py::arg("first_byte") = 0)
+      .def("read_host",
+           [](PeerRank& r, size_t first_byte, size_t nbytes) {
+             if (r.released()) throw std::runtime_error("the PeerRank is released");
+             if (first_byte > 2 * r.capacity_bytes() || nbytes > 2 * r.capacity_bytes() - first_byte)
+               throw std::invalid_argument("read_host: past the end of out");
+             py::array_t<uint8_t> a((py::ssize_t)nbytes);
+             void* p = a.mutable_data();
+             {
+               py::gil_scoped_release nogil;
+               r.read_host(p, first_byte, nbytes);
+             }
+             return a;
+           },
+           py::arg("first_byte"), py::arg("nbytes"))
+      .def("synchronize", &PeerRank::synchronize, nogil())
+      .def("release", &PeerRank::release, nogil())
+      .def_property_readonly("launches", &PeerRank::launches)
+      .def_property_readonly("capacity_bytes", &PeerRank::capacity_bytes)
+      .def_property_readonly("released", &PeerRank::released);
+}
+
+}  // namespace

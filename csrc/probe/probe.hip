@@ -18,7 +18,8 @@
 //                  against.
 //   K7 allreduce : the sum of every member's buffer, in every member's output, by kernels over peer
 //                  pointers (peer_allreduce.h): a fixed summation order, so the result is exact
-//                  against a CPU sum; the repository's own collective, next to RCCL's.
+//                  against a CPU sum; the repository's own collective, next to RCCL's.  PeerRank
+//                  (peer_rank.h) launches the same kernels for one rank of the peer communicator.
 //   K8 latency   : one wave follows a chain of dependent loads through a buffer of another device
 //                  (chase_latency.h): nanoseconds per access over the link, next to K1's GB/s.
 //   IPC read     : the K1 kernel on a buffer another process exported with hipIpcGetMemHandle (the
@@ -941,6 +942,10 @@ py::list peer_allreduce_arrays(const std::vector<int>& devs, const std::vector<p
   return r;
 }
 
+}  // namespace
+#include "peer_rank.h"  // one rank of the peer communicator's device backend, over the K7 launches above
+namespace {
+
 // K8 link latency: one wave on `exec_dev` follows a chain of dependent loads (chase_latency.h) that
 // lives in the memory of the chain's device, the orientation of copy_bw in read mode: the number for
 // (src, exec) sits where K1's GB/s for (src, dst) sits.  Time is taken inside the kernel (wall clock
@@ -1420,6 +1425,7 @@ PYBIND11_MODULE(_probe, m) {
         py::arg("algo") = "twoshot", py::arg("rounds") = 1, py::arg("out_dtype") = py::none(), py::arg("scale") = 1.0f,
         "K7 on the caller's arrays (uint16 bit patterns for bf16, float32 for fp32): the k members' results, "
         "scale x sum, in out_dtype (none: dtype; fp32 of bf16 inputs is the wide reduce)");
+  bind_peer_rank(m);
   m.def("chase_latency", &chase_latency, py::arg("src_dev"), py::arg("exec_dev"), py::arg("ws_bytes") = (size_t)1 << 30,
         py::arg("stride") = (size_t)128, py::arg("hops") = 4096, py::arg("chains") = 1, py::arg("iters") = 5,
         py::arg("warmup") = 1, py::arg("evict") = true,

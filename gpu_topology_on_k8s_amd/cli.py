@@ -9,7 +9,8 @@
             (the reference's legacy Policy JSON, design.md:92-113) or ``manifests`` (deploy YAML)
   validate  RCCL all-reduce over the allocated devices (GTK_GPU_GROUP or --devices): the
             placement validator of SURVEY.md §3.5 (flow step 8); --backend peer runs the K7 peer
-            all-reduce of csrc/probe instead, which needs no RCCL
+            all-reduce of csrc/probe instead, which needs no RCCL (--ranks thread: one thread per
+            member through the peer communicator, parallel/peer_comm.py)
   sim       run a small in-process cluster and print the scheduling decisions
   doctor    node / pod readiness checks (device nodes, discovery, extensions, IPC mode, CPU affinity,
             a pod's GROUP, cpuset and share guard), one JSON line each; --gpu adds HIP checks
@@ -387,6 +388,10 @@ def cmd_config(a) -> int:
     return 0
 
 
+#: ``validate --ranks thread`` compares every point with a host sum: larger buffers than this are refused
+THREAD_RANKS_MAX_BYTES = 256 << 20
+
+
 def validate_devices(a, env=None) -> List[int]:
     """HIP ordinals to validate: ``--devices`` (ordinals) as given; else the pod's node-local GROUP
     (``--group`` or ``GTK_GPU_GROUP``) resolved through ``GTK_GPU_BDFS`` / ``--topology`` by PCI
@@ -420,6 +425,11 @@ def cmd_validate(a) -> int:
     from ._native import load
     from .topology.cpus import bind_workload
 
+    if a.ranks == "thread":  # refused before anything native is loaded
+        if a.backend != "peer":
+            raise SystemExit("--ranks thread belongs to --backend peer")
+        if a.max_bytes > THREAD_RANKS_MAX_BYTES:
+            raise SystemExit(f"--ranks thread checks every point on the host: --max-bytes at most {THREAD_RANKS_MAX_BYTES} (256 MiB)")
     devs = validate_devices(a)
     # Gaia B6: the validator's host threads (RCCL proxies) on the pod's cores (GTK_CPUSET from Allocate)
     cpu_rep = bind_workload(a.cpu_bind, "")
@@ -427,6 +437,7 @@ def cmd_validate(a) -> int:
         print(json.dumps({"hip_devices": devs}))
         return 0
     extra = {}
+    selftest_wrong = 0
     if a.backend == "peer":  # K7, this repository's own kernels: _rccl (and librccl) are never loaded
         from .ops.probe import peer_sweep
 
@@ -434,10 +445,20 @@ def cmd_validate(a) -> int:
             raise SystemExit("--backend peer sums bf16 or fp32")
         if not 2 <= len(devs) <= 16:
             raise SystemExit(f"--backend peer takes 2 to 16 members, got {devs} (a device may repeat: --devices 0,0)")
-        keys = ("bytes", "count", "time_us", "algbw_gbps", "busbw_gbps", "wrong")
-        pts = [{**{k: p[k] for k in keys}, "backend": "peer", "algo": p["algo"]}
-               for p in peer_sweep(devs, _size_sweep(a.min_bytes, a.max_bytes, a.factor), a.dtype, a.algo, a.iters, a.warmup)]
-        extra = {"backend": "peer", "algo": a.algo}
+        sizes = _size_sweep(a.min_bytes, a.max_bytes, a.factor)
+        if a.ranks == "thread":  # one thread per member through the peer communicator, not one driver call for all
+            from .parallel.peer_comm import selftest, thread_sweep
+
+            st = selftest(devs)
+            selftest_wrong = st["wrong"]
+            print(json.dumps({"selftest": True, "k": len(devs), "devices": devs, "ranks": "thread", **st}), flush=True)
+            pts = thread_sweep(devs, sizes, a.dtype, a.algo, a.iters, a.warmup)
+            extra = {"backend": "peer", "algo": a.algo, "ranks": "thread", "selftest_wrong": selftest_wrong}
+        else:
+            keys = ("bytes", "count", "time_us", "algbw_gbps", "busbw_gbps", "wrong")
+            pts = [{**{k: p[k] for k in keys}, "backend": "peer", "algo": p["algo"]}
+                   for p in peer_sweep(devs, sizes, a.dtype, a.algo, a.iters, a.warmup)]
+            extra = {"backend": "peer", "algo": a.algo}
     else:
         rccl = load("_rccl")
         sizes = rccl.size_sweep(a.min_bytes, a.max_bytes, a.factor)
@@ -449,7 +470,7 @@ def cmd_validate(a) -> int:
     print(json.dumps({"summary": True, "k": len(devs), "devices": devs, "wrong": wrong, "peak_bytes": peak["bytes"],
                       "peak_algbw_gbps": round(peak["algbw_gbps"], 2), "peak_busbw_gbps": round(peak["busbw_gbps"], 2),
                       "cpuset_applied": {k: cpu_rep.get(k) for k in ("applied", "source", "cpus", "n", "reason")}, **extra}))
-    return 1 if wrong else 0
+    return 1 if wrong or selftest_wrong else 0
 
 
 def _size_sweep(min_bytes: int, max_bytes: int, factor: int) -> List[int]:
@@ -600,6 +621,9 @@ def main(argv=None) -> int:
     p.add_argument("--backend", default="rccl", choices=["rccl", "peer"],
                    help="rccl: librccl's all-reduce; peer: this repository's K7 kernels over peer pointers (no RCCL; bf16|fp32)")
     p.add_argument("--algo", default="both", choices=["oneshot", "twoshot", "both"], help="--backend peer: K7 algorithm(s)")
+    p.add_argument("--ranks", default="driver", choices=["driver", "thread"],
+                   help="--backend peer: driver = one in-process call drives every member (stream events); thread = one thread "
+                        "per member through the peer communicator (a self-test, then host-timed all_reduce calls checked on the host)")
     p.set_defaults(fn=cmd_validate)
     p = sub.add_parser("doctor", help="node / pod readiness checks (JSON lines); exit 1 on any failure")
     p.add_argument("--discovery", default="auto", choices=["auto", "amdsmi", "sysfs", "fake"])

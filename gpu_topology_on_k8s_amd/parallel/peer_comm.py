@@ -1,4 +1,4 @@
-"""Peer communicator: the protocol of the K7 collectives with one rank per process, on its host backend.
+"""Peer communicator: the per-rank protocol of the K7 collectives, on a host and on a device backend.
 
 Every rank owns a *window* (inputs) and an *out* buffer (results) and reads its peers'.  The phases are
 K7's (``csrc/probe/peer_allreduce.h``): a rank reads every window, sums in fp32 in rank order, scales,
@@ -15,30 +15,43 @@ the host (``PeerCommTimeout``).  Every collective is
 and never more than those two barriers.  The price is that every collective is host-synchronous: two
 store round trips and two (two-shot: three) stream synchronisations per call.
 
-Only ``backend="host"`` exists so far: numpy buffers shared between threads of one process, the phases
-computed by ``ops/peer_ref.py``, every access logged; two ranks touching overlapping vectors of one
-buffer inside the same barrier epoch, one of them writing, is a *conflict*.  That is the protocol's
-race detector, and it runs on the CPU.  The native backend (buffers exported by HIP IPC handle and
-mapped by every other rank, the K7 kernels on the mappings) is not part of the package: two ranks that
-mapped each other's buffers at the same time did not return from ``hipIpcOpenMemHandle``, and the
-cause has not been found.
+Two backends exist, both with the ranks as threads of one process:
+
+``backend="host"``: numpy buffers, the phases computed by ``ops/peer_ref.py``, every access logged; two
+ranks touching overlapping vectors of one buffer inside the same barrier epoch, one of them writing,
+is a *conflict*.  That is the protocol's race detector, and it runs on the CPU.
+
+``backend="device"``: every rank has its own device, stream and device buffers (``_probe.PeerRank``,
+``csrc/probe/peer_rank.h``) and launches the K7 kernels over its peers' device addresses, which the
+ranks publish through the store; across devices the access is ``hipDeviceEnablePeerAccess``, so no IPC
+call is made.  A pod gets its GPUs in one container, so one process with a thread per GPU validates an
+allocation (:func:`run_thread_ranks`, :func:`selftest`, ``gtk validate --backend peer --ranks thread``).
+
+The process backend (one rank per process, buffers exported by HIP IPC handle and mapped by every other
+rank, the K7 kernels on the mappings) is not part of the package: two ranks that mapped each other's
+buffers at the same time did not return from ``hipIpcOpenMemHandle``, and the cause has not been found.
+It would differ from the device backend in one step, publishing a handle and mapping it where the
+device backend publishes an address.
 """
 from __future__ import annotations
 
 import datetime
 import json
+import os
 import threading
 import time
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
 from ..ops.peer_ref import allreduce_ref, bf16_round, peer_slices
 
 __all__ = ["PeerComm", "PeerCommError", "PeerCommTimeout", "PeerCommMismatch", "HostFabric", "MemoryStore",
-           "selftest_cases", "case_input", "run_case", "MAX_WORLD"]
+           "selftest_cases", "case_input", "run_case", "run_thread_ranks", "selftest", "thread_sweep", "timed_all_reduce", "parked_bytes",
+           "MAX_WORLD"]
 
 MAX_WORLD = 16  # kMaxSrc of probe.hip
+BACKENDS = ("host", "device")
 _ELEM = {"bf16": 2, "fp32": 4}
 _NP = {"bf16": np.uint16, "fp32": np.float32}
 ALGOS = ("oneshot", "twoshot")
@@ -176,6 +189,13 @@ class _HostBackend:
     def synchronize(self) -> None:
         pass
 
+    def release(self, broken: bool = False) -> None:
+        pass
+
+    @property
+    def launches(self) -> int:
+        return self.f.launches  # of every rank: the fabric counts them together
+
     def reduce(self, v0: int, v1: int, in_dtype: str, out_dtype: str, scale: float) -> None:
         with self.f.lock:
             self.f.launches += 1
@@ -212,6 +232,78 @@ class _HostBackend:
         return self.f.out[self.rank][first * e:(first + n) * e].view(_NP[dtype]).copy()
 
 
+#: ``_probe.PeerRank`` objects of broken communicators, kept alive (see :meth:`_DeviceBackend.release`)
+_PARKED: List[object] = []
+_PARKED_LOCK = threading.Lock()
+
+
+def parked_bytes() -> int:
+    """Device memory held by ranks of broken ``backend="device"`` communicators that were closed but
+    not freed, in bytes (a window and an out of twice its size per rank)."""
+    with _PARKED_LOCK:
+        return sum(3 * int(r.capacity_bytes) for r in _PARKED)
+
+
+class _DeviceBackend:
+    """One rank's phase calls on its own device: ``_probe.PeerRank`` holds the window, the out and the
+    stream, and launches the K7 kernels over the peers' addresses."""
+
+    def __init__(self, rank: int, world: int, device: int, capacity_bytes: int):
+        from .._native import load
+
+        self.rank, self.world, self.device = rank, world, int(device)
+        self.epoch = 0  # kept for PeerComm._barrier; nothing here reads it
+        self.r = load("_probe").PeerRank(self.device, rank, world, capacity_bytes)
+
+    def record(self) -> Dict[str, int]:
+        """What this rank publishes to its peers.  ``pid`` says whose address space the addresses are in."""
+        return {"pid": os.getpid(), "device": self.device, "window": int(self.r.window_ptr()), "out": int(self.r.out_ptr())}
+
+    def open_peers(self, records: Sequence[Dict[str, int]]) -> None:
+        self.r.open_peers([int(p["device"]) for p in records], [int(p["window"]) for p in records], [int(p["out"]) for p in records])
+
+    def close_peers(self) -> None:
+        self.r.close_peers()
+
+    def synchronize(self) -> None:
+        self.r.synchronize()
+
+    def release(self, broken: bool = False) -> None:
+        """Frees the rank's stream and buffers, unless the communicator is broken.  A broken comm skipped
+        the barriers of ``close()``, so a peer's kernel may still be reading this rank's window or out,
+        and freeing them under it would turn a host timeout into a GPU fault.  The ``PeerRank`` is then
+        parked on a module-level list instead, and its memory stays allocated until the process ends
+        (:func:`parked_bytes`)."""
+        r, self.r = self.r, None
+        if r is None:
+            return
+        if broken:
+            with _PARKED_LOCK:
+                _PARKED.append(r)
+        else:
+            r.release()
+
+    @property
+    def launches(self) -> int:
+        return int(self.r.launches)
+
+    def reduce(self, v0: int, v1: int, in_dtype: str, out_dtype: str, scale: float) -> None:
+        self.r.reduce(v0, v1, in_dtype, out_dtype, scale)
+
+    def gather(self, slices: Sequence[Tuple[int, int]]) -> None:
+        self.r.gather([(int(a), int(b)) for a, b in slices])
+
+    def gather_windows(self, n_vec: int) -> None:
+        self.r.gather_windows(n_vec)
+
+    def write_host(self, a: np.ndarray, first_byte: int = 0) -> None:
+        self.r.write_host(np.ascontiguousarray(a).view(np.uint8).reshape(-1), first_byte)
+
+    def read_host(self, first: int, n: int, dtype: str) -> np.ndarray:
+        e = _ELEM[dtype]
+        return self.r.read_host(first * e, n * e).view(_NP[dtype])
+
+
 class PeerComm:
     """One rank of a ``world``-rank communicator on HIP device ``device``.
 
@@ -222,6 +314,10 @@ class PeerComm:
     (:meth:`write`), a collective leaves its result in out (:meth:`read`).  Every rank must issue the
     same collectives in the same order; the arguments are compared at the first barrier.  Any store
     error or timeout breaks the comm (``PeerCommTimeout``); later calls then raise at once.
+
+    ``backend="host"`` takes the :class:`HostFabric` the ranks share.  ``backend="device"`` takes none: the
+    rank allocates on ``device`` and the constructor exchanges addresses through the store, waiting up to
+    ``timeout_s`` for every rank; all ranks must be threads of this process (``PeerCommError`` otherwise).
     """
 
     def __init__(self, rank: int, world: int, device: int, store, capacity_bytes: int, timeout_s: float = 60.0,
@@ -241,13 +337,51 @@ class PeerComm:
         self.broken = False
         self._closed = False
         self._stale: List[List[str]] = [[], []]  # store keys to delete after the next barrier / the one after
-        if backend != "host":
-            raise ValueError(f'only backend="host" exists, got {backend!r}')
+        if backend not in BACKENDS:
+            raise ValueError(f'backend must be "host" or "device", got {backend!r}')
+        self.backend = backend
+        if backend == "device":
+            if fabric is not None:
+                raise ValueError('a HostFabric belongs to backend="host": backend="device" allocates on the device')
+            self._b = _DeviceBackend(rank, world, device, capacity_bytes)
+            try:
+                self._b.open_peers(self._exchange_pointers())
+            except BaseException:
+                # no peer can have launched on these buffers: that takes a barrier this rank never joined
+                b, self._b = self._b, None
+                b.release()
+                raise
+            return
         if fabric is None:
             raise ValueError('backend="host" shares a HostFabric between the ranks: pass fabric=')
         self._b = _HostBackend(rank, world, fabric)
-        self.backend = backend
         self._b.open_peers()  # no barrier: nothing reads a peer before barrier A of the first collective
+
+    def _exchange_pointers(self) -> List[Dict[str, int]]:
+        """Publishes this rank's device and buffer addresses and reads every rank's, through the store
+        (a process backend would publish an IPC handle here and map what it reads).  No barrier is needed:
+        nothing reads a peer before barrier A of the first collective.  The keys are deleted like the
+        descriptors', two barriers later, when every rank has long read them."""
+        keys = [f"{self._prefix}/ptr/{p}" for p in range(self.world)]
+        self._stale[1].append(keys[self.rank])
+        mine = json.dumps(self._b.record(), sort_keys=True)
+        self._store_call(lambda: self._store.set(keys[self.rank], mine), "publishing the buffer addresses failed")
+
+        def read():
+            self._store.wait(keys, datetime.timedelta(seconds=self.timeout_s))
+            return [json.loads(bytes(self._store.get(k)).decode()) for k in keys]
+
+        records = self._store_call(read, f"not every rank published its buffers within {self.timeout_s:.1f}s")
+        foreign = [p for p, rec in enumerate(records) if rec.get("pid") != os.getpid()]
+        if foreign:
+            raise PeerCommError(f'rank {self.rank}: backend="device" joins threads of one process, but ranks {foreign} '
+                                f"published addresses of another process (this one is {os.getpid()})")
+        return records
+
+    @property
+    def launches(self) -> int:
+        """Kernel launches made so far: this rank's on the device backend, every rank's on the host backend."""
+        return self._b.launches
 
     # -- the host barrier ---------------------------------------------------------------------
     def _barrier(self) -> None:
@@ -398,12 +532,20 @@ class PeerComm:
     def synchronize(self) -> None:
         self._b.synchronize()
 
+    def barrier(self) -> None:
+        """Synchronises this rank's stream and meets every rank at a barrier of its own, between collectives."""
+        self._check()
+        self._b.synchronize()
+        self._barrier()
+
     def close(self) -> None:
         """sync, barrier (nobody still reads a peer), close_peers, barrier (nobody still maps my buffers),
-        free; at last the keys this rank still owes the store are deleted.  A broken comm skips the barriers."""
+        free; at last the keys this rank still owes the store are deleted.  A broken comm skips the barriers,
+        and the device backend then keeps its buffers allocated (:func:`parked_bytes`): a peer may still read them."""
         if self._closed:
             return
         self._closed = True
+        b = self._b
         try:
             self._b.synchronize()
             if not self.broken:
@@ -419,6 +561,8 @@ class PeerComm:
             pass
         finally:
             self._b = None
+            if b is not None:
+                b.release(self.broken)
 
 
 def selftest_counts(k: int) -> List[int]:
@@ -470,3 +614,165 @@ def run_case(comm: PeerComm, case: Dict[str, object], inputs: Sequence[np.ndarra
 
 def _bits(a: np.ndarray) -> np.ndarray:
     return a.view(np.uint16 if a.dtype == np.uint16 else np.uint32)
+
+
+def run_thread_ranks(devices: Sequence[int], body: Callable[[PeerComm], object], capacity_bytes: int, timeout_s: float = 60.0,
+                     store=None, join_s: float = 600.0, comm_cls: Callable[..., PeerComm] = PeerComm) -> List[object]:
+    """One thread per rank, rank r on HIP device ``devices[r]`` (a device may repeat): each builds its
+    ``PeerComm(backend="device")`` on a shared :class:`MemoryStore`, runs ``body(comm)`` and always
+    closes.  Returns the ranks' results in rank order; if any rank raised, the error raised first in
+    time is re-raised (a later one is usually the others timing out on the rank that failed).
+
+    The threads are joined for at most ``join_s`` seconds in all.  When that runs out every
+    communicator is marked broken, so a rank's next call raises at once and a barrier it waits in ends
+    after ``timeout_s``; the threads get that long again and ``PeerCommError`` is raised.  ``comm_cls``
+    stands in for :class:`PeerComm` in tests."""
+    k = len(devices)
+    store = MemoryStore(timeout_s=timeout_s) if store is None else store
+    results: List[object] = [None] * k
+    errors: List[Tuple[int, BaseException]] = []
+    comms: List[Optional[PeerComm]] = [None] * k
+    lock = threading.Lock()
+
+    def run(r: int) -> None:
+        try:
+            comms[r] = comm = comm_cls(r, k, int(devices[r]), store, capacity_bytes, timeout_s=timeout_s, backend="device")
+            try:
+                results[r] = body(comm)
+            finally:
+                comm.close()
+        except BaseException as e:  # handed to the caller's thread
+            with lock:
+                errors.append((r, e))
+
+    threads = [threading.Thread(target=run, args=(r,), name=f"peer-rank-{r}", daemon=True) for r in range(k)]
+    for t in threads:
+        t.start()
+    deadline = time.monotonic() + join_s
+    for t in threads:
+        t.join(max(0.0, deadline - time.monotonic()))
+    late = [t.name for t in threads if t.is_alive()]
+    if late:
+        for c in comms:
+            if c is not None:
+                c.broken = True
+        deadline = time.monotonic() + timeout_s + 5.0
+        for t in threads:
+            t.join(max(0.0, deadline - time.monotonic()))
+        still = [t.name for t in threads if t.is_alive()]
+        raise PeerCommError(f"rank threads {late} did not end within {join_s:.0f}s" + (f"; {still} are still running" if still else ""))
+    if errors:
+        raise errors[0][1]
+    return results
+
+
+class _Once:
+    """``get(key, make)``: ``make()`` by the first rank that asks, the same object for the others."""
+
+    def __init__(self):
+        self._lock = threading.Lock()
+        self._made: Dict[object, object] = {}
+
+    def get(self, key, make, keep: Callable[[object], bool] = lambda k: True):
+        with self._lock:
+            if key not in self._made:
+                for old in [o for o in self._made if not keep(o)]:
+                    del self._made[old]
+                self._made[key] = make()
+            return self._made[key]
+
+
+def timed_all_reduce(comm: PeerComm, count: int, dtype: str, algo: str, iters: int, warmup_iters: int = 1) -> Tuple[float, float]:
+    """``warmup_iters`` untimed and ``iters`` timed ``all_reduce`` calls of what the window holds, on one
+    rank (every rank calls this).  Returns this rank's host seconds per call and, of those, the seconds
+    spent inside the call's two barriers.  The clock starts after a barrier and stops when the last call
+    has returned, which is after its last stream synchronise."""
+    for _ in range(warmup_iters):
+        comm.all_reduce(count, dtype, algo)
+    comm.barrier()
+    in_barriers, t0 = comm.barrier_s, time.perf_counter()
+    for _ in range(iters):
+        comm.all_reduce(count, dtype, algo)
+    return (time.perf_counter() - t0) / iters, (comm.barrier_s - in_barriers) / iters
+
+
+def thread_sweep(devices: Sequence[int], sizes: Sequence[int], dtype: str = "bf16", algo: str = "both", iters: int = 3,
+                 warmup_iters: int = 1, timeout_s: float = 60.0) -> List[Dict[str, object]]:
+    """``all_reduce`` on thread ranks over ``devices`` at every size (bytes) under ``algo`` (``oneshot``,
+    ``twoshot`` or ``both``): one dict per size and algorithm, in size order, with the keys of
+    ``ops.probe.peer_sweep`` and ``barrier_us``.
+
+    At each point every rank writes a seeded input, makes ``warmup_iters + iters`` calls and reads the
+    result back.  ``time_us`` is host time per call, the slowest rank's: the clock starts after a barrier
+    and stops when the last call has returned.  ``barrier_us`` is the mean over ranks of the host time
+    per call spent inside the call's two barriers.  ``wrong`` counts, over all ranks, the elements
+    whose bits differ from ``allreduce_ref``; the check runs on the host, so sizes should stay moderate."""
+    if algo != "both" and algo not in ALGOS:
+        raise ValueError(f"algo must be oneshot|twoshot|both, got {algo!r}")
+    if dtype not in _ELEM:
+        raise ValueError(f"dtype must be bf16|fp32, got {dtype!r}")
+    if iters < 1 or warmup_iters < 0:
+        raise ValueError("iters >= 1, warmup_iters >= 0")
+    k, elem = len(devices), _ELEM[dtype]
+    points = [(max(1, int(nbytes) // elem), a) for nbytes in sizes for a in (ALGOS if algo == "both" else (algo,))]
+    if not points:
+        return []
+    once = _Once()
+
+    def body(comm: PeerComm):
+        rows = []
+        for count, a in points:
+            xs = once.get(("in", count), lambda: [case_input(0, 0, p, count, dtype) for p in range(k)], lambda o: o[1] == count)
+            ref = once.get(("ref", count), lambda: allreduce_ref(xs, dtype), lambda o: o[1] == count)
+            comm.write(xs[comm.rank])
+            secs, in_barriers = timed_all_reduce(comm, count, dtype, a, iters, warmup_iters)
+            got = comm.read(0, count, dtype)
+            rows.append((secs, in_barriers, int(np.count_nonzero(_bits(got) != _bits(ref)))))
+        return rows
+
+    res = run_thread_ranks(devices, body, -(-max(c for c, _ in points) * elem // 16) * 16, timeout_s=timeout_s)
+    out: List[Dict[str, object]] = []
+    for i, (count, a) in enumerate(points):
+        secs = max(r[i][0] for r in res)
+        gbps = count * elem / secs / 1e9
+        out.append({"bytes": count * elem, "count": count, "time_us": secs * 1e6, "algbw_gbps": gbps,
+                    "busbw_gbps": gbps * 2.0 * (k - 1) / k, "wrong": sum(r[i][2] for r in res), "backend": "peer", "algo": a,
+                    "ranks": "thread", "barrier_us": sum(r[i][1] for r in res) / k * 1e6})
+    return out
+
+
+def _case_capacity(k: int, cases: Sequence[Dict[str, object]]) -> int:
+    """Window bytes the largest of ``cases`` needs (an all-gather holds every rank's slot)."""
+    need = max(_n_vec(int(c["count"]), c["dtype"]) * (k if c["op"] == "all_gather" else 1) for c in cases)
+    return max(16, need * 16)
+
+
+def selftest(devices: Sequence[int], counts: Optional[Sequence[int]] = None, timeout_s: float = 60.0) -> Dict[str, object]:
+    """Every case of :func:`selftest_cases`, each issued twice in a row with different inputs, on
+    thread ranks over ``devices`` (:func:`run_thread_ranks`), compared bit for bit with ``ops/peer_ref.py``.
+
+    ``wrong`` counts the collectives whose dtype, shape or bits differ from the reference on any rank;
+    ``barriers_per_collective`` lists the distinct numbers of barriers a collective took (``[2]``), and
+    ``launches`` is the kernel launches of all ranks together."""
+    k = len(devices)
+    cases = selftest_cases(k, counts)
+    once = _Once()  # every rank's inputs of (case, issue), made by the first rank that asks
+
+    def inputs(ci: int, issue: int) -> List[np.ndarray]:
+        make = lambda: [case_input(ci, issue, p, int(cases[ci]["count"]), cases[ci]["dtype"]) for p in range(k)]  # noqa: E731
+        return once.get((ci, issue), make, lambda o: o[0] >= ci - 1)  # ranks are never more than a collective apart
+
+    def body(comm: PeerComm):
+        wrong, barriers = set(), set()
+        for ci, case in enumerate(cases):
+            for issue in range(2):
+                before = comm.barriers
+                got, ref = run_case(comm, case, inputs(ci, issue))
+                barriers.add(comm.barriers - before)
+                if got.dtype != ref.dtype or got.shape != ref.shape or not np.array_equal(_bits(got), _bits(ref)):
+                    wrong.add((ci, issue))
+        return wrong, barriers, comm.launches
+
+    res = run_thread_ranks(devices, body, _case_capacity(k, cases), timeout_s=timeout_s)
+    return {"cases": len(cases), "collectives": 2 * len(cases), "wrong": len(set().union(*(r[0] for r in res))),
+            "barriers_per_collective": sorted(set().union(*(r[1] for r in res))), "launches": sum(r[2] for r in res)}
