@@ -1,7 +1,6 @@
-// K7: all-reduce (sum) over peer pointers, device side.  A fragment of csrc/probe/probe.hip, included
-// there at file scope once SrcSet / kMaxSrc (K5) are defined in its unnamed namespace, which the
-// code below joins.  Device code only, in the style of csrc/common/stream_copy.h: blocks of
-// gtk::kStreamBlock threads, 64-bit indices, 16-byte vectors.
+// K7: all-reduce (sum) over peer pointers, device side, over SrcSet / kMaxSrc of probe_common.h.
+// Device code only, in the style of csrc/common/stream_copy.h: blocks of gtk::kStreamBlock threads,
+// 64-bit indices, 16-byte vectors.
 //
 // Every member's buffers are padded with zeros to a whole number of vectors by the host driver, so
 // no kernel sees a scalar tail.  The sum of one element is fp32, taken in member order
@@ -11,14 +10,9 @@
 // link, fp32 written, which halves the link traffic of reducing a widened copy.
 //
 // No kernel here waits for another running kernel: the all-reduce's cross-member ordering is stream
-// events between launches (the host driver in probe.hip), visibility rests on kernel boundaries.
+// events between launches (the host driver in peer_driver.h), visibility rests on kernel boundaries.
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include <cstddef>
-#include <cstdint>
-
-#include "../common/stream_copy.h"
+#include "probe_common.h"
 
 namespace {
 

@@ -1,7 +1,6 @@
-// One rank's device state for the peer communicator (parallel/peer_comm.py, backend="device").  A
-// fragment of csrc/probe/probe.hip, included there at file scope after the K7 driver like
-// peer_allreduce.h; the code below joins its unnamed namespace.  Host code only: it launches the K7
-// kernels of peer_allreduce.h through launch_peer_reduce and adds no kernel and no instantiation.
+// One rank's device state for the peer communicator (parallel/peer_comm.py, backend="device").
+// Host code only: it launches the K7 kernels of peer_allreduce.h through the launch plan of
+// peer_driver.h, as PeerAllreduce does, and adds no kernel and no instantiation.
 //
 // A rank owns a window (inputs, `capacity` bytes), an out (results, twice that: the wide form writes
 // two vectors per input vector) and one non-blocking stream on its device.  Ranks are threads of one
@@ -12,6 +11,8 @@
 // released, since a rank blocked in hipStreamSynchronize must not keep another from its barrier.
 #pragma once
 #include <mutex>
+
+#include "peer_driver.h"
 
 namespace {
 
@@ -29,9 +30,7 @@ class PeerRank {
     if (rank < 0 || rank >= world) throw std::invalid_argument("rank out of range");
     if (capacity_bytes < 16 || capacity_bytes % 16) throw std::invalid_argument("capacity_bytes must be a positive multiple of 16");
     py::gil_scoped_release nogil;
-    int ndev = 0;
-    HIP_CHECK(hipGetDeviceCount(&ndev));
-    if (dev < 0 || dev >= ndev) throw std::invalid_argument("device index out of range");
+    check_dev(dev);
     cus_ = num_cus(dev);
     try {
       {
@@ -76,10 +75,8 @@ class PeerRank {
     if (devices.size() != k || windows.size() != k || outs.size() != k) throw std::invalid_argument("one device, window and out per rank");
     if (devices[rank_] != dev_ || windows[rank_] != window_ptr() || outs[rank_] != out_ptr())
       throw std::invalid_argument("this rank's own entry is not its device and buffers");
-    int ndev = 0;
-    HIP_CHECK(hipGetDeviceCount(&ndev));
+    check_devs(devices);
     for (size_t p = 0; p < k; ++p) {
-      if (devices[p] < 0 || devices[p] >= ndev) throw std::invalid_argument("device index out of range");
       check_allocation(windows[p], devices[p], cap_);
       check_allocation(outs[p], devices[p], 2 * cap_);
     }
@@ -87,8 +84,8 @@ class PeerRank {
       std::lock_guard<std::mutex> lock(peer_rank_mutex());
       for (size_t p = 0; p < k; ++p) enable_peer(dev_, devices[p]);
     }
-    share_ = 0;  // ranks sharing this device split its CUs, as the members of PeerAllreduce do
-    for (int d : devices) share_ += (d == dev_);
+    share_ = device_share(devices, dev_);  // as the members of PeerAllreduce do
+    outs_.resize(k);
     for (size_t p = 0; p < k; ++p) {
       windows_.p[p] = reinterpret_cast<const u32x4*>(windows[p]);
       outs_[p] = reinterpret_cast<const u32x4*>(outs[p]);
@@ -98,7 +95,7 @@ class PeerRank {
 
   void close_peers() {
     windows_ = SrcSet{};
-    for (auto& o : outs_) o = nullptr;
+    outs_.clear();
     open_ = false;
   }
 
@@ -110,8 +107,7 @@ class PeerRank {
     if (v0 > v1 || v1 > cap_ / 16) throw std::invalid_argument("reduce: vectors past the end of the window");
     if (v1 * t.ratio() > 2 * cap_ / 16) throw std::invalid_argument("reduce: vectors past the end of out");
     if (v0 == v1) return;
-    const size_t cap = std::max(1, cus_ * blocks_per_cu_ / share_);
-    const int grid = (int)std::max<size_t>(1, std::min(cap, (v1 - v0 + kBlock - 1) / kBlock));
+    const int grid = peer_reduce_grid(cus_, blocks_per_cu_, share_, v1 - v0);
     DeviceGuard g(dev_);
     launch_peer_reduce(t, windows_, world_, v0, v1, reinterpret_cast<u32x4*>(out_->p), scale, grid, stream_);
     ++launches_;
@@ -122,18 +118,13 @@ class PeerRank {
   void gather(const std::vector<std::pair<size_t, size_t>>& slices) {
     need_peers();
     if (slices.size() != (size_t)world_) throw std::invalid_argument("gather: one slice per rank");
-    SliceSet sl{};
-    int i = 0;
+    std::vector<PeerSlice> plan(world_);
     for (int p = 0; p < world_; ++p) {
       const size_t a = slices[p].first, b = slices[p].second;
       if (a > b || b > 2 * cap_ / 16) throw std::invalid_argument("gather: slice past the end of out");
-      if (p == rank_) continue;
-      sl.p[i] = outs_[p];
-      sl.first[i] = a;
-      sl.count[i] = b - a;
-      ++i;
+      plan[p] = PeerSlice{a, b - a};
     }
-    launch_gather(sl, world_ - 1);
+    launch_gather(peer_gather_slices(outs_, plan, rank_), world_ - 1);
   }
 
   // All-gather: vectors [p * n_vec, (p + 1) * n_vec) of rank p's window to the same vectors of this
@@ -211,10 +202,8 @@ class PeerRank {
   }
 
   void launch_gather(const SliceSet& sl, int nsrc) {
-    const int grid = gather_grid(dev_, blocks_per_cu_, nsrc, share_);
     DeviceGuard g(dev_);
-    peer_allgather_kernel<<<dim3(grid), dim3(kBlock), 0, stream_>>>(sl, nsrc, reinterpret_cast<u32x4*>(out_->p));
-    HIP_CHECK(hipGetLastError());
+    launch_peer_gather(sl, nsrc, reinterpret_cast<u32x4*>(out_->p), gather_grid_cus(cus_, blocks_per_cu_, nsrc, share_), stream_);
     ++launches_;
   }
 
@@ -242,7 +231,7 @@ class PeerRank {
   std::unique_ptr<DevBuf> window_, out_;
   hipStream_t stream_ = nullptr;
   SrcSet windows_{};
-  const u32x4* outs_[kMaxSrc] = {};
+  std::vector<const u32x4*> outs_;
   bool open_ = false, released_ = false;
   size_t launches_ = 0;
 };

@@ -17,7 +17,7 @@
 //                  the slowest member's ingress is the bound a ring all-reduce's busBW is measured
 //                  against.
 //   K7 allreduce : the sum of every member's buffer, in every member's output, by kernels over peer
-//                  pointers (peer_allreduce.h): a fixed summation order, so the result is exact
+//                  pointers (peer_allreduce.h, peer_driver.h): a fixed summation order, so it is exact
 //                  against a CPU sum; the repository's own collective, next to RCCL's.  PeerRank
 //                  (peer_rank.h) launches the same kernels for one rank of the peer communicator.
 //   K8 latency   : one wave follows a chain of dependent loads through a buffer of another device
@@ -32,46 +32,17 @@
 // 8 blocks (32 waves, the CU maximum) are resident per CU inside the 160 KiB LDS.  Grid = CUs x 8
 // with a grid-stride loop: >>256 workgroups fills all 8 XCDs; a streaming copy has no reuse so no
 // XCD remap is needed (each byte is touched once).
-#include <hip/hip_runtime.h>
-#include <pybind11/numpy.h>
-#include <pybind11/pybind11.h>
-#include <pybind11/stl.h>
+// This file is the one translation unit of _probe; every header includes what it needs.
+#include "chase_latency.h"   // K8 kernels and the chain's closed form
+#include "peer_allreduce.h"  // K7 kernels
+#include "peer_driver.h"     // K7 launch plan, PeerAllreduce and its two entry points
+#include "peer_rank.h"       // one rank of the peer communicator's device backend
+#include "probe_common.h"    // geometry, SrcSet, pattern fill and verifier, guards, grids, timers
 
-#include <algorithm>
-#include <chrono>
-#include <cstdint>
-#include <cstring>
-#include <memory>
-#include <optional>
-#include <stdexcept>
-#include <string>
-#include <vector>
-
-#include "../common/stream_copy.h"
-
-namespace py = pybind11;
-
-using gtk::u32x4;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-#define HIP_CHECK(expr)                                                                          \
-  do {                                                                                           \
-    hipError_t _e = (expr);                                                                      \
-    if (_e != hipSuccess)                                                                        \
-      throw std::runtime_error(std::string(#expr " failed: ") + hipGetErrorString(_e) + " at " + \
-                               __FILE__ + ":" + std::to_string(__LINE__));                       \
-  } while (0)
-
 namespace {
-
-// Equal to the all-reduce's kSelfCopy* (csrc/rccl/self_copy.h) today, but tuned on their own (these
-// on the LDS budget above, those on the 2 GiB headline): kept separate on purpose.
-constexpr int kBlock = 256;
-constexpr int kUnroll = 4;
-constexpr int kTileVec = kBlock * kUnroll;  // 16-byte vectors per block-iteration (16 KiB)
-constexpr int kBlocksPerCU = 8;
-static_assert(kBlock == gtk::kStreamBlock, "stream_copy.h indexes blocks of kStreamBlock threads");
 
 using gptr_t = const __attribute__((address_space(1))) void*;
 using lptr_t = __attribute__((address_space(3))) void*;
@@ -117,22 +88,12 @@ __global__ __launch_bounds__(kBlock) void copy_lds_kernel(const u32x4* __restric
 // K5 gather: one launch on the reader pulls from up to kMaxSrc peers at once (ingress over all of
 // its xGMI links together).  Block b serves source b % nsrc, so every source gets gridDim/nsrc
 // blocks spread over all XCDs; source s lands in dst[s * n_vec ...].
-constexpr int kMaxSrc = 16;
-struct SrcSet {
-  const u32x4* p[kMaxSrc];
-};
-
 __global__ __launch_bounds__(kBlock) void gather_lds_kernel(SrcSet srcs, int nsrc, u32x4* __restrict__ dst,
                                                             size_t n_vec) {
   __shared__ u32x4 lds[kTileVec];
   const int s = blockIdx.x % nsrc;
   copy_lds_stream<true>(srcs.p[s], dst + (size_t)s * n_vec, n_vec, lds, blockIdx.x / nsrc, gridDim.x / nsrc);
 }
-
-}  // namespace
-#include "peer_allreduce.h"  // K7 kernels, over SrcSet / kMaxSrc above
-#include "chase_latency.h"   // K8 kernels and the chain's closed form
-namespace {
 
 // Register-staged variant of the same stream (kUnroll independent 16-B loads in flight per lane).
 template <bool kNonTemporal>
@@ -161,21 +122,6 @@ __global__ __launch_bounds__(kBlock) void copy_chunk_kernel(const u32x4* __restr
                                                             size_t n_vec) {
   const size_t first = gtk::stream_slices<U>(src, dst, n_vec, blockIdx.x, gridDim.x);
   gtk::stream_vec_tail(src, dst, n_vec, first, blockIdx.x, gridDim.x);
-}
-
-__global__ __launch_bounds__(kBlock) void fill_pattern_kernel(unsigned int* __restrict__ p, size_t n_words,
-                                                              unsigned int seed) {
-  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n_words; i += (size_t)gridDim.x * kBlock)
-    p[i] = (unsigned int)(i * 2654435761u) ^ seed;
-}
-
-// Counts the words of p[0, n_words) that differ from what fill_pattern_kernel(seed) writes.
-__global__ __launch_bounds__(kBlock) void pattern_mismatch_kernel(const unsigned int* __restrict__ p, size_t n_words,
-                                                                  unsigned int seed, unsigned long long* bad) {
-  unsigned long long local = 0;
-  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n_words; i += (size_t)gridDim.x * kBlock)
-    local += (p[i] != ((unsigned int)(i * 2654435761u) ^ seed));
-  if (local) atomicAdd(bad, local);
 }
 
 // K4: MFMA warm-up.  Each wave keeps 4 independent 32x32 accumulators so back-to-back
@@ -248,146 +194,6 @@ __global__ __launch_bounds__(64) void xcc_census_kernel(unsigned int* __restrict
   if (threadIdx.x == 0) out[blockIdx.x] = (xcc << 16) | (hw & 0xFFFFu);
 }
 
-// ---------------------------------------------------------------------------------------------
-struct DeviceGuard {
-  int prev = 0;
-  explicit DeviceGuard(int dev) {
-    HIP_CHECK(hipGetDevice(&prev));
-    HIP_CHECK(hipSetDevice(dev));
-  }
-  ~DeviceGuard() { (void)hipSetDevice(prev); }
-};
-
-struct DevBuf {
-  void* p = nullptr;
-  int dev = -1;
-  size_t bytes = 0;
-  DevBuf(int d, size_t b) : dev(d), bytes(b) {
-    DeviceGuard g(d);
-    HIP_CHECK(hipMalloc(&p, b));
-  }
-  ~DevBuf() {
-    if (p) {
-      int prev = 0;
-      (void)hipGetDevice(&prev);
-      (void)hipSetDevice(dev);
-      (void)hipFree(p);
-      (void)hipSetDevice(prev);
-    }
-  }
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-};
-
-int num_cus(int dev) {
-  int cus = 0;
-  HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  return std::max(cus, 1);
-}
-
-void enable_peer(int from, int to) {
-  if (from == to) return;
-  int can = 0;
-  HIP_CHECK(hipDeviceCanAccessPeer(&can, from, to));
-  if (!can) throw std::runtime_error("device " + std::to_string(from) + " cannot access peer " + std::to_string(to));
-  DeviceGuard g(from);
-  hipError_t e = hipDeviceEnablePeerAccess(to, 0);
-  if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled)
-    throw std::runtime_error(std::string("hipDeviceEnablePeerAccess: ") + hipGetErrorString(e));
-  (void)hipGetLastError();
-}
-
-void check_bytes_iters(size_t bytes, int iters = 1) {
-  if (bytes < 16 || bytes % 16) throw std::invalid_argument("bytes must be a positive multiple of 16");
-  if (iters < 1) throw std::invalid_argument("iters >= 1");
-}
-
-// Blocks of a gather launch on `dev`: a multiple of nsrc, so every source gets the same block count.
-// Members of a ring that share a device (`share` of them) split its CUs.
-int gather_grid(int dev, int blocks_per_cu, int nsrc, int share = 1) {
-  const int per = std::max(1, num_cus(dev) * std::max(1, blocks_per_cu) / (nsrc * share));
-  return per * nsrc;
-}
-
-// GB/s of `bytes` moved per iteration, `iters` iterations in `ms`.
-double gbps(double bytes, double ms, int iters) { return bytes / (ms / 1e3 / iters) / 1e9; }
-
-// A non-blocking stream of the current device with the two events that bracket a timed section.
-struct TimedStream {
-  int dev = 0;
-  hipStream_t s = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  TimedStream() {
-    try {
-      HIP_CHECK(hipGetDevice(&dev));
-      HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-      for (hipEvent_t* e : {&e0, &e1}) HIP_CHECK(hipEventCreate(e));
-    } catch (...) {
-      release();
-      throw;
-    }
-  }
-  ~TimedStream() { release(); }
-  TimedStream(const TimedStream&) = delete;
-  TimedStream& operator=(const TimedStream&) = delete;
-  void begin() { HIP_CHECK(hipEventRecord(e0, s)); }
-  void end() { HIP_CHECK(hipEventRecord(e1, s)); }
-  float ms() {  // of begin() .. end(), once the stream has reached end()
-    float t = 0.f;
-    HIP_CHECK(hipEventSynchronize(e1));
-    HIP_CHECK(hipEventElapsedTime(&t, e0, e1));
-    return t;
-  }
-  float end_ms() {
-    end();
-    return ms();
-  }
-
- private:
-  void release() noexcept {
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(dev);
-    if (s) (void)hipStreamSynchronize(s);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (s) (void)hipStreamDestroy(s);
-    (void)hipSetDevice(prev);
-  }
-};
-
-// Event-timed `iters` launches of `launch` on a fresh non-blocking stream (after `warmup` untimed).
-template <class F>
-float time_launches(F launch, int iters, int warmup) {
-  TimedStream t;
-  for (int i = 0; i < warmup; ++i) launch(t.s);
-  HIP_CHECK(hipGetLastError());
-  t.begin();
-  for (int i = 0; i < iters; ++i) launch(t.s);
-  HIP_CHECK(hipGetLastError());
-  return t.end_ms();
-}
-
-void fill_pattern(int dev, void* p, size_t bytes, unsigned int seed) {
-  DeviceGuard g(dev);
-  hipLaunchKernelGGL(fill_pattern_kernel, dim3(num_cus(dev) * 4), dim3(kBlock), 0, 0, (unsigned int*)p, bytes / 4, seed);
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipDeviceSynchronize());
-}
-
-// Does p[0, n_words), memory of `dev`, hold pattern(seed) in every word?  One pass on the device.
-bool holds_pattern(int dev, const void* p, size_t n_words, unsigned int seed) {
-  DeviceGuard g(dev);
-  DevBuf bad(dev, sizeof(unsigned long long));
-  HIP_CHECK(hipMemset(bad.p, 0, sizeof(unsigned long long)));
-  hipLaunchKernelGGL(pattern_mismatch_kernel, dim3(num_cus(dev) * kBlocksPerCU), dim3(kBlock), 0, 0,
-                     (const unsigned int*)p, n_words, seed, (unsigned long long*)bad.p);
-  HIP_CHECK(hipGetLastError());
-  unsigned long long n = 0;
-  HIP_CHECK(hipMemcpy(&n, bad.p, sizeof(n), hipMemcpyDeviceToHost));
-  return n == 0;
-}
-
 void launch_copy(const std::string& kind, bool nt, const void* src, void* dst, size_t n_vec, int grid, hipStream_t s) {
   auto* S = reinterpret_cast<const u32x4*>(src);
   auto* D = reinterpret_cast<u32x4*>(dst);
@@ -426,10 +232,7 @@ CopyResult copy_bw_impl(int src_dev, int dst_dev, int exec_dev, size_t bytes, in
                         const std::string& kind, bool nontemporal, int blocks_per_cu) {
   check_bytes_iters(bytes, iters);
   if (exec_dev != src_dev && exec_dev != dst_dev) throw std::invalid_argument("exec_dev must be src or dst");
-  int ndev = 0;
-  HIP_CHECK(hipGetDeviceCount(&ndev));
-  for (int d : {src_dev, dst_dev})
-    if (d < 0 || d >= ndev) throw std::invalid_argument("device index out of range");
+  check_devs({src_dev, dst_dev});
   if (src_dev != dst_dev) enable_peer(exec_dev, exec_dev == src_dev ? dst_dev : src_dev);
 
   DevBuf src(src_dev, bytes), dst(dst_dev, bytes);
@@ -454,12 +257,8 @@ CopyResult copy_bw_impl(int src_dev, int dst_dev, int exec_dev, size_t bytes, in
 py::dict gather_bw(int dst_dev, const std::vector<int>& srcs, size_t bytes, int iters, int warmup, int blocks_per_cu) {
   if (srcs.empty() || srcs.size() > (size_t)kMaxSrc) throw std::invalid_argument("1..16 source devices");
   check_bytes_iters(bytes, iters);
-  int ndev = 0;
-  HIP_CHECK(hipGetDeviceCount(&ndev));
-  if (dst_dev < 0 || dst_dev >= ndev) throw std::invalid_argument("device index out of range");
-  for (int d : srcs) {
-    if (d < 0 || d >= ndev) throw std::invalid_argument("source device index out of range");
-  }
+  check_dev(dst_dev);
+  check_devs(srcs);
   auto seed_of = [](int dev) { return 0x51ed27u ^ (unsigned)(dev * 977); };
   float ms = 0.f;
   bool ok = true;
@@ -488,9 +287,7 @@ py::dict gather_bw(int dst_dev, const std::vector<int>& srcs, size_t bytes, int 
   r["dst"] = dst_dev;
   r["srcs"] = srcs;
   r["bytes_per_src"] = bytes;
-  r["iters"] = iters;
-  r["ms_per_iter"] = (double)ms / iters;
-  r["gbps"] = gbps((double)bytes * nsrc, ms, iters);
+  put_rate(r, (double)bytes * nsrc, ms, iters);
   r["ok"] = ok;
   return r;
 }
@@ -509,18 +306,14 @@ py::dict ring_bw(const std::vector<int>& devs, const std::vector<std::vector<int
   if (k < 2 || k > kMaxSrc + 1) throw std::invalid_argument("2..17 ring members");
   if ((int)peers.size() != k) throw std::invalid_argument("one peer list per member");
   check_bytes_iters(bytes, iters);
-  int ndev = 0;
-  HIP_CHECK(hipGetDeviceCount(&ndev));
-  for (int d : devs)
-    if (d < 0 || d >= ndev) throw std::invalid_argument("device index out of range");
+  check_devs(devs);
   for (int m = 0; m < k; ++m) {
     if (peers[m].empty() || peers[m].size() > (size_t)kMaxSrc) throw std::invalid_argument("1..16 peers per member");
     for (int p : peers[m])
       if (p < 0 || p >= k || p == m) throw std::invalid_argument("peers are other members' indices");
   }
   auto seed_of = [](int m) { return 0x6a09e667u ^ (unsigned)(m * 7919 + 1); };
-  std::vector<double> ms_member(k, 0.0);
-  double wall_ms = 0.0;
+  MemberTimes t;
   bool ok = true;
   {
     py::gil_scoped_release nogil;
@@ -534,49 +327,22 @@ py::dict ring_bw(const std::vector<int>& devs, const std::vector<std::vector<int
     }
     std::vector<SrcSet> sets(k);
     std::vector<int> grid(k);
-    std::vector<std::unique_ptr<TimedStream>> ts;
+    MemberStreams ts;
     for (int m = 0; m < k; ++m) {
       const int ns = (int)peers[m].size();
       for (int i = 0; i < ns; ++i) sets[m].p[i] = reinterpret_cast<const u32x4*>(src[peers[m][i]]->p);
-      // members sharing a device split its CUs, so the self-test does not oversubscribe one GPU
-      int share = 0;
-      for (int d : devs) share += (d == devs[m]);
-      grid[m] = gather_grid(devs[m], blocks_per_cu, ns, share);
+      grid[m] = gather_grid(devs[m], blocks_per_cu, ns, device_share(devs, devs[m]));
       DeviceGuard g(devs[m]);
       ts.emplace_back(new TimedStream());
     }
-    auto launch_round = [&]() {
+    t = time_member_rounds(devs, ts, warmup, iters, [&](int) {
       for (int m = 0; m < k; ++m) {
         DeviceGuard g(devs[m]);
         hipLaunchKernelGGL(gather_lds_kernel, dim3(grid[m]), dim3(kBlock), 0, ts[m]->s, sets[m], (int)peers[m].size(),
                            (u32x4*)inbox[m]->p, bytes / 16);
         HIP_CHECK(hipGetLastError());
       }
-    };
-    auto sync_all = [&]() {
-      for (int m = 0; m < k; ++m) {
-        DeviceGuard g(devs[m]);
-        HIP_CHECK(hipStreamSynchronize(ts[m]->s));
-      }
-    };
-    for (int i = 0; i < warmup; ++i) launch_round();
-    sync_all();
-    auto t0 = std::chrono::steady_clock::now();
-    for (int m = 0; m < k; ++m) {
-      DeviceGuard g(devs[m]);
-      ts[m]->begin();
-    }
-    for (int i = 0; i < iters; ++i) launch_round();
-    for (int m = 0; m < k; ++m) {
-      DeviceGuard g(devs[m]);
-      ts[m]->end();
-    }
-    sync_all();
-    wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    for (int m = 0; m < k; ++m) {
-      DeviceGuard g(devs[m]);
-      ms_member[m] = ts[m]->ms();
-    }
+    });
     ts.clear();
     // every inbox segment holds its peer's pattern
     for (int m = 0; m < k && ok; ++m)
@@ -587,364 +353,20 @@ py::dict ring_bw(const std::vector<int>& devs, const std::vector<std::vector<int
   std::vector<double> gbps(k);
   double bound = 0.0;
   for (int m = 0; m < k; ++m) {
-    gbps[m] = (double)bytes * peers[m].size() * iters / (ms_member[m] / 1e3) / 1e9;
+    gbps[m] = (double)bytes * peers[m].size() * iters / (t.ms_member[m] / 1e3) / 1e9;
     bound = (m == 0) ? gbps[m] : std::min(bound, gbps[m]);
   }
   r["devs"] = devs;
   r["peers"] = peers;
   r["bytes_per_peer"] = bytes;
   r["iters"] = iters;
-  r["ms_member"] = ms_member;
-  r["wall_ms"] = wall_ms;
+  r["ms_member"] = t.ms_member;
+  r["wall_ms"] = t.wall_ms;
   r["ingress_gbps"] = gbps;
   r["bound_gbps"] = bound;
   r["ok"] = ok;
   return r;
 }
-
-// K7 peer all-reduce: the sum of k members' buffers, left in every member's `out`, by this
-// repository's own kernels over peer pointers (peer_allreduce.h): no RCCL.  One process, one stream
-// per member as in K6, and members may repeat a device, so a 1-GPU box runs the k-member indexing
-// and ordering.  The sum is taken in member order in fp32 and rounded once, so every member's result
-// is bit-identical and equals a sequential CPU sum (ops/peer_ref.py).
-//   oneshot: member m reduces every member's whole `in` into its own `out`; k x N read per member,
-//            one launch, no dependency between members.
-//   twoshot: phase 1, member m reduces slice m of every `in` into slice m of its `out`; phase 2, it
-//            copies slice p from out[p] for every p != m.  Ingress per member 2(k-1)/k x N.
-// Members are ordered by stream events alone (no kernel waits for a running kernel): e1[m] follows
-// m's phase 1 and every member's phase 2 waits for all of them; e2[m] follows m's phase 2 and every
-// member's next phase 1 waits for all of them, since phase 2 of p reads the slice m then overwrites.
-struct PeerSlice {
-  size_t first, count;  // in 16-byte vectors
-};
-
-// Slice s of k: vectors [s*per, min(n_vec, (s+1)*per)), per = ceil(n_vec / k); trailing ones may be empty.
-std::vector<PeerSlice> peer_slices(size_t n_vec, int k) {
-  const size_t per = (n_vec + k - 1) / k;
-  std::vector<PeerSlice> out(k);
-  for (int s = 0; s < k; ++s) {
-    const size_t a = std::min(n_vec, (size_t)s * per), b = std::min(n_vec, (size_t)(s + 1) * per);
-    out[s] = PeerSlice{a, b - a};
-  }
-  return out;
-}
-
-// Member buckets of peer_reduce_kernel: k x U loads of 16 bytes per lane stay within 64 VGPRs.
-// The wide form (bf16 in, fp32 out) holds the same loads and eight accumulators, so it keeps the same U.
-template <typename TI, typename TO>
-void launch_peer_reduce(const SrcSet& set, int k, size_t v0, size_t v1, u32x4* dst, float scale, int grid, hipStream_t s) {
-  const dim3 g(grid), b(kBlock);
-  if (k <= 2)
-    peer_reduce_kernel<TI, TO, 2, 4><<<g, b, 0, s>>>(set, k, v0, v1, dst, scale);
-  else if (k <= 4)
-    peer_reduce_kernel<TI, TO, 4, 4><<<g, b, 0, s>>>(set, k, v0, v1, dst, scale);
-  else if (k <= 8)
-    peer_reduce_kernel<TI, TO, 8, 2><<<g, b, 0, s>>>(set, k, v0, v1, dst, scale);
-  else
-    peer_reduce_kernel<TI, TO, 16, 1><<<g, b, 0, s>>>(set, k, v0, v1, dst, scale);
-  HIP_CHECK(hipGetLastError());
-}
-
-// The element types of a reduce: bf16 -> bf16, fp32 -> fp32 and the wide bf16 -> fp32.
-struct PeerTypes {
-  bool in_bf16 = true, out_bf16 = true;
-  size_t in_elem() const { return in_bf16 ? 2 : 4; }
-  size_t out_elem() const { return out_bf16 ? 2 : 4; }
-  size_t ratio() const { return out_elem() / in_elem(); }  // output vectors per input vector
-};
-
-PeerTypes peer_types(const std::string& dtype, const std::string& out_dtype) {
-  if (dtype != "bf16" && dtype != "fp32") throw std::invalid_argument("dtype must be bf16|fp32");
-  const std::string& o = out_dtype.empty() ? dtype : out_dtype;
-  if (o != "bf16" && o != "fp32") throw std::invalid_argument("out_dtype must be bf16|fp32");
-  if (dtype == "fp32" && o == "bf16") throw std::invalid_argument("fp32 inputs reduce to fp32 only");
-  return PeerTypes{dtype == "bf16", o == "bf16"};
-}
-
-void launch_peer_reduce(PeerTypes t, const SrcSet& set, int k, size_t v0, size_t v1, u32x4* dst, float scale, int grid,
-                        hipStream_t s) {
-  if (!t.in_bf16)
-    launch_peer_reduce<float, float>(set, k, v0, v1, dst, scale, grid, s);
-  else if (t.out_bf16)
-    launch_peer_reduce<uint16_t, uint16_t>(set, k, v0, v1, dst, scale, grid, s);
-  else
-    launch_peer_reduce<uint16_t, float>(set, k, v0, v1, dst, scale, grid, s);
-}
-
-struct PeerAllreduce {
-  static constexpr size_t kMaxCount = (size_t)64 << 20;  // elements, through the array entry point
-
-  std::vector<int> devs;
-  int k = 0, nsets = 1;
-  bool bf16 = true, twoshot = false;
-  PeerTypes types;
-  float scale = 1.0f;
-  size_t count = 0, elem = 2, n_vec = 0;
-  std::vector<std::unique_ptr<DevBuf>> in[2], out;  // in[set][m]: rounds alternate between the sets
-  SrcSet srcs[2]{};
-  std::vector<PeerSlice> plan;
-  std::vector<SliceSet> gather;  // member m's phase 2: slice p of out[p], every p != m
-  std::vector<int> reduce_grid, gather_grid_;
-  std::vector<std::unique_ptr<TimedStream>> ts;
-  std::vector<hipEvent_t> e1, e2;
-  size_t rounds_done = 0;
-
-  static void check_args(const std::vector<int>& devs, size_t count, const std::string& dtype, const std::string& algo) {
-    if (devs.size() < 2 || devs.size() > (size_t)kMaxSrc) throw std::invalid_argument("2..16 members");
-    int ndev = 0;
-    HIP_CHECK(hipGetDeviceCount(&ndev));
-    for (int d : devs)
-      if (d < 0 || d >= ndev) throw std::invalid_argument("device index out of range");
-    if (count < 1) throw std::invalid_argument("count >= 1");
-    if (dtype != "bf16" && dtype != "fp32") throw std::invalid_argument("dtype must be bf16|fp32");
-    if (algo != "oneshot" && algo != "twoshot") throw std::invalid_argument("algo must be oneshot|twoshot");
-  }
-
-  PeerAllreduce(const std::vector<int>& devs_, size_t count_, const std::string& dtype, const std::string& algo,
-                int nsets_, int blocks_per_cu, const std::string& out_dtype = "", float scale_ = 1.0f)
-      : devs(devs_), k((int)devs_.size()), nsets(nsets_), bf16(dtype == "bf16"), twoshot(algo == "twoshot"),
-        types(peer_types(dtype, out_dtype)), scale(scale_), count(count_), elem(dtype == "bf16" ? 2 : 4), n_vec((count_ * (dtype == "bf16" ? 2 : 4) + 15) / 16),
-        plan(peer_slices(n_vec, k)), gather(k), reduce_grid(k), gather_grid_(k), e1(k, nullptr), e2(k, nullptr) {
-    for (int m = 0; m < k; ++m)
-      for (int p = 0; p < k; ++p) enable_peer(devs[m], devs[p]);
-    for (int m = 0; m < k; ++m) {
-      for (int s = 0; s < nsets; ++s) {
-        in[s].emplace_back(new DevBuf(devs[m], n_vec * 16));
-        srcs[s].p[m] = reinterpret_cast<const u32x4*>(in[s][m]->p);
-      }
-      out.emplace_back(new DevBuf(devs[m], n_vec * 16 * types.ratio()));
-    }
-    try {
-      for (int m = 0; m < k; ++m) {
-        int share = 0;  // members sharing a device split its CUs, as in K6
-        for (int d : devs) share += (d == devs[m]);
-        const size_t mine = twoshot ? plan[m].count : n_vec;  // no more blocks than vectors to reduce
-        const size_t cap = std::max(1, num_cus(devs[m]) * std::max(1, blocks_per_cu) / share);
-        reduce_grid[m] = (int)std::max<size_t>(1, std::min(cap, (mine + kBlock - 1) / kBlock));
-        gather_grid_[m] = gather_grid(devs[m], blocks_per_cu, k - 1, share);
-        int i = 0;
-        for (int p = 0; p < k; ++p) {
-          if (p == m) continue;
-          gather[m].p[i] = reinterpret_cast<const u32x4*>(out[p]->p);
-          gather[m].first[i] = plan[p].first * types.ratio();  // slices of the output type
-          gather[m].count[i] = plan[p].count * types.ratio();
-          ++i;
-        }
-        DeviceGuard g(devs[m]);
-        ts.emplace_back(new TimedStream());
-        HIP_CHECK(hipEventCreateWithFlags(&e1[m], hipEventDisableTiming));
-        HIP_CHECK(hipEventCreateWithFlags(&e2[m], hipEventDisableTiming));
-      }
-    } catch (...) {
-      release();
-      throw;
-    }
-  }
-  ~PeerAllreduce() { release(); }
-  PeerAllreduce(const PeerAllreduce&) = delete;
-  PeerAllreduce& operator=(const PeerAllreduce&) = delete;
-
-  size_t padded() const { return n_vec * 16 / elem; }  // elements of a buffer, zero padding included
-
-  void reduce(int m, int set, size_t v0, size_t v1) {
-    if (v0 == v1) return;
-    launch_peer_reduce(types, srcs[set], k, v0, v1, reinterpret_cast<u32x4*>(out[m]->p), scale, reduce_grid[m], ts[m]->s);
-  }
-
-  // One all-reduce of input set `set`, enqueued on every member's stream.  Every e1 / e2 is recorded
-  // before any stream is made to wait for it (a wait for an event never recorded is no wait).
-  void round(int set) {
-    for (int m = 0; m < k; ++m) {
-      DeviceGuard g(devs[m]);
-      if (!twoshot) {
-        reduce(m, set, 0, n_vec);
-        continue;
-      }
-      if (rounds_done)
-        for (int p = 0; p < k; ++p)
-          if (p != m) HIP_CHECK(hipStreamWaitEvent(ts[m]->s, e2[p], 0));
-      reduce(m, set, plan[m].first, plan[m].first + plan[m].count);
-      HIP_CHECK(hipEventRecord(e1[m], ts[m]->s));
-    }
-    for (int m = 0; twoshot && m < k; ++m) {
-      DeviceGuard g(devs[m]);
-      for (int p = 0; p < k; ++p)
-        if (p != m) HIP_CHECK(hipStreamWaitEvent(ts[m]->s, e1[p], 0));
-      peer_allgather_kernel<<<dim3(gather_grid_[m]), dim3(kBlock), 0, ts[m]->s>>>(gather[m], k - 1, (u32x4*)out[m]->p);
-      HIP_CHECK(hipGetLastError());
-      HIP_CHECK(hipEventRecord(e2[m], ts[m]->s));
-    }
-    ++rounds_done;
-  }
-
-  void sync_all() {
-    for (int m = 0; m < k; ++m) {
-      DeviceGuard g(devs[m]);
-      HIP_CHECK(hipStreamSynchronize(ts[m]->s));
-    }
-  }
-
-  // in[set][m] = pattern(seed_of(set, m)), padding zero.
-  static unsigned int seed_of(int set, int m) { return 0x243f6a88u ^ (unsigned)(set * 0x9e3779b9u) ^ (unsigned)(m * 7919 + 1); }
-  void fill(int set) {
-    for (int m = 0; m < k; ++m) {
-      DeviceGuard g(devs[m]);
-      const dim3 grid(num_cus(devs[m]) * 4), block(kBlock);
-      if (bf16)
-        peer_fill_kernel<uint16_t><<<grid, block>>>((uint16_t*)in[set][m]->p, count, padded(), seed_of(set, m));
-      else
-        peer_fill_kernel<float><<<grid, block>>>((float*)in[set][m]->p, count, padded(), seed_of(set, m));
-      HIP_CHECK(hipGetLastError());
-      HIP_CHECK(hipDeviceSynchronize());
-    }
-  }
-
-  // Elements of every member's `out` (padding included) that are not the sum of set `set`'s patterns.
-  unsigned long long wrong(int set) {
-    SeedSet seeds{};
-    for (int m = 0; m < k; ++m) seeds.s[m] = seed_of(set, m);
-    unsigned long long total = 0;
-    for (int m = 0; m < k; ++m) {
-      DeviceGuard g(devs[m]);
-      DevBuf bad(devs[m], sizeof(unsigned long long));
-      HIP_CHECK(hipMemset(bad.p, 0, sizeof(unsigned long long)));
-      const dim3 grid(num_cus(devs[m]) * kBlocksPerCU), block(kBlock);
-      if (bf16)
-        peer_check_kernel<uint16_t><<<grid, block>>>((const uint16_t*)out[m]->p, count, padded(), seeds, k,
-                                                     (unsigned long long*)bad.p);
-      else
-        peer_check_kernel<float><<<grid, block>>>((const float*)out[m]->p, count, padded(), seeds, k,
-                                                  (unsigned long long*)bad.p);
-      HIP_CHECK(hipGetLastError());
-      unsigned long long n = 0;
-      HIP_CHECK(hipMemcpy(&n, bad.p, sizeof(n), hipMemcpyDeviceToHost));
-      total += n;
-    }
-    return total;
-  }
-
- private:
-  void release() noexcept {
-    ts.clear();  // synchronises every stream first
-    for (int m = 0; m < k; ++m) {
-      int prev = 0;
-      (void)hipGetDevice(&prev);
-      (void)hipSetDevice(devs[m]);
-      if (e1[m]) (void)hipEventDestroy(e1[m]);
-      if (e2[m]) (void)hipEventDestroy(e2[m]);
-      e1[m] = e2[m] = nullptr;
-      (void)hipSetDevice(prev);
-    }
-  }
-};
-
-py::dict peer_allreduce(const std::vector<int>& devs, size_t count, const std::string& dtype, const std::string& algo,
-                        int iters, int warmup, int blocks_per_cu) {
-  PeerAllreduce::check_args(devs, count, dtype, algo);
-  if (iters < 1 || warmup < 0) throw std::invalid_argument("iters >= 1, warmup >= 0");
-  const int k = (int)devs.size();
-  std::vector<double> ms_member(k, 0.0);
-  double wall_ms = 0.0;
-  unsigned long long wrong = 0;
-  size_t bytes = 0;
-  {
-    py::gil_scoped_release nogil;
-    // with more than one round, consecutive rounds alternate between two input sets and the check uses
-    // the last round's: a round that ran ahead of the one before it leaves a mix of the two sums
-    const int total = warmup + iters;
-    PeerAllreduce ar(devs, count, dtype, algo, total >= 2 ? 2 : 1, blocks_per_cu);
-    bytes = count * ar.elem;
-    for (int s = 0; s < ar.nsets; ++s) ar.fill(s);
-    int r = 0;
-    for (; r < warmup; ++r) ar.round(r % ar.nsets);
-    ar.sync_all();
-    auto t0 = std::chrono::steady_clock::now();
-    for (int m = 0; m < k; ++m) {
-      DeviceGuard g(devs[m]);
-      ar.ts[m]->begin();
-    }
-    for (; r < total; ++r) ar.round(r % ar.nsets);
-    for (int m = 0; m < k; ++m) {
-      DeviceGuard g(devs[m]);
-      ar.ts[m]->end();
-    }
-    ar.sync_all();
-    wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    for (int m = 0; m < k; ++m) {
-      DeviceGuard g(devs[m]);
-      ms_member[m] = ar.ts[m]->ms();
-    }
-    wrong = ar.wrong((total - 1) % ar.nsets);
-  }
-  const double time_us = *std::max_element(ms_member.begin(), ms_member.end()) * 1e3 / iters;
-  py::dict r;
-  r["devs"] = devs;
-  r["dtype"] = dtype;
-  r["algo"] = algo;
-  r["iters"] = iters;
-  r["bytes"] = bytes;
-  r["count"] = count;
-  r["time_us"] = time_us;
-  r["algbw_gbps"] = (double)bytes / (time_us * 1e-6) / 1e9;
-  r["busbw_gbps"] = (double)bytes / (time_us * 1e-6) / 1e9 * (2.0 * (k - 1) / k);
-  r["ms_member"] = ms_member;
-  r["wall_ms"] = wall_ms;
-  r["wrong"] = wrong;
-  r["ok"] = wrong == 0;
-  return r;
-}
-
-// The same all-reduce on the caller's data: k one-dimensional arrays of equal length (uint16 bit
-// patterns for bf16, float32 for fp32) in, the k members' results out, after `rounds` all-reduces of
-// the same inputs.  `out_dtype` (none: the inputs') and `scale` select the wide and the scaled reduce.
-py::list peer_allreduce_arrays(const std::vector<int>& devs, const std::vector<py::array>& inputs, const std::string& dtype,
-                               const std::string& algo, int rounds, const std::optional<std::string>& out_dtype, float scale) {
-  if (inputs.size() != devs.size()) throw std::invalid_argument("one input array per member");
-  const size_t count = inputs.empty() ? 0 : (size_t)inputs[0].size();
-  PeerAllreduce::check_args(devs, count, dtype, algo);
-  if (count > PeerAllreduce::kMaxCount) throw std::invalid_argument("count <= 64 Mi elements");
-  if (rounds < 1) throw std::invalid_argument("rounds >= 1");
-  const PeerTypes types = peer_types(dtype, out_dtype.value_or(""));
-  const py::dtype want = dtype == "bf16" ? py::dtype::of<uint16_t>() : py::dtype::of<float>();
-  const py::dtype give = types.out_bf16 ? py::dtype::of<uint16_t>() : py::dtype::of<float>();
-  const int k = (int)devs.size();
-  std::vector<py::array> src, dst;
-  for (const py::array& a : inputs) {
-    if (a.ndim() != 1 || (size_t)a.size() != count || !a.dtype().is(want))
-      throw std::invalid_argument("inputs: one-dimensional arrays of one length, uint16 (bf16) or float32 (fp32)");
-    src.push_back(py::array::ensure(a, py::array::c_style));
-    dst.push_back(py::array(give, std::vector<py::ssize_t>{(py::ssize_t)count}));
-  }
-  std::vector<const void*> from(k);
-  std::vector<void*> to(k);
-  for (int m = 0; m < k; ++m) {
-    from[m] = src[m].data();
-    to[m] = dst[m].mutable_data();
-  }
-  {
-    py::gil_scoped_release nogil;
-    PeerAllreduce ar(devs, count, dtype, algo, 1, kBlocksPerCU, out_dtype.value_or(""), scale);
-    for (int m = 0; m < k; ++m) {
-      DeviceGuard g(devs[m]);
-      HIP_CHECK(hipMemset(ar.in[0][m]->p, 0, ar.n_vec * 16));
-      HIP_CHECK(hipMemcpy(ar.in[0][m]->p, from[m], count * ar.elem, hipMemcpyHostToDevice));
-      HIP_CHECK(hipDeviceSynchronize());
-    }
-    for (int r = 0; r < rounds; ++r) ar.round(0);
-    ar.sync_all();
-    for (int m = 0; m < k; ++m) {
-      DeviceGuard g(devs[m]);
-      HIP_CHECK(hipMemcpy(to[m], ar.out[m]->p, count * types.out_elem(), hipMemcpyDeviceToHost));
-    }
-  }
-  py::list r;
-  for (py::array& a : dst) r.append(a);
-  return r;
-}
-
-}  // namespace
-#include "peer_rank.h"  // one rank of the peer communicator's device backend, over the K7 launches above
-namespace {
 
 // K8 link latency: one wave on `exec_dev` follows a chain of dependent loads (chase_latency.h) that
 // lives in the memory of the chain's device, the orientation of copy_bw in read mode: the number for
@@ -982,11 +404,6 @@ class ChaseChain {
     if (hops < 1 || hops > kMaxHops) throw std::invalid_argument("1 <= hops <= 2^18");
     if (warmup < 0 || iters + warmup > kMaxLaunches) throw std::invalid_argument("warmup >= 0, iters + warmup <= 64");
     check_bytes_iters(kEvictBytes, iters);
-  }
-  static void check_dev(int dev) {
-    int ndev = 0;
-    HIP_CHECK(hipGetDeviceCount(&ndev));
-    if (dev < 0 || dev >= ndev) throw std::invalid_argument("device index out of range");
   }
 
   // Allocates the chain on `dev` and writes it there, once for every run() that follows.
@@ -1118,8 +535,7 @@ py::dict chase_latency(int src_dev, int exec_dev, size_t ws_bytes, size_t stride
   // every argument is checked before the chain is allocated or anything is launched
   ChaseChain::check_chain(ws_bytes, stride);
   ChaseChain::check_run(hops, chains, iters, warmup);
-  ChaseChain::check_dev(src_dev);
-  ChaseChain::check_dev(exec_dev);
+  check_devs({src_dev, exec_dev});
   ChaseChain chain(src_dev, ws_bytes, stride);
   return chain.run_py(exec_dev, hops, chains, iters, warmup, evict);
 }
@@ -1320,29 +736,44 @@ struct IpcMappings {
   IpcMappings& operator=(const IpcMappings&) = delete;
 };
 
-// K2 over IPC: the writer's kernel pushes a local patterned buffer into another process's buffer
-// through the imported mapping (remote stores, the direction RCCL's P2P write protocol uses).  The
-// owner checks the result (IpcBuffer.holds), since only it knows the write has landed in its memory.
-py::dict ipc_write_bw(const py::bytes& handle, int dev, size_t bytes, unsigned int seed, int iters, int warmup,
-                      int blocks_per_cu) {
+// One imported buffer and one local buffer of `dev`, the K1 LDS-DMA kernel between them.
+//   write (K2 over IPC): the kernel pushes a local patterned buffer into another process's buffer
+//     through the imported mapping (remote stores, the direction RCCL's P2P write protocol uses).  The
+//     owner checks the result (IpcBuffer.holds), since only it knows the write has landed in its memory.
+//   read: the imported buffer is streamed into the local one, which is then verified against `seed`.
+py::dict ipc_copy_bw(bool write, const py::bytes& handle, int dev, size_t bytes, unsigned int seed, int iters, int warmup,
+                     int blocks_per_cu) {
   check_bytes_iters(bytes, iters);
   IpcMappings map({handle}, dev);
   float ms = 0.f;
+  bool ok = true;
   {
     py::gil_scoped_release nogil;
     DeviceGuard g(dev);
-    DevBuf src(dev, bytes);
-    fill_pattern(dev, src.p, bytes, seed);
+    DevBuf local(dev, bytes);
+    if (write) fill_pattern(dev, local.p, bytes, seed);
+    const void* src = write ? local.p : map.p[0];
+    void* dst = write ? map.p[0] : local.p;
     const int grid = num_cus(dev) * std::max(1, blocks_per_cu);
-    ms = time_launches([&](hipStream_t s) { launch_copy("lds", true, src.p, map.p[0], bytes / 16, grid, s); }, iters, warmup);
+    ms = time_launches([&](hipStream_t s) { launch_copy("lds", true, src, dst, bytes / 16, grid, s); }, iters, warmup);
+    if (!write) ok = holds_pattern(dev, local.p, bytes / 4, seed);
   }
   py::dict d;
   d["dev"] = dev;
   d["bytes"] = bytes;
-  d["iters"] = iters;
-  d["ms_per_iter"] = ms / iters;
-  d["gbps"] = gbps((double)bytes, ms, iters);
+  put_rate(d, (double)bytes, ms, iters);
+  if (!write) d["ok"] = ok;
   return d;
+}
+
+py::dict ipc_write_bw(const py::bytes& handle, int dev, size_t bytes, unsigned int seed, int iters, int warmup,
+                      int blocks_per_cu) {
+  return ipc_copy_bw(true, handle, dev, bytes, seed, iters, warmup, blocks_per_cu);
+}
+
+py::dict ipc_read_bw(const py::bytes& handle, int dev, size_t bytes, unsigned int seed, int iters, int warmup,
+                     int blocks_per_cu) {
+  return ipc_copy_bw(false, handle, dev, bytes, seed, iters, warmup, blocks_per_cu);
 }
 
 // K5 over IPC: one gather launch pulls every imported buffer at once (segment i of the inbox from
@@ -1373,33 +804,7 @@ py::dict ipc_gather_bw(const std::vector<py::bytes>& handles, int dev, size_t by
   d["dev"] = dev;
   d["segments"] = nsrc;
   d["bytes_per_segment"] = bytes;
-  d["iters"] = iters;
-  d["ms_per_iter"] = ms / iters;
-  d["gbps"] = gbps((double)bytes * nsrc, ms, iters);
-  d["ok"] = ok;
-  return d;
-}
-
-py::dict ipc_read_bw(const py::bytes& handle, int dev, size_t bytes, unsigned int seed, int iters, int warmup,
-                     int blocks_per_cu) {
-  check_bytes_iters(bytes, iters);
-  IpcMappings map({handle}, dev);
-  float ms = 0.f;
-  bool ok = true;
-  {
-    py::gil_scoped_release nogil;
-    DeviceGuard g(dev);
-    DevBuf dst(dev, bytes);
-    const int grid = num_cus(dev) * std::max(1, blocks_per_cu);
-    ms = time_launches([&](hipStream_t s) { launch_copy("lds", true, map.p[0], dst.p, bytes / 16, grid, s); }, iters, warmup);
-    ok = holds_pattern(dev, dst.p, bytes / 4, seed);
-  }
-  py::dict d;
-  d["dev"] = dev;
-  d["bytes"] = bytes;
-  d["iters"] = iters;
-  d["ms_per_iter"] = ms / iters;
-  d["gbps"] = gbps((double)bytes, ms, iters);
+  put_rate(d, (double)bytes * nsrc, ms, iters);
   d["ok"] = ok;
   return d;
 }

@@ -1,4 +1,5 @@
-"""Python front-end of the HIP/CDNA4 link probe (``csrc/probe/probe.hip``).
+"""Python front-end of the HIP/CDNA4 link probe (``csrc/probe/probe.hip`` and the headers it
+includes: ``probe_common.h``, K7's ``peer_allreduce.h`` / ``peer_driver.h``, K8's ``chase_latency.h``).
 
 Seeds the link-cost matrix at node start (BASELINE.json north_star):
 
@@ -26,6 +27,7 @@ import numpy as np
 from .._native import load
 from ..topology.identity import DeviceMap
 from ..topology.model import Topology
+from .peer_ref import ELEM
 
 log = logging.getLogger(__name__)
 
@@ -163,7 +165,7 @@ def peer_sweep(devs: Sequence[int], sizes: Sequence[int], dtype: str = "bf16", a
     and algorithm, in size order, with ``fastest`` marking the quicker algorithm of each size."""
     if algo != "both" and algo not in PEER_ALGOS:
         raise ValueError(f"algo must be oneshot|twoshot|both, got {algo!r}")
-    elem = {"bf16": 2, "fp32": 4}.get(dtype)
+    elem = ELEM.get(dtype)
     if elem is None:
         raise ValueError(f"dtype must be bf16|fp32, got {dtype!r}")
     out: List[Dict[str, object]] = []

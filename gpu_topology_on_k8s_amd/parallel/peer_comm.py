@@ -1,9 +1,9 @@
 """Peer communicator: the per-rank protocol of the K7 collectives, on a host and on a device backend.
 
 Every rank owns a *window* (inputs) and an *out* buffer (results) and reads its peers'.  The phases are
-K7's (``csrc/probe/peer_allreduce.h``): a rank reads every window, sums in fp32 in rank order, scales,
-rounds once and writes its own out, so every rank holds the same bits and ``ops/peer_ref.py``
-reproduces them.
+K7's (``csrc/probe/peer_allreduce.h``, launched through ``csrc/probe/peer_driver.h``): a rank reads
+every window, sums in fp32 in rank order, scales, rounds once and writes its own out, so every rank
+holds the same bits and ``ops/peer_ref.py`` reproduces them.
 
 Cross-rank ordering is **host-side only**: ``synchronize()`` of the rank's stream, then a counting
 barrier on a c10d-style store, with a timeout.  It is the cross-process form of K7's stream events.
@@ -44,15 +44,14 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ..ops.peer_ref import allreduce_ref, bf16_round, peer_slices
+from ..ops.peer_ref import ELEM as _ELEM, allreduce_ref, bf16_round, bits as _bits, out_dtype_of as _out_dtype, peer_slices
 
 __all__ = ["PeerComm", "PeerCommError", "PeerCommTimeout", "PeerCommMismatch", "HostFabric", "MemoryStore",
            "selftest_cases", "case_input", "run_case", "run_thread_ranks", "selftest", "thread_sweep", "timed_all_reduce", "parked_bytes",
            "MAX_WORLD"]
 
-MAX_WORLD = 16  # kMaxSrc of probe.hip
+MAX_WORLD = 16  # kMaxSrc of csrc/probe/probe_common.h
 BACKENDS = ("host", "device")
-_ELEM = {"bf16": 2, "fp32": 4}
 _NP = {"bf16": np.uint16, "fp32": np.float32}
 ALGOS = ("oneshot", "twoshot")
 
@@ -67,17 +66,6 @@ class PeerCommTimeout(PeerCommError):
 
 class PeerCommMismatch(PeerCommError):
     """The ranks entered one collective with different arguments; raised on every rank, before any launch."""
-
-
-def _out_dtype(dtype: str, out_dtype: Optional[str]) -> str:
-    if dtype not in _ELEM:
-        raise ValueError(f"dtype must be bf16|fp32, got {dtype!r}")
-    out = dtype if out_dtype is None else out_dtype
-    if out not in _ELEM:
-        raise ValueError(f"out_dtype must be bf16|fp32, got {out!r}")
-    if dtype == "fp32" and out == "bf16":
-        raise ValueError("fp32 inputs reduce to fp32 only")
-    return out
 
 
 def _n_vec(count: int, dtype: str) -> int:
@@ -610,10 +598,6 @@ def run_case(comm: PeerComm, case: Dict[str, object], inputs: Sequence[np.ndarra
         return comm.read(0, count, out), allreduce_ref(inputs, dtype, out, case["scale"])
     first, n = comm.reduce_scatter(count, dtype, out, case["scale"])
     return comm.read(first, n, out), reduce_scatter_ref(inputs, dtype, out, case["scale"])[r]
-
-
-def _bits(a: np.ndarray) -> np.ndarray:
-    return a.view(np.uint16 if a.dtype == np.uint16 else np.uint32)
 
 
 def run_thread_ranks(devices: Sequence[int], body: Callable[[PeerComm], object], capacity_bytes: int, timeout_s: float = 60.0,

@@ -99,6 +99,27 @@ def test_pattern_verifier_is_not_vacuous(probe_mod):
     assert not b.holds(0x5EED ^ 1)
 
 
+_BAD_DEVICE_CALLS = {
+    "copy_bw src": lambda p: p.copy_bw(99, 0, 0, 1 << 20),
+    "copy_bw dst": lambda p: p.copy_bw(0, -1, 0, 1 << 20),
+    "gather_bw dst": lambda p: p.gather_bw(99, [0, 0], 1 << 20),
+    "gather_bw src": lambda p: p.gather_bw(0, [0, 99], 1 << 20),
+    "ring_bw": lambda p: p.ring_bw([0, 99], [[1], [0]], 1 << 20),
+    "ChaseChain": lambda p: p.ChaseChain(99, 1 << 20, 128),
+    "ChaseChain.run": lambda p: p.ChaseChain(0, 1 << 20, 128).run(99, hops=8, iters=1, warmup=0, evict=False),
+    "PeerRank": lambda p: p.PeerRank(99, 0, 2, 1 << 20),
+    "PeerRank negative": lambda p: p.PeerRank(-1, 0, 2, 1 << 20),
+}
+
+
+@pytest.mark.parametrize("call", sorted(_BAD_DEVICE_CALLS))
+def test_out_of_range_device_is_a_value_error(probe_mod, call):
+    """Every entry point that takes a device index refuses one the process does not have, as an
+    argument error (chase_latency and peer_allreduce: test_gpu_chase_latency, test_gpu_peer_allreduce)."""
+    with pytest.raises(ValueError, match="device index out of range"):
+        _BAD_DEVICE_CALLS[call](probe_mod)
+
+
 def test_gather_kernel_segments(probe_mod):
     """K5 gather: three source buffers streamed by one launch land in their own dst segments (the
     sources are local here; on a node they are the peers, same kernel); odd size exercises tails."""

@@ -1,4 +1,4 @@
-"""GPU tests of the K7 peer all-reduce (csrc/probe/peer_allreduce.h and its driver in probe.hip).
+"""GPU tests of the K7 peer all-reduce (csrc/probe/peer_allreduce.h and its driver, peer_driver.h).
 
 Members repeat device 0, which runs the k-member indexing, the slice plan and the event ordering on
 one GPU.  The exact tests compare every element of every member's output with the numpy reference
@@ -114,6 +114,24 @@ def test_timed_allreduce_checks_itself(dtype, algo):
     assert len(r["ms_member"]) == 4 and r["time_us"] == pytest.approx(max(r["ms_member"]) * 1e3 / 3)
     assert r["algbw_gbps"] > 0 and r["wall_ms"] > 0
     assert r["busbw_gbps"] == pytest.approx(r["algbw_gbps"] * 1.5)
+
+
+@pytest.mark.parametrize("k,vectors", [(3, None), (16, 15)])
+@pytest.mark.parametrize("iters", [1, 2])
+@pytest.mark.parametrize("algo", ALGOS)
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_timed_allreduce_without_warmup(dtype, algo, iters, k, vectors):
+    """The timed entry point with no round before the timed ones: one round on one input set
+    (iters=1), two rounds on two sets (iters=2).  k=3 with tiles, a tail and padding; k=16 with 15
+    vectors, so the last member's slice is empty and its two-shot reduce launches nothing."""
+    from gpu_topology_on_k8s_amd.ops.probe import peer_allreduce
+
+    elem = 2 if dtype == "bf16" else 4
+    count = 8 * 1024 * 3 + 11 if vectors is None else (16 // elem) * vectors
+    r = peer_allreduce([0] * k, count, dtype, algo, iters=iters, warmup_iters=0)
+    assert r["ok"] is True and r["wrong"] == 0, r
+    assert len(r["ms_member"]) == k
+    assert r["bytes"] == count * elem and r["count"] == count
 
 
 def test_argument_checks():
