@@ -2,7 +2,7 @@
 """K7 peer all-reduce next to its comparators, on given members and sizes, as one JSON document:
 
     python bench/peer_allreduce_bench.py [--members 0,0,0,0] [--sizes-mib 1,4,16,64,256,1024]
-                                         [--dtype bf16] [--iters 5] [--out FILE] [--md FILE]
+                                         [--dtype bf16] [--iters 5] [--wire native|fp8|both] [--out FILE] [--md FILE]
 
 Per size N (bytes per member):
   * the peer all-reduce under both algorithms (algBW, busBW, and the bytes each member moves:
@@ -10,6 +10,10 @@ Per size N (bytes per member):
   * K6 ``ring_bw(members, "all")`` in the same process, each member reading as many bytes as twoshot
     does ((2 - 1/k) x N over its k - 1 peers) and writing them: the copy-only rate of the same traffic;
   * RCCL's ``local_sweep`` when the members are distinct devices (RCCL refuses a repeated device).
+``--wire both`` measures the fp8 wire (``csrc/probe/peer_q8.h``: every member packs its input into e4m3
+codes with a scale per 32 elements, the members read that) right after the native one at every size and
+algorithm, in the same process, and reports it under ``<algo>_fp8`` with the bytes its two kernels move
+and the rate each reaches alone on member 0.
 Members that repeat a device give HBM rates of that one GPU, not xGMI rates.
 """
 import argparse
@@ -24,26 +28,51 @@ from gpu_topology_on_k8s_amd.ops import probe  # noqa: E402
 ELEM = {"bf16": 2, "fp32": 4}
 
 
-def member_bytes(algo: str, k: int, n: int) -> dict:
-    """Bytes one member reads and writes in one all-reduce of n bytes."""
-    return {"read": k * n if algo == "oneshot" else (2 * k - 1) * n // k, "written": n}
+def member_bytes(algo: str, k: int, n: int, wire: str = "native", elem: int = 2) -> dict:
+    """Bytes one member reads and writes in one all-reduce of n bytes of ``elem``-byte elements.
+
+    On the fp8 wire 32 elements pack into 33 bytes, P = 33 / (32 elem) x n per member.  The quantize
+    reads n and writes P; phase 1 reads k x P (one-shot) or k x P / k = P (two-shot) and writes n or
+    n / k; phase 2 of a two-shot is the native one: it reads and writes (k - 1) / k x n."""
+    if wire == "native":
+        return {"read": k * n if algo == "oneshot" else (2 * k - 1) * n // k, "written": n}
+    packed = n // elem * 33 // 32
+    quantize = {"read": n, "written": packed}
+    total = (k if algo == "oneshot" else 1) * packed
+    phase1 = {"read": total, "written": n if algo == "oneshot" else n // k}
+    gather = 0 if algo == "oneshot" else (k - 1) * n // k
+    return {"read": n + total + gather, "written": packed + n, "quantize": quantize, "sum": phase1}
 
 
-def measure(devs, sizes, dtype, iters, warmup):
+def point(devs, n, dtype, algo, iters, warmup, wire):
+    k = len(devs)
+    r = probe.peer_allreduce(devs, n // ELEM[dtype], dtype, algo, iters, warmup, wire=wire)
+    mv = member_bytes(algo, k, n, wire, ELEM[dtype])
+    secs = r["time_us"] * 1e-6
+    p = {"time_us": r["time_us"], "algbw_gbps": r["algbw_gbps"], "busbw_gbps": r["busbw_gbps"],
+         "wrong": r["wrong"], "member_read_bytes": mv["read"], "member_written_bytes": mv["written"],
+         "member_read_gbps": mv["read"] / secs / 1e9,
+         "member_traffic_gbps": (mv["read"] + mv["written"]) / secs / 1e9}
+    if wire == "fp8":  # member 0's two kernels alone on the device: the bytes each moves over its own time
+        for name in ("quantize", "sum"):
+            b = mv[name]["read"] + mv[name]["written"]
+            p[name] = {"time_us": r[name + "_us"], "bytes": b, "gbps": b / (r[name + "_us"] * 1e-6) / 1e9}
+    return p
+
+
+def measure(devs, sizes, dtype, iters, warmup, wire="native"):
     k = len(devs)
     distinct = len(set(devs)) == k
     rows = []
     for n in sizes:
         row = {"bytes": n}
-        for algo in probe.PEER_ALGOS:
-            r = probe.peer_allreduce(devs, n // ELEM[dtype], dtype, algo, iters, warmup)
-            mv = member_bytes(algo, k, n)
-            secs = r["time_us"] * 1e-6
-            row[algo] = {"time_us": r["time_us"], "algbw_gbps": r["algbw_gbps"], "busbw_gbps": r["busbw_gbps"],
-                         "wrong": r["wrong"], "member_read_bytes": mv["read"], "member_written_bytes": mv["written"],
-                         "member_read_gbps": mv["read"] / secs / 1e9,
-                         "member_traffic_gbps": (mv["read"] + mv["written"]) / secs / 1e9}
-        row["faster"] = min(probe.PEER_ALGOS, key=lambda a: row[a]["time_us"])
+        for algo in probe.PEER_ALGOS:  # with both wires, the fp8 one right after the native one
+            if wire != "fp8":
+                row[algo] = point(devs, n, dtype, algo, iters, warmup, "native")
+            if wire != "native":
+                row[algo + "_fp8"] = point(devs, n, dtype, algo, iters, warmup, "fp8")
+        algos = [a for a in probe.PEER_ALGOS if a in row] or [a + "_fp8" for a in probe.PEER_ALGOS]
+        row["faster"] = min(algos, key=lambda a: row[a]["time_us"])
         per_peer = max(16, member_bytes("twoshot", k, n)["read"] // (k - 1) // 16 * 16)
         r6 = probe.ring_bw(devs, "all", per_peer, iters, warmup)
         row["k6_all"] = {"bytes_per_peer": per_peer, "member_read_bytes": per_peer * (k - 1), "ok": r6["ok"],
@@ -55,12 +84,35 @@ def measure(devs, sizes, dtype, iters, warmup):
             row["rccl"] = {k_: p[k_] for k_ in ("time_us", "algbw_gbps", "busbw_gbps", "wrong")}
         rows.append(row)
         print(json.dumps(row), file=sys.stderr, flush=True)
-    crossover = next((r["bytes"] for i, r in enumerate(rows) if all(q["faster"] == "twoshot" for q in rows[i:])), None)
+    crossover = next((r["bytes"] for i, r in enumerate(rows) if all(q["faster"].startswith("twoshot") for q in rows[i:])), None)
     return {"members": list(devs), "k": k, "distinct_devices": distinct, "dtype": dtype, "iters": iters, "warmup": warmup,
-            "sizes": rows, "twoshot_faster_from_bytes": crossover}
+            "wire": wire, "sizes": rows, "twoshot_faster_from_bytes": crossover}
+
+
+def markdown_fp8(res) -> str:
+    """The fp8 wire next to the native one: one line per size and algorithm."""
+    mib = lambda b: f"{b / 2**20:.1f}"  # noqa: E731
+    native = res["wire"] == "both"
+    out = [f"### fp8 wire, members {res['members']} (k = {res['k']}), {res['dtype']}, {res['iters']} timed rounds", "",
+           "| N per member MiB | algorithm | native us | native algBW | fp8 us | fp8 algBW | fp8 / native time | native MiB read + written | "
+           "fp8 MiB read + written | quantize us | quantize GB/s | sum us | sum GB/s | wrong |",
+           "|---|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
+    for r in res["sizes"]:
+        for algo in probe.PEER_ALGOS:
+            f, o = r[algo + "_fp8"], r.get(algo)
+            nat = [f"{o['time_us']:.1f}", f"{o['algbw_gbps']:.1f}"] if native else ["", ""]
+            ratio = f"{f['time_us'] / o['time_us']:.2f}" if native else ""
+            moved = f"{mib(o['member_read_bytes'])} + {mib(o['member_written_bytes'])}" if native else ""
+            out.append(f"| {mib(r['bytes'])} | {algo} | {nat[0]} | {nat[1]} | {f['time_us']:.1f} | {f['algbw_gbps']:.1f} | {ratio} | {moved} "
+                       f"| {mib(f['member_read_bytes'])} + {mib(f['member_written_bytes'])} | {f['quantize']['time_us']:.1f} "
+                       f"| {f['quantize']['gbps']:.0f} | {f['sum']['time_us']:.1f} | {f['sum']['gbps']:.0f} | {f['wrong'] + (o['wrong'] if native else 0)} |")
+    out.append("")
+    return "\n".join(out)
 
 
 def markdown(res) -> str:
+    if res["wire"] == "fp8":
+        return markdown_fp8(res)
     k = res["k"]
     out = [f"### members {res['members']} (k = {k}), {res['dtype']}, {res['iters']} timed rounds", "",
            "| N per member | oneshot algBW | oneshot member read + written | twoshot algBW | twoshot member read + written | "
@@ -74,7 +126,7 @@ def markdown(res) -> str:
                    f"| {t['member_traffic_gbps']:.1f} | {k6['ingress_bound_gbps']:.1f} | {k6['member_traffic_gbps']:.1f} | {r['faster']} |")
     c = res["twoshot_faster_from_bytes"]
     out += ["", f"twoshot is the faster algorithm from {mib(c)} up." if c else "twoshot is not the faster algorithm at the largest size.", ""]
-    return "\n".join(out)
+    return "\n".join(out) + ("\n" + markdown_fp8(res) if res["wire"] == "both" else "")
 
 
 def main():
@@ -84,6 +136,8 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=sorted(ELEM))
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--wire", default="native", choices=["native", "fp8", "both"],
+                    help="fp8: the block-scaled e4m3 wire alone; both: it next to the native wire, interleaved")
     ap.add_argument("--out", default="", help="also write the JSON document here")
     ap.add_argument("--md", default="", help="also write the tables as Markdown here")
     a = ap.parse_args()
@@ -91,7 +145,7 @@ def main():
     sizes = [int(float(x) * (1 << 20)) for x in a.sizes_mib.split(",")]
     probe.warmup(groups[0][0], 100.0)
     doc = {"device": probe.device_props(groups[0][0])["name"], "rates": "GB/s (1e9 bytes/s)",
-           "runs": [measure(g, sizes, a.dtype, a.iters, a.warmup) for g in groups]}
+           "runs": [measure(g, sizes, a.dtype, a.iters, a.warmup, a.wire) for g in groups]}
     text = json.dumps(doc)
     print(text)
     for path, body in ((a.out, text + "\n"), (a.md, "\n".join(markdown(r) for r in doc["runs"]))):
@@ -99,7 +153,8 @@ def main():
             os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
             with open(path, "w") as f:
                 f.write(body)
-    return 1 if any(r[al]["wrong"] for run in doc["runs"] for r in run["sizes"] for al in probe.PEER_ALGOS) else 0
+    measured = [al + sfx for al in probe.PEER_ALGOS for sfx in ("", "_fp8")]
+    return 1 if any(r[al]["wrong"] for run in doc["runs"] for r in run["sizes"] for al in measured if al in r) else 0
 
 
 if __name__ == "__main__":

@@ -2,7 +2,7 @@
 """The peer communicator's thread-rank all_reduce next to the in-process driver's, as one JSON document:
 
     python bench/peer_comm_bench.py [--members 0,0,0,0] [--sizes-mib 1,4,16,64,256] [--dtype bf16]
-                                    [--iters 20] [--warmup 2] [--out FILE] [--md FILE]
+                                    [--iters 20] [--warmup 2] [--wire native|fp8] [--out FILE] [--md FILE]
 
 Both run the same K7 kernels on the same members at the same count, in one process:
   * thread ranks (``PeerComm(backend="device")``, one thread per member): host time per ``all_reduce``
@@ -13,7 +13,8 @@ Both run the same K7 kernels on the same members at the same count, in one proce
 Per size and algorithm the two are measured alternately, ``--reps`` times each, and the quicker
 repetition of each is reported.  Their ratio is the price of host-synchronous ordering: two store round
 trips and two (two-shot: three) stream synchronisations per call.  Members that repeat a device give
-HBM rates of that one GPU, not xGMI rates.
+HBM rates of that one GPU, not xGMI rates.  ``--wire fp8`` runs both on the fp8 wire: every rank packs its
+window first and the ranks read the packed forms.
 """
 import argparse
 import json
@@ -25,14 +26,15 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from gpu_topology_on_k8s_amd.ops import probe  # noqa: E402
-from gpu_topology_on_k8s_amd.ops.peer_ref import allreduce_ref  # noqa: E402
+from gpu_topology_on_k8s_amd.ops.peer_ref import Q8_BLOCK, allreduce_q8_ref, allreduce_ref, q8_blocks  # noqa: E402
 from gpu_topology_on_k8s_amd.parallel import peer_comm as pc  # noqa: E402
 
 ELEM = {"bf16": 2, "fp32": 4}
 
 
-def measure(devs, sizes, dtype, iters, warmup, reps):
+def measure(devs, sizes, dtype, iters, warmup, reps, wire="native"):
     k, elem = len(devs), ELEM[dtype]
+    fp8 = wire == "fp8"
     counts = [max(1, n // elem) for n in sizes]
     once = pc._Once()
     driver = {}  # (count, algo, rep) -> the driver's result, measured by rank 0 while the other ranks wait
@@ -41,20 +43,20 @@ def measure(devs, sizes, dtype, iters, warmup, reps):
         rows = []
         for count in counts:
             xs = once.get(("in", count), lambda: [pc.case_input(0, 0, p, count, dtype) for p in range(k)], lambda o: o[1] == count)
-            ref = once.get(("ref", count), lambda: allreduce_ref(xs, dtype), lambda o: o[1] == count)
+            ref = once.get(("ref", count), lambda: (allreduce_q8_ref if fp8 else allreduce_ref)(xs, dtype), lambda o: o[1] == count)
             comm.write(xs[comm.rank])
             for algo in pc.ALGOS:
                 for rep in range(reps):
-                    secs, in_barriers = pc.timed_all_reduce(comm, count, dtype, algo, iters, warmup)
+                    secs, in_barriers = pc.timed_all_reduce(comm, count, dtype, algo, iters, warmup, wire)
                     wrong = int(np.count_nonzero(pc._bits(comm.read(0, count, dtype)) != pc._bits(ref))) if rep == 0 else 0
                     rows.append((count, algo, rep, secs, in_barriers, wrong))
                     comm.barrier()  # every rank's stream is idle: the driver has the device to itself
                     if comm.rank == 0:
-                        driver[(count, algo, rep)] = probe.peer_allreduce(devs, count, dtype, algo, iters, warmup)
+                        driver[(count, algo, rep)] = probe.peer_allreduce(devs, count, dtype, algo, iters, warmup, wire=wire)
                     comm.barrier()
         return rows
 
-    cap = -(-max(counts) * elem // 16) * 16
+    cap = q8_blocks(max(counts)) * Q8_BLOCK * elem if fp8 else -(-max(counts) * elem // 16) * 16
     res = pc.run_thread_ranks(devs, body, cap, timeout_s=300.0, join_s=3000.0)
     out = []
     for count in counts:
@@ -75,11 +77,11 @@ def measure(devs, sizes, dtype, iters, warmup, reps):
         out.append(row)
         print(json.dumps(row), file=sys.stderr, flush=True)
     return {"members": list(devs), "k": k, "distinct_devices": len(set(devs)) == k, "dtype": dtype, "iters": iters, "warmup": warmup,
-            "reps": reps, "sizes": out}
+            "reps": reps, "wire": wire, "sizes": out}
 
 
 def markdown(res) -> str:
-    out = [f"### members {res['members']} (k = {res['k']}), {res['dtype']}, {res['iters']} timed calls, best of {res['reps']} alternated repetitions", "",
+    out = [f"### members {res['members']} (k = {res['k']}), {res['dtype']}, {res['wire']} wire, {res['iters']} timed calls, best of {res['reps']} alternated repetitions", "",
            "| N per member | algorithm | thread ranks us / call | of it in barriers | thread algBW | driver us / round | driver algBW | thread / driver |",
            "|---|---|---|---|---|---|---|---|"]
     for r in res["sizes"]:
@@ -98,6 +100,7 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=sorted(ELEM))
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--wire", default="native", choices=["native", "fp8"], help="fp8: the block-scaled e4m3 wire of csrc/probe/peer_q8.h")
     ap.add_argument("--reps", type=int, default=2, help="alternated repetitions of each measurement")
     ap.add_argument("--out", default="", help="also write the JSON document here")
     ap.add_argument("--md", default="", help="also write the tables as Markdown here")
@@ -106,7 +109,7 @@ def main():
     sizes = [int(float(x) * (1 << 20)) for x in a.sizes_mib.split(",")]
     probe.warmup(groups[0][0], 100.0)
     doc = {"device": probe.device_props(groups[0][0])["name"], "rates": "GB/s (1e9 bytes/s)",
-           "runs": [measure(g, sizes, a.dtype, a.iters, a.warmup, max(1, a.reps)) for g in groups]}
+           "runs": [measure(g, sizes, a.dtype, a.iters, a.warmup, max(1, a.reps), a.wire) for g in groups]}
     text = json.dumps(doc)
     print(text)
     for path, body in ((a.out, text + "\n"), (a.md, "\n".join(markdown(r) for r in doc["runs"]))):

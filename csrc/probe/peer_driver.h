@@ -12,8 +12,14 @@
 // Members are ordered by stream events alone (no kernel waits for a running kernel): e1[m] follows
 // m's phase 1 and every member's phase 2 waits for all of them; e2[m] follows m's phase 2 and every
 // member's next phase 1 waits for all of them, since phase 2 of p reads the slice m then overwrites.
+//   wire fp8: a round starts with every member packing its own `in` into its own packed buffer
+//            (peer_q8.h), phase 1 reads the packed buffers, blocks of 32 elements in place of vectors,
+//            and phase 2 is unchanged.  eq[m] follows m's quantize and every member's phase 1 waits for
+//            all of them; e1[m] follows m's phase 1 in one-shot too, and every member's next quantize
+//            waits for all of them, since phase 1 of p still reads the packed buffer m then overwrites.
 #pragma once
 #include "peer_allreduce.h"
+#include "peer_q8.h"
 #include "probe_common.h"
 
 namespace {
@@ -75,6 +81,45 @@ void launch_peer_reduce(PeerTypes t, const SrcSet& set, int k, size_t v0, size_t
     launch_peer_reduce<uint16_t, float>(set, k, v0, v1, dst, scale, grid, s);
 }
 
+// The fp8 wire's two launches.  The sum keeps the reduce's member buckets and U: k x U code vectors and as
+// many exponent words per lane, 80 VGPRs of loads, and sixteen accumulators.
+template <typename TO>
+void launch_peer_q8_sum(const SrcSet& packed, int k, size_t exp_vec, size_t b0, size_t b1, u32x4* dst, float scale, int grid,
+                        hipStream_t s) {
+  const dim3 g(grid), b(kBlock);
+  if (k <= 2)
+    peer_q8_sum_kernel<TO, 2, 4><<<g, b, 0, s>>>(packed, k, exp_vec, b0, b1, dst, scale);
+  else if (k <= 4)
+    peer_q8_sum_kernel<TO, 4, 4><<<g, b, 0, s>>>(packed, k, exp_vec, b0, b1, dst, scale);
+  else if (k <= 8)
+    peer_q8_sum_kernel<TO, 8, 2><<<g, b, 0, s>>>(packed, k, exp_vec, b0, b1, dst, scale);
+  else
+    peer_q8_sum_kernel<TO, 16, 1><<<g, b, 0, s>>>(packed, k, exp_vec, b0, b1, dst, scale);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_peer_q8_sum(bool out_bf16, const SrcSet& packed, int k, size_t exp_vec, size_t b0, size_t b1, u32x4* dst,
+                        float scale, int grid, hipStream_t s) {
+  if (out_bf16)
+    launch_peer_q8_sum<uint16_t>(packed, k, exp_vec, b0, b1, dst, scale, grid, s);
+  else
+    launch_peer_q8_sum<float>(packed, k, exp_vec, b0, b1, dst, scale, grid, s);
+}
+
+void launch_peer_q8_quantize(bool in_bf16, const u32x4* win, u32x4* packed, size_t exp_vec, size_t b0, size_t b1, size_t count,
+                             int grid, hipStream_t s) {
+  if (in_bf16)
+    peer_q8_quantize_kernel<uint16_t><<<dim3(grid), dim3(kBlock), 0, s>>>(win, packed, exp_vec, b0, b1, count);
+  else
+    peer_q8_quantize_kernel<float><<<dim3(grid), dim3(kBlock), 0, s>>>(win, packed, exp_vec, b0, b1, count);
+  HIP_CHECK(hipGetLastError());
+}
+
+bool peer_wire_fp8(const std::string& wire) {
+  if (wire != "native" && wire != "fp8") throw std::invalid_argument("wire must be native|fp8");
+  return wire == "fp8";
+}
+
 // Blocks of a reduce of `n_vec` vectors on a device of `cus` CUs that `share` members split: no more
 // blocks than vectors to reduce.
 int peer_reduce_grid(int cus, int blocks_per_cu, int share, size_t n_vec) {
@@ -109,14 +154,17 @@ struct PeerAllreduce {
   bool twoshot = false;
   PeerTypes types;
   float scale = 1.0f;
-  size_t count = 0, n_vec = 0;
+  bool fp8 = false;                 // the wire: members read each other's packed buffers, not their `in`
+  size_t count = 0, n_vec = 0;      // n_vec: vectors of an `in`
+  size_t n_blocks = 0;              // fp8: blocks of 32 elements, and `out` holds whole blocks
   std::vector<std::unique_ptr<DevBuf>> in[2], out;  // in[set][m]: rounds alternate between the sets
-  SrcSet srcs[2]{};
-  std::vector<PeerSlice> plan;
+  std::vector<std::unique_ptr<DevBuf>> packed;      // fp8: packed[m], member m's `in` of the current round
+  SrcSet srcs[2]{}, packs{};
+  std::vector<PeerSlice> plan;      // phase 1 of a two-shot: vectors of an `in`; fp8: blocks
   std::vector<SliceSet> gather;  // member m's phase 2: slice p of out[p], every p != m
-  std::vector<int> reduce_grid, gather_grid_;
+  std::vector<int> reduce_grid, gather_grid_, quantize_grid;
   MemberStreams ts;
-  std::vector<hipEvent_t> e1, e2;
+  std::vector<hipEvent_t> e1, e2, eq;
   size_t rounds_done = 0;
 
   // The dtypes are peer_types' to check, which the caller has passed before it comes here.
@@ -128,33 +176,44 @@ struct PeerAllreduce {
   }
 
   PeerAllreduce(const std::vector<int>& devs_, size_t count_, PeerTypes types_, const std::string& algo, int nsets_,
-                int blocks_per_cu, float scale_ = 1.0f)
-      : devs(devs_), k((int)devs_.size()), nsets(nsets_), twoshot(algo == "twoshot"), types(types_), scale(scale_),
-        count(count_), n_vec((count_ * types_.in_elem() + 15) / 16), plan(peer_slices(n_vec, k)), gather(k),
-        reduce_grid(k), gather_grid_(k), e1(k, nullptr), e2(k, nullptr) {
+                int blocks_per_cu, float scale_ = 1.0f, bool fp8_ = false)
+      : devs(devs_), k((int)devs_.size()), nsets(nsets_), twoshot(algo == "twoshot"), types(types_), scale(scale_), fp8(fp8_),
+        count(count_), n_vec((count_ * types_.in_elem() + 15) / 16), n_blocks((count_ + kQ8Block - 1) / kQ8Block),
+        plan(peer_slices(fp8_ ? n_blocks : n_vec, k)), gather(k), reduce_grid(k), gather_grid_(k), quantize_grid(k),
+        e1(k, nullptr), e2(k, nullptr), eq(k, nullptr) {
     for (int m = 0; m < k; ++m)
       for (int p = 0; p < k; ++p) enable_peer(devs[m], devs[p]);
     std::vector<const u32x4*> outs(k);
     std::vector<PeerSlice> out_plan(k);  // slices of the output type
+    // output vectors per unit of the plan, and of a whole `out`
+    const size_t per_unit = fp8 ? kQ8Block * types.out_elem() / 16 : types.ratio();
+    const size_t out_vec = fp8 ? n_blocks * per_unit : n_vec * per_unit;
     for (int m = 0; m < k; ++m) {
       for (int s = 0; s < nsets; ++s) {
         in[s].emplace_back(new DevBuf(devs[m], n_vec * 16));
         srcs[s].p[m] = reinterpret_cast<const u32x4*>(in[s][m]->p);
       }
-      out.emplace_back(new DevBuf(devs[m], n_vec * 16 * types.ratio()));
+      if (fp8) {
+        packed.emplace_back(new DevBuf(devs[m], q8_packed_vecs(n_blocks) * 16));
+        packs.p[m] = reinterpret_cast<const u32x4*>(packed[m]->p);
+      }
+      out.emplace_back(new DevBuf(devs[m], out_vec * 16));
       outs[m] = reinterpret_cast<const u32x4*>(out[m]->p);
-      out_plan[m] = PeerSlice{plan[m].first * types.ratio(), plan[m].count * types.ratio()};
+      out_plan[m] = PeerSlice{plan[m].first * per_unit, plan[m].count * per_unit};
     }
     try {
       for (int m = 0; m < k; ++m) {
         const int share = device_share(devs, devs[m]);  // as in K6
-        reduce_grid[m] = peer_reduce_grid(num_cus(devs[m]), blocks_per_cu, share, twoshot ? plan[m].count : n_vec);
+        const size_t units = twoshot ? plan[m].count : (fp8 ? n_blocks : n_vec);
+        reduce_grid[m] = peer_reduce_grid(num_cus(devs[m]), blocks_per_cu, share, fp8 ? 2 * units : units);
+        quantize_grid[m] = peer_reduce_grid(num_cus(devs[m]), blocks_per_cu, share, n_blocks * 64 / types.in_elem());
         gather_grid_[m] = gather_grid(devs[m], blocks_per_cu, k - 1, share);
         gather[m] = peer_gather_slices(outs, out_plan, m);
         DeviceGuard g(devs[m]);
         ts.emplace_back(new TimedStream());
         HIP_CHECK(hipEventCreateWithFlags(&e1[m], hipEventDisableTiming));
         HIP_CHECK(hipEventCreateWithFlags(&e2[m], hipEventDisableTiming));
+        HIP_CHECK(hipEventCreateWithFlags(&eq[m], hipEventDisableTiming));
       }
     } catch (...) {
       release();
@@ -167,30 +226,49 @@ struct PeerAllreduce {
 
   size_t padded() const { return n_vec * 16 / types.in_elem(); }  // elements of a buffer, zero padding included
 
+  // Phase 1 of member m over [v0, v1) of the plan's units: vectors of `in`, or blocks of the packed buffers.
   void reduce(int m, int set, size_t v0, size_t v1) {
     if (v0 == v1) return;
-    launch_peer_reduce(types, srcs[set], k, v0, v1, reinterpret_cast<u32x4*>(out[m]->p), scale, reduce_grid[m], ts[m]->s);
+    u32x4* dst = reinterpret_cast<u32x4*>(out[m]->p);
+    if (fp8)
+      launch_peer_q8_sum(types.out_bf16, packs, k, q8_exp_vec(n_blocks), v0, v1, dst, scale, reduce_grid[m], ts[m]->s);
+    else
+      launch_peer_reduce(types, srcs[set], k, v0, v1, dst, scale, reduce_grid[m], ts[m]->s);
+  }
+
+  void quantize(int m, int set) {
+    launch_peer_q8_quantize(types.in_bf16, srcs[set].p[m], reinterpret_cast<u32x4*>(packed[m]->p), q8_exp_vec(n_blocks), 0,
+                            n_blocks, count, quantize_grid[m], ts[m]->s);
   }
 
   // One all-reduce of input set `set`, enqueued on every member's stream.  Every e1 / e2 is recorded
   // before any stream is made to wait for it (a wait for an event never recorded is no wait).
   void round(int set) {
+    auto wait_others = [&](int m, const std::vector<hipEvent_t>& ev) {
+      for (int p = 0; p < k; ++p)
+        if (p != m) HIP_CHECK(hipStreamWaitEvent(ts[m]->s, ev[p], 0));
+    };
+    for (int m = 0; fp8 && m < k; ++m) {
+      DeviceGuard g(devs[m]);
+      if (rounds_done) wait_others(m, e1);  // last round's phase 1 of every member has read packed[m]
+      quantize(m, set);
+      HIP_CHECK(hipEventRecord(eq[m], ts[m]->s));
+    }
     for (int m = 0; m < k; ++m) {
       DeviceGuard g(devs[m]);
+      if (fp8) wait_others(m, eq);
       if (!twoshot) {
-        reduce(m, set, 0, n_vec);
+        reduce(m, set, 0, fp8 ? n_blocks : n_vec);
+        if (fp8) HIP_CHECK(hipEventRecord(e1[m], ts[m]->s));
         continue;
       }
-      if (rounds_done)
-        for (int p = 0; p < k; ++p)
-          if (p != m) HIP_CHECK(hipStreamWaitEvent(ts[m]->s, e2[p], 0));
+      if (rounds_done) wait_others(m, e2);
       reduce(m, set, plan[m].first, plan[m].first + plan[m].count);
       HIP_CHECK(hipEventRecord(e1[m], ts[m]->s));
     }
     for (int m = 0; twoshot && m < k; ++m) {
       DeviceGuard g(devs[m]);
-      for (int p = 0; p < k; ++p)
-        if (p != m) HIP_CHECK(hipStreamWaitEvent(ts[m]->s, e1[p], 0));
+      wait_others(m, e1);
       launch_peer_gather(gather[m], k - 1, (u32x4*)out[m]->p, gather_grid_[m], ts[m]->s);
       HIP_CHECK(hipEventRecord(e2[m], ts[m]->s));
     }
@@ -237,30 +315,46 @@ struct PeerAllreduce {
       (void)hipSetDevice(devs[m]);
       if (e1[m]) (void)hipEventDestroy(e1[m]);
       if (e2[m]) (void)hipEventDestroy(e2[m]);
-      e1[m] = e2[m] = nullptr;
+      if (eq[m]) (void)hipEventDestroy(eq[m]);
+      e1[m] = e2[m] = eq[m] = nullptr;
       (void)hipSetDevice(prev);
     }
   }
 };
 
 py::dict peer_allreduce(const std::vector<int>& devs, size_t count, const std::string& dtype, const std::string& algo,
-                        int iters, int warmup, int blocks_per_cu) {
+                        int iters, int warmup, int blocks_per_cu, const std::string& wire) {
   const PeerTypes types = peer_types(dtype, "");
+  const bool fp8 = peer_wire_fp8(wire);
   PeerAllreduce::check_args(devs, count, algo);
   if (iters < 1 || warmup < 0) throw std::invalid_argument("iters >= 1, warmup >= 0");
   const int k = (int)devs.size();
   MemberTimes t;
   unsigned long long wrong = 0;
   const size_t bytes = count * types.in_elem();
+  double quantize_us = 0.0, sum_us = 0.0;
   {
     py::gil_scoped_release nogil;
     // with more than one round, consecutive rounds alternate between two input sets and the check uses
     // the last round's: a round that ran ahead of the one before it leaves a mix of the two sums
     const int total = warmup + iters;
-    PeerAllreduce ar(devs, count, types, algo, total >= 2 ? 2 : 1, blocks_per_cu);
+    PeerAllreduce ar(devs, count, types, algo, total >= 2 ? 2 : 1, blocks_per_cu, 1.0f, fp8);
     for (int s = 0; s < ar.nsets; ++s) ar.fill(s);
     t = time_member_rounds(devs, ar.ts, warmup, iters, [&](int r) { ar.round(r % ar.nsets); });
     wrong = ar.wrong((total - 1) % ar.nsets);
+    if (fp8) {
+      // member 0's two kernels alone on an idle device, after the check: the same set as the last round,
+      // so `out` is rewritten with the same bits
+      const int set = (total - 1) % ar.nsets;
+      const size_t a = ar.twoshot ? ar.plan[0].first : 0, b = ar.twoshot ? a + ar.plan[0].count : ar.n_blocks;
+      DeviceGuard g(devs[0]);
+      ar.ts[0]->begin();
+      for (int i = 0; i < iters; ++i) ar.quantize(0, set);
+      quantize_us = ar.ts[0]->end_ms() * 1e3 / iters;
+      ar.ts[0]->begin();
+      for (int i = 0; i < iters; ++i) ar.reduce(0, set, a, b);
+      sum_us = ar.ts[0]->end_ms() * 1e3 / iters;
+    }
   }
   const double time_us = *std::max_element(t.ms_member.begin(), t.ms_member.end()) * 1e3 / iters;
   py::dict r;
@@ -277,6 +371,11 @@ py::dict peer_allreduce(const std::vector<int>& devs, size_t count, const std::s
   r["wall_ms"] = t.wall_ms;
   r["wrong"] = wrong;
   r["ok"] = wrong == 0;
+  r["wire"] = wire;
+  if (fp8) {
+    r["quantize_us"] = quantize_us;
+    r["sum_us"] = sum_us;
+  }
   return r;
 }
 
@@ -284,10 +383,12 @@ py::dict peer_allreduce(const std::vector<int>& devs, size_t count, const std::s
 // patterns for bf16, float32 for fp32) in, the k members' results out, after `rounds` all-reduces of
 // the same inputs.  `out_dtype` (none: the inputs') and `scale` select the wide and the scaled reduce.
 py::list peer_allreduce_arrays(const std::vector<int>& devs, const std::vector<py::array>& inputs, const std::string& dtype,
-                               const std::string& algo, int rounds, const std::optional<std::string>& out_dtype, float scale) {
+                               const std::string& algo, int rounds, const std::optional<std::string>& out_dtype, float scale,
+                               const std::string& wire) {
   if (inputs.size() != devs.size()) throw std::invalid_argument("one input array per member");
   const size_t count = inputs.empty() ? 0 : (size_t)inputs[0].size();
   const PeerTypes types = peer_types(dtype, out_dtype.value_or(""));
+  const bool fp8 = peer_wire_fp8(wire);
   PeerAllreduce::check_args(devs, count, algo);
   if (count > PeerAllreduce::kMaxCount) throw std::invalid_argument("count <= 64 Mi elements");
   if (rounds < 1) throw std::invalid_argument("rounds >= 1");
@@ -309,10 +410,11 @@ py::list peer_allreduce_arrays(const std::vector<int>& devs, const std::vector<p
   }
   {
     py::gil_scoped_release nogil;
-    PeerAllreduce ar(devs, count, types, algo, 1, kBlocksPerCU, scale);
+    PeerAllreduce ar(devs, count, types, algo, 1, kBlocksPerCU, scale, fp8);
     for (int m = 0; m < k; ++m) {
       DeviceGuard g(devs[m]);
-      HIP_CHECK(hipMemset(ar.in[0][m]->p, 0, ar.n_vec * 16));
+      // the fp8 wire masks what lies past the count itself: its padding is made non-zero on purpose
+      HIP_CHECK(hipMemset(ar.in[0][m]->p, fp8 ? 0x7b : 0, ar.n_vec * 16));
       HIP_CHECK(hipMemcpy(ar.in[0][m]->p, from[m], count * types.in_elem(), hipMemcpyHostToDevice));
       HIP_CHECK(hipDeviceSynchronize());
     }
@@ -326,6 +428,42 @@ py::list peer_allreduce_arrays(const std::vector<int>& devs, const std::vector<p
   py::list r;
   for (py::array& a : dst) r.append(a);
   return r;
+}
+
+// The quantize kernel alone on one array (uint16 bit patterns for bf16, float32 for fp32): the codes
+// (uint8, 32 per block, element order) and the block exponents (int32, unbiased) it wrote, in logical
+// order.  The window is filled with a non-zero byte first, so what lies past the count is not zero.
+py::tuple peer_q8_quantize(int dev, const py::array& array, const std::string& dtype) {
+  const PeerTypes types = peer_types(dtype, "");
+  check_dev(dev);
+  const py::dtype want = types.in_bf16 ? py::dtype::of<uint16_t>() : py::dtype::of<float>();
+  if (array.ndim() != 1 || array.size() < 1 || !array.dtype().is(want))
+    throw std::invalid_argument("a one-dimensional, non-empty array, uint16 (bf16) or float32 (fp32)");
+  const size_t count = (size_t)array.size();
+  if (count > PeerAllreduce::kMaxCount) throw std::invalid_argument("count <= 64 Mi elements");
+  const py::array src = py::array::ensure(array, py::array::c_style);
+  const size_t n_blocks = (count + kQ8Block - 1) / kQ8Block, in_bytes = n_blocks * kQ8Block * types.in_elem();
+  py::array_t<uint8_t> codes((py::ssize_t)(n_blocks * kQ8Block));
+  py::array_t<int32_t> exps((py::ssize_t)n_blocks);
+  std::vector<uint8_t> biased(n_blocks);
+  const void* from = src.data();
+  void* to = codes.mutable_data();
+  {
+    py::gil_scoped_release nogil;
+    DeviceGuard g(dev);
+    DevBuf win(dev, in_bytes), packed(dev, q8_packed_vecs(n_blocks) * 16);
+    HIP_CHECK(hipMemset(win.p, 0x7b, in_bytes));
+    HIP_CHECK(hipMemcpy(win.p, from, count * types.in_elem(), hipMemcpyHostToDevice));
+    const int grid = peer_reduce_grid(num_cus(dev), kBlocksPerCU, 1, in_bytes / 16);
+    launch_peer_q8_quantize(types.in_bf16, (const u32x4*)win.p, (u32x4*)packed.p, q8_exp_vec(n_blocks), 0, n_blocks, count, grid,
+                            nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(to, packed.p, n_blocks * kQ8Block, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(biased.data(), (const char*)packed.p + q8_exp_vec(n_blocks) * 16, n_blocks, hipMemcpyDeviceToHost));
+  }
+  int32_t* e = exps.mutable_data();
+  for (size_t b = 0; b < n_blocks; ++b) e[b] = (int32_t)biased[b] - kQ8Bias;
+  return py::make_tuple(codes, exps);
 }
 
 }  // namespace

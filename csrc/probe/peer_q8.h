@@ -1,0 +1,212 @@
+// K7 fp8 wire: a rank packs its window once, locally, into OCP e4m3fn codes with one power-of-two scale
+// per 32 elements, and its peers read the packed form: 33 bytes per 32 elements over the link against 64
+// for bf16 and 128 for fp32.  Device code only, in the style of peer_allreduce.h.
+//
+// Format (ops/peer_ref.py: q8_quantize_ref is the same rule in numpy, and decides):
+//   block b  = elements [32 b, 32 b + 32) of the call; elements at or past `count` are zero and are masked
+//              here, never trusted to be zero in the window.
+//   e        = the smallest integer with amax * 2^-e <= 448, clamped to [-100, 120] (amax == 0: -100), so
+//              2^e, 2^-e and every dequantised value are normal fp32 numbers and both scalings are exact.
+//   code     = x * 2^-e rounded to nearest even into e4m3fn, subnormal codes (quantum 2^-9) included;
+//              |x * 2^-e| <= 448, so nothing saturates.  value = float(code) * 2^e.
+// The sum is taken over the dequantised values in member order in fp32, multiplied once by `scale` and
+// rounded once, as peer_reduce_vecs does: every member computes the same bits, its own contribution
+// being its packed form too.
+//
+// Layout of a packed buffer made for NB blocks, in 16-byte vectors:
+//   vectors [0, 2 NB)                : the codes, one byte per element in element order, so block b is
+//                                      vectors 2 b and 2 b + 1 and code vector v holds elements [16 v, 16 v + 16);
+//   vectors [2 NB, 2 NB + ceil(NB/16)): one byte per block, e + 127 (the exponent field of 2^e in fp32),
+//                                      in block order, the last vector's rest unused.
+// That is 33 bytes per 32 elements, rounded up to a vector.  `exp_vec` = 2 NB is a property of the
+// buffer, not of the call, and the same on every member.  A lane of the sum reads the aligned 4-byte
+// word that holds its block's exponent: the 64 lanes of a wave cover 32 consecutive exponent bytes, two
+// vectors, which reach the memory pipeline as one request next to the wave's 1 KiB of codes.
+//
+// Conversions: v_cvt_pk_fp8_f32 and v_cvt_pk_f32_fp8 through their builtins, on values already scaled by
+// an exact fp32 multiply; the scaling forms (cvt_scalef32_*) are not used, so which way they apply their
+// scale operand plays no part here.  tests/test_gpu_peer_q8.py compares every code with the numpy rule.
+#pragma once
+#include "peer_allreduce.h"
+#include "probe_common.h"
+
+namespace {
+
+constexpr int kQ8Block = 32;                    // elements that share one scale
+constexpr int kQ8ExpMin = -100, kQ8ExpMax = 120;
+constexpr int kQ8Bias = 127;                    // the stored byte is e + 127
+
+// Vectors of a packed buffer for `n_blocks` blocks, and where its exponent bytes start.
+constexpr size_t q8_exp_vec(size_t n_blocks) { return 2 * n_blocks; }
+constexpr size_t q8_packed_vecs(size_t n_blocks) { return 2 * n_blocks + (n_blocks + 15) / 16; }
+
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ float q8_pow2(int n) { return __uint_as_float((unsigned int)(n + 127) << 23); }
+
+// amax = m * 2^E with m in [1, 2): e = E - 8 when m <= 1.75 (448 = 1.75 * 2^8), else E - 7.  A zero or
+// subnormal amax lands below the clamp, an infinite one above it.
+__device__ __forceinline__ int q8_block_exp(float amax) {
+  const unsigned int a = __float_as_uint(amax);
+  const int e = (int)(a >> 23) - 127 - 8 + (int)((a & 0x7fffffu) > 0x600000u);
+  return min(max(e, kQ8ExpMin), kQ8ExpMax);
+}
+
+// Two scaled values to two codes, the first in the low byte.
+__device__ __forceinline__ unsigned int q8_codes2(float a, float b) {
+  return (unsigned int)__builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false) & 0xffffu;
+}
+
+// One 16-byte vector `r` of the window, vector v of it (elements [v L, v L + L)), as one of the G
+// consecutive lanes that hold a block (bf16: 4 lanes of 8 elements; fp32: 8 lanes of 4): the block's amax
+// is log2(G) lane exchanges, with no memory and no other wave involved; every lane stores its own codes
+// (8 or 4 bytes), the first lane of a block the exponent byte.
+template <typename TI>
+__device__ __forceinline__ void q8_quantize_vec(const u32x4& r, size_t v, size_t count, u32x4* __restrict__ packed,
+                                                unsigned char* __restrict__ exps) {
+  constexpr int L = kPeerLanes<TI>;
+  constexpr int G = kQ8Block / L;
+  const size_t first = v * L;
+  float f[L];
+  peer_widen(r, f);
+#pragma unroll
+  for (int j = 0; j < L; ++j)
+    if (first + j >= count) f[j] = 0.f;
+  float amax = 0.f;
+#pragma unroll
+  for (int j = 0; j < L; ++j) amax = fmaxf(amax, fabsf(f[j]));
+#pragma unroll
+  for (int d = 1; d < G; d <<= 1) amax = fmaxf(amax, __shfl_xor(amax, d));
+  const int e = q8_block_exp(amax);
+  const float down = q8_pow2(-e);
+  unsigned int w[L / 4];
+#pragma unroll
+  for (int j = 0; j < L / 4; ++j)
+    w[j] = q8_codes2(f[4 * j] * down, f[4 * j + 1] * down) | (q8_codes2(f[4 * j + 2] * down, f[4 * j + 3] * down) << 16);
+  if constexpr (L == 8) {
+    u32x2 c;
+    c[0] = w[0];
+    c[1] = w[1];
+    __builtin_nontemporal_store(c, reinterpret_cast<u32x2*>(packed) + v);
+  } else {
+    __builtin_nontemporal_store(w[0], reinterpret_cast<unsigned int*>(packed) + v);
+  }
+  if (v % G == 0) exps[v / G] = (unsigned char)(e + kQ8Bias);
+}
+
+// Blocks [b0, b1) of the window to the same blocks of the rank's own packed buffer, one window vector
+// per lane and U of them per pass, a grid apart, all loaded before the first is converted.  b0 * G and
+// the grid's stride are multiples of G, so the lanes of a block take every branch together.
+template <typename TI>
+__global__ __launch_bounds__(gtk::kStreamBlock) void peer_q8_quantize_kernel(const u32x4* __restrict__ win,
+                                                                             u32x4* __restrict__ packed, size_t exp_vec,
+                                                                             size_t b0, size_t b1, size_t count) {
+  constexpr int L = kPeerLanes<TI>;
+  constexpr int G = kQ8Block / L;
+  constexpr int U = 4;
+  unsigned char* exps = reinterpret_cast<unsigned char*>(packed + exp_vec);
+  const size_t end = b1 * G, stride = (size_t)gridDim.x * gtk::kStreamBlock;
+  for (size_t base = b0 * G + (size_t)blockIdx.x * gtk::kStreamBlock + threadIdx.x; base < end; base += stride * U) {
+    u32x4 r[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const size_t v = base + (size_t)u * stride;
+      r[u] = u32x4{0u, 0u, 0u, 0u};
+      if (v < end && v * L < count) r[u] = __builtin_nontemporal_load(win + v);  // a vector wholly past the count is not read
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const size_t v = base + (size_t)u * stride;
+      if (v < end) q8_quantize_vec<TI>(r[u], v, count, packed, exps);
+    }
+  }
+}
+
+// The 16 values of one code vector: float(code) * 2^e, `ebyte` being the block's stored exponent byte.
+__device__ __forceinline__ void q8_widen(const u32x4& c, unsigned int ebyte, float (&f)[16]) {
+  const float up = __uint_as_float(ebyte << 23);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)c[j], false);
+    const f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)c[j], true);
+    f[4 * j] = lo[0] * up;
+    f[4 * j + 1] = lo[1] * up;
+    f[4 * j + 2] = hi[0] * up;
+    f[4 * j + 3] = hi[1] * up;
+  }
+}
+
+// The 16 results of code vector v: two vectors of a bf16 out at 2 v, four of an fp32 out at 4 v.
+template <typename TO>
+__device__ __forceinline__ void q8_store(const float (&acc)[16], u32x4* __restrict__ dst, size_t v) {
+  constexpr int L = kPeerLanes<TO>;
+#pragma unroll
+  for (int p = 0; p < 16 / L; ++p) {
+    float part[L];
+#pragma unroll
+    for (int j = 0; j < L; ++j) part[j] = acc[p * L + j];
+    __builtin_nontemporal_store(peer_narrow(part), dst + v * (16 / L) + p);
+  }
+}
+
+// peer_reduce_vecs on the packed form: U code vectors per lane, `stride` apart from `i`; the k x U code
+// loads and the k x U exponent words (member-major, all in flight before the first add), then per
+// position the sum in member order, one multiply by `scale`, one rounding and the stores.  r[][] and
+// x[][] are indexed by constants only.
+template <typename TO, int KB, int U>
+__device__ __forceinline__ void peer_q8_sum_vecs(const SrcSet& srcs, int k, size_t exp_vec, u32x4* __restrict__ dst, size_t i,
+                                                 size_t stride, float scale) {
+  u32x4 r[KB][U];
+  unsigned int x[KB][U];
+#pragma unroll
+  for (int m = 0; m < KB; ++m)
+    if (m < k) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const size_t v = i + (size_t)u * stride;
+        r[m][u] = __builtin_nontemporal_load(srcs.p[m] + v);
+        x[m][u] = __builtin_nontemporal_load(reinterpret_cast<const unsigned int*>(srcs.p[m] + exp_vec) + (v >> 3));
+      }
+    }
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const size_t v = i + (size_t)u * stride;
+    const unsigned int shift = 8u * (unsigned int)((v >> 1) & 3);  // block v / 2 is byte (v / 2) % 4 of word v / 8
+    float acc[16];
+    q8_widen(r[0][u], (x[0][u] >> shift) & 0xffu, acc);
+#pragma unroll
+    for (int m = 1; m < KB; ++m)
+      if (m < k) {
+        float y[16];
+        q8_widen(r[m][u], (x[m][u] >> shift) & 0xffu, y);
+#pragma unroll
+        for (int j = 0; j < 16; ++j) acc[j] = acc[j] + y[j];
+      }
+#pragma unroll
+    for (int j = 0; j < 16; ++j) acc[j] = acc[j] * scale;
+    q8_store<TO>(acc, dst, v);
+  }
+}
+
+// Blocks [b0, b1) of dst (whole blocks of the output type TO: float, or bf16 as raw u16) = scale * the
+// sum over members m < k of the dequantised blocks [b0, b1) of srcs.p[m], every member's packed buffer.
+// The range is code vectors [2 b0, 2 b1), cut as peer_reduce_kernel cuts its vectors: whole tiles in one
+// contiguous run per block, the rest one vector per lane over the whole grid.
+template <typename TO, int KB, int U>
+__global__ __launch_bounds__(gtk::kStreamBlock) void peer_q8_sum_kernel(SrcSet srcs, int k, size_t exp_vec, size_t b0,
+                                                                        size_t b1, u32x4* __restrict__ dst, float scale) {
+  const size_t v0 = 2 * b0, v1 = 2 * b1;
+  const size_t tile = (size_t)gtk::kStreamBlock * U;
+  const size_t n_tiles = (v1 - v0) / tile;
+  const size_t per = (n_tiles + gridDim.x - 1) / gridDim.x;
+  const size_t t0 = (size_t)blockIdx.x * per;
+  const size_t t1 = std::min(n_tiles, t0 + per);
+  for (size_t t = t0; t < t1; ++t)
+    peer_q8_sum_vecs<TO, KB, U>(srcs, k, exp_vec, dst, v0 + t * tile + threadIdx.x, gtk::kStreamBlock, scale);
+  for (size_t i = v0 + n_tiles * tile + (size_t)blockIdx.x * gtk::kStreamBlock + threadIdx.x; i < v1;
+       i += (size_t)gridDim.x * gtk::kStreamBlock)
+    peer_q8_sum_vecs<TO, KB, 1>(srcs, k, exp_vec, dst, i, 0, scale);
+}
+
+}  // namespace

@@ -1,9 +1,10 @@
 // One rank's device state for the peer communicator (parallel/peer_comm.py, backend="device").
-// Host code only: it launches the K7 kernels of peer_allreduce.h through the launch plan of
+// Host code only: it launches the K7 kernels of peer_allreduce.h and peer_q8.h through the launch plan of
 // peer_driver.h, as PeerAllreduce does, and adds no kernel and no instantiation.
 //
 // A rank owns a window (inputs, `capacity` bytes), an out (results, twice that: the wide form writes
-// two vectors per input vector) and one non-blocking stream on its device.  Ranks are threads of one
+// two vectors per input vector), a packed buffer (the fp8 wire's form of the window, sized for a window
+// full of bf16: capacity / 64 blocks) and one non-blocking stream on its device.  Ranks are threads of one
 // process, so a peer's buffer is reached through its plain device address and, across devices,
 // hipDeviceEnablePeerAccess: no IPC call.  A PeerRank is used by one thread.  Nothing here waits on
 // the GPU for another rank: no event is shared between ranks and no kernel spins, so ordering between
@@ -37,11 +38,13 @@ class PeerRank {
         std::lock_guard<std::mutex> lock(peer_rank_mutex());
         window_.reset(new DevBuf(dev, cap_));
         out_.reset(new DevBuf(dev, 2 * cap_));
+        packed_.reset(new DevBuf(dev, packed_bytes()));
       }
       DeviceGuard g(dev);
       HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
       HIP_CHECK(hipMemsetAsync(window_->p, 0, cap_, stream_));
       HIP_CHECK(hipMemsetAsync(out_->p, 0, 2 * cap_, stream_));
+      HIP_CHECK(hipMemsetAsync(packed_->p, 0, packed_bytes(), stream_));
       HIP_CHECK(hipStreamSynchronize(stream_));
     } catch (...) {
       release_locked();
@@ -62,23 +65,31 @@ class PeerRank {
 
   uintptr_t window_ptr() const { return reinterpret_cast<uintptr_t>(live().window_->p); }
   uintptr_t out_ptr() const { return reinterpret_cast<uintptr_t>(live().out_->p); }
+  uintptr_t packed_ptr() const { return reinterpret_cast<uintptr_t>(live().packed_->p); }
   size_t capacity_bytes() const { return cap_; }
+  size_t max_blocks() const { return cap_ / (kQ8Block * 2); }  // blocks of 32 bf16 elements the window holds
+  size_t packed_bytes() const { return std::max<size_t>(16, q8_packed_vecs(max_blocks()) * 16); }
   size_t launches() const { return launches_; }
   bool released() const { return released_; }
 
   // Every rank's device and buffer addresses, this rank's own included (and checked to be its own).
   // A peer's address must be the base of a device allocation of this process on the device it names,
   // at least as large as this rank's buffers: the kernels index a peer's buffer as they index their own.
-  void open_peers(const std::vector<int>& devices, const std::vector<uintptr_t>& windows, const std::vector<uintptr_t>& outs) {
+  // `packeds` is optional: without the peers' packed buffers the fp8 phases stay unavailable.
+  void open_peers(const std::vector<int>& devices, const std::vector<uintptr_t>& windows, const std::vector<uintptr_t>& outs,
+                  const std::optional<std::vector<uintptr_t>>& packeds = std::nullopt) {
     live();
     const size_t k = (size_t)world_;
     if (devices.size() != k || windows.size() != k || outs.size() != k) throw std::invalid_argument("one device, window and out per rank");
-    if (devices[rank_] != dev_ || windows[rank_] != window_ptr() || outs[rank_] != out_ptr())
+    if (packeds && packeds->size() != k) throw std::invalid_argument("one packed buffer per rank");
+    if (devices[rank_] != dev_ || windows[rank_] != window_ptr() || outs[rank_] != out_ptr() ||
+        (packeds && (*packeds)[rank_] != packed_ptr()))
       throw std::invalid_argument("this rank's own entry is not its device and buffers");
     check_devs(devices);
     for (size_t p = 0; p < k; ++p) {
       check_allocation(windows[p], devices[p], cap_);
       check_allocation(outs[p], devices[p], 2 * cap_);
+      if (packeds) check_allocation((*packeds)[p], devices[p], packed_bytes());
     }
     {
       std::lock_guard<std::mutex> lock(peer_rank_mutex());
@@ -89,14 +100,16 @@ class PeerRank {
     for (size_t p = 0; p < k; ++p) {
       windows_.p[p] = reinterpret_cast<const u32x4*>(windows[p]);
       outs_[p] = reinterpret_cast<const u32x4*>(outs[p]);
+      packeds_.p[p] = packeds ? reinterpret_cast<const u32x4*>((*packeds)[p]) : nullptr;
     }
     open_ = true;
+    open_q8_ = packeds.has_value();
   }
 
   void close_peers() {
-    windows_ = SrcSet{};
+    windows_ = packeds_ = SrcSet{};
     outs_.clear();
-    open_ = false;
+    open_ = open_q8_ = false;
   }
 
   // out[v0, v1) of this rank = scale x the sum over ranks of window[v0, v1), vectors of the input type
@@ -110,6 +123,36 @@ class PeerRank {
     const int grid = peer_reduce_grid(cus_, blocks_per_cu_, share_, v1 - v0);
     DeviceGuard g(dev_);
     launch_peer_reduce(t, windows_, world_, v0, v1, reinterpret_cast<u32x4*>(out_->p), scale, grid, stream_);
+    ++launches_;
+  }
+
+  // The fp8 wire's first phase: blocks [b0, b1) of this rank's window (32 elements of `in_dtype` each,
+  // elements at or past `count` taken as zero) to the same blocks of its packed buffer.
+  void quantize(size_t b0, size_t b1, size_t count, const std::string& in_dtype) {
+    const PeerTypes t = peer_types(in_dtype, "");
+    need_q8();
+    if (b0 > b1 || b1 * kQ8Block * t.in_elem() > cap_) throw std::invalid_argument("quantize: blocks past the end of the window");
+    if (b1 > max_blocks()) throw std::invalid_argument("quantize: blocks past the end of the packed buffer");
+    if (b0 == b1) return;
+    const int grid = peer_reduce_grid(cus_, blocks_per_cu_, share_, (b1 - b0) * kQ8Block * t.in_elem() / 16);
+    DeviceGuard g(dev_);
+    launch_peer_q8_quantize(t.in_bf16, reinterpret_cast<const u32x4*>(window_->p), reinterpret_cast<u32x4*>(packed_->p),
+                            q8_exp_vec(max_blocks()), b0, b1, count, grid, stream_);
+    ++launches_;
+  }
+
+  // Blocks [b0, b1) of this rank's out (whole blocks of `out_dtype`) = scale x the sum over ranks of the
+  // same blocks of their packed buffers.
+  void reduce_q8(size_t b0, size_t b1, const std::string& out_dtype, float scale) {
+    const PeerTypes t = peer_types("bf16", out_dtype);  // the packed form carries no input type: any output is allowed
+    need_q8();
+    if (b0 > b1 || b1 > max_blocks()) throw std::invalid_argument("reduce_q8: blocks past the end of the packed buffer");
+    if (b1 * kQ8Block * t.out_elem() > 2 * cap_) throw std::invalid_argument("reduce_q8: blocks past the end of out");
+    if (b0 == b1) return;
+    const int grid = peer_reduce_grid(cus_, blocks_per_cu_, share_, 2 * (b1 - b0));
+    DeviceGuard g(dev_);
+    launch_peer_q8_sum(t.out_bf16, packeds_, world_, q8_exp_vec(max_blocks()), b0, b1, reinterpret_cast<u32x4*>(out_->p), scale, grid,
+                       stream_);
     ++launches_;
   }
 
@@ -184,6 +227,10 @@ class PeerRank {
     live();
     if (!open_) throw std::runtime_error("open_peers first");
   }
+  void need_q8() const {
+    need_peers();
+    if (!open_q8_) throw std::runtime_error("the fp8 phases need open_peers with the peers' packed buffers");
+  }
 
   static void check_allocation(uintptr_t addr, int dev, size_t bytes) {
     void* p = reinterpret_cast<void*>(addr);
@@ -223,16 +270,17 @@ class PeerRank {
     std::lock_guard<std::mutex> lock(peer_rank_mutex());
     window_.reset();
     out_.reset();
+    packed_.reset();
   }
 
   int dev_, rank_, world_;
   size_t cap_;
   int blocks_per_cu_, cus_ = 1, share_ = 1;
-  std::unique_ptr<DevBuf> window_, out_;
+  std::unique_ptr<DevBuf> window_, out_, packed_;
   hipStream_t stream_ = nullptr;
-  SrcSet windows_{};
+  SrcSet windows_{}, packeds_{};
   std::vector<const u32x4*> outs_;
-  bool open_ = false, released_ = false;
+  bool open_ = false, open_q8_ = false, released_ = false;
   size_t launches_ = 0;
 };
 
@@ -245,10 +293,14 @@ void bind_peer_rank(py::module_& m) {
            py::arg("blocks_per_cu") = kBlocksPerCU)
       .def("window_ptr", &PeerRank::window_ptr)
       .def("out_ptr", &PeerRank::out_ptr)
-      .def("open_peers", &PeerRank::open_peers, py::arg("devices"), py::arg("windows"), py::arg("outs"), nogil())
+      .def("packed_ptr", &PeerRank::packed_ptr)
+      .def("open_peers", &PeerRank::open_peers, py::arg("devices"), py::arg("windows"), py::arg("outs"),
+           py::arg("packeds") = py::none(), nogil())
       .def("close_peers", &PeerRank::close_peers, nogil())
       .def("reduce", &PeerRank::reduce, py::arg("v0"), py::arg("v1"), py::arg("in_dtype"), py::arg("out_dtype"), py::arg("scale") = 1.0f,
            nogil())
+      .def("quantize", &PeerRank::quantize, py::arg("b0"), py::arg("b1"), py::arg("count"), py::arg("in_dtype"), nogil())
+      .def("reduce_q8", &PeerRank::reduce_q8, py::arg("b0"), py::arg("b1"), py::arg("out_dtype"), py::arg("scale") = 1.0f, nogil())
       .def("gather", &PeerRank::gather, py::arg("slices"), nogil())
       .def("gather_windows", &PeerRank::gather_windows, py::arg("n_vec"), nogil())
       .def("write_host",
@@ -279,6 +331,7 @@ void bind_peer_rank(py::module_& m) {
       .def("release", &PeerRank::release, nogil())
       .def_property_readonly("launches", &PeerRank::launches)
       .def_property_readonly("capacity_bytes", &PeerRank::capacity_bytes)
+      .def_property_readonly("packed_bytes", &PeerRank::packed_bytes)
       .def_property_readonly("released", &PeerRank::released);
 }
 

@@ -18,7 +18,9 @@
 //                  against.
 //   K7 allreduce : the sum of every member's buffer, in every member's output, by kernels over peer
 //                  pointers (peer_allreduce.h, peer_driver.h): a fixed summation order, so it is exact
-//                  against a CPU sum; the repository's own collective, next to RCCL's.  PeerRank
+//                  against a CPU sum; the repository's own collective, next to RCCL's.  On the fp8 wire
+//                  (peer_q8.h) every member packs its input into block-scaled e4m3 first and the members
+//                  read that, 33 bytes per 32 elements, with the same fixed order and exactness.  PeerRank
 //                  (peer_rank.h) launches the same kernels for one rank of the peer communicator.
 //   K8 latency   : one wave follows a chain of dependent loads through a buffer of another device
 //                  (chase_latency.h): nanoseconds per access over the link, next to K1's GB/s.
@@ -35,7 +37,8 @@
 // This file is the one translation unit of _probe; every header includes what it needs.
 #include "chase_latency.h"   // K8 kernels and the chain's closed form
 #include "peer_allreduce.h"  // K7 kernels
-#include "peer_driver.h"     // K7 launch plan, PeerAllreduce and its two entry points
+#include "peer_driver.h"     // K7 launch plan, PeerAllreduce and its entry points
+#include "peer_q8.h"         // K7 fp8 wire: block-scaled e4m3 quantize and sum kernels
 #include "peer_rank.h"       // one rank of the peer communicator's device backend
 #include "probe_common.h"    // geometry, SrcSet, pattern fill and verifier, guards, grids, timers
 
@@ -825,11 +828,16 @@ PYBIND11_MODULE(_probe, m) {
         py::arg("warmup") = 1, py::arg("blocks_per_cu") = kBlocksPerCU);
   m.def("peer_allreduce", &peer_allreduce, py::arg("devs"), py::arg("count"), py::arg("dtype") = "bf16",
         py::arg("algo") = "twoshot", py::arg("iters") = 3, py::arg("warmup") = 1, py::arg("blocks_per_cu") = kBlocksPerCU,
-        "K7: timed all-reduce (sum) of device-made inputs over peer pointers; every member's result checked");
+        py::arg("wire") = "native",
+        "K7: timed all-reduce (sum) of device-made inputs over peer pointers; every member's result checked; "
+        "wire=\"fp8\": members read each other's block-scaled e4m3 form (peer_q8.h)");
   m.def("peer_allreduce_arrays", &peer_allreduce_arrays, py::arg("devs"), py::arg("inputs"), py::arg("dtype") = "bf16",
         py::arg("algo") = "twoshot", py::arg("rounds") = 1, py::arg("out_dtype") = py::none(), py::arg("scale") = 1.0f,
+        py::arg("wire") = "native",
         "K7 on the caller's arrays (uint16 bit patterns for bf16, float32 for fp32): the k members' results, "
         "scale x sum, in out_dtype (none: dtype; fp32 of bf16 inputs is the wide reduce)");
+  m.def("peer_q8_quantize", &peer_q8_quantize, py::arg("dev"), py::arg("array"), py::arg("dtype") = "bf16",
+        "the fp8 wire's quantize kernel on one array: (codes uint8, block exponents int32) in logical order");
   bind_peer_rank(m);
   m.def("chase_latency", &chase_latency, py::arg("src_dev"), py::arg("exec_dev"), py::arg("ws_bytes") = (size_t)1 << 30,
         py::arg("stride") = (size_t)128, py::arg("hops") = 4096, py::arg("chains") = 1, py::arg("iters") = 5,

@@ -135,7 +135,7 @@ def targets() -> List[Target]:
                HERE / "bin" / "engine_selftest", ["-g", "-O1", "-fsanitize=address,undefined", "-fno-omit-frame-pointer"],
                deps=[CSRC / "placement" / "engine.h"], pybind=False, shared=False),
         Target("_probe", [CSRC / "probe" / "probe.hip"], "hipcc", HERE / f"_probe{EXT}",
-               deps=[stream_copy] + [CSRC / "probe" / h for h in ("probe_common.h", "peer_allreduce.h", "peer_driver.h",
+               deps=[stream_copy] + [CSRC / "probe" / h for h in ("probe_common.h", "peer_allreduce.h", "peer_q8.h", "peer_driver.h",
                                                                   "peer_rank.h", "chase_latency.h")]),
         Target("_rccl", [CSRC / "rccl" / "rccl_module.hip"], "hipcc", HERE / f"_rccl{EXT}",
                [f"-L{rocm_lib}", "-lrccl", f"-Wl,-rpath,{rocm_lib}"],

@@ -425,6 +425,9 @@ def cmd_validate(a) -> int:
     from ._native import load
     from .topology.cpus import bind_workload
 
+    if a.wire != "native" and a.backend != "peer":  # misuse, like an unknown choice: usage error
+        print("gtk validate: error: --wire fp8 belongs to --backend peer", file=sys.stderr)
+        return 2
     if a.ranks == "thread":  # refused before anything native is loaded
         if a.backend != "peer":
             raise SystemExit("--ranks thread belongs to --backend peer")
@@ -450,15 +453,15 @@ def cmd_validate(a) -> int:
             from .parallel.peer_comm import selftest, thread_sweep
 
             st = selftest(devs)
-            selftest_wrong = st["wrong"]
             print(json.dumps({"selftest": True, "k": len(devs), "devices": devs, "ranks": "thread", **st}), flush=True)
-            pts = thread_sweep(devs, sizes, a.dtype, a.algo, a.iters, a.warmup)
-            extra = {"backend": "peer", "algo": a.algo, "ranks": "thread", "selftest_wrong": selftest_wrong}
+            selftest_wrong = st["wrong"] + st["q8_wrong"]
+            pts = thread_sweep(devs, sizes, a.dtype, a.algo, a.iters, a.warmup, wire=a.wire)
+            extra = {"backend": "peer", "algo": a.algo, "ranks": "thread", "selftest_wrong": selftest_wrong, "wire": a.wire}
         else:
             keys = ("bytes", "count", "time_us", "algbw_gbps", "busbw_gbps", "wrong")
             pts = [{**{k: p[k] for k in keys}, "backend": "peer", "algo": p["algo"]}
-                   for p in peer_sweep(devs, sizes, a.dtype, a.algo, a.iters, a.warmup)]
-            extra = {"backend": "peer", "algo": a.algo}
+                   for p in peer_sweep(devs, sizes, a.dtype, a.algo, a.iters, a.warmup, wire=a.wire)]
+            extra = {"backend": "peer", "algo": a.algo, "wire": a.wire}
     else:
         rccl = load("_rccl")
         sizes = rccl.size_sweep(a.min_bytes, a.max_bytes, a.factor)
@@ -621,6 +624,9 @@ def main(argv=None) -> int:
     p.add_argument("--backend", default="rccl", choices=["rccl", "peer"],
                    help="rccl: librccl's all-reduce; peer: this repository's K7 kernels over peer pointers (no RCCL; bf16|fp32)")
     p.add_argument("--algo", default="both", choices=["oneshot", "twoshot", "both"], help="--backend peer: K7 algorithm(s)")
+    p.add_argument("--wire", default="native", choices=["native", "fp8"],
+                   help="--backend peer: native = members read each other's inputs; fp8 = each member packs its input into "
+                        "e4m3 codes with one power-of-two scale per 32 elements and the members read that (33 bytes per 32 elements)")
     p.add_argument("--ranks", default="driver", choices=["driver", "thread"],
                    help="--backend peer: driver = one in-process call drives every member (stream events); thread = one thread "
                         "per member through the peer communicator (a self-test, then host-timed all_reduce calls checked on the host)")

@@ -4,6 +4,10 @@
 The kernels sum every element in fp32 in member order, ``((x0 + x1) + x2) + ...``, multiply once by
 the call's scale and round once, so a sequential numpy sum reproduces their result bit for bit; :func:`peer_slices` is the driver's
 slice plan of the two-shot algorithm.
+
+The fp8 wire (``csrc/probe/peer_q8.h``) has its reference here too: :func:`q8_quantize_ref` packs one
+rank's input into OCP e4m3fn codes with one power-of-two scale per 32 elements, and
+:func:`allreduce_q8_ref` sums the dequantised values exactly as :func:`allreduce_ref` sums the inputs.
 """
 from __future__ import annotations
 
@@ -11,7 +15,9 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-__all__ = ["ELEM", "peer_slices", "bf16_round", "bf16_to_f32", "bits", "out_dtype_of", "allreduce_ref", "reduce_scatter_ref"]
+__all__ = ["ELEM", "peer_slices", "bf16_round", "bf16_to_f32", "bits", "out_dtype_of", "allreduce_ref", "reduce_scatter_ref",
+           "Q8_BLOCK", "Q8_EXP_MIN", "Q8_EXP_MAX", "q8_blocks", "q8_slices", "q8_quantize_ref", "q8_dequantize_ref",
+           "allreduce_q8_ref", "reduce_scatter_q8_ref"]
 
 ELEM = {"bf16": 2, "fp32": 4}  # bytes per element
 
@@ -78,3 +84,93 @@ def reduce_scatter_ref(inputs: Sequence[np.ndarray], dtype: str, out_dtype: Opti
     per = 16 // ELEM[dtype]
     count = int(full.shape[0])
     return [full[min(count, a * per):min(count, b * per)] for a, b in peer_slices(-(-count // per), len(inputs))]
+
+
+# -- the fp8 wire -------------------------------------------------------------------------------
+Q8_BLOCK = 32                      # elements that share one scale
+Q8_EXP_MIN, Q8_EXP_MAX = -100, 120  # the block exponent's clamp: 2^e, 2^-e and every dequantised value stay normal in fp32
+
+
+def q8_blocks(count: int) -> int:
+    """Blocks of 32 elements that hold ``count`` elements."""
+    return -(-int(count) // Q8_BLOCK)
+
+
+def q8_slices(n_blocks: int, k: int) -> List[Tuple[int, int]]:
+    """:func:`peer_slices` applied to blocks: ``[first, end)`` in blocks of each of ``k`` members' slice."""
+    return peer_slices(n_blocks, k)
+
+
+def _e4m3_values() -> np.ndarray:
+    """float32 value of every OCP e4m3fn code (0x7f and 0xff, the NaNs, as 0: no finite input makes them)."""
+    c = np.arange(256)
+    e, m = (c >> 3) & 15, c & 7
+    mag = np.where(e == 0, m * 2.0 ** -9, (8 + m) * 2.0 ** (e.astype(np.float64) - 10))
+    mag[(c & 0x7F) == 0x7F] = 0.0
+    return (np.where(c & 0x80, -mag, mag)).astype(np.float32)
+
+
+_E4M3 = _e4m3_values()
+
+
+def q8_quantize_ref(x: np.ndarray, dtype: str, count: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """The packed form of one rank's input ``x`` (finite; uint16 bit patterns for ``bf16``, float32 for
+    ``fp32``), of which the first ``count`` elements (none: all) are data and everything after them is
+    zero: ``(codes uint8 [n_blocks * 32], exps int32 [n_blocks])``.
+
+    Per block of 32 elements, ``e`` is the smallest integer with ``amax * 2^-e <= 448``, clamped to
+    ``[-100, 120]`` (``amax == 0``: -100), and an element's code is ``x * 2^-e`` rounded to nearest even
+    into e4m3fn, subnormal codes (quantum ``2^-9``) included.  A code carries its element's sign bit."""
+    if dtype not in ELEM:
+        raise ValueError(f"dtype must be bf16|fp32, got {dtype!r}")
+    v = bf16_to_f32(x) if dtype == "bf16" else np.ascontiguousarray(x, dtype=np.float32)
+    count = int(v.shape[0]) if count is None else int(count)
+    if not 0 <= count <= v.shape[0]:
+        raise ValueError("count past the end of x")
+    nb = q8_blocks(count)
+    full = np.zeros(nb * Q8_BLOCK, np.float32)
+    full[:count] = v[:count]
+    amax = np.abs(full).reshape(nb, Q8_BLOCK).max(axis=1) if nb else np.zeros(0, np.float32)
+    m, ex = np.frexp(amax)  # amax = m * 2^ex, m in [0.5, 1); 448 = 0.875 * 2^9
+    e = np.where(amax == 0, Q8_EXP_MIN, np.clip(ex - 9 + (m > 0.875), Q8_EXP_MIN, Q8_EXP_MAX)).astype(np.int32)
+    y = np.ldexp(full, -np.repeat(e, Q8_BLOCK)).astype(np.float32)  # exact, or too small for any code but 0
+    a = np.abs(y).astype(np.float64)
+    _, ea = np.frexp(a)  # a in [2^(ea - 1), 2^ea): three mantissa bits below the leading one
+    quantum = np.ldexp(1.0, np.maximum(ea - 4, -9))
+    r = np.rint(a / quantum) * quantum  # numpy's rint rounds halves to even
+    mr, er = np.frexp(r)
+    normal = r >= 2.0 ** -6
+    code = np.where(normal, (er - 1 + 7) * 8 + np.rint((mr * 2 - 1) * 8), np.rint(r * 512)).astype(np.int64)
+    code = np.minimum(code, 0x7E)  # only a non-finite or out-of-range input gets here
+    return (code | (np.signbit(y).astype(np.int64) << 7)).astype(np.uint8), e
+
+
+def q8_dequantize_ref(codes: np.ndarray, exps: np.ndarray) -> np.ndarray:
+    """float32 ``float(code) * 2^e`` of every element, exact: the values a member contributes to a sum."""
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    exps = np.ascontiguousarray(exps).astype(np.int32)
+    if codes.shape[0] != exps.shape[0] * Q8_BLOCK:
+        raise ValueError("32 codes per exponent")
+    return np.ldexp(_E4M3[codes], np.repeat(exps, Q8_BLOCK)).astype(np.float32)
+
+
+def allreduce_q8_ref(inputs: Sequence[np.ndarray], dtype: str, out_dtype: Optional[str] = None, scale: float = 1.0) -> np.ndarray:
+    """:func:`allreduce_ref` on the fp8 wire: every member's input, its own included, goes through
+    :func:`q8_quantize_ref` and :func:`q8_dequantize_ref` first; then the same sequential fp32 sum in
+    member order, the one multiply by ``scale`` and the one rounding to ``out_dtype``."""
+    out = out_dtype_of(dtype, out_dtype)
+    if not inputs:
+        raise ValueError("no inputs")
+    count = int(np.asarray(inputs[0]).shape[0])
+    wide = [q8_dequantize_ref(*q8_quantize_ref(a, dtype))[:count] for a in inputs]
+    acc = allreduce_ref(wide, "fp32", "fp32", scale)
+    return bf16_round(acc) if out == "bf16" else acc
+
+
+def reduce_scatter_q8_ref(inputs: Sequence[np.ndarray], dtype: str, out_dtype: Optional[str] = None,
+                          scale: float = 1.0) -> List[np.ndarray]:
+    """Rank r's piece of the reduce-scatter on the fp8 wire: the elements of slice r of :func:`q8_slices`
+    over the input's blocks, clipped to the count.  The pieces concatenate to :func:`allreduce_q8_ref`."""
+    full = allreduce_q8_ref(inputs, dtype, out_dtype, scale)
+    count = int(full.shape[0])
+    return [full[min(count, a * Q8_BLOCK):min(count, b * Q8_BLOCK)] for a, b in q8_slices(q8_blocks(count), len(inputs))]

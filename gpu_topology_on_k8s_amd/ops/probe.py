@@ -1,5 +1,5 @@
 """Python front-end of the HIP/CDNA4 link probe (``csrc/probe/probe.hip`` and the headers it
-includes: ``probe_common.h``, K7's ``peer_allreduce.h`` / ``peer_driver.h``, K8's ``chase_latency.h``).
+includes: ``probe_common.h``, K7's ``peer_allreduce.h`` / ``peer_q8.h`` / ``peer_driver.h``, K8's ``chase_latency.h``).
 
 Seeds the link-cost matrix at node start (BASELINE.json north_star):
 
@@ -33,7 +33,7 @@ log = logging.getLogger(__name__)
 
 __all__ = ["device_count", "device_props", "warmup", "copy_bw", "gather_bw", "measure_matrix", "measure_ingress",
            "probe_topology", "probe_in_child", "ingress_bound", "ring_peers", "ring_bw", "measure_ring", "ring_in_child",
-           "peer_allreduce", "peer_allreduce_arrays", "peer_sweep", "PEER_ALGOS", "PROBE_PRESETS",
+           "peer_allreduce", "peer_allreduce_arrays", "peer_q8_quantize", "peer_sweep", "PEER_ALGOS", "PROBE_PRESETS",
            "chase_latency", "measure_latency", "LATENCY_PRESETS"]
 
 #: bytes per transfer / timed iterations / repeats of every pair (the link's median is published, its
@@ -141,28 +141,42 @@ PEER_ALGOS = ("oneshot", "twoshot")
 
 
 def peer_allreduce(devs: Sequence[int], count: int, dtype: str = "bf16", algo: str = "twoshot", iters: int = 3,
-                   warmup_iters: int = 1, blocks_per_cu: int = 8) -> Dict[str, object]:
+                   warmup_iters: int = 1, blocks_per_cu: int = 8, wire: str = "native") -> Dict[str, object]:
     """K7: all-reduce (sum) of ``count`` elements over the members ``devs`` (HIP ordinals, which may
     repeat) by this repository's own peer kernels, timed like ``_rccl.local_sweep`` (``algbw_gbps``,
-    ``busbw_gbps`` = algBW x 2(k-1)/k) and checked on every member (``wrong``, ``ok``)."""
+    ``busbw_gbps`` = algBW x 2(k-1)/k) and checked on every member (``wrong``, ``ok``).
+
+    ``wire="fp8"``: every member first packs its input into e4m3 codes with one power-of-two scale per 32
+    elements and the members read each other's packed form, 33 bytes per 32 elements
+    (``csrc/probe/peer_q8.h``); the result then also carries ``quantize_us`` and ``sum_us``, member 0's two
+    kernels timed alone."""
     return dict(_p().peer_allreduce([int(d) for d in devs], int(count), dtype, algo, int(iters), int(warmup_iters),
-                                    int(blocks_per_cu)))
+                                    int(blocks_per_cu), wire))
+
+
+def peer_q8_quantize(dev: int, array: np.ndarray, dtype: str = "bf16") -> Tuple[np.ndarray, np.ndarray]:
+    """The fp8 wire's quantize kernel on one array: ``(codes uint8, block exponents int32)``, the bits
+    ``ops.peer_ref.q8_quantize_ref`` gives."""
+    codes, exps = _p().peer_q8_quantize(int(dev), array, dtype)
+    return codes, exps
 
 
 def peer_allreduce_arrays(devs: Sequence[int], inputs: Sequence[np.ndarray], dtype: str = "bf16", algo: str = "twoshot",
-                          rounds: int = 1, out_dtype: Optional[str] = None, scale: float = 1.0) -> List[np.ndarray]:
+                          rounds: int = 1, out_dtype: Optional[str] = None, scale: float = 1.0,
+                          wire: str = "native") -> List[np.ndarray]:
     """K7 on the caller's data: one array per member (uint16 bit patterns for ``bf16``, float32 for
     ``fp32``) in, every member's result out; ``ops.peer_ref.allreduce_ref`` gives the same bits.
     ``out_dtype="fp32"`` of ``bf16`` inputs is the wide reduce (bf16 read, fp32 summed and written);
-    ``scale`` multiplies the fp32 sum once before the one rounding (``1 / k`` for a mean)."""
+    ``scale`` multiplies the fp32 sum once before the one rounding (``1 / k`` for a mean).  With
+    ``wire="fp8"`` the bits are ``ops.peer_ref.allreduce_q8_ref``'s."""
     return list(_p().peer_allreduce_arrays([int(d) for d in devs], list(inputs), dtype, algo, int(rounds), out_dtype,
-                                           float(scale)))
+                                           float(scale), wire))
 
 
 def peer_sweep(devs: Sequence[int], sizes: Sequence[int], dtype: str = "bf16", algo: str = "both", iters: int = 3,
-               warmup_iters: int = 1) -> List[Dict[str, object]]:
-    """K7 at every size (bytes) under ``algo`` (``oneshot``, ``twoshot`` or ``both``): one dict per size
-    and algorithm, in size order, with ``fastest`` marking the quicker algorithm of each size."""
+               warmup_iters: int = 1, wire: str = "native") -> List[Dict[str, object]]:
+    """K7 at every size (bytes) under ``algo`` (``oneshot``, ``twoshot`` or ``both``) on ``wire``: one dict per
+    size and algorithm, in size order, with ``fastest`` marking the quicker algorithm of each size."""
     if algo != "both" and algo not in PEER_ALGOS:
         raise ValueError(f"algo must be oneshot|twoshot|both, got {algo!r}")
     elem = ELEM.get(dtype)
@@ -170,7 +184,7 @@ def peer_sweep(devs: Sequence[int], sizes: Sequence[int], dtype: str = "bf16", a
         raise ValueError(f"dtype must be bf16|fp32, got {dtype!r}")
     out: List[Dict[str, object]] = []
     for nbytes in sizes:
-        pts = [peer_allreduce(devs, max(1, int(nbytes) // elem), dtype, a, iters, warmup_iters)
+        pts = [peer_allreduce(devs, max(1, int(nbytes) // elem), dtype, a, iters, warmup_iters, wire=wire)
                for a in (PEER_ALGOS if algo == "both" else (algo,))]
         best = min(pts, key=lambda p: p["time_us"])
         for p in pts:

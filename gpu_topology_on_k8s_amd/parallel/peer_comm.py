@@ -15,6 +15,23 @@ the host (``PeerCommTimeout``).  Every collective is
 and never more than those two barriers.  The price is that every collective is host-synchronous: two
 store round trips and two (two-shot: three) stream synchronisations per call.
 
+``wire="fp8"`` (``all_reduce``, ``reduce_scatter``) adds a third buffer per rank, *packed*: the rank's
+window as e4m3 codes with one power-of-two scale per 32 elements (``csrc/probe/peer_q8.h``,
+``ops/peer_ref.q8_quantize_ref``), 33 bytes per 32 elements.  Peers read that instead of the window, and a
+rank's own contribution is its packed form too, so every rank still holds the same bits
+(``ops/peer_ref.allreduce_q8_ref``).  The quantize reads only the rank's own window and writes only its
+own packed buffer, whose last readers finished before the previous collective's barrier B, so it runs
+before barrier A and the collective still costs two barriers:
+
+    quantize -> synchronize -> barrier A -> phase 1 on packed -> synchronize -> barrier B (-> phase 2)
+
+Phase 1 works on blocks of 32 elements, sliced by ``q8_slices``; phase 2 of a two-shot is the same gather
+of out at the output precision.  Per element and member the packed value is off by at most ``amax / 14``
+of its block (``2^(e+4)`` with ``amax * 2^-e > 224``).  The wire fits ``reduce_scatter`` best, where every
+byte that crosses a link is packed: the ZeRO-1 gradient path.  Because the quantize comes before the
+descriptors are compared, a rank that asks for ``wire="fp8"`` in a mismatched call has made that one
+launch, on its own buffers alone, when ``PeerCommMismatch`` is raised; no rank has touched a peer.
+
 Two backends exist, both with the ranks as threads of one process:
 
 ``backend="host"``: numpy buffers, the phases computed by ``ops/peer_ref.py``, every access logged; two
@@ -44,16 +61,19 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ..ops.peer_ref import ELEM as _ELEM, allreduce_ref, bf16_round, bits as _bits, out_dtype_of as _out_dtype, peer_slices
+from ..ops.peer_ref import (ELEM as _ELEM, Q8_BLOCK, allreduce_q8_ref, allreduce_ref, bf16_round, bits as _bits,
+                            out_dtype_of as _out_dtype, peer_slices, q8_blocks, q8_dequantize_ref, q8_quantize_ref, q8_slices)
 
 __all__ = ["PeerComm", "PeerCommError", "PeerCommTimeout", "PeerCommMismatch", "HostFabric", "MemoryStore",
-           "selftest_cases", "case_input", "run_case", "run_thread_ranks", "selftest", "thread_sweep", "timed_all_reduce", "parked_bytes",
+           "selftest_cases", "selftest_cases_q8", "case_input", "run_case", "run_thread_ranks", "selftest", "thread_sweep", "timed_all_reduce", "parked_bytes",
            "MAX_WORLD"]
 
 MAX_WORLD = 16  # kMaxSrc of csrc/probe/probe_common.h
 BACKENDS = ("host", "device")
 _NP = {"bf16": np.uint16, "fp32": np.float32}
 ALGOS = ("oneshot", "twoshot")
+WIRES = (None, "native", "fp8")  # None and "native" are the same call: the windows as they are
+_Q8_BIAS = 127  # a block's stored exponent byte is e + 127, as in csrc/probe/peer_q8.h
 
 
 class PeerCommError(RuntimeError):
@@ -70,6 +90,17 @@ class PeerCommMismatch(PeerCommError):
 
 def _n_vec(count: int, dtype: str) -> int:
     return -(-int(count) * _ELEM[dtype] // 16)
+
+
+def _max_blocks(capacity_bytes: int) -> int:
+    """Blocks a rank's packed buffer holds: a window full of bf16."""
+    return capacity_bytes // (2 * Q8_BLOCK)
+
+
+def _packed_bytes(capacity_bytes: int) -> int:
+    """Bytes of a rank's packed buffer: 32 code bytes per block, then one exponent byte per block, in vectors."""
+    nb = _max_blocks(capacity_bytes)
+    return max(16, (2 * nb + -(-nb // 16)) * 16)
 
 
 class MemoryStore:
@@ -119,13 +150,14 @@ class MemoryStore:
 
 
 class HostFabric:
-    """The buffers of ``backend="host"`` (one window and one out per rank, shared by the ranks'
-    threads) and the access log the conflict check reads."""
+    """The buffers of ``backend="host"`` (one window, one out and one packed buffer per rank, shared by
+    the ranks' threads) and the access log the conflict check reads."""
 
     def __init__(self, world: int, capacity_bytes: int):
         self.world, self.capacity_bytes = world, capacity_bytes
         self.window = [np.zeros(capacity_bytes, np.uint8) for _ in range(world)]
         self.out = [np.zeros(2 * capacity_bytes, np.uint8) for _ in range(world)]
+        self.packed = [np.zeros(_packed_bytes(capacity_bytes), np.uint8) for _ in range(world)]
         self.lock = threading.Lock()
         #: (accessor, owner, buffer, v0, v1, "r" | "w", the accessor's barrier count)
         self.log: List[Tuple[int, int, str, int, int, str, int]] = []
@@ -153,8 +185,8 @@ class HostFabric:
 
 
 class _HostBackend:
-    """One rank's phase calls (reduce, gather, gather_windows, host copies) on a :class:`HostFabric`,
-    computed by ``ops/peer_ref.py``."""
+    """One rank's phase calls (reduce, quantize, reduce_q8, gather, gather_windows, host copies) on a
+    :class:`HostFabric`, computed by ``ops/peer_ref.py``."""
 
     def __init__(self, rank: int, world: int, fabric: HostFabric):
         self.rank, self.world, self.f = rank, world, fabric
@@ -193,6 +225,45 @@ class _HostBackend:
         ratio = _ELEM[out_dtype] // _ELEM[in_dtype]
         self._out(self.rank, v0 * ratio, v1 * ratio, "w")[:] = allreduce_ref(xs, in_dtype, out_dtype, scale).view(np.uint8)
 
+    def _packed(self, p: int, b0: int, b1: int, mode: str) -> Tuple[np.ndarray, np.ndarray]:
+        """Blocks ``[b0, b1)`` of rank p's packed buffer: its code bytes and its exponent bytes, logged in vectors."""
+        nb = _max_blocks(self.f.capacity_bytes)
+        self.f.access(self.rank, p, "packed", 2 * b0, 2 * b1, mode, self.epoch)
+        self.f.access(self.rank, p, "packed", 2 * nb + b0 // 16, 2 * nb + -(-b1 // 16), mode, self.epoch)
+        return self.f.packed[p][Q8_BLOCK * b0:Q8_BLOCK * b1], self.f.packed[p][Q8_BLOCK * nb + b0:Q8_BLOCK * nb + b1]
+
+    def quantize(self, b0: int, b1: int, count: int, in_dtype: str) -> None:
+        e = _ELEM[in_dtype]
+        if b0 > b1 or b1 * Q8_BLOCK * e > self.f.capacity_bytes:
+            raise ValueError("quantize: blocks past the end of the window")
+        with self.f.lock:
+            self.f.launches += 1
+        if b0 == b1:
+            return
+        first = b0 * Q8_BLOCK
+        n = max(0, min(int(count), b1 * Q8_BLOCK) - first)  # the elements of the range before the count: no others are read
+        x = np.zeros((b1 - b0) * Q8_BLOCK, _NP[in_dtype])
+        x[:n] = self._win(self.rank, first * e // 16, -(-(first + n) * e // 16), "r").view(_NP[in_dtype])[:n]
+        codes, exps = q8_quantize_ref(x, in_dtype)
+        c, x8 = self._packed(self.rank, b0, b1, "w")
+        c[:], x8[:] = codes, (exps + _Q8_BIAS).astype(np.uint8)
+
+    def reduce_q8(self, b0: int, b1: int, out_dtype: str, scale: float) -> None:
+        e = _ELEM[out_dtype]
+        if b0 > b1 or b1 > _max_blocks(self.f.capacity_bytes) or b1 * Q8_BLOCK * e > 2 * self.f.capacity_bytes:
+            raise ValueError("reduce_q8: blocks past the end of the packed buffer or of out")
+        with self.f.lock:
+            self.f.launches += 1
+        if b0 == b1:
+            return
+        xs = []
+        for p in range(self.world):
+            c, x8 = self._packed(p, b0, b1, "r")
+            xs.append(q8_dequantize_ref(c.copy(), x8.astype(np.int32) - _Q8_BIAS))
+        acc = allreduce_ref(xs, "fp32", "fp32", scale)
+        res = bf16_round(acc) if out_dtype == "bf16" else acc
+        self._out(self.rank, b0 * Q8_BLOCK * e // 16, b1 * Q8_BLOCK * e // 16, "w")[:] = res.view(np.uint8)
+
     def gather(self, slices: Sequence[Tuple[int, int]]) -> None:
         with self.f.lock:
             self.f.launches += 1
@@ -227,14 +298,14 @@ _PARKED_LOCK = threading.Lock()
 
 def parked_bytes() -> int:
     """Device memory held by ranks of broken ``backend="device"`` communicators that were closed but
-    not freed, in bytes (a window and an out of twice its size per rank)."""
+    not freed, in bytes (a window, an out of twice its size and a packed buffer per rank)."""
     with _PARKED_LOCK:
-        return sum(3 * int(r.capacity_bytes) for r in _PARKED)
+        return sum(3 * int(r.capacity_bytes) + int(r.packed_bytes) for r in _PARKED)
 
 
 class _DeviceBackend:
-    """One rank's phase calls on its own device: ``_probe.PeerRank`` holds the window, the out and the
-    stream, and launches the K7 kernels over the peers' addresses."""
+    """One rank's phase calls on its own device: ``_probe.PeerRank`` holds the window, the out, the packed
+    buffer and the stream, and launches the K7 kernels over the peers' addresses."""
 
     def __init__(self, rank: int, world: int, device: int, capacity_bytes: int):
         from .._native import load
@@ -245,10 +316,12 @@ class _DeviceBackend:
 
     def record(self) -> Dict[str, int]:
         """What this rank publishes to its peers.  ``pid`` says whose address space the addresses are in."""
-        return {"pid": os.getpid(), "device": self.device, "window": int(self.r.window_ptr()), "out": int(self.r.out_ptr())}
+        return {"pid": os.getpid(), "device": self.device, "window": int(self.r.window_ptr()), "out": int(self.r.out_ptr()),
+                "packed": int(self.r.packed_ptr())}
 
     def open_peers(self, records: Sequence[Dict[str, int]]) -> None:
-        self.r.open_peers([int(p["device"]) for p in records], [int(p["window"]) for p in records], [int(p["out"]) for p in records])
+        self.r.open_peers([int(p["device"]) for p in records], [int(p["window"]) for p in records], [int(p["out"]) for p in records],
+                          [int(p["packed"]) for p in records])
 
     def close_peers(self) -> None:
         self.r.close_peers()
@@ -277,6 +350,12 @@ class _DeviceBackend:
 
     def reduce(self, v0: int, v1: int, in_dtype: str, out_dtype: str, scale: float) -> None:
         self.r.reduce(v0, v1, in_dtype, out_dtype, scale)
+
+    def quantize(self, b0: int, b1: int, count: int, in_dtype: str) -> None:
+        self.r.quantize(b0, b1, count, in_dtype)
+
+    def reduce_q8(self, b0: int, b1: int, out_dtype: str, scale: float) -> None:
+        self.r.reduce_q8(b0, b1, out_dtype, scale)
 
     def gather(self, slices: Sequence[Tuple[int, int]]) -> None:
         self.r.gather([(int(a), int(b)) for a, b in slices])
@@ -437,23 +516,48 @@ class PeerComm:
         self._barrier()
 
     # -- collectives --------------------------------------------------------------------------
-    def _reduce_args(self, op: str, count: int, dtype: str, algo: str, out_dtype: Optional[str], scale: float):
+    def _reduce_args(self, op: str, count: int, dtype: str, algo: str, out_dtype: Optional[str], scale: float,
+                     wire: Optional[str] = None):
+        """The checked arguments of a reduce: its units (vectors of the window; blocks of 32 elements on the
+        fp8 wire), the output dtype, the scale as the kernel gets it, and the call's descriptor."""
         self._check()
         out = _out_dtype(dtype, out_dtype)
         if algo not in ALGOS:
             raise ValueError(f"algo must be oneshot|twoshot, got {algo!r}")
+        if wire not in WIRES:
+            raise ValueError(f'wire must be None, "native" or "fp8", got {wire!r}')
         if count < 1:
             raise ValueError("count >= 1")
+        scale = float(np.float32(scale))
+        desc = {"op": op, "count": int(count), "dtype": dtype, "out_dtype": out, "algo": algo, "scale": scale}
+        if wire == "fp8":
+            n = q8_blocks(count)
+            if n * Q8_BLOCK * _ELEM[dtype] > self.capacity_bytes:
+                raise ValueError(f"{count} {dtype} elements, rounded up to blocks of {Q8_BLOCK}, exceed the window of "
+                                 f"{self.capacity_bytes} bytes")
+            return n, out, scale, {**desc, "wire": "fp8"}
         n = _n_vec(count, dtype)
         if n * 16 > self.capacity_bytes:
             raise ValueError(f"{count} {dtype} elements exceed the window of {self.capacity_bytes} bytes")
-        scale = float(np.float32(scale))
-        return n, out, scale, {"op": op, "count": int(count), "dtype": dtype, "out_dtype": out, "algo": algo, "scale": scale}
+        return n, out, scale, desc
 
     def all_reduce(self, count: int, dtype: str = "bf16", algo: str = "twoshot", out_dtype: Optional[str] = None,
-                   scale: float = 1.0) -> None:
-        """out[0, count) of every rank = ``scale`` x the sum over ranks of window[0, count), in ``out_dtype``."""
-        n, out, scale, desc = self._reduce_args("all_reduce", count, dtype, algo, out_dtype, scale)
+                   scale: float = 1.0, wire: Optional[str] = None) -> None:
+        """out[0, count) of every rank = ``scale`` x the sum over ranks of window[0, count), in ``out_dtype``.
+        ``wire="fp8"``: of the windows' packed forms (see the module docstring)."""
+        n, out, scale, desc = self._reduce_args("all_reduce", count, dtype, algo, out_dtype, scale, wire)
+        if wire == "fp8":
+            per = Q8_BLOCK * _ELEM[out] // 16  # output vectors per block
+            plan = q8_slices(n, self.world)
+            self._b.quantize(0, n, count, dtype)
+            self._enter(desc)
+            a, b = (0, n) if algo == "oneshot" else plan[self.rank]
+            self._b.reduce_q8(a, b, out, scale)
+            self._leave()
+            if algo == "twoshot":  # as below
+                self._b.gather([(a * per, b * per) for a, b in plan])
+                self._b.synchronize()
+            return
         ratio = _ELEM[out] // _ELEM[dtype]
         plan = peer_slices(n, self.world)
         self._enter(desc)
@@ -469,10 +573,20 @@ class PeerComm:
         self._b.gather([(a * ratio, b * ratio) for a, b in plan])
         self._b.synchronize()
 
-    def reduce_scatter(self, count: int, dtype: str = "bf16", out_dtype: Optional[str] = None, scale: float = 1.0) -> Tuple[int, int]:
-        """Rank r reduces slice r of ``peer_slices`` only.  Returns the ``(first, n)`` elements of out,
-        in ``out_dtype``, that hold this rank's piece (``n`` may be 0)."""
-        n, out, scale, desc = self._reduce_args("reduce_scatter", count, dtype, "oneshot", out_dtype, scale)
+    def reduce_scatter(self, count: int, dtype: str = "bf16", out_dtype: Optional[str] = None, scale: float = 1.0,
+                       wire: Optional[str] = None) -> Tuple[int, int]:
+        """Rank r reduces slice r of ``peer_slices`` only (``wire="fp8"``: of ``q8_slices``, over blocks of the
+        packed forms).  Returns the ``(first, n)`` elements of out, in ``out_dtype``, that hold this rank's
+        piece (``n`` may be 0)."""
+        n, out, scale, desc = self._reduce_args("reduce_scatter", count, dtype, "oneshot", out_dtype, scale, wire)
+        if wire == "fp8":
+            a, b = q8_slices(n, self.world)[self.rank]
+            self._b.quantize(0, n, count, dtype)
+            self._enter(desc)
+            self._b.reduce_q8(a, b, out, scale)
+            self._leave()
+            first, end = min(count, a * Q8_BLOCK), min(count, b * Q8_BLOCK)
+            return first, end - first
         a, b = peer_slices(n, self.world)[self.rank]
         self._enter(desc)
         self._b.reduce(a, b, dtype, out, scale)
@@ -572,6 +686,27 @@ def selftest_cases(k: int, counts: Optional[Sequence[int]] = None) -> List[Dict[
     return cases
 
 
+def selftest_counts_q8(k: int) -> List[int]:
+    # one element; under one block; one block; a block and an element; k - 1 blocks (the last slice is empty);
+    # past a 16-block exponent vector with a ragged end; and whole tiles with a tail.  The host packs every
+    # member's input of every case again for the reference, so the largest count stays moderate.
+    return [1, 31, 32, 33, 32 * (k - 1), 512 * k + 37, 8 * 1024 * k + 11]
+
+
+def selftest_cases_q8(k: int, counts: Optional[Sequence[int]] = None) -> List[Dict[str, object]]:
+    """The fp8 wire's cases: ``all_reduce`` under both algorithms and ``reduce_scatter``, the three dtype pairs
+    (the wide one with ``scale = 1 / k``), at every count."""
+    cases: List[Dict[str, object]] = []
+    for count in (selftest_counts_q8(k) if counts is None else counts):
+        for dtype, out, scale in (("bf16", "bf16", 1.0), ("fp32", "fp32", 1.0), ("bf16", "fp32", 1.0 / k)):
+            for algo in ALGOS:
+                cases.append({"op": "all_reduce", "count": count, "dtype": dtype, "out_dtype": out, "algo": algo, "scale": scale,
+                              "wire": "fp8"})
+            cases.append({"op": "reduce_scatter", "count": count, "dtype": dtype, "out_dtype": out, "algo": "oneshot", "scale": scale,
+                          "wire": "fp8"})
+    return cases
+
+
 def case_input(case_index: int, issue: int, rank: int, count: int, dtype: str) -> np.ndarray:
     """Rank ``rank``'s N(0, 1) input of the ``issue``-th issue of case ``case_index``; any rank can make any rank's."""
     rng = np.random.default_rng([case_index, issue, rank, count])
@@ -582,10 +717,17 @@ def case_input(case_index: int, issue: int, rank: int, count: int, dtype: str) -
 def run_case(comm: PeerComm, case: Dict[str, object], inputs: Sequence[np.ndarray]) -> Tuple[np.ndarray, np.ndarray]:
     """Issues one case on ``comm`` with ``inputs[comm.rank]`` as this rank's data; returns (got, reference),
     both computed by this rank, the reference from every rank's input."""
-    from ..ops.peer_ref import reduce_scatter_ref
+    from ..ops.peer_ref import reduce_scatter_q8_ref, reduce_scatter_ref
 
     op, count, dtype, out = case["op"], int(case["count"]), case["dtype"], case["out_dtype"]
     k, r = comm.world, comm.rank
+    if case.get("wire") == "fp8":
+        comm.write(inputs[r])
+        if op == "all_reduce":
+            comm.all_reduce(count, dtype, case["algo"], out, case["scale"], wire="fp8")
+            return comm.read(0, count, out), allreduce_q8_ref(inputs, dtype, out, case["scale"])
+        first, n = comm.reduce_scatter(count, dtype, out, case["scale"], wire="fp8")
+        return comm.read(first, n, out), reduce_scatter_q8_ref(inputs, dtype, out, case["scale"])[r]
     if op == "all_gather":
         comm.write(inputs[r], comm.gather_slot(count, dtype))
         n = comm.all_gather(count, dtype)
@@ -666,22 +808,23 @@ class _Once:
             return self._made[key]
 
 
-def timed_all_reduce(comm: PeerComm, count: int, dtype: str, algo: str, iters: int, warmup_iters: int = 1) -> Tuple[float, float]:
+def timed_all_reduce(comm: PeerComm, count: int, dtype: str, algo: str, iters: int, warmup_iters: int = 1,
+                     wire: Optional[str] = None) -> Tuple[float, float]:
     """``warmup_iters`` untimed and ``iters`` timed ``all_reduce`` calls of what the window holds, on one
     rank (every rank calls this).  Returns this rank's host seconds per call and, of those, the seconds
     spent inside the call's two barriers.  The clock starts after a barrier and stops when the last call
     has returned, which is after its last stream synchronise."""
     for _ in range(warmup_iters):
-        comm.all_reduce(count, dtype, algo)
+        comm.all_reduce(count, dtype, algo, wire=wire)
     comm.barrier()
     in_barriers, t0 = comm.barrier_s, time.perf_counter()
     for _ in range(iters):
-        comm.all_reduce(count, dtype, algo)
+        comm.all_reduce(count, dtype, algo, wire=wire)
     return (time.perf_counter() - t0) / iters, (comm.barrier_s - in_barriers) / iters
 
 
 def thread_sweep(devices: Sequence[int], sizes: Sequence[int], dtype: str = "bf16", algo: str = "both", iters: int = 3,
-                 warmup_iters: int = 1, timeout_s: float = 60.0) -> List[Dict[str, object]]:
+                 warmup_iters: int = 1, timeout_s: float = 60.0, wire: Optional[str] = None) -> List[Dict[str, object]]:
     """``all_reduce`` on thread ranks over ``devices`` at every size (bytes) under ``algo`` (``oneshot``,
     ``twoshot`` or ``both``): one dict per size and algorithm, in size order, with the keys of
     ``ops.probe.peer_sweep`` and ``barrier_us``.
@@ -690,13 +833,17 @@ def thread_sweep(devices: Sequence[int], sizes: Sequence[int], dtype: str = "bf1
     result back.  ``time_us`` is host time per call, the slowest rank's: the clock starts after a barrier
     and stops when the last call has returned.  ``barrier_us`` is the mean over ranks of the host time
     per call spent inside the call's two barriers.  ``wrong`` counts, over all ranks, the elements
-    whose bits differ from ``allreduce_ref``; the check runs on the host, so sizes should stay moderate."""
+    whose bits differ from ``allreduce_ref`` (``wire="fp8"``: from ``allreduce_q8_ref``, and the rows carry
+    ``"wire"``); the check runs on the host, so sizes should stay moderate."""
     if algo != "both" and algo not in ALGOS:
         raise ValueError(f"algo must be oneshot|twoshot|both, got {algo!r}")
     if dtype not in _ELEM:
         raise ValueError(f"dtype must be bf16|fp32, got {dtype!r}")
     if iters < 1 or warmup_iters < 0:
         raise ValueError("iters >= 1, warmup_iters >= 0")
+    if wire not in WIRES:
+        raise ValueError(f'wire must be None, "native" or "fp8", got {wire!r}')
+    fp8 = wire == "fp8"
     k, elem = len(devices), _ELEM[dtype]
     points = [(max(1, int(nbytes) // elem), a) for nbytes in sizes for a in (ALGOS if algo == "both" else (algo,))]
     if not points:
@@ -707,28 +854,33 @@ def thread_sweep(devices: Sequence[int], sizes: Sequence[int], dtype: str = "bf1
         rows = []
         for count, a in points:
             xs = once.get(("in", count), lambda: [case_input(0, 0, p, count, dtype) for p in range(k)], lambda o: o[1] == count)
-            ref = once.get(("ref", count), lambda: allreduce_ref(xs, dtype), lambda o: o[1] == count)
+            ref = once.get(("ref", count), lambda: (allreduce_q8_ref if fp8 else allreduce_ref)(xs, dtype), lambda o: o[1] == count)
             comm.write(xs[comm.rank])
-            secs, in_barriers = timed_all_reduce(comm, count, dtype, a, iters, warmup_iters)
+            secs, in_barriers = timed_all_reduce(comm, count, dtype, a, iters, warmup_iters, wire)
             got = comm.read(0, count, dtype)
             rows.append((secs, in_barriers, int(np.count_nonzero(_bits(got) != _bits(ref)))))
         return rows
 
-    res = run_thread_ranks(devices, body, -(-max(c for c, _ in points) * elem // 16) * 16, timeout_s=timeout_s)
+    most = max(c for c, _ in points)
+    res = run_thread_ranks(devices, body, q8_blocks(most) * Q8_BLOCK * elem if fp8 else -(-most * elem // 16) * 16, timeout_s=timeout_s)
     out: List[Dict[str, object]] = []
     for i, (count, a) in enumerate(points):
         secs = max(r[i][0] for r in res)
         gbps = count * elem / secs / 1e9
         out.append({"bytes": count * elem, "count": count, "time_us": secs * 1e6, "algbw_gbps": gbps,
                     "busbw_gbps": gbps * 2.0 * (k - 1) / k, "wrong": sum(r[i][2] for r in res), "backend": "peer", "algo": a,
-                    "ranks": "thread", "barrier_us": sum(r[i][1] for r in res) / k * 1e6})
+                    "ranks": "thread", "barrier_us": sum(r[i][1] for r in res) / k * 1e6, **({"wire": "fp8"} if fp8 else {})})
     return out
 
 
 def _case_capacity(k: int, cases: Sequence[Dict[str, object]]) -> int:
     """Window bytes the largest of ``cases`` needs (an all-gather holds every rank's slot)."""
-    need = max(_n_vec(int(c["count"]), c["dtype"]) * (k if c["op"] == "all_gather" else 1) for c in cases)
-    return max(16, need * 16)
+    def vecs(c):
+        if c.get("wire") == "fp8":  # whole blocks
+            return q8_blocks(int(c["count"])) * Q8_BLOCK * _ELEM[c["dtype"]] // 16
+        return _n_vec(int(c["count"]), c["dtype"]) * (k if c["op"] == "all_gather" else 1)
+
+    return max(16, max(vecs(c) for c in cases) * 16)
 
 
 def selftest(devices: Sequence[int], counts: Optional[Sequence[int]] = None, timeout_s: float = 60.0) -> Dict[str, object]:
@@ -737,9 +889,13 @@ def selftest(devices: Sequence[int], counts: Optional[Sequence[int]] = None, tim
 
     ``wrong`` counts the collectives whose dtype, shape or bits differ from the reference on any rank;
     ``barriers_per_collective`` lists the distinct numbers of barriers a collective took (``[2]``), and
-    ``launches`` is the kernel launches of all ranks together."""
+    ``launches`` is the kernel launches of all ranks together.  Those keys describe the cases of
+    :func:`selftest_cases`; the fp8 wire's (:func:`selftest_cases_q8`, at their own counts when ``counts`` is
+    none) run after them on the same communicators and are reported as ``q8_cases``, ``q8_collectives``,
+    ``q8_wrong`` and ``q8_launches``.  ``barriers_per_collective`` covers both sets."""
     k = len(devices)
-    cases = selftest_cases(k, counts)
+    native = selftest_cases(k, counts)
+    cases = native + selftest_cases_q8(k, counts)
     once = _Once()  # every rank's inputs of (case, issue), made by the first rank that asks
 
     def inputs(ci: int, issue: int) -> List[np.ndarray]:
@@ -747,16 +903,21 @@ def selftest(devices: Sequence[int], counts: Optional[Sequence[int]] = None, tim
         return once.get((ci, issue), make, lambda o: o[0] >= ci - 1)  # ranks are never more than a collective apart
 
     def body(comm: PeerComm):
-        wrong, barriers = set(), set()
+        wrong, barriers, launches = set(), set(), 0
         for ci, case in enumerate(cases):
+            if ci == len(native):
+                launches = comm.launches
             for issue in range(2):
                 before = comm.barriers
                 got, ref = run_case(comm, case, inputs(ci, issue))
                 barriers.add(comm.barriers - before)
                 if got.dtype != ref.dtype or got.shape != ref.shape or not np.array_equal(_bits(got), _bits(ref)):
                     wrong.add((ci, issue))
-        return wrong, barriers, comm.launches
+        return wrong, barriers, launches, comm.launches - launches
 
     res = run_thread_ranks(devices, body, _case_capacity(k, cases), timeout_s=timeout_s)
-    return {"cases": len(cases), "collectives": 2 * len(cases), "wrong": len(set().union(*(r[0] for r in res))),
-            "barriers_per_collective": sorted(set().union(*(r[1] for r in res))), "launches": sum(r[2] for r in res)}
+    bad = set().union(*(r[0] for r in res))
+    n, nq = len(native), len(cases) - len(native)
+    return {"cases": n, "collectives": 2 * n, "wrong": sum(ci < n for ci, _ in bad),
+            "barriers_per_collective": sorted(set().union(*(r[1] for r in res))), "launches": sum(r[2] for r in res),
+            "q8_cases": nq, "q8_collectives": 2 * nq, "q8_wrong": sum(ci >= n for ci, _ in bad), "q8_launches": sum(r[3] for r in res)}
