@@ -52,6 +52,10 @@ struct Hyper {
 //     part = the gradient's sum-of-squares partials (``sq_norm_parts``); every block sums them itself
 //     tptr = optimizer step count AFTER this step (``sq_norm_parts`` advanced it in stream order)
 //   Bias corrections 1 - beta^t and the clipping factor min(1, clip / ||g * grad_scale||) follow.
+//   The gradient may hold anything.  A NaN norm gives a NaN factor, as torch.clamp(.., max=1) does in
+//   the host form (models/optim.py), and with it a NaN in every element: a fminf would return 1 and
+//   switch the clipping off quietly.  An infinite norm gives the factor 0.  Without clipping a NaN or
+//   an Inf in the gradient reaches its own element of master, m, v and W alone.
 template <bool DEV>
 __device__ __forceinline__ Hyper hyper(const float* __restrict__ hp, const float* __restrict__ part, int nparts,
                                        const float* __restrict__ tptr) {
@@ -66,7 +70,8 @@ __device__ __forceinline__ Hyper hyper(const float* __restrict__ hp, const float
     float s = 0.f;
     for (int i = threadIdx.x; i < nparts; i += 256) s += part[i];
     const float norm = sqrtf(block_sum(s)) * h.gs;
-    h.gs = h.gs * fminf(1.f, clip / (norm + 1e-6f));
+    const float f = clip / (norm + 1e-6f);
+    h.gs = h.gs * (f > 1.f ? 1.f : f);  // not fminf: a NaN passes
   }
   const float t = tptr[0];
   h.bc1 = 1.f - powf(h.b1, t);

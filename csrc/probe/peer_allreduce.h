@@ -9,6 +9,11 @@
 // sum reproduces them (ops/peer_ref.py).  The output may be wider than the input: bf16 read over the
 // link, fp32 written, which halves the link traffic of reducing a widened copy.
 //
+// The inputs may hold anything.  The adds, the multiply and the rounding are IEEE: subnormals of fp32
+// and of bf16 are kept, never flushed; Inf + -Inf and anything with a NaN give NaN; -0 + -0 = -0; a sum
+// that reaches 0x7F7F8000 rounds to a bf16 Inf.  Which NaN comes out (sign, payload) is the hardware's
+// choice, the same on every member; tests/test_gpu_peer_nonfinite.py compares the rest bit for bit.
+//
 // No kernel here waits for another running kernel: the all-reduce's cross-member ordering is stream
 // events between launches (the host driver in peer_driver.h), visibility rests on kernel boundaries.
 #pragma once

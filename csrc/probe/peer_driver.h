@@ -433,13 +433,16 @@ py::list peer_allreduce_arrays(const std::vector<int>& devs, const std::vector<p
 // The quantize kernel alone on one array (uint16 bit patterns for bf16, float32 for fp32): the codes
 // (uint8, 32 per block, element order) and the block exponents (int32, unbiased) it wrote, in logical
 // order.  The window is filled with a non-zero byte first, so what lies past the count is not zero.
-py::tuple peer_q8_quantize(int dev, const py::array& array, const std::string& dtype) {
+// `count` (none: the array's size) is the call's element count: the array's elements at and past it
+// lie in the window after the count, as far as the count's last block reaches.
+py::tuple peer_q8_quantize(int dev, const py::array& array, const std::string& dtype, const py::object& count_arg) {
   const PeerTypes types = peer_types(dtype, "");
   check_dev(dev);
   const py::dtype want = types.in_bf16 ? py::dtype::of<uint16_t>() : py::dtype::of<float>();
   if (array.ndim() != 1 || array.size() < 1 || !array.dtype().is(want))
     throw std::invalid_argument("a one-dimensional, non-empty array, uint16 (bf16) or float32 (fp32)");
-  const size_t count = (size_t)array.size();
+  const size_t count = count_arg.is_none() ? (size_t)array.size() : count_arg.cast<size_t>();
+  if (count < 1 || count > (size_t)array.size()) throw std::invalid_argument("1 <= count <= the array's size");
   if (count > PeerAllreduce::kMaxCount) throw std::invalid_argument("count <= 64 Mi elements");
   const py::array src = py::array::ensure(array, py::array::c_style);
   const size_t n_blocks = (count + kQ8Block - 1) / kQ8Block, in_bytes = n_blocks * kQ8Block * types.in_elem();
@@ -453,7 +456,7 @@ py::tuple peer_q8_quantize(int dev, const py::array& array, const std::string& d
     DeviceGuard g(dev);
     DevBuf win(dev, in_bytes), packed(dev, q8_packed_vecs(n_blocks) * 16);
     HIP_CHECK(hipMemset(win.p, 0x7b, in_bytes));
-    HIP_CHECK(hipMemcpy(win.p, from, count * types.in_elem(), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(win.p, from, std::min((size_t)array.size() * types.in_elem(), in_bytes), hipMemcpyHostToDevice));
     const int grid = peer_reduce_grid(num_cus(dev), kBlocksPerCU, 1, in_bytes / 16);
     launch_peer_q8_quantize(types.in_bf16, (const u32x4*)win.p, (u32x4*)packed.p, q8_exp_vec(n_blocks), 0, n_blocks, count, grid,
                             nullptr);

@@ -9,6 +9,12 @@
 //              2^e, 2^-e and every dequantised value are normal fp32 numbers and both scalings are exact.
 //   code     = x * 2^-e rounded to nearest even into e4m3fn, subnormal codes (quantum 2^-9) included;
 //              |x * 2^-e| <= 448, so nothing saturates.  value = float(code) * 2^e.
+//   non-finite: the amax is taken over the block's elements that are not NaN (fmaxf drops a quieted NaN),
+//              after the count's mask; an Inf counts, so its block has e = 120, and an all-NaN block e = -100.
+//              A NaN or an Inf gets a code with (code & 0x7f) == 0x7f, the format's NaN (e4m3fn has no
+//              infinity; the code's sign bit is unspecified), which widens to NaN; the block's finite
+//              elements are coded by the ordinary rule with that e.  Under e = 120 a magnitude of at
+//              least 248 * 2^120 rounds to the code of 256 and widens to 2^128 = Inf.
 // The sum is taken over the dequantised values in member order in fp32, multiplied once by `scale` and
 // rounded once, as peer_reduce_vecs does: every member computes the same bits, its own contribution
 // being its packed form too.
@@ -70,12 +76,16 @@ __device__ __forceinline__ void q8_quantize_vec(const u32x4& r, size_t v, size_t
   const size_t first = v * L;
   float f[L];
   peer_widen(r, f);
+  if (first + L > count) {  // the vector the count ends in, and those after it: every other one skips the mask
 #pragma unroll
-  for (int j = 0; j < L; ++j)
-    if (first + j >= count) f[j] = 0.f;
+    for (int j = 0; j < L; ++j)
+      if (first + j >= count) f[j] = 0.f;
+  }
+  // The amax leaves NaNs out.  fmaxf drops a quiet NaN, but a signalling one makes v_max_f32 return a
+  // NaN (IEEE mode), and the window's bits reach it as they are: so every element is quieted first.
   float amax = 0.f;
 #pragma unroll
-  for (int j = 0; j < L; ++j) amax = fmaxf(amax, fabsf(f[j]));
+  for (int j = 0; j < L; ++j) amax = fmaxf(amax, fabsf(__builtin_canonicalizef(f[j])));
 #pragma unroll
   for (int d = 1; d < G; d <<= 1) amax = fmaxf(amax, __shfl_xor(amax, d));
   const int e = q8_block_exp(amax);

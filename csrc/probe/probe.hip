@@ -837,7 +837,9 @@ PYBIND11_MODULE(_probe, m) {
         "K7 on the caller's arrays (uint16 bit patterns for bf16, float32 for fp32): the k members' results, "
         "scale x sum, in out_dtype (none: dtype; fp32 of bf16 inputs is the wide reduce)");
   m.def("peer_q8_quantize", &peer_q8_quantize, py::arg("dev"), py::arg("array"), py::arg("dtype") = "bf16",
-        "the fp8 wire's quantize kernel on one array: (codes uint8, block exponents int32) in logical order");
+        py::arg("count") = py::none(),
+        "the fp8 wire's quantize kernel on one array: (codes uint8, block exponents int32) in logical order; "
+        "count (none: all): the elements that are data, the rest lies in the window after them");
   bind_peer_rank(m);
   m.def("chase_latency", &chase_latency, py::arg("src_dev"), py::arg("exec_dev"), py::arg("ws_bytes") = (size_t)1 << 30,
         py::arg("stride") = (size_t)128, py::arg("hops") = 4096, py::arg("chains") = 1, py::arg("iters") = 5,

@@ -5,6 +5,12 @@ The kernels sum every element in fp32 in member order, ``((x0 + x1) + x2) + ...`
 the call's scale and round once, so a sequential numpy sum reproduces their result bit for bit; :func:`peer_slices` is the driver's
 slice plan of the two-shot algorithm.
 
+The references cover all of IEEE 754, not finite normal values alone.  numpy's fp32 add and multiply are
+IEEE: subnormals are kept, ``Inf + -Inf`` and anything with a NaN give NaN, ``-0 + -0 = -0``.  A result
+is compared with its reference by :func:`mismatches`: where the reference is NaN the result must be a
+NaN (of any sign and payload: which payload an add or a rounding keeps is the hardware's choice), and
+every other element, infinities, subnormals and signed zeros included, must have the reference's bits.
+
 The fp8 wire (``csrc/probe/peer_q8.h``) has its reference here too: :func:`q8_quantize_ref` packs one
 rank's input into OCP e4m3fn codes with one power-of-two scale per 32 elements, and
 :func:`allreduce_q8_ref` sums the dequantised values exactly as :func:`allreduce_ref` sums the inputs.
@@ -16,7 +22,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 __all__ = ["ELEM", "peer_slices", "bf16_round", "bf16_to_f32", "bits", "out_dtype_of", "allreduce_ref", "reduce_scatter_ref",
-           "Q8_BLOCK", "Q8_EXP_MIN", "Q8_EXP_MAX", "q8_blocks", "q8_slices", "q8_quantize_ref", "q8_dequantize_ref",
+           "is_nan_bits", "mismatches", "Q8_BLOCK", "Q8_EXP_MIN", "Q8_EXP_MAX", "q8_blocks", "q8_slices", "q8_quantize_ref", "q8_dequantize_ref",
            "allreduce_q8_ref", "reduce_scatter_q8_ref"]
 
 ELEM = {"bf16": 2, "fp32": 4}  # bytes per element
@@ -32,9 +38,16 @@ def peer_slices(n_vec: int, k: int) -> List[Tuple[int, int]]:
 
 
 def bf16_round(x: np.ndarray) -> np.ndarray:
-    """bf16 bit patterns (uint16) of finite float32 ``x``, round to nearest even on the bit pattern."""
+    """bf16 bit patterns (uint16) of float32 ``x``.  Finite values and the infinities round to nearest
+    even on the bit pattern, so a finite value at or above ``0x7F7F8000`` (bf16's maximum and half a unit
+    in its last place) becomes Inf and an fp32 subnormal rounds into bf16's subnormals.  A NaN becomes
+    the upper half of its own pattern with the quiet bit ``0x0040`` set: its sign and the top six payload
+    bits are kept and the mantissa is never zero, so ``0x7F800001`` gives ``0x7FC0`` and ``0xFFFFFFFF``
+    gives ``0xFFFF``; rounding the pattern would carry them into +Inf and -0."""
     b = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
-    return ((b + (np.uint32(0x7FFF) + ((b >> np.uint32(16)) & np.uint32(1)))) >> np.uint32(16)).astype(np.uint16)
+    r = ((b + (np.uint32(0x7FFF) + ((b >> np.uint32(16)) & np.uint32(1)))) >> np.uint32(16)).astype(np.uint16)
+    nan = (b & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000)
+    return np.where(nan, ((b >> np.uint32(16)) | np.uint32(0x0040)).astype(np.uint16), r)
 
 
 def bf16_to_f32(bits: np.ndarray) -> np.ndarray:
@@ -45,6 +58,25 @@ def bf16_to_f32(bits: np.ndarray) -> np.ndarray:
 def bits(a: np.ndarray) -> np.ndarray:
     """The one bit-pattern view of a result: bf16 patterns (uint16) as they are, float32 as uint32."""
     return a.view(np.uint16 if a.dtype == np.uint16 else np.uint32)
+
+
+def is_nan_bits(a: np.ndarray) -> np.ndarray:
+    """Which elements of a result (bf16 patterns as uint16, or float32) are NaN: the exponent all ones
+    and a non-zero mantissa."""
+    b = bits(a)
+    if b.dtype == np.uint16:
+        return (b & np.uint16(0x7FFF)) > np.uint16(0x7F80)
+    return (b & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000)
+
+
+def mismatches(got: np.ndarray, ref: np.ndarray) -> np.ndarray:
+    """The indices at which ``got`` is not what ``ref`` demands, no element left out: where the reference
+    is NaN ``got`` must be a NaN, everywhere else its bits must be the reference's.  Type and shape must
+    be the reference's too (``ValueError``)."""
+    if got.dtype != ref.dtype or got.shape != ref.shape:
+        raise ValueError(f"result is {got.dtype}{got.shape}, reference {ref.dtype}{ref.shape}")
+    want_nan = is_nan_bits(ref)
+    return np.flatnonzero(np.where(want_nan, ~is_nan_bits(got), bits(got) != bits(ref)))
 
 
 def out_dtype_of(dtype: str, out_dtype: Optional[str]) -> str:
@@ -60,18 +92,19 @@ def out_dtype_of(dtype: str, out_dtype: Optional[str]) -> str:
 
 
 def allreduce_ref(inputs: Sequence[np.ndarray], dtype: str, out_dtype: Optional[str] = None, scale: float = 1.0) -> np.ndarray:
-    """What every member holds after the all-reduce of ``inputs`` (finite values; uint16 bit patterns
-    for ``bf16``, float32 for ``fp32``): a sequential fp32 sum in member order, one fp32 multiply by
-    ``scale`` (rounded to fp32 first, as the kernel's argument is), then one rounding to ``out_dtype``
+    """What every member holds after the all-reduce of ``inputs`` (any values, non-finite and
+    subnormal ones included; uint16 bit patterns for ``bf16``, float32 for ``fp32``): a sequential fp32 sum
+    in member order, one fp32 multiply by ``scale`` (rounded to fp32 first, as the kernel's argument is), then one rounding to ``out_dtype``
     (none: ``dtype``; ``fp32`` of ``bf16`` inputs keeps the fp32 sum)."""
     out = out_dtype_of(dtype, out_dtype)
     if not inputs:
         raise ValueError("no inputs")
     wide = [bf16_to_f32(a) if dtype == "bf16" else np.ascontiguousarray(a, dtype=np.float32) for a in inputs]
     acc = wide[0].copy()
-    for x in wide[1:]:
-        acc = (acc + x).astype(np.float32)
-    acc = (acc * np.float32(scale)).astype(np.float32)
+    with np.errstate(over="ignore", invalid="ignore"):  # a sum that overflows is Inf and Inf - Inf is NaN: results, not faults
+        for x in wide[1:]:
+            acc = (acc + x).astype(np.float32)
+        acc = (acc * np.float32(scale)).astype(np.float32)
     return bf16_round(acc) if out == "bf16" else acc
 
 
@@ -102,11 +135,11 @@ def q8_slices(n_blocks: int, k: int) -> List[Tuple[int, int]]:
 
 
 def _e4m3_values() -> np.ndarray:
-    """float32 value of every OCP e4m3fn code (0x7f and 0xff, the NaNs, as 0: no finite input makes them)."""
+    """float32 value of every OCP e4m3fn code; 0x7f and 0xff, the format's only non-finite codes, are NaN."""
     c = np.arange(256)
     e, m = (c >> 3) & 15, c & 7
     mag = np.where(e == 0, m * 2.0 ** -9, (8 + m) * 2.0 ** (e.astype(np.float64) - 10))
-    mag[(c & 0x7F) == 0x7F] = 0.0
+    mag[(c & 0x7F) == 0x7F] = np.nan
     return (np.where(c & 0x80, -mag, mag)).astype(np.float32)
 
 
@@ -114,13 +147,20 @@ _E4M3 = _e4m3_values()
 
 
 def q8_quantize_ref(x: np.ndarray, dtype: str, count: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
-    """The packed form of one rank's input ``x`` (finite; uint16 bit patterns for ``bf16``, float32 for
+    """The packed form of one rank's input ``x`` (uint16 bit patterns for ``bf16``, float32 for
     ``fp32``), of which the first ``count`` elements (none: all) are data and everything after them is
     zero: ``(codes uint8 [n_blocks * 32], exps int32 [n_blocks])``.
 
     Per block of 32 elements, ``e`` is the smallest integer with ``amax * 2^-e <= 448``, clamped to
     ``[-100, 120]`` (``amax == 0``: -100), and an element's code is ``x * 2^-e`` rounded to nearest even
-    into e4m3fn, subnormal codes (quantum ``2^-9``) included.  A code carries its element's sign bit."""
+    into e4m3fn, subnormal codes (quantum ``2^-9``) included.  A code carries its element's sign bit.
+
+    Non-finite elements: the amax is taken over the block's elements that are not NaN, after the count's
+    mask.  An Inf counts, so its block has ``e = 120``; a block whose data is all NaN has amax 0 and
+    ``e = -100``.  A NaN or an Inf gets a code with ``code & 0x7F == 0x7F``, the format's NaN, since e4m3fn
+    has no infinity; here it carries the element's sign bit, but that bit is unspecified and a comparison
+    masks it.  The block's finite elements are coded by the ordinary rule with that ``e``, so a NaN
+    costs its neighbours nothing and an Inf leaves them what ``2^120`` leaves."""
     if dtype not in ELEM:
         raise ValueError(f"dtype must be bf16|fp32, got {dtype!r}")
     v = bf16_to_f32(x) if dtype == "bf16" else np.ascontiguousarray(x, dtype=np.float32)
@@ -130,10 +170,13 @@ def q8_quantize_ref(x: np.ndarray, dtype: str, count: Optional[int] = None) -> T
     nb = q8_blocks(count)
     full = np.zeros(nb * Q8_BLOCK, np.float32)
     full[:count] = v[:count]
-    amax = np.abs(full).reshape(nb, Q8_BLOCK).max(axis=1) if nb else np.zeros(0, np.float32)
-    m, ex = np.frexp(amax)  # amax = m * 2^ex, m in [0.5, 1); 448 = 0.875 * 2^9
-    e = np.where(amax == 0, Q8_EXP_MIN, np.clip(ex - 9 + (m > 0.875), Q8_EXP_MIN, Q8_EXP_MAX)).astype(np.int32)
-    y = np.ldexp(full, -np.repeat(e, Q8_BLOCK)).astype(np.float32)  # exact, or too small for any code but 0
+    special = ~np.isfinite(full)
+    mag = np.where(np.isnan(full), np.float32(0), np.abs(full))  # a NaN takes no part in the amax
+    amax = mag.reshape(nb, Q8_BLOCK).max(axis=1) if nb else np.zeros(0, np.float32)
+    m, ex = np.frexp(np.where(np.isinf(amax), np.float32(0), amax))  # amax = m * 2^ex, m in [0.5, 1); 448 = 0.875 * 2^9
+    e = np.where(amax == 0, Q8_EXP_MIN, np.clip(ex - 9 + (m > 0.875), Q8_EXP_MIN, Q8_EXP_MAX))
+    e = np.where(np.isinf(amax), Q8_EXP_MAX, e).astype(np.int32)
+    y = np.ldexp(np.where(special, np.float32(0), full), -np.repeat(e, Q8_BLOCK)).astype(np.float32)  # exact, or too small for any code but 0
     a = np.abs(y).astype(np.float64)
     _, ea = np.frexp(a)  # a in [2^(ea - 1), 2^ea): three mantissa bits below the leading one
     quantum = np.ldexp(1.0, np.maximum(ea - 4, -9))
@@ -141,17 +184,22 @@ def q8_quantize_ref(x: np.ndarray, dtype: str, count: Optional[int] = None) -> T
     mr, er = np.frexp(r)
     normal = r >= 2.0 ** -6
     code = np.where(normal, (er - 1 + 7) * 8 + np.rint((mr * 2 - 1) * 8), np.rint(r * 512)).astype(np.int64)
-    code = np.minimum(code, 0x7E)  # only a non-finite or out-of-range input gets here
-    return (code | (np.signbit(y).astype(np.int64) << 7)).astype(np.uint8), e
+    code = np.where(special, 0x7F, np.minimum(code, 0x7E))  # no finite element reaches the minimum
+    return (code | (np.signbit(full).astype(np.int64) << 7)).astype(np.uint8), e
 
 
 def q8_dequantize_ref(codes: np.ndarray, exps: np.ndarray) -> np.ndarray:
-    """float32 ``float(code) * 2^e`` of every element, exact: the values a member contributes to a sum."""
+    """float32 ``float(code) * 2^e`` of every element, exact: the values a member contributes to a sum.
+    The codes ``0x7F`` and ``0xFF`` give NaN, so a NaN or an Inf that went in comes out as a NaN.  The one
+    finite input that does not come out finite: under ``e = 120`` a magnitude of at least ``248 * 2^120``
+    (fp32 ``0x7F780000``, bf16 ``0x7F78``) rounds to the code of 256, and ``256 * 2^120 = 2^128`` is Inf in
+    fp32, in numpy's ``ldexp`` as in the kernel's multiply."""
     codes = np.ascontiguousarray(codes, dtype=np.uint8)
     exps = np.ascontiguousarray(exps).astype(np.int32)
     if codes.shape[0] != exps.shape[0] * Q8_BLOCK:
         raise ValueError("32 codes per exponent")
-    return np.ldexp(_E4M3[codes], np.repeat(exps, Q8_BLOCK)).astype(np.float32)
+    with np.errstate(over="ignore"):  # 256 * 2^120 is Inf, see above
+        return np.ldexp(_E4M3[codes], np.repeat(exps, Q8_BLOCK)).astype(np.float32)
 
 
 def allreduce_q8_ref(inputs: Sequence[np.ndarray], dtype: str, out_dtype: Optional[str] = None, scale: float = 1.0) -> np.ndarray:

@@ -154,10 +154,11 @@ def peer_allreduce(devs: Sequence[int], count: int, dtype: str = "bf16", algo: s
                                     int(blocks_per_cu), wire))
 
 
-def peer_q8_quantize(dev: int, array: np.ndarray, dtype: str = "bf16") -> Tuple[np.ndarray, np.ndarray]:
+def peer_q8_quantize(dev: int, array: np.ndarray, dtype: str = "bf16", count: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
     """The fp8 wire's quantize kernel on one array: ``(codes uint8, block exponents int32)``, the bits
-    ``ops.peer_ref.q8_quantize_ref`` gives."""
-    codes, exps = _p().peer_q8_quantize(int(dev), array, dtype)
+    ``ops.peer_ref.q8_quantize_ref`` gives.  ``count`` (none: all) is the number of elements that are data;
+    the array's later elements lie in the window after them, up to the end of the count's last block."""
+    codes, exps = _p().peer_q8_quantize(int(dev), array, dtype, None if count is None else int(count))
     return codes, exps
 
 

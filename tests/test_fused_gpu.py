@@ -721,3 +721,195 @@ def test_embedding_backward_into_the_flat_slot(hip):
     used = torch.zeros(V, dtype=torch.bool, device="cuda")
     used[tok] = True
     assert not outs[0][~used].any()
+
+
+# -- non-finite and subnormal gradients through the optimizer ---------------------------------
+def _bad_values(gdtype):
+    """name -> (value, what the sum of squares must be): a NaN, an Inf, and 3e38, whose square overflows."""
+    big = torch.tensor(3.0e38, dtype=gdtype).item()
+    assert math.isfinite(big) and big > 2.0e38
+    return {"nan": (float("nan"), "nan"), "inf": (float("inf"), "inf"), "-inf": (float("-inf"), "inf"), "3e38": (big, "inf")}
+
+
+def _is(x, what):
+    return math.isnan(x) if what == "nan" else x == float("inf")
+
+
+@pytest.mark.parametrize("gdtype", [torch.bfloat16, torch.float32])
+def test_sum_of_squares_carries_nan_inf_and_overflow(hip, ternary, gdtype):
+    """One bad element in the first vector, inside the four-in-flight loop, in the tail loop and in the
+    ragged last stride of the 1024-block grid (the strides are 262144 vectors), and at the sizes 8 and
+    8 * 257: a NaN makes the sum NaN, an Inf or a square that overflows makes it +Inf, a NaN next to an
+    Inf makes it NaN; the step counter advances all the same.  A gradient of subnormals only, whose
+    squares all underflow, sums to exactly 0."""
+    x, _ = ternary
+    n, stride = x.numel(), 262144
+    assert n // 8 == 5 * stride + 777
+    g = x.to(gdtype)
+    spots = {n: [3, 8 * (2 * stride + 12345) + 7, 8 * (4 * stride + 999), 8 * (5 * stride + 776) + 7], 8: [0, 7], 8 * 257: [5, 8 * 255 + 7, 8 * 256]}
+    for name, (bad, what) in _bad_values(gdtype).items():
+        for k, where in spots.items():
+            for i in where:
+                old = g[i].item()
+                g[i] = bad
+                tick = torch.tensor([6.0], device="cuda")
+                parts = hip.sq_norm_parts(g[:k], tick)
+                assert _is(parts.sum().item(), what) and tick.item() == 7.0, (name, k, i)
+                assert int((~torch.isfinite(parts)).sum().item()) == 1  # one block saw it
+                assert _is(hip.sq_norm(g[:k]).item(), what), (name, k, i)
+                g[i] = old
+    for k, where in spots.items():  # a NaN and an Inf in one gradient: NaN
+        old = g[where[0]].item(), g[where[-1]].item()
+        g[where[0]], g[where[-1]] = float("inf"), float("nan")
+        assert math.isnan(hip.sq_norm(g[:k]).item()) and math.isnan(hip.sq_norm_parts(g[:k], None).sum().item())
+        g[where[0]], g[where[-1]] = float("nan"), float("-inf")
+        assert math.isnan(hip.sq_norm(g[:k]).item()) and math.isnan(hip.sq_norm_parts(g[:k], None).sum().item())
+        g[where[0]], g[where[-1]] = old
+    assert torch.equal(g, x.to(gdtype))
+    # subnormals only: bf16 0x0001 .. 0x007F, fp32 0x00000001 .. 0x007FFFFF, both signs
+    i = torch.arange(n, device="cuda")
+    if gdtype == torch.bfloat16:  # the sign bit as the most negative integer added to the magnitude
+        sub = ((i % 127 + 1) - (i & 1) * 0x8000).to(torch.int16).view(torch.bfloat16)
+    else:
+        sub = ((i * 2654435761 % 0x7FFFFF + 1) - (i & 1) * 0x80000000).to(torch.int32).view(torch.float32)
+    assert sub.float().abs().max().item() < 2.0 ** -126
+    for k in (8, 8 * 257, n):
+        tick = torch.tensor([1.0], device="cuda")
+        parts = hip.sq_norm_parts(sub[:k], tick)
+        assert not parts.any() and tick.item() == 2.0
+        assert hip.sq_norm(sub[:k]).item() == 0.0
+
+
+@pytest.mark.parametrize("bad", ["nan", "inf"])
+@pytest.mark.parametrize("gdtype", [torch.bfloat16, torch.float32])
+@pytest.mark.parametrize("n", [8 * 257, 1 << 18])
+def test_adamw_step_dev_follows_the_host_form_on_a_non_finite_norm(hip, n, gdtype, bad):
+    """Clip on, one NaN or one Inf in the gradient.  The host form gets the factor torch computes in
+    ``FlatAdamW.step``.  A NaN norm: the factor is NaN and every element of master, m, v and W is NaN in
+    both forms, so the event stays loud.  An Inf norm: the factor is exactly 0; where the gradient is
+    finite the forms agree within the bound of the fp32 ``powf`` of the bias corrections, where it is
+    Inf (Inf * 0) the elements are NaN in both."""
+    torch.manual_seed(11)
+    g = torch.randint(-3, 4, (n,), device="cuda").to(gdtype)
+    at = n // 2 + 3
+    g[at] = float(bad)
+    master = torch.randn(n, device="cuda")
+    st = dict(zip(_ADAMW_KEYS, (master, torch.randn(n, device="cuda").abs() * 0.01, torch.randn(n, device="cuda").abs() * 0.001,
+                                g, master.to(torch.bfloat16))))
+    ref = {k: x.clone() for k, x in st.items()}
+    lr, b1, b2, eps, wd, gs, t, clip = 1e-3, 0.9, 0.95, 1e-8, 0.1, 0.5, 3, 1.0
+    part = hip.sq_norm_parts(g, None)
+    hp_dev = torch.tensor([lr, b1, b2, eps, wd, gs, clip, 0.0], device="cuda")
+    hip.adamw_step_dev(st["master"], st["m"], st["v"], st["g"], st["w"], hp_dev, part, torch.tensor([float(t)], device="cuda"))
+    norm = part.sum().sqrt() * gs
+    factor = torch.clamp(clip / (norm + 1e-6), max=1.0) * torch.tensor(gs, dtype=torch.float32, device="cuda")
+    hp = torch.tensor([lr, b1, b2, eps, wd, 0.0, 1 - b1 ** t, 1 - b2 ** t], dtype=torch.float64).float().cuda()
+    hp[5:6].copy_(factor.reshape(1))
+    hip.adamw_step(ref["master"], ref["m"], ref["v"], ref["g"], ref["w"], hp)
+    if bad == "nan":
+        assert math.isnan(factor.item())
+        for k in ("master", "m", "v", "w"):
+            assert bool(torch.isnan(ref[k]).all()), ("host", k)
+            assert bool(torch.isnan(st[k]).all()), ("dev", k)
+        return
+    assert factor.item() == 0.0
+    hit = torch.isinf(g.float())
+    assert int(hit.sum().item()) == 1
+    for k in ("master", "m", "v", "w"):
+        assert torch.equal(torch.isnan(ref[k]), hit) and torch.equal(torch.isnan(st[k]), hit), k
+    for k in ("master", "m", "v"):
+        assert torch.allclose(st[k][~hit], ref[k][~hit], rtol=1e-4, atol=1e-6), k
+    assert torch.equal(st["w"][~hit], st["master"][~hit].to(torch.bfloat16))
+
+
+def _poison(g, where, value):
+    out = g.clone()
+    out[torch.tensor(where, device=g.device)] = value
+    return out
+
+
+def _assert_isolated(got, base, where, bad, what):
+    """``got`` (the run with ``bad`` at ``where``) against ``base`` (the run with 1.0 there): a NaN gradient
+    makes master, m, v and W NaN at its index; an Inf gradient makes m and v +Inf (they are sums with it)
+    and master and W NaN (Inf / Inf); every other element has the other run's bits."""
+    idx = torch.tensor(where, device="cuda")
+    hit = torch.zeros(base["master"].numel(), dtype=torch.bool, device="cuda")
+    hit[idx] = True
+    for k in ("master", "m", "v", "w"):
+        assert not bool(torch.isfinite(got[k][idx]).any()), (what, k)
+        if bad == "nan" or k in ("master", "w"):
+            assert bool(torch.isnan(got[k][idx]).all()), (what, k)
+        else:
+            assert bool((got[k][idx] == float("inf")).all()), (what, k)
+        assert bool(torch.isfinite(base[k]).all()), (what, k)
+        view = torch.int16 if got[k].dtype == torch.bfloat16 else torch.int32
+        assert torch.equal(got[k].view(view)[~hit], base[k].view(view)[~hit]), (what, k)
+
+
+@pytest.mark.parametrize("bad", ["nan", "inf"])
+@pytest.mark.parametrize("gdtype", [torch.bfloat16, torch.float32])
+@pytest.mark.parametrize("form", ["host", "dev"])
+def test_adamw_flat_isolates_one_bad_gradient_element(hip, form, gdtype, bad):
+    """Clip off, n = 8 * 257: a bad element at the first and at the last element of an 8-vector, in the first
+    vector, in the last vector of the first block and in the one vector of the second block."""
+    n = 8 * 257
+    where = [0, 8 * 100, 8 * 100 + 7, 8 * 255 + 7, 8 * 256, n - 1]
+    torch.manual_seed(5)
+    st = {"master": torch.randn(n, device="cuda"), "m": torch.randn(n, device="cuda").abs() * 0.01,
+          "v": torch.randn(n, device="cuda").abs() * 0.001, "g": torch.randn(n, device="cuda", dtype=gdtype)}
+    st["w"] = st["master"].to(torch.bfloat16)
+    b1, b2, tt = 0.9, 0.95, 3
+    runs = {}
+    for name, value in (("base", 1.0), ("bad", float(bad))):
+        run = {k: x.clone() for k, x in st.items()}
+        run["g"] = _poison(st["g"], where, value)
+        if form == "dev":
+            hp = torch.tensor([1e-3, b1, b2, 1e-8, 0.1, 0.5, -1.0, 0.0], device="cuda")
+            hip.adamw_step_dev(run["master"], run["m"], run["v"], run["g"], run["w"], hp, None, torch.tensor([float(tt)], device="cuda"))
+        else:
+            hp = torch.tensor([1e-3, b1, b2, 1e-8, 0.1, 0.5, 1 - b1 ** tt, 1 - b2 ** tt], device="cuda")
+            hip.adamw_step(run["master"], run["m"], run["v"], run["g"], run["w"], hp)
+        runs[name] = run
+    _assert_isolated(runs["bad"], runs["base"], where, bad, (form, gdtype))
+
+
+@pytest.mark.parametrize("bad", ["nan", "inf"])
+@pytest.mark.parametrize("gdtype", [torch.bfloat16, torch.float32])
+@pytest.mark.parametrize("dev,ahead", [(False, 1), (False, 2), (False, 4), (True, 1)])
+def test_adamw_step_t_isolates_one_bad_gradient_element_and_its_transpose(hip, dev, ahead, gdtype, bad):
+    """Clip off, the plan of ``_adamw_t_case``: a bad element at the first and last element of an 8-vector,
+    in the first and last row of a tile (and of the tile next to it), in the last column tile of a
+    matrix, and inside both ranges.  W^T is NaN exactly at the transposed positions."""
+    flat, st = _adamw_t_case(gdtype)
+    mats, tiles, ranges, maxr = flat.adamw_plan()
+    o = flat.offsets
+    rc = {"w1": [(0, 0), (0, 7), (63, 255), (64, 8), (191, 248)], "w2": [(0, 256), (63, 511)], "w3": [(63, 511), (128, 767), (255, 0)]}
+    where = [o[name] + r * flat.shapes[name][1] + c for name, cells in rc.items() for r, c in cells]
+    where += [o["a"] + 5, o["a"] + 127, o["b"], o["b"] + 63]
+    b1, b2, tt = 0.9, 0.95, 3
+    runs, wts = {}, {}
+    for name, value in (("base", 1.0), ("bad", float(bad))):
+        run = {k: x.clone() for k, x in st.items()}
+        run["g"] = _poison(st["g"], where, value)
+        wt = torch.zeros_like(flat.data_t)
+        if dev:
+            hp = torch.tensor([1e-3, b1, b2, 1e-8, 0.1, 0.5, -1.0, 0.0], device="cuda")
+            hip.adamw_step_t(run["master"], run["m"], run["v"], run["g"], run["w"], wt, hp, mats, tiles, ranges, maxr, None,
+                             torch.tensor([float(tt)], device="cuda"), 1)
+        else:
+            hp = torch.tensor([1e-3, b1, b2, 1e-8, 0.1, 0.5, 1 - b1 ** tt, 1 - b2 ** tt], device="cuda")
+            hip.adamw_step_t(run["master"], run["m"], run["v"], run["g"], run["w"], wt, hp, mats, tiles, ranges, maxr, None, None, ahead)
+        runs[name], wts[name] = run, wt
+    _assert_isolated(runs["bad"], runs["base"], where, bad, (dev, ahead, gdtype))
+    assert int(torch.isnan(wts["bad"]).sum().item()) == sum(len(c) for c in rc.values()) and not bool(torch.isnan(wts["base"]).any())
+    for name, cells in rc.items():
+        R, C = flat.shapes[name]
+        ot = flat.t_offsets[name]
+        wt_bad, wt_base = wts["bad"][ot:ot + R * C].view(C, R), wts["base"][ot:ot + R * C].view(C, R)
+        w_bad = runs["bad"]["w"][o[name]:o[name] + R * C].view(R, C)
+        assert torch.equal(wt_bad.view(torch.int16), w_bad.t().contiguous().view(torch.int16)), name
+        hit = torch.zeros(C, R, dtype=torch.bool, device="cuda")
+        for r, c in cells:
+            hit[c, r] = True
+        assert torch.equal(torch.isnan(wt_bad), hit), name
+        assert torch.equal(wt_bad.view(torch.int16)[~hit], wt_base.view(torch.int16)[~hit]), name

@@ -4,7 +4,7 @@ catch it (a mutation-testing pass; README "Mutation testing of the control plane
 
     python tools/mutants.py                  # every group
     python tools/mutants.py --only ledger    # one group (ledger, cache, plugin, informer, rbac, numa, cordon, objective, dp, guard,
-                                             # banding, gaia, repartition, extender, contract)
+                                             # banding, gaia, repartition, extender, contract, peer_ref)
 
 Each mutant replaces one line (or a few) of a source file, runs the group's tests with pytest-xdist,
 and restores the file whatever happens.  ``CAUGHT`` = some test failed, ``SURVIVED`` = the tests did
@@ -50,6 +50,7 @@ PLUGIN_MAIN = "gpu_topology_on_k8s_amd/deviceplugin/__main__.py"
 KUBELET = "gpu_topology_on_k8s_amd/deviceplugin/kubelet.py"
 CORE = "gpu_topology_on_k8s_amd/placement/core.py"
 ENGINE = "csrc/placement/engine.cpp"
+PEER_REF = "gpu_topology_on_k8s_amd/ops/peer_ref.py"
 
 MUTANTS: List[Mutant] = [
     # allocation ledger (cross-extender bind safety)
@@ -230,6 +231,14 @@ MUTANTS: List[Mutant] = [
     Mutant("extender", SCHED, "        rank = obj + node_packing_term(free, k, t.n, self.cfg.policy)", "        rank = obj"),
     Mutant("extender", SCHED, "                if dev_mem <= 0:", "                if False:"),
     Mutant("extender", SCHED, '        if s > 1 and unit != "slice":', "        if False:"),
+    # the K7 references on non-finite values (CPU only)
+    Mutant("peer_ref", PEER_REF, "    mag[(c & 0x7F) == 0x7F] = np.nan", "    mag[(c & 0x7F) == 0x7F] = 0.0"),
+    Mutant("peer_ref", PEER_REF, "    mag = np.where(np.isnan(full), np.float32(0), np.abs(full))  # a NaN takes no part in the amax",
+           "    mag = np.abs(full)"),
+    Mutant("peer_ref", PEER_REF, "    return np.where(nan, ((b >> np.uint32(16)) | np.uint32(0x0040)).astype(np.uint16), r)", "    return r"),
+    Mutant("peer_ref", PEER_REF, "    code = np.where(special, 0x7F, np.minimum(code, 0x7E))  # no finite element reaches the minimum",
+           "    code = np.minimum(code, 0x7E)"),
+    Mutant("peer_ref", PEER_REF, "    e = np.where(np.isinf(amax), Q8_EXP_MAX, e).astype(np.int32)", "    e = e.astype(np.int32)"),
 ]
 
 TESTS = {
@@ -254,6 +263,7 @@ TESTS = {
     "extender": ["tests/test_shares.py", "tests/test_extender.py", "tests/test_cluster_features.py"],
     "contract": ["tests/test_k8s.py", "tests/test_extender.py", "tests/test_extender_fuzz.py", "tests/test_extender_ledger.py",
                  "tests/test_deviceplugin.py", "tests/test_cluster_features.py"],
+    "peer_ref": ["tests/test_peer_nonfinite_cpu.py"],
 }
 
 GUARD_TARGETS = "vgpu_guard,vgpu_selftest_asan,vgpu_selftest_tsan"
