@@ -2,7 +2,7 @@
 """K7 peer all-reduce next to its comparators, on given members and sizes, as one JSON document:
 
     python bench/peer_allreduce_bench.py [--members 0,0,0,0] [--sizes-mib 1,4,16,64,256,1024]
-                                         [--dtype bf16] [--iters 5] [--wire native|fp8|both] [--out FILE] [--md FILE]
+                                         [--dtype bf16] [--iters 5] [--wire native|fp8|both|fp8x2|all] [--out FILE] [--md FILE]
 
 Per size N (bytes per member):
   * the peer all-reduce under both algorithms (algBW, busBW, and the bytes each member moves:
@@ -14,6 +14,9 @@ Per size N (bytes per member):
 codes with a scale per 32 elements, the members read that) right after the native one at every size and
 algorithm, in the same process, and reports it under ``<algo>_fp8`` with the bytes its two kernels move
 and the rate each reaches alone on member 0.
+``--wire fp8x2`` measures the two-shot whose gather phase is packed too (``twoshot_fp8x2``: quantize, repack,
+unpack), and ``--wire all`` the two-shot on the native wire, then on ``fp8``, then on ``fp8x2`` at every size,
+interleaved in one process, with the three kernels of ``fp8x2`` alone on member 0.
 Members that repeat a device give HBM rates of that one GPU, not xGMI rates.
 """
 import argparse
@@ -28,20 +31,45 @@ from gpu_topology_on_k8s_amd.ops import probe  # noqa: E402
 ELEM = {"bf16": 2, "fp32": 4}
 
 
-def member_bytes(algo: str, k: int, n: int, wire: str = "native", elem: int = 2) -> dict:
+def member_bytes(algo: str, k: int, n: int, wire: str = "native", elem: int = 2, out_elem: int = 0) -> dict:
     """Bytes one member reads and writes in one all-reduce of n bytes of ``elem``-byte elements.
 
     On the fp8 wire 32 elements pack into 33 bytes, P = 33 / (32 elem) x n per member.  The quantize
     reads n and writes P; phase 1 reads k x P (one-shot) or k x P / k = P (two-shot) and writes n or
-    n / k; phase 2 of a two-shot is the native one: it reads and writes (k - 1) / k x n."""
+    n / k; phase 2 of a two-shot is the native one: it reads and writes (k - 1) / k x n.
+
+    On the fp8x2 wire (two-shot only) the quantize is the same; the repack reads k x P / k = P and writes
+    P / k; the unpack reads all k slices, P, and writes the whole result, n x ``out_elem`` / ``elem``
+    (``out_elem`` 0: the input's)."""
     if wire == "native":
         return {"read": k * n if algo == "oneshot" else (2 * k - 1) * n // k, "written": n}
     packed = n // elem * 33 // 32
     quantize = {"read": n, "written": packed}
+    if wire == "fp8x2":
+        if algo != "twoshot":
+            raise ValueError("the fp8x2 wire is a two-shot")
+        repack = {"read": packed, "written": packed // k}
+        unpack = {"read": packed, "written": n * (out_elem or elem) // elem}
+        return {"read": n + 2 * packed, "written": packed + packed // k + unpack["written"], "quantize": quantize, "sum": repack,
+                "gather": unpack}
     total = (k if algo == "oneshot" else 1) * packed
     phase1 = {"read": total, "written": n if algo == "oneshot" else n // k}
     gather = 0 if algo == "oneshot" else (k - 1) * n // k
     return {"read": n + total + gather, "written": packed + n, "quantize": quantize, "sum": phase1}
+
+
+def key(algo: str, wire: str) -> str:
+    return algo if wire == "native" else f"{algo}_{wire}"
+
+
+def plan(wire: str):
+    """The (algorithm, wire) points of one size, in the order they are measured: with ``both`` the fp8 wire
+    right after the native one under each algorithm, with ``all`` the two-shot on the three wires."""
+    if wire == "fp8x2":
+        return [("twoshot", "fp8x2")]
+    if wire == "all":
+        return [("twoshot", w) for w in ("native", "fp8", "fp8x2")]
+    return [(a, w) for a in probe.PEER_ALGOS for w in ("native", "fp8") if wire in (w, "both")]
 
 
 def point(devs, n, dtype, algo, iters, warmup, wire):
@@ -53,8 +81,8 @@ def point(devs, n, dtype, algo, iters, warmup, wire):
          "wrong": r["wrong"], "member_read_bytes": mv["read"], "member_written_bytes": mv["written"],
          "member_read_gbps": mv["read"] / secs / 1e9,
          "member_traffic_gbps": (mv["read"] + mv["written"]) / secs / 1e9}
-    if wire == "fp8":  # member 0's two kernels alone on the device: the bytes each moves over its own time
-        for name in ("quantize", "sum"):
+    if wire != "native":  # member 0's kernels alone on the device: the bytes each moves over its own time
+        for name in ("quantize", "sum") + (("gather",) if wire == "fp8x2" else ()):
             b = mv[name]["read"] + mv[name]["written"]
             p[name] = {"time_us": r[name + "_us"], "bytes": b, "gbps": b / (r[name + "_us"] * 1e-6) / 1e9}
     return p
@@ -66,13 +94,10 @@ def measure(devs, sizes, dtype, iters, warmup, wire="native"):
     rows = []
     for n in sizes:
         row = {"bytes": n}
-        for algo in probe.PEER_ALGOS:  # with both wires, the fp8 one right after the native one
-            if wire != "fp8":
-                row[algo] = point(devs, n, dtype, algo, iters, warmup, "native")
-            if wire != "native":
-                row[algo + "_fp8"] = point(devs, n, dtype, algo, iters, warmup, "fp8")
-        algos = [a for a in probe.PEER_ALGOS if a in row] or [a + "_fp8" for a in probe.PEER_ALGOS]
-        row["faster"] = min(algos, key=lambda a: row[a]["time_us"])
+        for algo, w in plan(wire):
+            row[key(algo, w)] = point(devs, n, dtype, algo, iters, warmup, w)
+        first = plan(wire)[0][1]  # the algorithms are compared on one wire, the first one measured
+        row["faster"] = min((key(a, w) for a, w in plan(wire) if w == first), key=lambda a: row[a]["time_us"])
         per_peer = max(16, member_bytes("twoshot", k, n)["read"] // (k - 1) // 16 * 16)
         r6 = probe.ring_bw(devs, "all", per_peer, iters, warmup)
         row["k6_all"] = {"bytes_per_peer": per_peer, "member_read_bytes": per_peer * (k - 1), "ok": r6["ok"],
@@ -84,7 +109,8 @@ def measure(devs, sizes, dtype, iters, warmup, wire="native"):
             row["rccl"] = {k_: p[k_] for k_ in ("time_us", "algbw_gbps", "busbw_gbps", "wrong")}
         rows.append(row)
         print(json.dumps(row), file=sys.stderr, flush=True)
-    crossover = next((r["bytes"] for i, r in enumerate(rows) if all(q["faster"].startswith("twoshot") for q in rows[i:])), None)
+    both_algos = len({a for a, _ in plan(wire)}) > 1  # fp8x2 and all measure the two-shot alone: no crossover to report
+    crossover = next((r["bytes"] for i, r in enumerate(rows) if both_algos and all(q["faster"].startswith("twoshot") for q in rows[i:])), None)
     return {"members": list(devs), "k": k, "distinct_devices": distinct, "dtype": dtype, "iters": iters, "warmup": warmup,
             "wire": wire, "sizes": rows, "twoshot_faster_from_bytes": crossover}
 
@@ -110,9 +136,35 @@ def markdown_fp8(res) -> str:
     return "\n".join(out)
 
 
+def markdown_fp8x2(res) -> str:
+    """The two-shot on the fp8x2 wire, next to the native and the fp8 one where they were measured: one line per size."""
+    mib = lambda b: f"{b / 2**20:.1f}"  # noqa: E731
+    others = [w for w in ("native", "fp8") if res["wire"] == "all"]
+    head = ["N per member MiB"] + [f"{w} us" for w in others] + ["fp8x2 us", "fp8x2 algBW"] + [f"fp8x2 / {w} time" for w in others]
+    head += [f"{w} MiB read + written" for w in others + ["fp8x2"]]
+    head += [f"{name} {unit}" for name in ("quantize", "repack", "unpack") for unit in ("us", "GB/s")]
+    head += (["fp8 sum us", "fp8 sum GB/s"] if others else []) + ["wrong"]  # the sum kernel in the repack's position
+    out = [f"### fp8x2 wire, two-shot, members {res['members']} (k = {res['k']}), {res['dtype']}, {res['iters']} timed rounds", "",
+           "| " + " | ".join(head) + " |", "|" + "---|" * len(head)]
+    for r in res["sizes"]:
+        x, o = r["twoshot_fp8x2"], [r[key("twoshot", w)] for w in others]
+        cells = [mib(r["bytes"])] + [f"{p['time_us']:.1f}" for p in o] + [f"{x['time_us']:.1f}", f"{x['algbw_gbps']:.1f}"]
+        cells += [f"{x['time_us'] / p['time_us']:.2f}" for p in o]
+        cells += [f"{mib(p['member_read_bytes'])} + {mib(p['member_written_bytes'])}" for p in o + [x]]
+        for name in ("quantize", "sum", "gather"):
+            cells += [f"{x[name]['time_us']:.1f}", f"{x[name]['gbps']:.0f}"]
+        if others:
+            cells += [f"{o[1]['sum']['time_us']:.1f}", f"{o[1]['sum']['gbps']:.0f}"]
+        out.append("| " + " | ".join(cells + [str(x["wrong"] + sum(p["wrong"] for p in o))]) + " |")
+    out.append("")
+    return "\n".join(out)
+
+
 def markdown(res) -> str:
     if res["wire"] == "fp8":
         return markdown_fp8(res)
+    if res["wire"] in ("fp8x2", "all"):
+        return markdown_fp8x2(res)
     k = res["k"]
     out = [f"### members {res['members']} (k = {k}), {res['dtype']}, {res['iters']} timed rounds", "",
            "| N per member | oneshot algBW | oneshot member read + written | twoshot algBW | twoshot member read + written | "
@@ -136,8 +188,9 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=sorted(ELEM))
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--wire", default="native", choices=["native", "fp8", "both"],
-                    help="fp8: the block-scaled e4m3 wire alone; both: it next to the native wire, interleaved")
+    ap.add_argument("--wire", default="native", choices=["native", "fp8", "both", "fp8x2", "all"],
+                    help="fp8: the block-scaled e4m3 wire alone; both: it next to the native wire, interleaved; fp8x2: the "
+                         "two-shot with its gather phase packed too; all: the two-shot on native, fp8 and fp8x2, interleaved")
     ap.add_argument("--out", default="", help="also write the JSON document here")
     ap.add_argument("--md", default="", help="also write the tables as Markdown here")
     a = ap.parse_args()
@@ -153,7 +206,7 @@ def main():
             os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
             with open(path, "w") as f:
                 f.write(body)
-    measured = [al + sfx for al in probe.PEER_ALGOS for sfx in ("", "_fp8")]
+    measured = [al + sfx for al in probe.PEER_ALGOS for sfx in ("", "_fp8", "_fp8x2")]
     return 1 if any(r[al]["wrong"] for run in doc["runs"] for r in run["sizes"] for al in measured if al in r) else 0
 
 

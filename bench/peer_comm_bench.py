@@ -2,7 +2,7 @@
 """The peer communicator's thread-rank all_reduce next to the in-process driver's, as one JSON document:
 
     python bench/peer_comm_bench.py [--members 0,0,0,0] [--sizes-mib 1,4,16,64,256] [--dtype bf16]
-                                    [--iters 20] [--warmup 2] [--wire native|fp8] [--out FILE] [--md FILE]
+                                    [--iters 20] [--warmup 2] [--wire native|fp8|fp8x2] [--out FILE] [--md FILE]
 
 Both run the same K7 kernels on the same members at the same count, in one process:
   * thread ranks (``PeerComm(backend="device")``, one thread per member): host time per ``all_reduce``
@@ -14,7 +14,7 @@ Per size and algorithm the two are measured alternately, ``--reps`` times each, 
 repetition of each is reported.  Their ratio is the price of host-synchronous ordering: two store round
 trips and two (two-shot: three) stream synchronisations per call.  Members that repeat a device give
 HBM rates of that one GPU, not xGMI rates.  ``--wire fp8`` runs both on the fp8 wire: every rank packs its
-window first and the ranks read the packed forms.
+window first and the ranks read the packed forms; ``--wire fp8x2`` the two-shot alone, its gather phase packed too.
 """
 import argparse
 import json
@@ -26,7 +26,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from gpu_topology_on_k8s_amd.ops import probe  # noqa: E402
-from gpu_topology_on_k8s_amd.ops.peer_ref import Q8_BLOCK, allreduce_q8_ref, allreduce_ref, q8_blocks  # noqa: E402
+from gpu_topology_on_k8s_amd.ops.peer_ref import Q8_BLOCK, q8_blocks  # noqa: E402
 from gpu_topology_on_k8s_amd.parallel import peer_comm as pc  # noqa: E402
 
 ELEM = {"bf16": 2, "fp32": 4}
@@ -34,7 +34,8 @@ ELEM = {"bf16": 2, "fp32": 4}
 
 def measure(devs, sizes, dtype, iters, warmup, reps, wire="native"):
     k, elem = len(devs), ELEM[dtype]
-    fp8 = wire == "fp8"
+    fp8 = wire in ("fp8", "fp8x2")
+    algos = ("twoshot",) if wire == "fp8x2" else pc.ALGOS  # the one algorithm with a gather phase to pack
     counts = [max(1, n // elem) for n in sizes]
     once = pc._Once()
     driver = {}  # (count, algo, rep) -> the driver's result, measured by rank 0 while the other ranks wait
@@ -43,9 +44,9 @@ def measure(devs, sizes, dtype, iters, warmup, reps, wire="native"):
         rows = []
         for count in counts:
             xs = once.get(("in", count), lambda: [pc.case_input(0, 0, p, count, dtype) for p in range(k)], lambda o: o[1] == count)
-            ref = once.get(("ref", count), lambda: (allreduce_q8_ref if fp8 else allreduce_ref)(xs, dtype), lambda o: o[1] == count)
+            ref = once.get(("ref", count), lambda: pc._WIRE_REF[wire](xs, dtype), lambda o: o[1] == count)
             comm.write(xs[comm.rank])
-            for algo in pc.ALGOS:
+            for algo in algos:
                 for rep in range(reps):
                     secs, in_barriers = pc.timed_all_reduce(comm, count, dtype, algo, iters, warmup, wire)
                     wrong = int(np.count_nonzero(pc._bits(comm.read(0, count, dtype)) != pc._bits(ref))) if rep == 0 else 0
@@ -61,7 +62,7 @@ def measure(devs, sizes, dtype, iters, warmup, reps, wire="native"):
     out = []
     for count in counts:
         row = {"bytes": count * elem, "count": count}
-        for algo in pc.ALGOS:
+        for algo in algos:
             mine = [[r for r in rank_rows if r[:2] == (count, algo)] for rank_rows in res]
             t_reps = [max(rows[rep][3] for rows in mine) * 1e6 for rep in range(reps)]  # the slowest rank of each repetition
             best = min(range(reps), key=lambda i: t_reps[i])
@@ -85,7 +86,7 @@ def markdown(res) -> str:
            "| N per member | algorithm | thread ranks us / call | of it in barriers | thread algBW | driver us / round | driver algBW | thread / driver |",
            "|---|---|---|---|---|---|---|---|"]
     for r in res["sizes"]:
-        for algo in pc.ALGOS:
+        for algo in (al for al in pc.ALGOS if al in r):
             a = r[algo]
             out.append(f"| {r['bytes'] / 2**20:.1f} MiB | {algo} | {a['thread_time_us']:.1f} | {a['thread_barrier_us']:.1f} | {a['thread_algbw_gbps']:.1f} "
                        f"| {a['driver_time_us']:.1f} | {a['driver_algbw_gbps']:.1f} | {a['thread_over_driver']:.2f} |")
@@ -100,7 +101,8 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=sorted(ELEM))
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--wire", default="native", choices=["native", "fp8"], help="fp8: the block-scaled e4m3 wire of csrc/probe/peer_q8.h")
+    ap.add_argument("--wire", default="native", choices=["native", "fp8", "fp8x2"],
+                    help="fp8: the block-scaled e4m3 wire of csrc/probe/peer_q8.h; fp8x2: the two-shot with its gather phase packed too")
     ap.add_argument("--reps", type=int, default=2, help="alternated repetitions of each measurement")
     ap.add_argument("--out", default="", help="also write the JSON document here")
     ap.add_argument("--md", default="", help="also write the tables as Markdown here")
@@ -117,7 +119,8 @@ def main():
             os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
             with open(path, "w") as f:
                 f.write(body)
-    return 1 if any(r[al][w] for run in doc["runs"] for r in run["sizes"] for al in pc.ALGOS for w in ("thread_wrong", "driver_wrong")) else 0
+    return 1 if any(r[al][w] for run in doc["runs"] for r in run["sizes"] for al in pc.ALGOS if al in r
+                    for w in ("thread_wrong", "driver_wrong")) else 0
 
 
 if __name__ == "__main__":

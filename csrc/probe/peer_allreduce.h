@@ -143,9 +143,12 @@ __global__ __launch_bounds__(gtk::kStreamBlock) void peer_allgather_kernel(Slice
 }
 
 // Test inputs: element i of the member with seed `seed` is a small integer in [-8, 7], so a sum over
-// up to 16 members lies in [-128, 112] and is exact in bf16 as in fp32.
-__device__ __forceinline__ int peer_pattern(size_t i, unsigned int seed) {
-  return (int)((((unsigned int)i * 2654435761u + seed * 40503u) >> 16) & 15u) - 8;
+// up to 16 members lies in [-128, 112] and is exact in bf16 as in fp32.  `narrow` keeps the integer's
+// lowest bit alone, a value in {-1, 0}: a sum over up to 16 members is then an integer in [-16, 0], which
+// has at most four significant bits and so survives a packing into e4m3 under any block scale.
+__device__ __forceinline__ int peer_pattern(size_t i, unsigned int seed, bool narrow = false) {
+  const int p = (int)((((unsigned int)i * 2654435761u + seed * 40503u) >> 16) & 15u) - 8;
+  return narrow ? -(p & 1) : p;
 }
 __device__ __forceinline__ void peer_put(float* p, float x) { *p = x; }
 __device__ __forceinline__ void peer_put(uint16_t* p, float x) { *p = (uint16_t)(__float_as_uint(x) >> 16); }
@@ -155,10 +158,10 @@ __device__ __forceinline__ float peer_get(const uint16_t* p) { return __uint_as_
 // p[0, count) = pattern(seed); p[count, padded) = 0.
 template <typename T>
 __global__ __launch_bounds__(gtk::kStreamBlock) void peer_fill_kernel(T* __restrict__ p, size_t count, size_t padded,
-                                                                      unsigned int seed) {
+                                                                      unsigned int seed, bool narrow = false) {
   for (size_t i = (size_t)blockIdx.x * gtk::kStreamBlock + threadIdx.x; i < padded;
        i += (size_t)gridDim.x * gtk::kStreamBlock)
-    peer_put(p + i, i < count ? (float)peer_pattern(i, seed) : 0.f);
+    peer_put(p + i, i < count ? (float)peer_pattern(i, seed, narrow) : 0.f);
 }
 
 struct SeedSet {
@@ -170,13 +173,13 @@ struct SeedSet {
 template <typename T>
 __global__ __launch_bounds__(gtk::kStreamBlock) void peer_check_kernel(const T* __restrict__ p, size_t count,
                                                                        size_t padded, SeedSet seeds, int k,
-                                                                       unsigned long long* bad) {
+                                                                       unsigned long long* bad, bool narrow = false) {
   unsigned long long local = 0;
   for (size_t i = (size_t)blockIdx.x * gtk::kStreamBlock + threadIdx.x; i < padded;
        i += (size_t)gridDim.x * gtk::kStreamBlock) {
     int want = 0;
     if (i < count)
-      for (int m = 0; m < k; ++m) want += peer_pattern(i, seeds.s[m]);
+      for (int m = 0; m < k; ++m) want += peer_pattern(i, seeds.s[m], narrow);
     local += (peer_get(p + i) != (float)want);
   }
   if (local) atomicAdd(bad, local);

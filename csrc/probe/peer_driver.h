@@ -17,6 +17,12 @@
 //            and phase 2 is unchanged.  eq[m] follows m's quantize and every member's phase 1 waits for
 //            all of them; e1[m] follows m's phase 1 in one-shot too, and every member's next quantize
 //            waits for all of them, since phase 1 of p still reads the packed buffer m then overwrites.
+//   wire fp8x2: a two-shot on the fp8 wire whose phase 1 packs its sums again into member m's second packed
+//            buffer (peer_q8_repack_kernel) and whose phase 2 unpacks all k slices, m's own included, from
+//            those buffers into out[m] (peer_q8_unpack_kernel): no member reads another's `out`.  The events
+//            are the two-shot's: the e2 wait before phase 1 holds back the overwrite of the second packed
+//            buffer m until every member's last phase 2 has read it, as it held back the overwrite of slice m
+//            of out[m]; the e1 wait before phase 2 lets a slice be read once its owner has packed it.
 #pragma once
 #include "peer_allreduce.h"
 #include "peer_q8.h"
@@ -115,9 +121,41 @@ void launch_peer_q8_quantize(bool in_bf16, const u32x4* win, u32x4* packed, size
   HIP_CHECK(hipGetLastError());
 }
 
-bool peer_wire_fp8(const std::string& wire) {
-  if (wire != "native" && wire != "fp8") throw std::invalid_argument("wire must be native|fp8");
-  return wire == "fp8";
+// The fp8x2 wire's two launches.  The repack keeps the sum's member buckets and U: its loads are the sum's,
+// and where the sum narrows and stores sixteen results it scales and converts them in place.
+void launch_peer_q8_repack(const SrcSet& packed, int k, size_t exp_vec, size_t b0, size_t b1, u32x4* packed_out, float scale,
+                           int grid, hipStream_t s) {
+  const dim3 g(grid), b(kBlock);
+  if (k <= 2)
+    peer_q8_repack_kernel<2, 4><<<g, b, 0, s>>>(packed, k, exp_vec, b0, b1, packed_out, scale);
+  else if (k <= 4)
+    peer_q8_repack_kernel<4, 4><<<g, b, 0, s>>>(packed, k, exp_vec, b0, b1, packed_out, scale);
+  else if (k <= 8)
+    peer_q8_repack_kernel<8, 2><<<g, b, 0, s>>>(packed, k, exp_vec, b0, b1, packed_out, scale);
+  else
+    peer_q8_repack_kernel<16, 1><<<g, b, 0, s>>>(packed, k, exp_vec, b0, b1, packed_out, scale);
+  HIP_CHECK(hipGetLastError());
+}
+
+// `sl` holds blocks, not vectors: slice p is blocks [first, first + count) of rank p's second packed buffer.
+void launch_peer_q8_unpack(bool out_bf16, const SliceSet& sl, int nsrc, size_t exp_vec, u32x4* dst, int grid, hipStream_t s) {
+  if (out_bf16)
+    peer_q8_unpack_kernel<uint16_t><<<dim3(grid), dim3(kBlock), 0, s>>>(sl, nsrc, exp_vec, dst);
+  else
+    peer_q8_unpack_kernel<float><<<dim3(grid), dim3(kBlock), 0, s>>>(sl, nsrc, exp_vec, dst);
+  HIP_CHECK(hipGetLastError());
+}
+
+// The wire of a call: native, fp8 (phase 1 reads packed buffers) or fp8x2 (phase 2 of a two-shot does too).
+struct PeerWire {
+  bool fp8 = false, x2 = false;
+};
+
+PeerWire peer_wire(const std::string& wire, const std::string& algo) {
+  if (wire != "native" && wire != "fp8" && wire != "fp8x2") throw std::invalid_argument("wire must be native|fp8|fp8x2");
+  if (wire == "fp8x2" && algo == "oneshot")
+    throw std::invalid_argument("wire fp8x2 packs the gather phase of a twoshot: a oneshot has none");
+  return PeerWire{wire != "native", wire == "fp8x2"};
 }
 
 // Blocks of a reduce of `n_vec` vectors on a device of `cus` CUs that `share` members split: no more
@@ -155,11 +193,14 @@ struct PeerAllreduce {
   PeerTypes types;
   float scale = 1.0f;
   bool fp8 = false;                 // the wire: members read each other's packed buffers, not their `in`
+  bool x2 = false;                  // fp8x2: phase 2 reads the members' second packed buffers, not their `out`
   size_t count = 0, n_vec = 0;      // n_vec: vectors of an `in`
   size_t n_blocks = 0;              // fp8: blocks of 32 elements, and `out` holds whole blocks
   std::vector<std::unique_ptr<DevBuf>> in[2], out;  // in[set][m]: rounds alternate between the sets
   std::vector<std::unique_ptr<DevBuf>> packed;      // fp8: packed[m], member m's `in` of the current round
+  std::vector<std::unique_ptr<DevBuf>> packed_out;  // fp8x2: packed_out[m], slice m of the round's sum, packed by m
   SrcSet srcs[2]{}, packs{};
+  SliceSet unpack_set{};            // fp8x2: every member's phase 2, slice p (blocks) of packed_out[p] for every p
   std::vector<PeerSlice> plan;      // phase 1 of a two-shot: vectors of an `in`; fp8: blocks
   std::vector<SliceSet> gather;  // member m's phase 2: slice p of out[p], every p != m
   std::vector<int> reduce_grid, gather_grid_, quantize_grid;
@@ -176,10 +217,10 @@ struct PeerAllreduce {
   }
 
   PeerAllreduce(const std::vector<int>& devs_, size_t count_, PeerTypes types_, const std::string& algo, int nsets_,
-                int blocks_per_cu, float scale_ = 1.0f, bool fp8_ = false)
-      : devs(devs_), k((int)devs_.size()), nsets(nsets_), twoshot(algo == "twoshot"), types(types_), scale(scale_), fp8(fp8_),
-        count(count_), n_vec((count_ * types_.in_elem() + 15) / 16), n_blocks((count_ + kQ8Block - 1) / kQ8Block),
-        plan(peer_slices(fp8_ ? n_blocks : n_vec, k)), gather(k), reduce_grid(k), gather_grid_(k), quantize_grid(k),
+                int blocks_per_cu, float scale_ = 1.0f, PeerWire wire = PeerWire{})
+      : devs(devs_), k((int)devs_.size()), nsets(nsets_), twoshot(algo == "twoshot"), types(types_), scale(scale_), fp8(wire.fp8),
+        x2(wire.x2), count(count_), n_vec((count_ * types_.in_elem() + 15) / 16), n_blocks((count_ + kQ8Block - 1) / kQ8Block),
+        plan(peer_slices(wire.fp8 ? n_blocks : n_vec, k)), gather(k), reduce_grid(k), gather_grid_(k), quantize_grid(k),
         e1(k, nullptr), e2(k, nullptr), eq(k, nullptr) {
     for (int m = 0; m < k; ++m)
       for (int p = 0; p < k; ++p) enable_peer(devs[m], devs[p]);
@@ -197,6 +238,12 @@ struct PeerAllreduce {
         packed.emplace_back(new DevBuf(devs[m], q8_packed_vecs(n_blocks) * 16));
         packs.p[m] = reinterpret_cast<const u32x4*>(packed[m]->p);
       }
+      if (x2) {
+        packed_out.emplace_back(new DevBuf(devs[m], q8_packed_vecs(n_blocks) * 16));
+        unpack_set.p[m] = reinterpret_cast<const u32x4*>(packed_out[m]->p);
+        unpack_set.first[m] = plan[m].first;
+        unpack_set.count[m] = plan[m].count;
+      }
       out.emplace_back(new DevBuf(devs[m], out_vec * 16));
       outs[m] = reinterpret_cast<const u32x4*>(out[m]->p);
       out_plan[m] = PeerSlice{plan[m].first * per_unit, plan[m].count * per_unit};
@@ -207,7 +254,7 @@ struct PeerAllreduce {
         const size_t units = twoshot ? plan[m].count : (fp8 ? n_blocks : n_vec);
         reduce_grid[m] = peer_reduce_grid(num_cus(devs[m]), blocks_per_cu, share, fp8 ? 2 * units : units);
         quantize_grid[m] = peer_reduce_grid(num_cus(devs[m]), blocks_per_cu, share, n_blocks * 64 / types.in_elem());
-        gather_grid_[m] = gather_grid(devs[m], blocks_per_cu, k - 1, share);
+        gather_grid_[m] = gather_grid(devs[m], blocks_per_cu, x2 ? k : k - 1, share);
         gather[m] = peer_gather_slices(outs, out_plan, m);
         DeviceGuard g(devs[m]);
         ts.emplace_back(new TimedStream());
@@ -230,7 +277,10 @@ struct PeerAllreduce {
   void reduce(int m, int set, size_t v0, size_t v1) {
     if (v0 == v1) return;
     u32x4* dst = reinterpret_cast<u32x4*>(out[m]->p);
-    if (fp8)
+    if (x2)
+      launch_peer_q8_repack(packs, k, q8_exp_vec(n_blocks), v0, v1, reinterpret_cast<u32x4*>(packed_out[m]->p), scale,
+                            reduce_grid[m], ts[m]->s);
+    else if (fp8)
       launch_peer_q8_sum(types.out_bf16, packs, k, q8_exp_vec(n_blocks), v0, v1, dst, scale, reduce_grid[m], ts[m]->s);
     else
       launch_peer_reduce(types, srcs[set], k, v0, v1, dst, scale, reduce_grid[m], ts[m]->s);
@@ -239,6 +289,15 @@ struct PeerAllreduce {
   void quantize(int m, int set) {
     launch_peer_q8_quantize(types.in_bf16, srcs[set].p[m], reinterpret_cast<u32x4*>(packed[m]->p), q8_exp_vec(n_blocks), 0,
                             n_blocks, count, quantize_grid[m], ts[m]->s);
+  }
+
+  // Phase 2 of member m: the other members' slices of their `out`; fp8x2: every slice of the second packed buffers.
+  void gather_phase(int m) {
+    u32x4* dst = reinterpret_cast<u32x4*>(out[m]->p);
+    if (x2)
+      launch_peer_q8_unpack(types.out_bf16, unpack_set, k, q8_exp_vec(n_blocks), dst, gather_grid_[m], ts[m]->s);
+    else
+      launch_peer_gather(gather[m], k - 1, dst, gather_grid_[m], ts[m]->s);
   }
 
   // One all-reduce of input set `set`, enqueued on every member's stream.  Every e1 / e2 is recorded
@@ -269,22 +328,23 @@ struct PeerAllreduce {
     for (int m = 0; twoshot && m < k; ++m) {
       DeviceGuard g(devs[m]);
       wait_others(m, e1);
-      launch_peer_gather(gather[m], k - 1, (u32x4*)out[m]->p, gather_grid_[m], ts[m]->s);
+      gather_phase(m);
       HIP_CHECK(hipEventRecord(e2[m], ts[m]->s));
     }
     ++rounds_done;
   }
 
-  // in[set][m] = pattern(seed_of(set, m)), padding zero.
+  // in[set][m] = pattern(seed_of(set, m)), padding zero.  fp8x2 narrows the pattern: the sum of k patterns in
+  // [-8, 7] needs more than the 4 bits a second packing keeps, a sum of values in {-1, 0} does not.
   static unsigned int seed_of(int set, int m) { return 0x243f6a88u ^ (unsigned)(set * 0x9e3779b9u) ^ (unsigned)(m * 7919 + 1); }
   void fill(int set) {
     for (int m = 0; m < k; ++m) {
       DeviceGuard g(devs[m]);
       const dim3 grid(num_cus(devs[m]) * 4), block(kBlock);
       if (types.in_bf16)
-        peer_fill_kernel<uint16_t><<<grid, block>>>((uint16_t*)in[set][m]->p, count, padded(), seed_of(set, m));
+        peer_fill_kernel<uint16_t><<<grid, block>>>((uint16_t*)in[set][m]->p, count, padded(), seed_of(set, m), x2);
       else
-        peer_fill_kernel<float><<<grid, block>>>((float*)in[set][m]->p, count, padded(), seed_of(set, m));
+        peer_fill_kernel<float><<<grid, block>>>((float*)in[set][m]->p, count, padded(), seed_of(set, m), x2);
       HIP_CHECK(hipGetLastError());
       HIP_CHECK(hipDeviceSynchronize());
     }
@@ -299,9 +359,9 @@ struct PeerAllreduce {
       total += count_on_device(devs[m], [&](unsigned long long* bad) {
         const dim3 grid(num_cus(devs[m]) * kBlocksPerCU), block(kBlock);
         if (types.in_bf16)
-          peer_check_kernel<uint16_t><<<grid, block>>>((const uint16_t*)out[m]->p, count, padded(), seeds, k, bad);
+          peer_check_kernel<uint16_t><<<grid, block>>>((const uint16_t*)out[m]->p, count, padded(), seeds, k, bad, x2);
         else
-          peer_check_kernel<float><<<grid, block>>>((const float*)out[m]->p, count, padded(), seeds, k, bad);
+          peer_check_kernel<float><<<grid, block>>>((const float*)out[m]->p, count, padded(), seeds, k, bad, x2);
       });
     return total;
   }
@@ -325,26 +385,27 @@ struct PeerAllreduce {
 py::dict peer_allreduce(const std::vector<int>& devs, size_t count, const std::string& dtype, const std::string& algo,
                         int iters, int warmup, int blocks_per_cu, const std::string& wire) {
   const PeerTypes types = peer_types(dtype, "");
-  const bool fp8 = peer_wire_fp8(wire);
   PeerAllreduce::check_args(devs, count, algo);
+  const PeerWire w = peer_wire(wire, algo);
+  const bool fp8 = w.fp8;
   if (iters < 1 || warmup < 0) throw std::invalid_argument("iters >= 1, warmup >= 0");
   const int k = (int)devs.size();
   MemberTimes t;
   unsigned long long wrong = 0;
   const size_t bytes = count * types.in_elem();
-  double quantize_us = 0.0, sum_us = 0.0;
+  double quantize_us = 0.0, sum_us = 0.0, gather_us = 0.0;
   {
     py::gil_scoped_release nogil;
     // with more than one round, consecutive rounds alternate between two input sets and the check uses
     // the last round's: a round that ran ahead of the one before it leaves a mix of the two sums
     const int total = warmup + iters;
-    PeerAllreduce ar(devs, count, types, algo, total >= 2 ? 2 : 1, blocks_per_cu, 1.0f, fp8);
+    PeerAllreduce ar(devs, count, types, algo, total >= 2 ? 2 : 1, blocks_per_cu, 1.0f, w);
     for (int s = 0; s < ar.nsets; ++s) ar.fill(s);
     t = time_member_rounds(devs, ar.ts, warmup, iters, [&](int r) { ar.round(r % ar.nsets); });
     wrong = ar.wrong((total - 1) % ar.nsets);
     if (fp8) {
-      // member 0's two kernels alone on an idle device, after the check: the same set as the last round,
-      // so `out` is rewritten with the same bits
+      // member 0's kernels alone on an idle device, after the check: the same set as the last round,
+      // so `out` (fp8x2: its slice of the second packed buffer, then `out`) is rewritten with the same bits
       const int set = (total - 1) % ar.nsets;
       const size_t a = ar.twoshot ? ar.plan[0].first : 0, b = ar.twoshot ? a + ar.plan[0].count : ar.n_blocks;
       DeviceGuard g(devs[0]);
@@ -354,6 +415,11 @@ py::dict peer_allreduce(const std::vector<int>& devs, size_t count, const std::s
       ar.ts[0]->begin();
       for (int i = 0; i < iters; ++i) ar.reduce(0, set, a, b);
       sum_us = ar.ts[0]->end_ms() * 1e3 / iters;
+      if (w.x2) {
+        ar.ts[0]->begin();
+        for (int i = 0; i < iters; ++i) ar.gather_phase(0);
+        gather_us = ar.ts[0]->end_ms() * 1e3 / iters;
+      }
     }
   }
   const double time_us = *std::max_element(t.ms_member.begin(), t.ms_member.end()) * 1e3 / iters;
@@ -375,6 +441,7 @@ py::dict peer_allreduce(const std::vector<int>& devs, size_t count, const std::s
   if (fp8) {
     r["quantize_us"] = quantize_us;
     r["sum_us"] = sum_us;
+    if (w.x2) r["gather_us"] = gather_us;
   }
   return r;
 }
@@ -388,8 +455,9 @@ py::list peer_allreduce_arrays(const std::vector<int>& devs, const std::vector<p
   if (inputs.size() != devs.size()) throw std::invalid_argument("one input array per member");
   const size_t count = inputs.empty() ? 0 : (size_t)inputs[0].size();
   const PeerTypes types = peer_types(dtype, out_dtype.value_or(""));
-  const bool fp8 = peer_wire_fp8(wire);
   PeerAllreduce::check_args(devs, count, algo);
+  const PeerWire w = peer_wire(wire, algo);
+  const bool fp8 = w.fp8;
   if (count > PeerAllreduce::kMaxCount) throw std::invalid_argument("count <= 64 Mi elements");
   if (rounds < 1) throw std::invalid_argument("rounds >= 1");
   const py::dtype want = types.in_bf16 ? py::dtype::of<uint16_t>() : py::dtype::of<float>();
@@ -410,7 +478,7 @@ py::list peer_allreduce_arrays(const std::vector<int>& devs, const std::vector<p
   }
   {
     py::gil_scoped_release nogil;
-    PeerAllreduce ar(devs, count, types, algo, 1, kBlocksPerCU, scale, fp8);
+    PeerAllreduce ar(devs, count, types, algo, 1, kBlocksPerCU, scale, w);
     for (int m = 0; m < k; ++m) {
       DeviceGuard g(devs[m]);
       // the fp8 wire masks what lies past the count itself: its padding is made non-zero on purpose

@@ -29,6 +29,16 @@
 // word that holds its block's exponent: the 64 lanes of a wave cover 32 consecutive exponent bytes, two
 // vectors, which reach the memory pipeline as one request next to the wave's 1 KiB of codes.
 //
+// A two-shot may pack its second phase too (wire fp8x2; ops/peer_ref.py: allreduce_q8x2_ref decides).  Phase 1
+// then keeps the scaled fp32 sums of its slice in registers and packs them by the same block rule (the
+// same e, clamp and NaN/Inf coding, blocks counted from element 0 of the call) into the rank's second
+// packed buffer, of the layout above; phase 2 reads every rank's slice of those buffers, the rank's own
+// included, widens it and stores it at the output precision.  Every member's result is then the
+// dequantised form of one packing, so all hold the same bits, and the cast to the output type is exact:
+// at most 4 significant bits and e in [-100, 120] fit bf16.  An Inf in the sum comes out as NaN (e4m3fn
+// has no infinity), a magnitude of at least 248 * 2^120 as Inf.  Both phases then move 33 bytes per 32
+// elements over the links.
+//
 // Conversions: v_cvt_pk_fp8_f32 and v_cvt_pk_f32_fp8 through their builtins, on values already scaled by
 // an exact fp32 multiply; the scaling forms (cvt_scalef32_*) are not used, so which way they apply their
 // scale operand plays no part here.  tests/test_gpu_peer_q8.py compares every code with the numpy rule.
@@ -217,6 +227,119 @@ __global__ __launch_bounds__(gtk::kStreamBlock) void peer_q8_sum_kernel(SrcSet s
   for (size_t i = v0 + n_tiles * tile + (size_t)blockIdx.x * gtk::kStreamBlock + threadIdx.x; i < v1;
        i += (size_t)gridDim.x * gtk::kStreamBlock)
     peer_q8_sum_vecs<TO, KB, 1>(srcs, k, exp_vec, dst, i, 0, scale);
+}
+
+// peer_q8_sum_vecs up to the multiply by `scale` (k x U code vectors and exponent words in flight, the sum
+// in member order), then the 16 results a lane holds are packed, not stored: a block is the two adjacent
+// lanes with code vectors 2 b and 2 b + 1, so its amax is one lane exchange after the canonicalise / fmaxf
+// of q8_quantize_vec; every lane stores its 16 codes as one vector, the even lane the exponent byte.
+template <int KB, int U>
+__device__ __forceinline__ void peer_q8_repack_vecs(const SrcSet& srcs, int k, size_t exp_vec, u32x4* __restrict__ packed,
+                                                    unsigned char* __restrict__ exps, size_t i, size_t stride, float scale) {
+  u32x4 r[KB][U];
+  unsigned int x[KB][U];
+#pragma unroll
+  for (int m = 0; m < KB; ++m)
+    if (m < k) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const size_t v = i + (size_t)u * stride;
+        r[m][u] = __builtin_nontemporal_load(srcs.p[m] + v);
+        x[m][u] = __builtin_nontemporal_load(reinterpret_cast<const unsigned int*>(srcs.p[m] + exp_vec) + (v >> 3));
+      }
+    }
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const size_t v = i + (size_t)u * stride;
+    const unsigned int shift = 8u * (unsigned int)((v >> 1) & 3);
+    float acc[16];
+    q8_widen(r[0][u], (x[0][u] >> shift) & 0xffu, acc);
+#pragma unroll
+    for (int m = 1; m < KB; ++m)
+      if (m < k) {
+        float y[16];
+        q8_widen(r[m][u], (x[m][u] >> shift) & 0xffu, y);
+#pragma unroll
+        for (int j = 0; j < 16; ++j) acc[j] = acc[j] + y[j];
+      }
+#pragma unroll
+    for (int j = 0; j < 16; ++j) acc[j] = acc[j] * scale;
+    float amax = 0.f;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) amax = fmaxf(amax, fabsf(__builtin_canonicalizef(acc[j])));
+    amax = fmaxf(amax, __shfl_xor(amax, 1));
+    const int e = q8_block_exp(amax);
+    const float down = q8_pow2(-e);
+    u32x4 c;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      c[j] = q8_codes2(acc[4 * j] * down, acc[4 * j + 1] * down) | (q8_codes2(acc[4 * j + 2] * down, acc[4 * j + 3] * down) << 16);
+    __builtin_nontemporal_store(c, packed + v);
+    if ((v & 1) == 0) exps[v >> 1] = (unsigned char)(e + kQ8Bias);
+  }
+}
+
+// Phase 1 of the fp8x2 two-shot: blocks [b0, b1) of `packed` (the rank's second packed buffer, its
+// exponent bytes at `exp_vec` too) = the packed form of scale * the sum over members m < k of the
+// dequantised blocks [b0, b1) of srcs.p[m].  The range is cut as peer_q8_sum_kernel cuts it.  The first
+// code vector 2 b0, the tile (kStreamBlock x U) and the tail's grid stride are even, so a lane's vector
+// has the parity of its threadIdx.x: lanes 2 j and 2 j + 1 of one wave hold the two vectors of one block.
+// The tile runs have no per-lane branch, and in the tail an even vector below the even end 2 b1 has its
+// odd neighbour below it as well, so the two lanes of a block take every branch together.
+template <int KB, int U>
+__global__ __launch_bounds__(gtk::kStreamBlock) void peer_q8_repack_kernel(SrcSet srcs, int k, size_t exp_vec, size_t b0,
+                                                                           size_t b1, u32x4* __restrict__ packed, float scale) {
+  unsigned char* exps = reinterpret_cast<unsigned char*>(packed + exp_vec);
+  const size_t v0 = 2 * b0, v1 = 2 * b1;
+  const size_t tile = (size_t)gtk::kStreamBlock * U;
+  const size_t n_tiles = (v1 - v0) / tile;
+  const size_t per = (n_tiles + gridDim.x - 1) / gridDim.x;
+  const size_t t0 = (size_t)blockIdx.x * per;
+  const size_t t1 = std::min(n_tiles, t0 + per);
+  for (size_t t = t0; t < t1; ++t)
+    peer_q8_repack_vecs<KB, U>(srcs, k, exp_vec, packed, exps, v0 + t * tile + threadIdx.x, gtk::kStreamBlock, scale);
+  for (size_t i = v0 + n_tiles * tile + (size_t)blockIdx.x * gtk::kStreamBlock + threadIdx.x; i < v1;
+       i += (size_t)gridDim.x * gtk::kStreamBlock)
+    peer_q8_repack_vecs<KB, 1>(srcs, k, exp_vec, packed, exps, i, 0, scale);
+}
+
+// Phase 2 of the fp8x2 two-shot: slice s is blocks [first, first + count) of sl.p[s], a rank's second
+// packed buffer (this rank's own is one of them), widened with the exponent byte read as the sum reads
+// it and stored to the same blocks of dst in the output type TO.  Block b of the grid serves slice
+// b % nsrc with gridDim / nsrc blocks, as peer_allgather_kernel does; slices may be empty.  U code
+// vectors and exponent words per lane are loaded before the first is converted.
+template <typename TO>
+__global__ __launch_bounds__(gtk::kStreamBlock) void peer_q8_unpack_kernel(SliceSet sl, int nsrc, size_t exp_vec,
+                                                                           u32x4* __restrict__ dst) {
+  constexpr int U = 4;
+  const int s = blockIdx.x % nsrc;
+  const size_t blk = blockIdx.x / nsrc, nblk = gridDim.x / nsrc;
+  const u32x4* src = sl.p[s];
+  const unsigned int* exps = reinterpret_cast<const unsigned int*>(src + exp_vec);
+  const size_t v1 = 2 * (sl.first[s] + sl.count[s]), stride = nblk * gtk::kStreamBlock;
+  for (size_t base = 2 * sl.first[s] + blk * gtk::kStreamBlock + threadIdx.x; base < v1; base += stride * U) {
+    u32x4 r[U];
+    unsigned int x[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const size_t v = base + (size_t)u * stride;
+      r[u] = u32x4{0u, 0u, 0u, 0u};
+      x[u] = 0u;
+      if (v < v1) {
+        r[u] = __builtin_nontemporal_load(src + v);
+        x[u] = __builtin_nontemporal_load(exps + (v >> 3));
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const size_t v = base + (size_t)u * stride;
+      if (v < v1) {
+        float f[16];
+        q8_widen(r[u], (x[u] >> (8u * (unsigned int)((v >> 1) & 3))) & 0xffu, f);
+        q8_store<TO>(f, dst, v);
+      }
+    }
+  }
 }
 
 }  // namespace

@@ -4,7 +4,8 @@
 //
 // A rank owns a window (inputs, `capacity` bytes), an out (results, twice that: the wide form writes
 // two vectors per input vector), a packed buffer (the fp8 wire's form of the window, sized for a window
-// full of bf16: capacity / 64 blocks) and one non-blocking stream on its device.  Ranks are threads of one
+// full of bf16: capacity / 64 blocks), a second packed buffer of that size (the fp8x2 wire's form of the rank's
+// slice of a sum, which its peers gather from) and one non-blocking stream on its device.  Ranks are threads of one
 // process, so a peer's buffer is reached through its plain device address and, across devices,
 // hipDeviceEnablePeerAccess: no IPC call.  A PeerRank is used by one thread.  Nothing here waits on
 // the GPU for another rank: no event is shared between ranks and no kernel spins, so ordering between
@@ -39,12 +40,14 @@ class PeerRank {
         window_.reset(new DevBuf(dev, cap_));
         out_.reset(new DevBuf(dev, 2 * cap_));
         packed_.reset(new DevBuf(dev, packed_bytes()));
+        packed_out_.reset(new DevBuf(dev, packed_bytes()));
       }
       DeviceGuard g(dev);
       HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
       HIP_CHECK(hipMemsetAsync(window_->p, 0, cap_, stream_));
       HIP_CHECK(hipMemsetAsync(out_->p, 0, 2 * cap_, stream_));
       HIP_CHECK(hipMemsetAsync(packed_->p, 0, packed_bytes(), stream_));
+      HIP_CHECK(hipMemsetAsync(packed_out_->p, 0, packed_bytes(), stream_));
       HIP_CHECK(hipStreamSynchronize(stream_));
     } catch (...) {
       release_locked();
@@ -66,6 +69,7 @@ class PeerRank {
   uintptr_t window_ptr() const { return reinterpret_cast<uintptr_t>(live().window_->p); }
   uintptr_t out_ptr() const { return reinterpret_cast<uintptr_t>(live().out_->p); }
   uintptr_t packed_ptr() const { return reinterpret_cast<uintptr_t>(live().packed_->p); }
+  uintptr_t packed_out_ptr() const { return reinterpret_cast<uintptr_t>(live().packed_out_->p); }
   size_t capacity_bytes() const { return cap_; }
   size_t max_blocks() const { return cap_ / (kQ8Block * 2); }  // blocks of 32 bf16 elements the window holds
   size_t packed_bytes() const { return std::max<size_t>(16, q8_packed_vecs(max_blocks()) * 16); }
@@ -75,21 +79,26 @@ class PeerRank {
   // Every rank's device and buffer addresses, this rank's own included (and checked to be its own).
   // A peer's address must be the base of a device allocation of this process on the device it names,
   // at least as large as this rank's buffers: the kernels index a peer's buffer as they index their own.
-  // `packeds` is optional: without the peers' packed buffers the fp8 phases stay unavailable.
+  // `packeds` is optional: without the peers' packed buffers the fp8 phases stay unavailable; so is
+  // `packed_outs`, the peers' second packed buffers, without which the fp8x2 phases stay unavailable.
   void open_peers(const std::vector<int>& devices, const std::vector<uintptr_t>& windows, const std::vector<uintptr_t>& outs,
-                  const std::optional<std::vector<uintptr_t>>& packeds = std::nullopt) {
+                  const std::optional<std::vector<uintptr_t>>& packeds = std::nullopt,
+                  const std::optional<std::vector<uintptr_t>>& packed_outs = std::nullopt) {
     live();
     const size_t k = (size_t)world_;
     if (devices.size() != k || windows.size() != k || outs.size() != k) throw std::invalid_argument("one device, window and out per rank");
-    if (packeds && packeds->size() != k) throw std::invalid_argument("one packed buffer per rank");
+    if ((packeds && packeds->size() != k) || (packed_outs && packed_outs->size() != k))
+      throw std::invalid_argument("one packed buffer per rank");
+    if (packed_outs && !packeds) throw std::invalid_argument("the second packed buffers come with the first");
     if (devices[rank_] != dev_ || windows[rank_] != window_ptr() || outs[rank_] != out_ptr() ||
-        (packeds && (*packeds)[rank_] != packed_ptr()))
+        (packeds && (*packeds)[rank_] != packed_ptr()) || (packed_outs && (*packed_outs)[rank_] != packed_out_ptr()))
       throw std::invalid_argument("this rank's own entry is not its device and buffers");
     check_devs(devices);
     for (size_t p = 0; p < k; ++p) {
       check_allocation(windows[p], devices[p], cap_);
       check_allocation(outs[p], devices[p], 2 * cap_);
       if (packeds) check_allocation((*packeds)[p], devices[p], packed_bytes());
+      if (packed_outs) check_allocation((*packed_outs)[p], devices[p], packed_bytes());
     }
     {
       std::lock_guard<std::mutex> lock(peer_rank_mutex());
@@ -97,19 +106,23 @@ class PeerRank {
     }
     share_ = device_share(devices, dev_);  // as the members of PeerAllreduce do
     outs_.resize(k);
+    packed_outs_.assign(k, nullptr);
     for (size_t p = 0; p < k; ++p) {
       windows_.p[p] = reinterpret_cast<const u32x4*>(windows[p]);
       outs_[p] = reinterpret_cast<const u32x4*>(outs[p]);
       packeds_.p[p] = packeds ? reinterpret_cast<const u32x4*>((*packeds)[p]) : nullptr;
+      if (packed_outs) packed_outs_[p] = reinterpret_cast<const u32x4*>((*packed_outs)[p]);
     }
     open_ = true;
     open_q8_ = packeds.has_value();
+    open_q8x2_ = packed_outs.has_value();
   }
 
   void close_peers() {
     windows_ = packeds_ = SrcSet{};
     outs_.clear();
-    open_ = open_q8_ = false;
+    packed_outs_.clear();
+    open_ = open_q8_ = open_q8x2_ = false;
   }
 
   // out[v0, v1) of this rank = scale x the sum over ranks of window[v0, v1), vectors of the input type
@@ -153,6 +166,41 @@ class PeerRank {
     DeviceGuard g(dev_);
     launch_peer_q8_sum(t.out_bf16, packeds_, world_, q8_exp_vec(max_blocks()), b0, b1, reinterpret_cast<u32x4*>(out_->p), scale, grid,
                        stream_);
+    ++launches_;
+  }
+
+  // Phase 1 of the fp8x2 two-shot: blocks [b0, b1) of this rank's second packed buffer = the packed form of
+  // scale x the sum over ranks of the same blocks of their packed buffers.
+  void repack_q8(size_t b0, size_t b1, float scale) {
+    need_q8x2();
+    if (b0 > b1 || b1 > max_blocks()) throw std::invalid_argument("repack_q8: blocks past the end of the packed buffers");
+    if (b0 == b1) return;
+    const int grid = peer_reduce_grid(cus_, blocks_per_cu_, share_, 2 * (b1 - b0));
+    DeviceGuard g(dev_);
+    launch_peer_q8_repack(packeds_, world_, q8_exp_vec(max_blocks()), b0, b1, reinterpret_cast<u32x4*>(packed_out_->p), scale, grid,
+                          stream_);
+    ++launches_;
+  }
+
+  // Phase 2 of the fp8x2 two-shot: blocks [a, b) of the second packed buffer of rank p, widened to the same
+  // blocks of this rank's out (whole blocks of `out_dtype`), for every p, this rank included.  One launch;
+  // slices may be empty.
+  void unpack_q8(const std::vector<std::pair<size_t, size_t>>& slices, const std::string& out_dtype) {
+    const PeerTypes t = peer_types("bf16", out_dtype);  // as reduce_q8: the packed form carries no input type
+    need_q8x2();
+    if (slices.size() != (size_t)world_) throw std::invalid_argument("unpack_q8: one slice per rank");
+    SliceSet sl{};
+    for (int p = 0; p < world_; ++p) {
+      const size_t a = slices[p].first, b = slices[p].second;
+      if (a > b || b > max_blocks()) throw std::invalid_argument("unpack_q8: blocks past the end of the packed buffers");
+      if (b * kQ8Block * t.out_elem() > 2 * cap_) throw std::invalid_argument("unpack_q8: blocks past the end of out");
+      sl.p[p] = packed_outs_[p];
+      sl.first[p] = a;
+      sl.count[p] = b - a;
+    }
+    DeviceGuard g(dev_);
+    launch_peer_q8_unpack(t.out_bf16, sl, world_, q8_exp_vec(max_blocks()), reinterpret_cast<u32x4*>(out_->p),
+                          gather_grid_cus(cus_, blocks_per_cu_, world_, share_), stream_);
     ++launches_;
   }
 
@@ -214,7 +262,7 @@ class PeerRank {
     HIP_CHECK(hipStreamSynchronize(stream_));
   }
 
-  // Synchronises, destroys the stream, frees both buffers.  Idempotent.  The caller must know that no
+  // Synchronises, destroys the stream, frees the buffers.  Idempotent.  The caller must know that no
   // peer still reads this rank's buffers.
   void release() { release_locked(); }
 
@@ -230,6 +278,11 @@ class PeerRank {
   void need_q8() const {
     need_peers();
     if (!open_q8_) throw std::runtime_error("the fp8 phases need open_peers with the peers' packed buffers");
+  }
+
+  void need_q8x2() const {
+    need_q8();
+    if (!open_q8x2_) throw std::runtime_error("the fp8x2 phases need open_peers with the peers' second packed buffers");
   }
 
   static void check_allocation(uintptr_t addr, int dev, size_t bytes) {
@@ -271,16 +324,17 @@ class PeerRank {
     window_.reset();
     out_.reset();
     packed_.reset();
+    packed_out_.reset();
   }
 
   int dev_, rank_, world_;
   size_t cap_;
   int blocks_per_cu_, cus_ = 1, share_ = 1;
-  std::unique_ptr<DevBuf> window_, out_, packed_;
+  std::unique_ptr<DevBuf> window_, out_, packed_, packed_out_;
   hipStream_t stream_ = nullptr;
   SrcSet windows_{}, packeds_{};
-  std::vector<const u32x4*> outs_;
-  bool open_ = false, open_q8_ = false, released_ = false;
+  std::vector<const u32x4*> outs_, packed_outs_;
+  bool open_ = false, open_q8_ = false, open_q8x2_ = false, released_ = false;
   size_t launches_ = 0;
 };
 
@@ -294,13 +348,16 @@ void bind_peer_rank(py::module_& m) {
       .def("window_ptr", &PeerRank::window_ptr)
       .def("out_ptr", &PeerRank::out_ptr)
       .def("packed_ptr", &PeerRank::packed_ptr)
+      .def("packed_out_ptr", &PeerRank::packed_out_ptr)
       .def("open_peers", &PeerRank::open_peers, py::arg("devices"), py::arg("windows"), py::arg("outs"),
-           py::arg("packeds") = py::none(), nogil())
+           py::arg("packeds") = py::none(), py::arg("packed_outs") = py::none(), nogil())
       .def("close_peers", &PeerRank::close_peers, nogil())
       .def("reduce", &PeerRank::reduce, py::arg("v0"), py::arg("v1"), py::arg("in_dtype"), py::arg("out_dtype"), py::arg("scale") = 1.0f,
            nogil())
       .def("quantize", &PeerRank::quantize, py::arg("b0"), py::arg("b1"), py::arg("count"), py::arg("in_dtype"), nogil())
       .def("reduce_q8", &PeerRank::reduce_q8, py::arg("b0"), py::arg("b1"), py::arg("out_dtype"), py::arg("scale") = 1.0f, nogil())
+      .def("repack_q8", &PeerRank::repack_q8, py::arg("b0"), py::arg("b1"), py::arg("scale") = 1.0f, nogil())
+      .def("unpack_q8", &PeerRank::unpack_q8, py::arg("slices"), py::arg("out_dtype"), nogil())
       .def("gather", &PeerRank::gather, py::arg("slices"), nogil())
       .def("gather_windows", &PeerRank::gather_windows, py::arg("n_vec"), nogil())
       .def("write_host",

@@ -20,7 +20,8 @@
 //                  pointers (peer_allreduce.h, peer_driver.h): a fixed summation order, so it is exact
 //                  against a CPU sum; the repository's own collective, next to RCCL's.  On the fp8 wire
 //                  (peer_q8.h) every member packs its input into block-scaled e4m3 first and the members
-//                  read that, 33 bytes per 32 elements, with the same fixed order and exactness.  PeerRank
+//                  read that, 33 bytes per 32 elements, with the same fixed order and exactness; on the
+//                  fp8x2 wire a two-shot packs its sums again and gathers the packed form too.  PeerRank
 //                  (peer_rank.h) launches the same kernels for one rank of the peer communicator.
 //   K8 latency   : one wave follows a chain of dependent loads through a buffer of another device
 //                  (chase_latency.h): nanoseconds per access over the link, next to K1's GB/s.
@@ -38,7 +39,7 @@
 #include "chase_latency.h"   // K8 kernels and the chain's closed form
 #include "peer_allreduce.h"  // K7 kernels
 #include "peer_driver.h"     // K7 launch plan, PeerAllreduce and its entry points
-#include "peer_q8.h"         // K7 fp8 wire: block-scaled e4m3 quantize and sum kernels
+#include "peer_q8.h"         // K7 fp8 wire: block-scaled e4m3 quantize, sum, repack and unpack kernels
 #include "peer_rank.h"       // one rank of the peer communicator's device backend
 #include "probe_common.h"    // geometry, SrcSet, pattern fill and verifier, guards, grids, timers
 
@@ -830,7 +831,8 @@ PYBIND11_MODULE(_probe, m) {
         py::arg("algo") = "twoshot", py::arg("iters") = 3, py::arg("warmup") = 1, py::arg("blocks_per_cu") = kBlocksPerCU,
         py::arg("wire") = "native",
         "K7: timed all-reduce (sum) of device-made inputs over peer pointers; every member's result checked; "
-        "wire=\"fp8\": members read each other's block-scaled e4m3 form (peer_q8.h)");
+        "wire=\"fp8\": members read each other's block-scaled e4m3 form (peer_q8.h); wire=\"fp8x2\" (twoshot): the "
+        "gather phase reads packed sums too");
   m.def("peer_allreduce_arrays", &peer_allreduce_arrays, py::arg("devs"), py::arg("inputs"), py::arg("dtype") = "bf16",
         py::arg("algo") = "twoshot", py::arg("rounds") = 1, py::arg("out_dtype") = py::none(), py::arg("scale") = 1.0f,
         py::arg("wire") = "native",

@@ -426,7 +426,10 @@ def cmd_validate(a) -> int:
     from .topology.cpus import bind_workload
 
     if a.wire != "native" and a.backend != "peer":  # misuse, like an unknown choice: usage error
-        print("gtk validate: error: --wire fp8 belongs to --backend peer", file=sys.stderr)
+        print(f"gtk validate: error: --wire {a.wire} belongs to --backend peer", file=sys.stderr)
+        return 2
+    if a.wire == "fp8x2" and a.algo == "oneshot":
+        print("gtk validate: error: --wire fp8x2 packs the gather phase of a twoshot: --algo twoshot or both", file=sys.stderr)
         return 2
     if a.ranks == "thread":  # refused before anything native is loaded
         if a.backend != "peer":
@@ -449,19 +452,20 @@ def cmd_validate(a) -> int:
         if not 2 <= len(devs) <= 16:
             raise SystemExit(f"--backend peer takes 2 to 16 members, got {devs} (a device may repeat: --devices 0,0)")
         sizes = _size_sweep(a.min_bytes, a.max_bytes, a.factor)
+        algo = "twoshot" if a.wire == "fp8x2" else a.algo  # the one algorithm with a gather phase to pack
         if a.ranks == "thread":  # one thread per member through the peer communicator, not one driver call for all
             from .parallel.peer_comm import selftest, thread_sweep
 
-            st = selftest(devs)
+            st = selftest(devs, wire=a.wire)
             print(json.dumps({"selftest": True, "k": len(devs), "devices": devs, "ranks": "thread", **st}), flush=True)
-            selftest_wrong = st["wrong"] + st["q8_wrong"]
-            pts = thread_sweep(devs, sizes, a.dtype, a.algo, a.iters, a.warmup, wire=a.wire)
-            extra = {"backend": "peer", "algo": a.algo, "ranks": "thread", "selftest_wrong": selftest_wrong, "wire": a.wire}
+            selftest_wrong = st["wrong"] + st["q8_wrong"] + st.get("q8x2_wrong", 0)
+            pts = thread_sweep(devs, sizes, a.dtype, algo, a.iters, a.warmup, wire=a.wire)
+            extra = {"backend": "peer", "algo": algo, "ranks": "thread", "selftest_wrong": selftest_wrong, "wire": a.wire}
         else:
             keys = ("bytes", "count", "time_us", "algbw_gbps", "busbw_gbps", "wrong")
             pts = [{**{k: p[k] for k in keys}, "backend": "peer", "algo": p["algo"]}
-                   for p in peer_sweep(devs, sizes, a.dtype, a.algo, a.iters, a.warmup, wire=a.wire)]
-            extra = {"backend": "peer", "algo": a.algo, "wire": a.wire}
+                   for p in peer_sweep(devs, sizes, a.dtype, algo, a.iters, a.warmup, wire=a.wire)]
+            extra = {"backend": "peer", "algo": algo, "wire": a.wire}
     else:
         rccl = load("_rccl")
         sizes = rccl.size_sweep(a.min_bytes, a.max_bytes, a.factor)
@@ -624,9 +628,10 @@ def main(argv=None) -> int:
     p.add_argument("--backend", default="rccl", choices=["rccl", "peer"],
                    help="rccl: librccl's all-reduce; peer: this repository's K7 kernels over peer pointers (no RCCL; bf16|fp32)")
     p.add_argument("--algo", default="both", choices=["oneshot", "twoshot", "both"], help="--backend peer: K7 algorithm(s)")
-    p.add_argument("--wire", default="native", choices=["native", "fp8"],
+    p.add_argument("--wire", default="native", choices=["native", "fp8", "fp8x2"],
                    help="--backend peer: native = members read each other's inputs; fp8 = each member packs its input into "
-                        "e4m3 codes with one power-of-two scale per 32 elements and the members read that (33 bytes per 32 elements)")
+                        "e4m3 codes with one power-of-two scale per 32 elements and the members read that (33 bytes per 32 elements); "
+                        "fp8x2 = the two-shot alone, its gather phase packed the same way")
     p.add_argument("--ranks", default="driver", choices=["driver", "thread"],
                    help="--backend peer: driver = one in-process call drives every member (stream events); thread = one thread "
                         "per member through the peer communicator (a self-test, then host-timed all_reduce calls checked on the host)")

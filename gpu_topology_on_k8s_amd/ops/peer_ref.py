@@ -14,6 +14,8 @@ every other element, infinities, subnormals and signed zeros included, must have
 The fp8 wire (``csrc/probe/peer_q8.h``) has its reference here too: :func:`q8_quantize_ref` packs one
 rank's input into OCP e4m3fn codes with one power-of-two scale per 32 elements, and
 :func:`allreduce_q8_ref` sums the dequantised values exactly as :func:`allreduce_ref` sums the inputs.
+:func:`allreduce_q8x2_ref` is the two-shot whose gather phase is packed too (``wire="fp8x2"``): the scaled fp32 sum
+goes through the same block rule once more, and every member takes its result from that packed form.
 """
 from __future__ import annotations
 
@@ -23,7 +25,7 @@ import numpy as np
 
 __all__ = ["ELEM", "peer_slices", "bf16_round", "bf16_to_f32", "bits", "out_dtype_of", "allreduce_ref", "reduce_scatter_ref",
            "is_nan_bits", "mismatches", "Q8_BLOCK", "Q8_EXP_MIN", "Q8_EXP_MAX", "q8_blocks", "q8_slices", "q8_quantize_ref", "q8_dequantize_ref",
-           "allreduce_q8_ref", "reduce_scatter_q8_ref"]
+           "allreduce_q8_ref", "reduce_scatter_q8_ref", "allreduce_q8x2_ref"]
 
 ELEM = {"bf16": 2, "fp32": 4}  # bytes per element
 
@@ -222,3 +224,21 @@ def reduce_scatter_q8_ref(inputs: Sequence[np.ndarray], dtype: str, out_dtype: O
     full = allreduce_q8_ref(inputs, dtype, out_dtype, scale)
     count = int(full.shape[0])
     return [full[min(count, a * Q8_BLOCK):min(count, b * Q8_BLOCK)] for a, b in q8_slices(q8_blocks(count), len(inputs))]
+
+
+def allreduce_q8x2_ref(inputs: Sequence[np.ndarray], dtype: str, out_dtype: Optional[str] = None, scale: float = 1.0) -> np.ndarray:
+    """The two-shot all-reduce with both phases on the fp8 wire (``wire="fp8x2"``).  The fp32 result of
+    :func:`allreduce_q8_ref` (the sum in member order of the members' dequantised packed forms, multiplied
+    once by ``scale``, not rounded to bf16) is packed by :func:`q8_quantize_ref` unchanged: blocks counted
+    from element 0 of the call, the same ``e``, clamp and NaN/Inf coding, elements at or past the count
+    zero.  What every member holds, the slice's owner included, is the dequantised form of that, cast to
+    ``out_dtype``.  The cast is exact: a dequantised value has at most 4 significant bits and ``e`` lies in
+    ``[-100, 120]``, so bf16 holds it.
+
+    An Inf in the sum comes out as NaN, since e4m3fn has no infinity, and a magnitude of at least
+    ``248 * 2^120`` comes out Inf.  Per element the result is off from ``allreduce_q8_ref(..., "fp32")`` by at
+    most ``amax / 14`` of its block of the scaled sum."""
+    out = out_dtype_of(dtype, out_dtype)
+    s = allreduce_q8_ref(inputs, dtype, "fp32", scale)
+    back = q8_dequantize_ref(*q8_quantize_ref(s, "fp32"))[:s.shape[0]]
+    return bf16_round(back) if out == "bf16" else back

@@ -149,7 +149,10 @@ def peer_allreduce(devs: Sequence[int], count: int, dtype: str = "bf16", algo: s
     ``wire="fp8"``: every member first packs its input into e4m3 codes with one power-of-two scale per 32
     elements and the members read each other's packed form, 33 bytes per 32 elements
     (``csrc/probe/peer_q8.h``); the result then also carries ``quantize_us`` and ``sum_us``, member 0's two
-    kernels timed alone."""
+    kernels timed alone.  ``wire="fp8x2"`` (``algo="twoshot"`` only, ``ValueError`` otherwise): phase 1 packs its sums
+    again and phase 2 unpacks every member's slice, so both phases move packed bytes; the device-made inputs
+    are then values in {-1, 0}, whose sums survive the second packing, and ``gather_us`` is member 0's unpack
+    kernel timed alone."""
     return dict(_p().peer_allreduce([int(d) for d in devs], int(count), dtype, algo, int(iters), int(warmup_iters),
                                     int(blocks_per_cu), wire))
 
@@ -169,7 +172,8 @@ def peer_allreduce_arrays(devs: Sequence[int], inputs: Sequence[np.ndarray], dty
     ``fp32``) in, every member's result out; ``ops.peer_ref.allreduce_ref`` gives the same bits.
     ``out_dtype="fp32"`` of ``bf16`` inputs is the wide reduce (bf16 read, fp32 summed and written);
     ``scale`` multiplies the fp32 sum once before the one rounding (``1 / k`` for a mean).  With
-    ``wire="fp8"`` the bits are ``ops.peer_ref.allreduce_q8_ref``'s."""
+    ``wire="fp8"`` the bits are ``ops.peer_ref.allreduce_q8_ref``'s, with ``wire="fp8x2"`` (``algo="twoshot"`` only)
+    ``ops.peer_ref.allreduce_q8x2_ref``'s."""
     return list(_p().peer_allreduce_arrays([int(d) for d in devs], list(inputs), dtype, algo, int(rounds), out_dtype,
                                            float(scale), wire))
 
@@ -177,7 +181,8 @@ def peer_allreduce_arrays(devs: Sequence[int], inputs: Sequence[np.ndarray], dty
 def peer_sweep(devs: Sequence[int], sizes: Sequence[int], dtype: str = "bf16", algo: str = "both", iters: int = 3,
                warmup_iters: int = 1, wire: str = "native") -> List[Dict[str, object]]:
     """K7 at every size (bytes) under ``algo`` (``oneshot``, ``twoshot`` or ``both``) on ``wire``: one dict per
-    size and algorithm, in size order, with ``fastest`` marking the quicker algorithm of each size."""
+    size and algorithm, in size order, with ``fastest`` marking the quicker algorithm of each size.
+    ``wire="fp8x2"`` belongs to ``algo="twoshot"``."""
     if algo != "both" and algo not in PEER_ALGOS:
         raise ValueError(f"algo must be oneshot|twoshot|both, got {algo!r}")
     elem = ELEM.get(dtype)

@@ -25,12 +25,28 @@ before barrier A and the collective still costs two barriers:
 
     quantize -> synchronize -> barrier A -> phase 1 on packed -> synchronize -> barrier B (-> phase 2)
 
-Phase 1 works on blocks of 32 elements, sliced by ``q8_slices``; phase 2 of a two-shot is the same gather
-of out at the output precision.  Per element and member the packed value is off by at most ``amax / 14``
+Phase 1 works on blocks of 32 elements, sliced by ``q8_slices``; with ``wire="fp8"`` phase 2 of a two-shot is
+the same gather of out at the output precision.  Per element and member the packed value is off by at most ``amax / 14``
 of its block (``2^(e+4)`` with ``amax * 2^-e > 224``).  The wire fits ``reduce_scatter`` best, where every
 byte that crosses a link is packed: the ZeRO-1 gradient path.  Because the quantize comes before the
 descriptors are compared, a rank that asks for ``wire="fp8"`` in a mismatched call has made that one
 launch, on its own buffers alone, when ``PeerCommMismatch`` is raised; no rank has touched a peer.
+
+``wire="fp8x2"`` (``all_reduce`` with ``algo="twoshot"`` alone: nothing else has a gather phase) packs that
+gather too.  Phase 1 packs the scaled fp32 sums of the rank's slice by the same block rule into a fourth
+buffer per rank, *packed_out*, and phase 2 unpacks every rank's slice of those buffers, the rank's own
+included, into out, so every rank holds the same bits (``ops/peer_ref.allreduce_q8x2_ref``) and both phases
+move 33 bytes per 32 elements over the links:
+
+    quantize -> synchronize -> barrier A -> repack -> synchronize -> barrier B -> unpack -> synchronize
+
+Phase 2 cannot read the first packed buffer: that one is rewritten by the next collective's quantize
+*before* barrier A, which is safe only because its last readers finish before barrier B, and phase 2 runs
+after barrier B.  *packed_out* is written by its owner alone, in phase 1, after barrier A; every rank reads
+it in phase 2, after barrier B; and it is next written after the next barrier A, which a rank enters only
+after synchronising its own phase 2.  The second rounding costs at most ``amax / 14`` of the block of the
+scaled sum per element; an Inf in the sum comes out as NaN, since e4m3fn has no infinity, and a magnitude of
+at least ``248 * 2^120`` comes out Inf.
 
 Two backends exist, both with the ranks as threads of one process:
 
@@ -61,18 +77,19 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ..ops.peer_ref import (ELEM as _ELEM, Q8_BLOCK, allreduce_q8_ref, allreduce_ref, bf16_round, bits as _bits,
+from ..ops.peer_ref import (ELEM as _ELEM, Q8_BLOCK, allreduce_q8_ref, allreduce_q8x2_ref, allreduce_ref, bf16_round, bits as _bits,
                             out_dtype_of as _out_dtype, peer_slices, q8_blocks, q8_dequantize_ref, q8_quantize_ref, q8_slices)
 
 __all__ = ["PeerComm", "PeerCommError", "PeerCommTimeout", "PeerCommMismatch", "HostFabric", "MemoryStore",
-           "selftest_cases", "selftest_cases_q8", "case_input", "run_case", "run_thread_ranks", "selftest", "thread_sweep", "timed_all_reduce", "parked_bytes",
+           "selftest_cases", "selftest_cases_q8", "selftest_cases_q8x2", "case_input", "run_case", "run_thread_ranks", "selftest", "thread_sweep", "timed_all_reduce", "parked_bytes",
            "MAX_WORLD"]
 
 MAX_WORLD = 16  # kMaxSrc of csrc/probe/probe_common.h
 BACKENDS = ("host", "device")
 _NP = {"bf16": np.uint16, "fp32": np.float32}
 ALGOS = ("oneshot", "twoshot")
-WIRES = (None, "native", "fp8")  # None and "native" are the same call: the windows as they are
+WIRES = (None, "native", "fp8", "fp8x2")  # None and "native" are the same call: the windows as they are
+_WIRE_REF = {None: allreduce_ref, "native": allreduce_ref, "fp8": allreduce_q8_ref, "fp8x2": allreduce_q8x2_ref}
 _Q8_BIAS = 127  # a block's stored exponent byte is e + 127, as in csrc/probe/peer_q8.h
 
 
@@ -150,7 +167,7 @@ class MemoryStore:
 
 
 class HostFabric:
-    """The buffers of ``backend="host"`` (one window, one out and one packed buffer per rank, shared by
+    """The buffers of ``backend="host"`` (one window, one out and two packed buffers per rank, shared by
     the ranks' threads) and the access log the conflict check reads."""
 
     def __init__(self, world: int, capacity_bytes: int):
@@ -158,6 +175,7 @@ class HostFabric:
         self.window = [np.zeros(capacity_bytes, np.uint8) for _ in range(world)]
         self.out = [np.zeros(2 * capacity_bytes, np.uint8) for _ in range(world)]
         self.packed = [np.zeros(_packed_bytes(capacity_bytes), np.uint8) for _ in range(world)]
+        self.packed_out = [np.zeros(_packed_bytes(capacity_bytes), np.uint8) for _ in range(world)]
         self.lock = threading.Lock()
         #: (accessor, owner, buffer, v0, v1, "r" | "w", the accessor's barrier count)
         self.log: List[Tuple[int, int, str, int, int, str, int]] = []
@@ -185,7 +203,7 @@ class HostFabric:
 
 
 class _HostBackend:
-    """One rank's phase calls (reduce, quantize, reduce_q8, gather, gather_windows, host copies) on a
+    """One rank's phase calls (reduce, quantize, reduce_q8, repack_q8, unpack_q8, gather, gather_windows, host copies) on a
     :class:`HostFabric`, computed by ``ops/peer_ref.py``."""
 
     def __init__(self, rank: int, world: int, fabric: HostFabric):
@@ -225,12 +243,14 @@ class _HostBackend:
         ratio = _ELEM[out_dtype] // _ELEM[in_dtype]
         self._out(self.rank, v0 * ratio, v1 * ratio, "w")[:] = allreduce_ref(xs, in_dtype, out_dtype, scale).view(np.uint8)
 
-    def _packed(self, p: int, b0: int, b1: int, mode: str) -> Tuple[np.ndarray, np.ndarray]:
-        """Blocks ``[b0, b1)`` of rank p's packed buffer: its code bytes and its exponent bytes, logged in vectors."""
+    def _packed(self, p: int, b0: int, b1: int, mode: str, name: str = "packed") -> Tuple[np.ndarray, np.ndarray]:
+        """Blocks ``[b0, b1)`` of rank p's packed buffer ``name`` (``packed`` or ``packed_out``): its code bytes and
+        its exponent bytes, logged in vectors under that name."""
         nb = _max_blocks(self.f.capacity_bytes)
-        self.f.access(self.rank, p, "packed", 2 * b0, 2 * b1, mode, self.epoch)
-        self.f.access(self.rank, p, "packed", 2 * nb + b0 // 16, 2 * nb + -(-b1 // 16), mode, self.epoch)
-        return self.f.packed[p][Q8_BLOCK * b0:Q8_BLOCK * b1], self.f.packed[p][Q8_BLOCK * nb + b0:Q8_BLOCK * nb + b1]
+        buf = getattr(self.f, name)[p]
+        self.f.access(self.rank, p, name, 2 * b0, 2 * b1, mode, self.epoch)
+        self.f.access(self.rank, p, name, 2 * nb + b0 // 16, 2 * nb + -(-b1 // 16), mode, self.epoch)
+        return buf[Q8_BLOCK * b0:Q8_BLOCK * b1], buf[Q8_BLOCK * nb + b0:Q8_BLOCK * nb + b1]
 
     def quantize(self, b0: int, b1: int, count: int, in_dtype: str) -> None:
         e = _ELEM[in_dtype]
@@ -256,13 +276,41 @@ class _HostBackend:
             self.f.launches += 1
         if b0 == b1:
             return
+        acc = self._sum_q8(b0, b1, scale)
+        res = bf16_round(acc) if out_dtype == "bf16" else acc
+        self._out(self.rank, b0 * Q8_BLOCK * e // 16, b1 * Q8_BLOCK * e // 16, "w")[:] = res.view(np.uint8)
+
+    def _sum_q8(self, b0: int, b1: int, scale: float) -> np.ndarray:
+        """``scale`` x the fp32 sum in rank order of blocks ``[b0, b1)`` of every rank's packed buffer."""
         xs = []
         for p in range(self.world):
             c, x8 = self._packed(p, b0, b1, "r")
             xs.append(q8_dequantize_ref(c.copy(), x8.astype(np.int32) - _Q8_BIAS))
-        acc = allreduce_ref(xs, "fp32", "fp32", scale)
-        res = bf16_round(acc) if out_dtype == "bf16" else acc
-        self._out(self.rank, b0 * Q8_BLOCK * e // 16, b1 * Q8_BLOCK * e // 16, "w")[:] = res.view(np.uint8)
+        return allreduce_ref(xs, "fp32", "fp32", scale)
+
+    def repack_q8(self, b0: int, b1: int, scale: float) -> None:
+        if b0 > b1 or b1 > _max_blocks(self.f.capacity_bytes):
+            raise ValueError("repack_q8: blocks past the end of the packed buffers")
+        with self.f.lock:
+            self.f.launches += 1
+        if b0 == b1:
+            return
+        codes, exps = q8_quantize_ref(self._sum_q8(b0, b1, scale), "fp32")
+        c, x8 = self._packed(self.rank, b0, b1, "w", "packed_out")
+        c[:], x8[:] = codes, (exps + _Q8_BIAS).astype(np.uint8)
+
+    def unpack_q8(self, slices: Sequence[Tuple[int, int]], out_dtype: str) -> None:
+        e = _ELEM[out_dtype]
+        if any(a > b or b > _max_blocks(self.f.capacity_bytes) or b * Q8_BLOCK * e > 2 * self.f.capacity_bytes for a, b in slices):
+            raise ValueError("unpack_q8: blocks past the end of the packed buffers or of out")
+        with self.f.lock:
+            self.f.launches += 1
+        for p, (a, b) in enumerate(slices):
+            if b > a:
+                c, x8 = self._packed(p, a, b, "r", "packed_out")
+                res = q8_dequantize_ref(c.copy(), x8.astype(np.int32) - _Q8_BIAS)
+                res = bf16_round(res) if out_dtype == "bf16" else res
+                self._out(self.rank, a * Q8_BLOCK * e // 16, b * Q8_BLOCK * e // 16, "w")[:] = res.view(np.uint8)
 
     def gather(self, slices: Sequence[Tuple[int, int]]) -> None:
         with self.f.lock:
@@ -298,14 +346,14 @@ _PARKED_LOCK = threading.Lock()
 
 def parked_bytes() -> int:
     """Device memory held by ranks of broken ``backend="device"`` communicators that were closed but
-    not freed, in bytes (a window, an out of twice its size and a packed buffer per rank)."""
+    not freed, in bytes (a window, an out of twice its size and two packed buffers per rank)."""
     with _PARKED_LOCK:
-        return sum(3 * int(r.capacity_bytes) + int(r.packed_bytes) for r in _PARKED)
+        return sum(3 * int(r.capacity_bytes) + 2 * int(r.packed_bytes) for r in _PARKED)
 
 
 class _DeviceBackend:
-    """One rank's phase calls on its own device: ``_probe.PeerRank`` holds the window, the out, the packed
-    buffer and the stream, and launches the K7 kernels over the peers' addresses."""
+    """One rank's phase calls on its own device: ``_probe.PeerRank`` holds the window, the out, the two packed
+    buffers and the stream, and launches the K7 kernels over the peers' addresses."""
 
     def __init__(self, rank: int, world: int, device: int, capacity_bytes: int):
         from .._native import load
@@ -317,11 +365,11 @@ class _DeviceBackend:
     def record(self) -> Dict[str, int]:
         """What this rank publishes to its peers.  ``pid`` says whose address space the addresses are in."""
         return {"pid": os.getpid(), "device": self.device, "window": int(self.r.window_ptr()), "out": int(self.r.out_ptr()),
-                "packed": int(self.r.packed_ptr())}
+                "packed": int(self.r.packed_ptr()), "packed_out": int(self.r.packed_out_ptr())}
 
     def open_peers(self, records: Sequence[Dict[str, int]]) -> None:
         self.r.open_peers([int(p["device"]) for p in records], [int(p["window"]) for p in records], [int(p["out"]) for p in records],
-                          [int(p["packed"]) for p in records])
+                          [int(p["packed"]) for p in records], [int(p["packed_out"]) for p in records])
 
     def close_peers(self) -> None:
         self.r.close_peers()
@@ -356,6 +404,12 @@ class _DeviceBackend:
 
     def reduce_q8(self, b0: int, b1: int, out_dtype: str, scale: float) -> None:
         self.r.reduce_q8(b0, b1, out_dtype, scale)
+
+    def repack_q8(self, b0: int, b1: int, scale: float) -> None:
+        self.r.repack_q8(b0, b1, scale)
+
+    def unpack_q8(self, slices: Sequence[Tuple[int, int]], out_dtype: str) -> None:
+        self.r.unpack_q8([(int(a), int(b)) for a, b in slices], out_dtype)
 
     def gather(self, slices: Sequence[Tuple[int, int]]) -> None:
         self.r.gather([(int(a), int(b)) for a, b in slices])
@@ -525,17 +579,19 @@ class PeerComm:
         if algo not in ALGOS:
             raise ValueError(f"algo must be oneshot|twoshot, got {algo!r}")
         if wire not in WIRES:
-            raise ValueError(f'wire must be None, "native" or "fp8", got {wire!r}')
+            raise ValueError(f'wire must be None, "native", "fp8" or "fp8x2", got {wire!r}')
+        if wire == "fp8x2" and (op != "all_reduce" or algo != "twoshot"):
+            raise ValueError('wire="fp8x2" packs the gather phase of all_reduce(algo="twoshot"): nothing else has one')
         if count < 1:
             raise ValueError("count >= 1")
         scale = float(np.float32(scale))
         desc = {"op": op, "count": int(count), "dtype": dtype, "out_dtype": out, "algo": algo, "scale": scale}
-        if wire == "fp8":
+        if wire in ("fp8", "fp8x2"):
             n = q8_blocks(count)
             if n * Q8_BLOCK * _ELEM[dtype] > self.capacity_bytes:
                 raise ValueError(f"{count} {dtype} elements, rounded up to blocks of {Q8_BLOCK}, exceed the window of "
                                  f"{self.capacity_bytes} bytes")
-            return n, out, scale, {**desc, "wire": "fp8"}
+            return n, out, scale, {**desc, "wire": wire}
         n = _n_vec(count, dtype)
         if n * 16 > self.capacity_bytes:
             raise ValueError(f"{count} {dtype} elements exceed the window of {self.capacity_bytes} bytes")
@@ -544,8 +600,19 @@ class PeerComm:
     def all_reduce(self, count: int, dtype: str = "bf16", algo: str = "twoshot", out_dtype: Optional[str] = None,
                    scale: float = 1.0, wire: Optional[str] = None) -> None:
         """out[0, count) of every rank = ``scale`` x the sum over ranks of window[0, count), in ``out_dtype``.
-        ``wire="fp8"``: of the windows' packed forms (see the module docstring)."""
+        ``wire="fp8"``: of the windows' packed forms; ``wire="fp8x2"`` (two-shot only): the same, packed once more
+        for the gather (see the module docstring)."""
         n, out, scale, desc = self._reduce_args("all_reduce", count, dtype, algo, out_dtype, scale, wire)
+        if wire == "fp8x2":
+            plan = q8_slices(n, self.world)
+            self._b.quantize(0, n, count, dtype)
+            self._enter(desc)
+            self._b.repack_q8(*plan[self.rank], scale)
+            self._leave()
+            # every slice comes from its owner's packed_out, this rank's own too; as below, no barrier after it
+            self._b.unpack_q8(plan, out)
+            self._b.synchronize()
+            return
         if wire == "fp8":
             per = Q8_BLOCK * _ELEM[out] // 16  # output vectors per block
             plan = q8_slices(n, self.world)
@@ -707,6 +774,14 @@ def selftest_cases_q8(k: int, counts: Optional[Sequence[int]] = None) -> List[Di
     return cases
 
 
+def selftest_cases_q8x2(k: int, counts: Optional[Sequence[int]] = None) -> List[Dict[str, object]]:
+    """The fp8x2 wire's cases: the two-shot ``all_reduce``, the three dtype pairs (the wide one with
+    ``scale = 1 / k``), at every count of :func:`selftest_counts_q8`."""
+    return [{"op": "all_reduce", "count": count, "dtype": dtype, "out_dtype": out, "algo": "twoshot", "scale": scale, "wire": "fp8x2"}
+            for count in (selftest_counts_q8(k) if counts is None else counts)
+            for dtype, out, scale in (("bf16", "bf16", 1.0), ("fp32", "fp32", 1.0), ("bf16", "fp32", 1.0 / k))]
+
+
 def case_input(case_index: int, issue: int, rank: int, count: int, dtype: str) -> np.ndarray:
     """Rank ``rank``'s N(0, 1) input of the ``issue``-th issue of case ``case_index``; any rank can make any rank's."""
     rng = np.random.default_rng([case_index, issue, rank, count])
@@ -721,6 +796,10 @@ def run_case(comm: PeerComm, case: Dict[str, object], inputs: Sequence[np.ndarra
 
     op, count, dtype, out = case["op"], int(case["count"]), case["dtype"], case["out_dtype"]
     k, r = comm.world, comm.rank
+    if case.get("wire") == "fp8x2":
+        comm.write(inputs[r])
+        comm.all_reduce(count, dtype, case["algo"], out, case["scale"], wire="fp8x2")
+        return comm.read(0, count, out), allreduce_q8x2_ref(inputs, dtype, out, case["scale"])
     if case.get("wire") == "fp8":
         comm.write(inputs[r])
         if op == "all_reduce":
@@ -833,8 +912,9 @@ def thread_sweep(devices: Sequence[int], sizes: Sequence[int], dtype: str = "bf1
     result back.  ``time_us`` is host time per call, the slowest rank's: the clock starts after a barrier
     and stops when the last call has returned.  ``barrier_us`` is the mean over ranks of the host time
     per call spent inside the call's two barriers.  ``wrong`` counts, over all ranks, the elements
-    whose bits differ from ``allreduce_ref`` (``wire="fp8"``: from ``allreduce_q8_ref``, and the rows carry
-    ``"wire"``); the check runs on the host, so sizes should stay moderate."""
+    whose bits differ from ``allreduce_ref`` (``wire="fp8"``: from ``allreduce_q8_ref``, ``wire="fp8x2"``: from
+    ``allreduce_q8x2_ref``, and the rows carry ``"wire"``; ``"fp8x2"`` runs the two-shot alone, so ``algo`` must be
+    ``twoshot`` or ``both``); the check runs on the host, so sizes should stay moderate."""
     if algo != "both" and algo not in ALGOS:
         raise ValueError(f"algo must be oneshot|twoshot|both, got {algo!r}")
     if dtype not in _ELEM:
@@ -842,10 +922,13 @@ def thread_sweep(devices: Sequence[int], sizes: Sequence[int], dtype: str = "bf1
     if iters < 1 or warmup_iters < 0:
         raise ValueError("iters >= 1, warmup_iters >= 0")
     if wire not in WIRES:
-        raise ValueError(f'wire must be None, "native" or "fp8", got {wire!r}')
-    fp8 = wire == "fp8"
+        raise ValueError(f'wire must be None, "native", "fp8" or "fp8x2", got {wire!r}')
+    if wire == "fp8x2" and algo == "oneshot":
+        raise ValueError('wire="fp8x2" packs the gather phase of a twoshot: algo must be twoshot or both')
+    fp8 = wire in ("fp8", "fp8x2")
+    algos = ("twoshot",) if wire == "fp8x2" else ALGOS if algo == "both" else (algo,)
     k, elem = len(devices), _ELEM[dtype]
-    points = [(max(1, int(nbytes) // elem), a) for nbytes in sizes for a in (ALGOS if algo == "both" else (algo,))]
+    points = [(max(1, int(nbytes) // elem), a) for nbytes in sizes for a in algos]
     if not points:
         return []
     once = _Once()
@@ -854,7 +937,7 @@ def thread_sweep(devices: Sequence[int], sizes: Sequence[int], dtype: str = "bf1
         rows = []
         for count, a in points:
             xs = once.get(("in", count), lambda: [case_input(0, 0, p, count, dtype) for p in range(k)], lambda o: o[1] == count)
-            ref = once.get(("ref", count), lambda: (allreduce_q8_ref if fp8 else allreduce_ref)(xs, dtype), lambda o: o[1] == count)
+            ref = once.get(("ref", count), lambda: _WIRE_REF[wire](xs, dtype), lambda o: o[1] == count)
             comm.write(xs[comm.rank])
             secs, in_barriers = timed_all_reduce(comm, count, dtype, a, iters, warmup_iters, wire)
             got = comm.read(0, count, dtype)
@@ -869,21 +952,22 @@ def thread_sweep(devices: Sequence[int], sizes: Sequence[int], dtype: str = "bf1
         gbps = count * elem / secs / 1e9
         out.append({"bytes": count * elem, "count": count, "time_us": secs * 1e6, "algbw_gbps": gbps,
                     "busbw_gbps": gbps * 2.0 * (k - 1) / k, "wrong": sum(r[i][2] for r in res), "backend": "peer", "algo": a,
-                    "ranks": "thread", "barrier_us": sum(r[i][1] for r in res) / k * 1e6, **({"wire": "fp8"} if fp8 else {})})
+                    "ranks": "thread", "barrier_us": sum(r[i][1] for r in res) / k * 1e6, **({"wire": wire} if fp8 else {})})
     return out
 
 
 def _case_capacity(k: int, cases: Sequence[Dict[str, object]]) -> int:
     """Window bytes the largest of ``cases`` needs (an all-gather holds every rank's slot)."""
     def vecs(c):
-        if c.get("wire") == "fp8":  # whole blocks
+        if c.get("wire") in ("fp8", "fp8x2"):  # whole blocks
             return q8_blocks(int(c["count"])) * Q8_BLOCK * _ELEM[c["dtype"]] // 16
         return _n_vec(int(c["count"]), c["dtype"]) * (k if c["op"] == "all_gather" else 1)
 
     return max(16, max(vecs(c) for c in cases) * 16)
 
 
-def selftest(devices: Sequence[int], counts: Optional[Sequence[int]] = None, timeout_s: float = 60.0) -> Dict[str, object]:
+def selftest(devices: Sequence[int], counts: Optional[Sequence[int]] = None, timeout_s: float = 60.0,
+             wire: Optional[str] = None) -> Dict[str, object]:
     """Every case of :func:`selftest_cases`, each issued twice in a row with different inputs, on
     thread ranks over ``devices`` (:func:`run_thread_ranks`), compared bit for bit with ``ops/peer_ref.py``.
 
@@ -892,10 +976,15 @@ def selftest(devices: Sequence[int], counts: Optional[Sequence[int]] = None, tim
     ``launches`` is the kernel launches of all ranks together.  Those keys describe the cases of
     :func:`selftest_cases`; the fp8 wire's (:func:`selftest_cases_q8`, at their own counts when ``counts`` is
     none) run after them on the same communicators and are reported as ``q8_cases``, ``q8_collectives``,
-    ``q8_wrong`` and ``q8_launches``.  ``barriers_per_collective`` covers both sets."""
+    ``q8_wrong`` and ``q8_launches``.  ``wire="fp8x2"`` adds the cases of :func:`selftest_cases_q8x2` after those,
+    reported as ``q8x2_cases``, ``q8x2_collectives``, ``q8x2_wrong`` and ``q8x2_launches``.
+    ``barriers_per_collective`` covers every set."""
+    if wire not in WIRES:
+        raise ValueError(f'wire must be None, "native", "fp8" or "fp8x2", got {wire!r}')
     k = len(devices)
     native = selftest_cases(k, counts)
-    cases = native + selftest_cases_q8(k, counts)
+    q8 = selftest_cases_q8(k, counts)
+    cases = native + q8 + (selftest_cases_q8x2(k, counts) if wire == "fp8x2" else [])
     once = _Once()  # every rank's inputs of (case, issue), made by the first rank that asks
 
     def inputs(ci: int, issue: int) -> List[np.ndarray]:
@@ -903,21 +992,28 @@ def selftest(devices: Sequence[int], counts: Optional[Sequence[int]] = None, tim
         return once.get((ci, issue), make, lambda o: o[0] >= ci - 1)  # ranks are never more than a collective apart
 
     def body(comm: PeerComm):
-        wrong, barriers, launches = set(), set(), 0
+        wrong, barriers, marks = set(), set(), {}
         for ci, case in enumerate(cases):
-            if ci == len(native):
-                launches = comm.launches
+            if ci in (len(native), len(native) + len(q8)):
+                marks[ci] = comm.launches
             for issue in range(2):
                 before = comm.barriers
                 got, ref = run_case(comm, case, inputs(ci, issue))
                 barriers.add(comm.barriers - before)
                 if got.dtype != ref.dtype or got.shape != ref.shape or not np.array_equal(_bits(got), _bits(ref)):
                     wrong.add((ci, issue))
-        return wrong, barriers, launches, comm.launches - launches
+        first_q8, end_q8 = marks[len(native)], marks.get(len(native) + len(q8), comm.launches)
+        return wrong, barriers, first_q8, end_q8 - first_q8, comm.launches - end_q8
 
     res = run_thread_ranks(devices, body, _case_capacity(k, cases), timeout_s=timeout_s)
     bad = set().union(*(r[0] for r in res))
-    n, nq = len(native), len(cases) - len(native)
-    return {"cases": n, "collectives": 2 * n, "wrong": sum(ci < n for ci, _ in bad),
-            "barriers_per_collective": sorted(set().union(*(r[1] for r in res))), "launches": sum(r[2] for r in res),
-            "q8_cases": nq, "q8_collectives": 2 * nq, "q8_wrong": sum(ci >= n for ci, _ in bad), "q8_launches": sum(r[3] for r in res)}
+    n, nq = len(native), len(q8)
+    rep = {"cases": n, "collectives": 2 * n, "wrong": sum(ci < n for ci, _ in bad),
+           "barriers_per_collective": sorted(set().union(*(r[1] for r in res))), "launches": sum(r[2] for r in res),
+           "q8_cases": nq, "q8_collectives": 2 * nq, "q8_wrong": sum(n <= ci < n + nq for ci, _ in bad),
+           "q8_launches": sum(r[3] for r in res)}
+    if wire == "fp8x2":
+        nx = len(cases) - n - nq
+        rep.update({"q8x2_cases": nx, "q8x2_collectives": 2 * nx, "q8x2_wrong": sum(ci >= n + nq for ci, _ in bad),
+                    "q8x2_launches": sum(r[4] for r in res)})
+    return rep
