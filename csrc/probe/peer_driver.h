@@ -194,6 +194,7 @@ struct PeerAllreduce {
   float scale = 1.0f;
   bool fp8 = false;                 // the wire: members read each other's packed buffers, not their `in`
   bool x2 = false;                  // fp8x2: phase 2 reads the members' second packed buffers, not their `out`
+  bool dry = false;                 // tests: a round records and waits for its events but launches no kernel
   size_t count = 0, n_vec = 0;      // n_vec: vectors of an `in`
   size_t n_blocks = 0;              // fp8: blocks of 32 elements, and `out` holds whole blocks
   std::vector<std::unique_ptr<DevBuf>> in[2], out;  // in[set][m]: rounds alternate between the sets
@@ -275,7 +276,7 @@ struct PeerAllreduce {
 
   // Phase 1 of member m over [v0, v1) of the plan's units: vectors of `in`, or blocks of the packed buffers.
   void reduce(int m, int set, size_t v0, size_t v1) {
-    if (v0 == v1) return;
+    if (v0 == v1 || dry) return;
     u32x4* dst = reinterpret_cast<u32x4*>(out[m]->p);
     if (x2)
       launch_peer_q8_repack(packs, k, q8_exp_vec(n_blocks), v0, v1, reinterpret_cast<u32x4*>(packed_out[m]->p), scale,
@@ -287,12 +288,14 @@ struct PeerAllreduce {
   }
 
   void quantize(int m, int set) {
+    if (dry) return;
     launch_peer_q8_quantize(types.in_bf16, srcs[set].p[m], reinterpret_cast<u32x4*>(packed[m]->p), q8_exp_vec(n_blocks), 0,
                             n_blocks, count, quantize_grid[m], ts[m]->s);
   }
 
   // Phase 2 of member m: the other members' slices of their `out`; fp8x2: every slice of the second packed buffers.
   void gather_phase(int m) {
+    if (dry) return;
     u32x4* dst = reinterpret_cast<u32x4*>(out[m]->p);
     if (x2)
       launch_peer_q8_unpack(types.out_bf16, unpack_set, k, q8_exp_vec(n_blocks), dst, gather_grid_[m], ts[m]->s);
@@ -350,6 +353,20 @@ struct PeerAllreduce {
     }
   }
 
+  // Every byte the rounds write before anything reads it, set to 0xFF: each member's `out` (NaN in every
+  // element as bf16 and as fp32) and the packed buffers of the fp8 wires (NaN codes, the largest exponent).
+  // None of them is written between hipMalloc and the first round, and the allocator may hand back a block
+  // that an earlier call freed holding the very sums the check looks for.  Before the rounds, synchronised.
+  void poison() {
+    for (int m = 0; m < k; ++m) {
+      DeviceGuard g(devs[m]);
+      HIP_CHECK(hipMemset(out[m]->p, 0xFF, out[m]->bytes));
+      if (fp8) HIP_CHECK(hipMemset(packed[m]->p, 0xFF, packed[m]->bytes));
+      if (x2) HIP_CHECK(hipMemset(packed_out[m]->p, 0xFF, packed_out[m]->bytes));
+      HIP_CHECK(hipDeviceSynchronize());
+    }
+  }
+
   // Elements of every member's `out` (padding included) that are not the sum of set `set`'s patterns.
   unsigned long long wrong(int set) {
     SeedSet seeds{};
@@ -383,7 +400,7 @@ struct PeerAllreduce {
 };
 
 py::dict peer_allreduce(const std::vector<int>& devs, size_t count, const std::string& dtype, const std::string& algo,
-                        int iters, int warmup, int blocks_per_cu, const std::string& wire) {
+                        int iters, int warmup, int blocks_per_cu, const std::string& wire, bool dry_run) {
   const PeerTypes types = peer_types(dtype, "");
   PeerAllreduce::check_args(devs, count, algo);
   const PeerWire w = peer_wire(wire, algo);
@@ -400,7 +417,9 @@ py::dict peer_allreduce(const std::vector<int>& devs, size_t count, const std::s
     // the last round's: a round that ran ahead of the one before it leaves a mix of the two sums
     const int total = warmup + iters;
     PeerAllreduce ar(devs, count, types, algo, total >= 2 ? 2 : 1, blocks_per_cu, 1.0f, w);
+    ar.dry = dry_run;
     for (int s = 0; s < ar.nsets; ++s) ar.fill(s);
+    ar.poison();
     t = time_member_rounds(devs, ar.ts, warmup, iters, [&](int r) { ar.round(r % ar.nsets); });
     wrong = ar.wrong((total - 1) % ar.nsets);
     if (fp8) {
@@ -438,6 +457,7 @@ py::dict peer_allreduce(const std::vector<int>& devs, size_t count, const std::s
   r["wrong"] = wrong;
   r["ok"] = wrong == 0;
   r["wire"] = wire;
+  r["dry_run"] = dry_run;
   if (fp8) {
     r["quantize_us"] = quantize_us;
     r["sum_us"] = sum_us;
@@ -486,6 +506,7 @@ py::list peer_allreduce_arrays(const std::vector<int>& devs, const std::vector<p
       HIP_CHECK(hipMemcpy(ar.in[0][m]->p, from[m], count * types.in_elem(), hipMemcpyHostToDevice));
       HIP_CHECK(hipDeviceSynchronize());
     }
+    ar.poison();
     for (int r = 0; r < rounds; ++r) ar.round(0);
     sync_streams(devs, ar.ts);
     for (int m = 0; m < k; ++m) {

@@ -228,12 +228,12 @@ struct CopyResult {
   int src, dst, exec, iters, grid;
   size_t bytes;
   std::string kind;
-  bool nontemporal, ok;
+  bool nontemporal, ok, dry_run;
   double ms_per_iter, gbps;
 };
 
 CopyResult copy_bw_impl(int src_dev, int dst_dev, int exec_dev, size_t bytes, int iters, int warmup,
-                        const std::string& kind, bool nontemporal, int blocks_per_cu) {
+                        const std::string& kind, bool nontemporal, int blocks_per_cu, bool dry_run = false) {
   check_bytes_iters(bytes, iters);
   if (exec_dev != src_dev && exec_dev != dst_dev) throw std::invalid_argument("exec_dev must be src or dst");
   check_devs({src_dev, dst_dev});
@@ -243,30 +243,38 @@ CopyResult copy_bw_impl(int src_dev, int dst_dev, int exec_dev, size_t bytes, in
   const size_t n_vec = bytes / 16;
   const unsigned int seed = 0x9e3779b9u ^ (unsigned)(src_dev * 131 + dst_dev);
   fill_pattern(src_dev, src.p, bytes, seed);
+  poison_pattern(dst_dev, dst.p, bytes, seed);
   const int grid = num_cus(exec_dev) * std::max(1, blocks_per_cu);
   float ms = 0.f;
   {
     DeviceGuard g(exec_dev);
-    ms = time_launches([&](hipStream_t s) { launch_copy(kind, nontemporal, src.p, dst.p, n_vec, grid, s); }, iters, warmup);
+    ms = time_launches([&](hipStream_t s) {
+      if (!dry_run) launch_copy(kind, nontemporal, src.p, dst.p, n_vec, grid, s);
+    }, iters, warmup);
   }
   const bool ok = holds_pattern(dst_dev, dst.p, bytes / 4, seed);
   // gbps = bytes copied per second (one direction over the link; for a self copy HBM moves 2x)
-  return CopyResult{src_dev, dst_dev, exec_dev, iters, grid, bytes, kind, nontemporal, ok, (double)ms / iters,
+  return CopyResult{src_dev, dst_dev, exec_dev, iters, grid, bytes, kind, nontemporal, ok, dry_run, (double)ms / iters,
                     gbps((double)bytes, ms, iters)};
 }
 
 // K5: aggregate ingress of `dst_dev` reading `bytes` from every device in `srcs` concurrently.
-// A source equal to dst_dev is a local stream (one buffer per entry), which lets a 1-GPU box check
-// the kernel's segment indexing; on a node the sources are the peers.
-py::dict gather_bw(int dst_dev, const std::vector<int>& srcs, size_t bytes, int iters, int warmup, int blocks_per_cu) {
+// A source equal to dst_dev is a local stream (one buffer per entry); on a node the sources are the
+// peers.  Every source is seeded by its slot in `srcs`, not by its device, and segment i is checked
+// against slot i's seed (`seeds` in the result): with a device repeated, the only form a 1-GPU box
+// can run, a gather that read one source for every segment or swapped two segments still fails.
+py::dict gather_bw(int dst_dev, const std::vector<int>& srcs, size_t bytes, int iters, int warmup, int blocks_per_cu,
+                   bool dry_run) {
   if (srcs.empty() || srcs.size() > (size_t)kMaxSrc) throw std::invalid_argument("1..16 source devices");
   check_bytes_iters(bytes, iters);
   check_dev(dst_dev);
   check_devs(srcs);
-  auto seed_of = [](int dev) { return 0x51ed27u ^ (unsigned)(dev * 977); };
+  auto seed_of = [](int slot) { return 0x51ed27u ^ (unsigned)(slot * 977 + 1); };
   float ms = 0.f;
   bool ok = true;
   const int nsrc = (int)srcs.size();
+  std::vector<unsigned int> seeds(nsrc);
+  for (int i = 0; i < nsrc; ++i) seeds[i] = seed_of(i);
   {
     py::gil_scoped_release nogil;
     for (int d : srcs) enable_peer(dst_dev, d);
@@ -274,25 +282,29 @@ py::dict gather_bw(int dst_dev, const std::vector<int>& srcs, size_t bytes, int 
     SrcSet set{};
     for (int i = 0; i < nsrc; ++i) {
       src_bufs.emplace_back(new DevBuf(srcs[i], bytes));
-      fill_pattern(srcs[i], src_bufs.back()->p, bytes, seed_of(srcs[i]));
+      fill_pattern(srcs[i], src_bufs.back()->p, bytes, seeds[i]);
       set.p[i] = reinterpret_cast<const u32x4*>(src_bufs.back()->p);
     }
     DevBuf dst(dst_dev, bytes * (size_t)nsrc);
+    for (int i = 0; i < nsrc; ++i) poison_pattern(dst_dev, (char*)dst.p + (size_t)i * bytes, bytes, seeds[i]);
     DeviceGuard g(dst_dev);
     const int grid = gather_grid(dst_dev, blocks_per_cu, nsrc);
     ms = time_launches([&](hipStream_t s) {
+      if (dry_run) return;
       hipLaunchKernelGGL(gather_lds_kernel, dim3(grid), dim3(kBlock), 0, s, set, nsrc, (u32x4*)dst.p, bytes / 16);
     }, iters, warmup);
     // every segment holds its source's pattern
     for (int i = 0; i < nsrc && ok; ++i)
-      ok = holds_pattern(dst_dev, (const char*)dst.p + (size_t)i * bytes, bytes / 4, seed_of(srcs[i]));
+      ok = holds_pattern(dst_dev, (const char*)dst.p + (size_t)i * bytes, bytes / 4, seeds[i]);
   }
   py::dict r;
   r["dst"] = dst_dev;
   r["srcs"] = srcs;
+  r["seeds"] = seeds;
   r["bytes_per_src"] = bytes;
   put_rate(r, (double)bytes * nsrc, ms, iters);
   r["ok"] = ok;
+  r["dry_run"] = dry_run;
   return r;
 }
 
@@ -305,7 +317,7 @@ py::dict gather_bw(int dst_dev, const std::vector<int>& srcs, size_t bytes, int 
 // ring bound is the slowest member (a ring all-reduce's busBW is every member's ingress rate, so
 // the slowest one caps it).  Members may repeat a device: on one GPU that checks the indexing.
 py::dict ring_bw(const std::vector<int>& devs, const std::vector<std::vector<int>>& peers, size_t bytes, int iters,
-                 int warmup, int blocks_per_cu) {
+                 int warmup, int blocks_per_cu, bool dry_run) {
   const int k = (int)devs.size();
   if (k < 2 || k > kMaxSrc + 1) throw std::invalid_argument("2..17 ring members");
   if ((int)peers.size() != k) throw std::invalid_argument("one peer list per member");
@@ -328,6 +340,8 @@ py::dict ring_bw(const std::vector<int>& devs, const std::vector<std::vector<int
       src.emplace_back(new DevBuf(devs[m], bytes));
       inbox.emplace_back(new DevBuf(devs[m], bytes * peers[m].size()));
       fill_pattern(devs[m], src[m]->p, bytes, seed_of(m));
+      for (size_t i = 0; i < peers[m].size(); ++i)
+        poison_pattern(devs[m], (char*)inbox[m]->p + i * bytes, bytes, seed_of(peers[m][i]));
     }
     std::vector<SrcSet> sets(k);
     std::vector<int> grid(k);
@@ -340,7 +354,7 @@ py::dict ring_bw(const std::vector<int>& devs, const std::vector<std::vector<int
       ts.emplace_back(new TimedStream());
     }
     t = time_member_rounds(devs, ts, warmup, iters, [&](int) {
-      for (int m = 0; m < k; ++m) {
+      for (int m = 0; m < k && !dry_run; ++m) {
         DeviceGuard g(devs[m]);
         hipLaunchKernelGGL(gather_lds_kernel, dim3(grid[m]), dim3(kBlock), 0, ts[m]->s, sets[m], (int)peers[m].size(),
                            (u32x4*)inbox[m]->p, bytes / 16);
@@ -360,8 +374,11 @@ py::dict ring_bw(const std::vector<int>& devs, const std::vector<std::vector<int
     gbps[m] = (double)bytes * peers[m].size() * iters / (t.ms_member[m] / 1e3) / 1e9;
     bound = (m == 0) ? gbps[m] : std::min(bound, gbps[m]);
   }
+  std::vector<unsigned int> seeds(k);
+  for (int m = 0; m < k; ++m) seeds[m] = seed_of(m);
   r["devs"] = devs;
   r["peers"] = peers;
+  r["seeds"] = seeds;
   r["bytes_per_peer"] = bytes;
   r["iters"] = iters;
   r["ms_member"] = t.ms_member;
@@ -369,6 +386,7 @@ py::dict ring_bw(const std::vector<int>& devs, const std::vector<std::vector<int
   r["ingress_gbps"] = gbps;
   r["bound_gbps"] = bound;
   r["ok"] = ok;
+  r["dry_run"] = dry_run;
   return r;
 }
 
@@ -557,15 +575,16 @@ py::dict to_dict(const CopyResult& c) {
   r["ms_per_iter"] = c.ms_per_iter;
   r["gbps"] = c.gbps;
   r["ok"] = c.ok;
+  r["dry_run"] = c.dry_run;
   return r;
 }
 
 py::dict copy_bw(int src_dev, int dst_dev, int exec_dev, size_t bytes, int iters, int warmup, const std::string& kind,
-                 bool nontemporal, int blocks_per_cu) {
+                 bool nontemporal, int blocks_per_cu, bool dry_run) {
   CopyResult c;
   {
     py::gil_scoped_release nogil;
-    c = copy_bw_impl(src_dev, dst_dev, exec_dev, bytes, iters, warmup, kind, nontemporal, blocks_per_cu);
+    c = copy_bw_impl(src_dev, dst_dev, exec_dev, bytes, iters, warmup, kind, nontemporal, blocks_per_cu, dry_run);
   }
   return to_dict(c);
 }
@@ -711,6 +730,17 @@ class IpcBuffer {
     py::gil_scoped_release nogil;
     return holds_pattern(buf_.dev, buf_.p, buf_.bytes / 4, seed);
   }
+  // The count holds() compares with 0: words that differ from pattern(seed).
+  unsigned long long mismatches(unsigned int seed) const {
+    py::gil_scoped_release nogil;
+    return pattern_mismatches(buf_.dev, buf_.p, buf_.bytes / 4, seed);
+  }
+  // One word of the buffer overwritten from the host (tests of the verifier: a single wrong word is counted).
+  void poke(size_t word_index, unsigned int value) {
+    if (word_index >= buf_.bytes / 4) throw std::out_of_range("poke: word index outside the buffer");
+    DeviceGuard g(buf_.dev);
+    HIP_CHECK(hipMemcpy((unsigned int*)buf_.p + word_index, &value, sizeof(value), hipMemcpyHostToDevice));
+  }
 
  private:
   DevBuf buf_;
@@ -743,7 +773,8 @@ struct IpcMappings {
 // One imported buffer and one local buffer of `dev`, the K1 LDS-DMA kernel between them.
 //   write (K2 over IPC): the kernel pushes a local patterned buffer into another process's buffer
 //     through the imported mapping (remote stores, the direction RCCL's P2P write protocol uses).  The
-//     owner checks the result (IpcBuffer.holds), since only it knows the write has landed in its memory.
+//     owner checks the result (IpcBuffer.holds), since only it knows the write has landed in its memory;
+//     the destination holds the owner's own pattern, so the caller pushes another seed (`gtk ipc` does).
 //   read: the imported buffer is streamed into the local one, which is then verified against `seed`.
 py::dict ipc_copy_bw(bool write, const py::bytes& handle, int dev, size_t bytes, unsigned int seed, int iters, int warmup,
                      int blocks_per_cu) {
@@ -755,7 +786,10 @@ py::dict ipc_copy_bw(bool write, const py::bytes& handle, int dev, size_t bytes,
     py::gil_scoped_release nogil;
     DeviceGuard g(dev);
     DevBuf local(dev, bytes);
-    if (write) fill_pattern(dev, local.p, bytes, seed);
+    if (write)
+      fill_pattern(dev, local.p, bytes, seed);
+    else
+      poison_pattern(dev, local.p, bytes, seed);
     const void* src = write ? local.p : map.p[0];
     void* dst = write ? map.p[0] : local.p;
     const int grid = num_cus(dev) * std::max(1, blocks_per_cu);
@@ -797,6 +831,7 @@ py::dict ipc_gather_bw(const std::vector<py::bytes>& handles, int dev, size_t by
     SrcSet set{};
     for (int i = 0; i < nsrc; ++i) set.p[i] = reinterpret_cast<const u32x4*>(map.p[i]);
     DevBuf inbox(dev, bytes * (size_t)nsrc);
+    for (int i = 0; i < nsrc; ++i) poison_pattern(dev, (char*)inbox.p + (size_t)i * bytes, bytes, seeds[i]);
     const int grid = gather_grid(dev, blocks_per_cu, nsrc);
     ms = time_launches([&](hipStream_t s) {
       hipLaunchKernelGGL(gather_lds_kernel, dim3(grid), dim3(kBlock), 0, s, set, nsrc, (u32x4*)inbox.p, bytes / 16);
@@ -822,17 +857,18 @@ PYBIND11_MODULE(_probe, m) {
   m.def("can_access_peer", &can_access_peer, py::arg("a"), py::arg("b"));
   m.def("copy_bw", &copy_bw, py::arg("src_dev"), py::arg("dst_dev"), py::arg("exec_dev"), py::arg("bytes"),
         py::arg("iters") = 10, py::arg("warmup") = 2, py::arg("kind") = "lds", py::arg("nontemporal") = false,
-        py::arg("blocks_per_cu") = kBlocksPerCU);
+        py::arg("blocks_per_cu") = kBlocksPerCU, py::arg("dry_run") = false,
+        "K1/K2/K3; dry_run (tests only): everything but the copy launches, so ok says what the check makes of an idle kernel");
   m.def("gather_bw", &gather_bw, py::arg("dst_dev"), py::arg("srcs"), py::arg("bytes") = (size_t)64 << 20,
-        py::arg("iters") = 3, py::arg("warmup") = 1, py::arg("blocks_per_cu") = kBlocksPerCU);
+        py::arg("iters") = 3, py::arg("warmup") = 1, py::arg("blocks_per_cu") = kBlocksPerCU, py::arg("dry_run") = false);
   m.def("ring_bw", &ring_bw, py::arg("devs"), py::arg("peers"), py::arg("bytes") = (size_t)64 << 20, py::arg("iters") = 3,
-        py::arg("warmup") = 1, py::arg("blocks_per_cu") = kBlocksPerCU);
+        py::arg("warmup") = 1, py::arg("blocks_per_cu") = kBlocksPerCU, py::arg("dry_run") = false);
   m.def("peer_allreduce", &peer_allreduce, py::arg("devs"), py::arg("count"), py::arg("dtype") = "bf16",
         py::arg("algo") = "twoshot", py::arg("iters") = 3, py::arg("warmup") = 1, py::arg("blocks_per_cu") = kBlocksPerCU,
-        py::arg("wire") = "native",
+        py::arg("wire") = "native", py::arg("dry_run") = false,
         "K7: timed all-reduce (sum) of device-made inputs over peer pointers; every member's result checked; "
         "wire=\"fp8\": members read each other's block-scaled e4m3 form (peer_q8.h); wire=\"fp8x2\" (twoshot): the "
-        "gather phase reads packed sums too");
+        "gather phase reads packed sums too; dry_run (tests only): everything but the kernels of the rounds");
   m.def("peer_allreduce_arrays", &peer_allreduce_arrays, py::arg("devs"), py::arg("inputs"), py::arg("dtype") = "bf16",
         py::arg("algo") = "twoshot", py::arg("rounds") = 1, py::arg("out_dtype") = py::none(), py::arg("scale") = 1.0f,
         py::arg("wire") = "native",
@@ -861,6 +897,8 @@ PYBIND11_MODULE(_probe, m) {
       .def(py::init<int, size_t, unsigned int>(), py::arg("dev"), py::arg("bytes"), py::arg("seed") = 0x5eedu)
       .def("handle", &IpcBuffer::handle)
       .def("holds", &IpcBuffer::holds, py::arg("seed"), "does the buffer hold pattern(seed)? (after a peer's IPC write)")
+      .def("mismatches", &IpcBuffer::mismatches, py::arg("seed"), "words that differ from pattern(seed)")
+      .def("poke", &IpcBuffer::poke, py::arg("word_index"), py::arg("value"), "overwrite one 32-bit word")
       .def_property_readonly("bytes", &IpcBuffer::bytes)
       .def_property_readonly("seed", &IpcBuffer::seed);
   m.def("ipc_write_bw", &ipc_write_bw, py::arg("handle"), py::arg("dev"), py::arg("bytes"), py::arg("seed"),

@@ -252,6 +252,12 @@ void fill_pattern(int dev, void* p, size_t bytes, unsigned int seed) {
   HIP_CHECK(hipDeviceSynchronize());
 }
 
+// A destination that will be checked against pattern(seed), before anything is launched into it:
+// pattern(~seed), which differs from pattern(seed) in every bit of every word.  hipMalloc may hand back
+// a block that an earlier call freed holding the very pattern the check looks for; after this only the
+// launches under test can make a word right.  Synchronised, so none of it falls into a timed section.
+void poison_pattern(int dev, void* p, size_t bytes, unsigned int seed) { fill_pattern(dev, p, bytes, ~seed); }
+
 // What one kernel on `dev` counts: `launch(counter)` starts it on the null stream with a cleared
 // 8-byte counter of that device, which is then copied back.
 template <class F>
@@ -266,12 +272,16 @@ unsigned long long count_on_device(int dev, F launch) {
   return n;
 }
 
-// Does p[0, n_words), memory of `dev`, hold pattern(seed) in every word?  One pass on the device.
-bool holds_pattern(int dev, const void* p, size_t n_words, unsigned int seed) {
-  return 0 == count_on_device(dev, [&](unsigned long long* bad) {
+// Words of p[0, n_words), memory of `dev`, that differ from pattern(seed).  One pass on the device.
+unsigned long long pattern_mismatches(int dev, const void* p, size_t n_words, unsigned int seed) {
+  return count_on_device(dev, [&](unsigned long long* bad) {
     hipLaunchKernelGGL(pattern_mismatch_kernel, dim3(num_cus(dev) * kBlocksPerCU), dim3(kBlock), 0, 0,
                        (const unsigned int*)p, n_words, seed, bad);
   });
+}
+
+bool holds_pattern(int dev, const void* p, size_t n_words, unsigned int seed) {
+  return 0 == pattern_mismatches(dev, p, n_words, seed);
 }
 
 }  // namespace

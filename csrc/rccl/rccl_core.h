@@ -146,6 +146,16 @@ struct RankState {
     RCCL_HIP_CHECK(hipGetLastError());
   }
 
+  // `recv` persists from call to call and the fill and the check depend on the element index alone, so
+  // after one good all-reduce it already holds what the next check looks for.  Stream-ordered 0xFF bytes
+  // over the elements about to be checked: NaN in every element as bf16, fp16 and fp32, and the check counts
+  // each one, so only the all-reduce that follows can make it pass.  For the out-of-place check alone (in
+  // place, `send` is refilled by fill()), never for step(), capture(), replay() or a timed loop.
+  void poison(size_t count, ncclDataType_t t) {
+    set_device();
+    RCCL_HIP_CHECK(hipMemsetAsync(recv, 0xFF, count * elem_size(t), stream));
+  }
+
   unsigned long long check(size_t count, ncclDataType_t t, bool inplace) {
     set_device();
     unsigned long long* d_bad = nullptr;
@@ -200,6 +210,7 @@ struct SweepPoint {
   size_t count = 0;
   double time_us = 0, algbw = 0, busbw = 0;
   unsigned long long wrong = 0;
+  bool dry_run = false;
 };
 
 // ---------------------------------------------------------------------------------- single process
@@ -225,7 +236,10 @@ class LocalGroup {
   LocalGroup(const LocalGroup&) = delete;
   LocalGroup& operator=(const LocalGroup&) = delete;
 
-  SweepPoint run(size_t bytes, const std::string& dtype, int iters, int warmup, bool inplace, bool check) {
+  // `dry_run` (tests only): everything but the all-reduces, so `wrong` says what the check makes of a
+  // collective that did nothing.
+  SweepPoint run(size_t bytes, const std::string& dtype, int iters, int warmup, bool inplace, bool check,
+                 bool dry_run = false) {
     size_t elem = 0;
     ncclDataType_t t = parse_dtype(dtype, &elem);
     const size_t count = std::max<size_t>(1, bytes / elem);
@@ -234,8 +248,13 @@ class LocalGroup {
     SweepPoint p;
     p.bytes = bytes;
     p.count = count;
+    p.dry_run = dry_run;
+    dry_run_ = dry_run;
     if (check) {
-      for (auto& r : ranks_) r.fill(count, t);
+      for (auto& r : ranks_) {
+        r.fill(count, t);
+        if (!inplace) r.poison(count, t);
+      }
       launch_all(count, t, inplace);
       sync_all();
       for (auto& r : ranks_) p.wrong += r.check(count, t, inplace);
@@ -277,6 +296,7 @@ class LocalGroup {
 
  private:
   void launch_all(size_t count, ncclDataType_t t, bool inplace) {
+    if (dry_run_) return;
     NCCL_CHECK(ncclGroupStart());
     for (auto& r : ranks_) {
       r.set_device();
@@ -291,6 +311,7 @@ class LocalGroup {
     }
   }
   std::vector<RankState> ranks_;
+  bool dry_run_ = false;  // of the run() in progress
 };
 
 inline std::vector<size_t> size_sweep(size_t min_bytes, size_t max_bytes, int factor) {

@@ -73,10 +73,15 @@ class Comm {
   }
 
   // Fresh fill + one all-reduce + exact check; returns the number of wrong elements on this rank.
-  unsigned long long check(bool inplace) {
+  // `dry_run` (tests only, one rank: the other ranks of a larger communicator would wait for this one)
+  // leaves the all-reduce out, so the count says what the check makes of a collective that did nothing.
+  unsigned long long check(bool inplace, bool dry_run) {
     if (!count_) throw std::runtime_error("prepare() first");
+    if (dry_run && st_.nranks != 1) throw std::invalid_argument("check(dry_run=True) is for a one-rank communicator");
+    st_.set_device();
     st_.fill(count_, t_);
-    st_.allreduce(count_, t_, inplace);
+    if (!inplace) st_.poison(count_, t_);
+    if (!dry_run) st_.allreduce(count_, t_, inplace);
     return st_.check(count_, t_, inplace);
   }
 
@@ -141,6 +146,23 @@ class Comm {
     return py::bytes(host);
   }
 
+  // The mirror of read_result: `data`, whole elements, over the result from element `first` on, copied
+  // behind the work already on the stream (tests of the verifier and of what a replay rewrites).
+  void write_result(size_t first, const py::bytes& data, bool inplace) {
+    if (!count_ || !st_.send || !st_.recv) throw std::runtime_error("prepare() first");
+    const std::string host = data;
+    if (host.size() % elem_) throw std::invalid_argument("write_result: data must be whole elements");
+    const size_t n = host.size() / elem_;
+    if (first > count_ || n > count_ - first) throw std::out_of_range("write_result: range outside the prepared buffer");
+    if (n) {
+      py::gil_scoped_release nogil;
+      st_.set_device();
+      char* dst = static_cast<char*>(inplace ? st_.send : st_.recv) + first * elem_;
+      RCCL_HIP_CHECK(hipMemcpyAsync(dst, host.data(), n * elem_, hipMemcpyHostToDevice, st_.stream));
+      RCCL_HIP_CHECK(hipStreamSynchronize(st_.stream));
+    }
+  }
+
   size_t bytes() const { return count_ * elem_; }
   size_t count() const { return count_; }
   int rank() const { return st_.rank; }
@@ -194,12 +216,12 @@ py::bytes unique_id() {
 }
 
 py::list local_sweep(const std::vector<int>& devs, const std::vector<size_t>& sizes, const std::string& dtype, int iters,
-                     int warmup, bool inplace, bool check) {
+                     int warmup, bool inplace, bool check, bool dry_run) {
   std::vector<SweepPoint> pts;
   {
     py::gil_scoped_release nogil;
     LocalGroup g(devs);
-    for (size_t b : sizes) pts.push_back(g.run(b, dtype, iters, warmup, inplace, check));
+    for (size_t b : sizes) pts.push_back(g.run(b, dtype, iters, warmup, inplace, check, dry_run));
   }
   py::list out;
   for (const auto& p : pts) {
@@ -210,6 +232,7 @@ py::list local_sweep(const std::vector<int>& devs, const std::vector<size_t>& si
     d["algbw_gbps"] = p.algbw;
     d["busbw_gbps"] = p.busbw;
     d["wrong"] = p.wrong;
+    d["dry_run"] = p.dry_run;
     out.append(d);
   }
   return out;
@@ -230,7 +253,7 @@ PYBIND11_MODULE(_rccl, m) {
   m.def("bus_factor", &bus_factor, py::arg("k"));
   m.def("size_sweep", &size_sweep, py::arg("min_bytes"), py::arg("max_bytes"), py::arg("factor") = 2);
   m.def("local_sweep", &local_sweep, py::arg("devs"), py::arg("sizes"), py::arg("dtype") = "bf16", py::arg("iters") = 20,
-        py::arg("warmup") = 5, py::arg("inplace") = false, py::arg("check") = true);
+        py::arg("warmup") = 5, py::arg("inplace") = false, py::arg("check") = true, py::arg("dry_run") = false);
   py::class_<Comm>(m, "Comm")
       .def(py::init<py::bytes, int, int, int, int, int>(), py::arg("uid"), py::arg("nranks"), py::arg("rank"),
            py::arg("device"), py::arg("min_ctas") = 0, py::arg("max_ctas") = 0)
@@ -242,9 +265,11 @@ PYBIND11_MODULE(_rccl, m) {
       .def_property_readonly("graph_ops", &Comm::graph_ops)
       .def("verify", &Comm::verify, py::call_guard<py::gil_scoped_release>())
       .def("synchronize", &Comm::synchronize, py::call_guard<py::gil_scoped_release>())
-      .def("check", &Comm::check, py::arg("inplace") = false, py::call_guard<py::gil_scoped_release>())
+      .def("check", &Comm::check, py::arg("inplace") = false, py::arg("dry_run") = false,
+           py::call_guard<py::gil_scoped_release>())
       .def("destroy", &Comm::destroy, py::call_guard<py::gil_scoped_release>())
       .def("read_result", &Comm::read_result, py::arg("first"), py::arg("n"), py::arg("inplace") = false)
+      .def("write_result", &Comm::write_result, py::arg("first"), py::arg("data"), py::arg("inplace") = false)
       .def_property_readonly("bytes", &Comm::bytes)
       .def_property_readonly("count", &Comm::count)
       .def_property_readonly("rank", &Comm::rank)

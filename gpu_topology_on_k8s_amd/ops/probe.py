@@ -69,14 +69,19 @@ def warmup(dev: int, ms: float = 50.0, random_operands: bool = False) -> Dict[st
 
 
 def copy_bw(src: int, dst: int, nbytes: int = 256 << 20, iters: int = 10, warmup_iters: int = 2, mode: str = "read",
-            kind: str = "lds", nontemporal: bool = False, blocks_per_cu: int = 8) -> Dict[str, object]:
+            kind: str = "lds", nontemporal: bool = False, blocks_per_cu: int = 8, dry_run: bool = False) -> Dict[str, object]:
+    """K1/K2/K3.  ``dry_run`` (tests only) does everything but launch the copy, here and in the other entry
+    points that take it: ``ok`` then says what the check makes of a kernel that did nothing."""
     exec_dev = dst if mode == "read" else src
-    return dict(_p().copy_bw(src, dst, exec_dev, int(nbytes), int(iters), int(warmup_iters), kind, bool(nontemporal), int(blocks_per_cu)))
+    return dict(_p().copy_bw(src, dst, exec_dev, int(nbytes), int(iters), int(warmup_iters), kind, bool(nontemporal),
+                             int(blocks_per_cu), dry_run=bool(dry_run)))
 
 
-def gather_bw(dst: int, srcs: Sequence[int], nbytes: int = 64 << 20, iters: int = 3, warmup_iters: int = 1) -> Dict[str, object]:
+def gather_bw(dst: int, srcs: Sequence[int], nbytes: int = 64 << 20, iters: int = 3, warmup_iters: int = 1,
+              dry_run: bool = False) -> Dict[str, object]:
     """K5: one kernel on ``dst`` reads ``nbytes`` from every device in ``srcs`` at once (aggregate ingress)."""
-    return dict(_p().gather_bw(int(dst), [int(s) for s in srcs], int(nbytes), int(iters), int(warmup_iters)))
+    return dict(_p().gather_bw(int(dst), [int(s) for s in srcs], int(nbytes), int(iters), int(warmup_iters),
+                               dry_run=bool(dry_run)))
 
 
 def ring_peers(k: int, pattern: str = "all") -> List[List[int]]:
@@ -93,10 +98,11 @@ def ring_peers(k: int, pattern: str = "all") -> List[List[int]]:
 
 
 def ring_bw(devs: Sequence[int], pattern: str = "all", nbytes: int = 64 << 20, iters: int = 3,
-            warmup_iters: int = 1) -> Dict[str, object]:
+            warmup_iters: int = 1, dry_run: bool = False) -> Dict[str, object]:
     """K6: every member (HIP ordinal ``devs[m]``) gathers from its ``pattern`` peers at the same time;
     ``bound_gbps`` = the slowest member's ingress (the ceiling of a ring all-reduce's busBW)."""
-    r = dict(_p().ring_bw([int(d) for d in devs], ring_peers(len(devs), pattern), int(nbytes), int(iters), int(warmup_iters)))
+    r = dict(_p().ring_bw([int(d) for d in devs], ring_peers(len(devs), pattern), int(nbytes), int(iters), int(warmup_iters),
+                          dry_run=bool(dry_run)))
     r["pattern"] = pattern
     return r
 
@@ -141,7 +147,8 @@ PEER_ALGOS = ("oneshot", "twoshot")
 
 
 def peer_allreduce(devs: Sequence[int], count: int, dtype: str = "bf16", algo: str = "twoshot", iters: int = 3,
-                   warmup_iters: int = 1, blocks_per_cu: int = 8, wire: str = "native") -> Dict[str, object]:
+                   warmup_iters: int = 1, blocks_per_cu: int = 8, wire: str = "native",
+                   dry_run: bool = False) -> Dict[str, object]:
     """K7: all-reduce (sum) of ``count`` elements over the members ``devs`` (HIP ordinals, which may
     repeat) by this repository's own peer kernels, timed like ``_rccl.local_sweep`` (``algbw_gbps``,
     ``busbw_gbps`` = algBW x 2(k-1)/k) and checked on every member (``wrong``, ``ok``).
@@ -154,7 +161,7 @@ def peer_allreduce(devs: Sequence[int], count: int, dtype: str = "bf16", algo: s
     are then values in {-1, 0}, whose sums survive the second packing, and ``gather_us`` is member 0's unpack
     kernel timed alone."""
     return dict(_p().peer_allreduce([int(d) for d in devs], int(count), dtype, algo, int(iters), int(warmup_iters),
-                                    int(blocks_per_cu), wire))
+                                    int(blocks_per_cu), wire, bool(dry_run)))
 
 
 def peer_q8_quantize(dev: int, array: np.ndarray, dtype: str = "bf16", count: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:

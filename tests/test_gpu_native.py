@@ -125,6 +125,8 @@ def test_gather_kernel_segments(probe_mod):
     sources are local here; on a node they are the peers, same kernel); odd size exercises tails."""
     r = probe_mod.gather_bw(0, [0, 0, 0], (16 << 20) + 4112, 2, 1)
     assert r["ok"] and r["bytes_per_src"] == (16 << 20) + 4112
+    # seeded by slot, not by device: three different segments, so one read three times or two swapped fail
+    assert len(r["seeds"]) == 3 and len(set(r["seeds"])) == 3, r
 
 
 def test_gather_kernel_rate(probe_mod):
