@@ -2,7 +2,8 @@
 """The peer communicator's thread-rank all_reduce next to the in-process driver's, as one JSON document:
 
     python bench/peer_comm_bench.py [--members 0,0,0,0] [--sizes-mib 1,4,16,64,256] [--dtype bf16]
-                                    [--iters 20] [--warmup 2] [--wire native|fp8|fp8x2] [--out FILE] [--md FILE]
+                                    [--iters 20] [--warmup 2] [--wire native|fp8|fp8x2] [--error-feedback]
+                                    [--out FILE] [--md FILE]
 
 Both run the same K7 kernels on the same members at the same count, in one process:
   * thread ranks (``PeerComm(backend="device")``, one thread per member): host time per ``all_reduce``
@@ -15,6 +16,11 @@ repetition of each is reported.  Their ratio is the price of host-synchronous or
 trips and two (two-shot: three) stream synchronisations per call.  Members that repeat a device give
 HBM rates of that one GPU, not xGMI rates.  ``--wire fp8`` runs both on the fp8 wire: every rank packs its
 window first and the ranks read the packed forms; ``--wire fp8x2`` the two-shot alone, its gather phase packed too.
+
+``--error-feedback`` measures something else: the thread ranks' fp8 ``reduce_scatter`` and two-shot ``all_reduce``
+with and without error feedback, the two alternated ``--reps`` times in one process, the quicker repetition of
+each reported.  The feedback form's quantize reads and writes the rank's fp32 residual next to the window; the
+link bytes, the launches and the barriers are the plain call's.  No driver run is made.
 """
 import argparse
 import json
@@ -81,6 +87,86 @@ def measure(devs, sizes, dtype, iters, warmup, reps, wire="native"):
             "reps": reps, "wire": wire, "sizes": out}
 
 
+EF_CALLS = ("reduce_scatter", "twoshot")
+
+
+def measure_ef(devs, sizes, dtype, iters, warmup, reps):
+    """Host seconds per call of the fp8 ``reduce_scatter`` and two-shot ``all_reduce`` on thread ranks, without and
+    with error feedback, alternated.  The plain result is checked against the reference; after the feedback
+    calls every residual must lie within 1/13 of its block's input amax."""
+    import time
+
+    from gpu_topology_on_k8s_amd.ops.peer_ref import allreduce_q8_ref, bf16_to_f32
+
+    k, elem = len(devs), ELEM[dtype]
+    counts = [max(1, n // elem) for n in sizes]
+    once = pc._Once()
+
+    def call(comm, what, count, fed):
+        if what == "reduce_scatter":
+            comm.reduce_scatter(count, dtype, wire="fp8", error_feedback=fed)
+        else:
+            comm.all_reduce(count, dtype, "twoshot", wire="fp8", error_feedback=fed)
+
+    def timed(comm, what, count, fed):
+        for _ in range(warmup):
+            call(comm, what, count, fed)
+        comm.barrier()
+        t0 = time.perf_counter()
+        for _ in range(iters):
+            call(comm, what, count, fed)
+        secs = (time.perf_counter() - t0) / iters
+        comm.barrier()  # no rank goes on to check its result, holding the interpreter, while another still reads its clock
+        return secs
+
+    def body(comm):
+        rows = []
+        for count in counts:
+            xs = once.get(("in", count), lambda: [pc.case_input(0, 0, p, count, dtype) for p in range(k)], lambda o: o[1] == count)
+            ref = once.get(("ref", count), lambda: allreduce_q8_ref(xs, dtype), lambda o: o[1] == count)
+            comm.write(xs[comm.rank])
+            n = q8_blocks(count) * Q8_BLOCK
+            mine = np.zeros(n, np.float32)
+            mine[:count] = np.abs(bf16_to_f32(xs[comm.rank]) if dtype == "bf16" else xs[comm.rank])
+            bound = np.repeat(mine.reshape(-1, Q8_BLOCK).max(axis=1), Q8_BLOCK) / np.float32(13)
+            for what in EF_CALLS:
+                for r in range(reps):
+                    plain = timed(comm, what, count, False)
+                    wrong = int(np.count_nonzero(pc._bits(comm.read(0, count, dtype)) != pc._bits(ref))) if what == "twoshot" and r == 0 else 0
+                    comm.reset_error_feedback()
+                    fed = timed(comm, what, count, True)
+                    over = int(np.count_nonzero(np.abs(comm.residual(0, n)) > bound))
+                    rows.append((count, what, r, plain, fed, wrong, over))
+        return rows
+
+    res = pc.run_thread_ranks(devs, body, q8_blocks(max(counts)) * Q8_BLOCK * elem, timeout_s=300.0, join_s=3000.0)
+    out = []
+    for count in counts:
+        row = {"bytes": count * elem, "count": count}
+        for what in EF_CALLS:
+            mine = [[r for r in rank_rows if r[:2] == (count, what)] for rank_rows in res]
+            plain = [max(rows[r][3] for rows in mine) * 1e6 for r in range(reps)]  # the slowest rank of each repetition
+            fed = [max(rows[r][4] for rows in mine) * 1e6 for r in range(reps)]
+            row[what] = {"plain_time_us": min(plain), "ef_time_us": min(fed), "ef_over_plain": min(fed) / min(plain),
+                         "plain_time_us_reps": plain, "ef_time_us_reps": fed, "plain_wrong": sum(r[5] for rows in mine for r in rows),
+                         "residual_over_bound": sum(r[6] for rows in mine for r in rows)}
+        out.append(row)
+        print(json.dumps(row), file=sys.stderr, flush=True)
+    return {"members": list(devs), "k": k, "distinct_devices": len(set(devs)) == k, "dtype": dtype, "iters": iters, "warmup": warmup,
+            "reps": reps, "wire": "fp8", "error_feedback": True, "sizes": out}
+
+
+def markdown_ef(res) -> str:
+    out = [f"### members {res['members']} (k = {res['k']}), {res['dtype']}, fp8 wire, thread ranks, {res['iters']} timed calls, best of {res['reps']} alternated repetitions", "",
+           "| N per member | call | plain us / call | with feedback us / call | feedback / plain |", "|---|---|---|---|---|"]
+    for r in res["sizes"]:
+        for what in EF_CALLS:
+            a = r[what]
+            out.append(f"| {r['bytes'] / 2**20:.1f} MiB | {what} | {a['plain_time_us']:.1f} | {a['ef_time_us']:.1f} | {a['ef_over_plain']:.2f} |")
+    out.append("")
+    return "\n".join(out)
+
+
 def markdown(res) -> str:
     out = [f"### members {res['members']} (k = {res['k']}), {res['dtype']}, {res['wire']} wire, {res['iters']} timed calls, best of {res['reps']} alternated repetitions", "",
            "| N per member | algorithm | thread ranks us / call | of it in barriers | thread algBW | driver us / round | driver algBW | thread / driver |",
@@ -103,6 +189,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--wire", default="native", choices=["native", "fp8", "fp8x2"],
                     help="fp8: the block-scaled e4m3 wire of csrc/probe/peer_q8.h; fp8x2: the two-shot with its gather phase packed too")
+    ap.add_argument("--error-feedback", action="store_true",
+                    help="thread ranks alone: the fp8 reduce_scatter and two-shot all_reduce without and with error feedback, alternated")
     ap.add_argument("--reps", type=int, default=2, help="alternated repetitions of each measurement")
     ap.add_argument("--out", default="", help="also write the JSON document here")
     ap.add_argument("--md", default="", help="also write the tables as Markdown here")
@@ -110,6 +198,19 @@ def main():
     groups = [[int(x) for x in m.split(",")] for m in (a.members or ["0,0,0,0"])]
     sizes = [int(float(x) * (1 << 20)) for x in a.sizes_mib.split(",")]
     probe.warmup(groups[0][0], 100.0)
+    if a.error_feedback:
+        if a.wire == "fp8x2":
+            ap.error("--error-feedback compares the calls of the fp8 wire")
+        doc = {"device": probe.device_props(groups[0][0])["name"],
+               "runs": [measure_ef(g, sizes, a.dtype, a.iters, a.warmup, max(1, a.reps)) for g in groups]}
+        text = json.dumps(doc)
+        print(text)
+        for path, body in ((a.out, text + "\n"), (a.md, "\n".join(markdown_ef(r) for r in doc["runs"]))):
+            if path:
+                os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+                with open(path, "w") as f:
+                    f.write(body)
+        return 1 if any(r[w][key] for run in doc["runs"] for r in run["sizes"] for w in EF_CALLS for key in ("plain_wrong", "residual_over_bound")) else 0
     doc = {"device": probe.device_props(groups[0][0])["name"], "rates": "GB/s (1e9 bytes/s)",
            "runs": [measure(g, sizes, a.dtype, a.iters, a.warmup, max(1, a.reps), a.wire) for g in groups]}
     text = json.dumps(doc)

@@ -121,6 +121,17 @@ void launch_peer_q8_quantize(bool in_bf16, const u32x4* win, u32x4* packed, size
   HIP_CHECK(hipGetLastError());
 }
 
+// The quantize with error feedback: `residual`, the member's own fp32 buffer (one float per element of the
+// window), is added before the packing and rewritten with what the packing dropped, in blocks [b0, b1).
+void launch_peer_q8_quantize_ef(bool in_bf16, const u32x4* win, u32x4* packed, size_t exp_vec, size_t b0, size_t b1, size_t count,
+                                u32x4* residual, int grid, hipStream_t s) {
+  if (in_bf16)
+    peer_q8_quantize_ef_kernel<uint16_t><<<dim3(grid), dim3(kBlock), 0, s>>>(win, packed, exp_vec, b0, b1, count, residual);
+  else
+    peer_q8_quantize_ef_kernel<float><<<dim3(grid), dim3(kBlock), 0, s>>>(win, packed, exp_vec, b0, b1, count, residual);
+  HIP_CHECK(hipGetLastError());
+}
+
 // The fp8x2 wire's two launches.  The repack keeps the sum's member buckets and U: its loads are the sum's,
 // and where the sum narrows and stores sixteen results it scales and converts them in place.
 void launch_peer_q8_repack(const SrcSet& packed, int k, size_t exp_vec, size_t b0, size_t b1, u32x4* packed_out, float scale,
@@ -524,7 +535,10 @@ py::list peer_allreduce_arrays(const std::vector<int>& devs, const std::vector<p
 // order.  The window is filled with a non-zero byte first, so what lies past the count is not zero.
 // `count` (none: the array's size) is the call's element count: the array's elements at and past it
 // lie in the window after the count, as far as the count's last block reaches.
-py::tuple peer_q8_quantize(int dev, const py::array& array, const std::string& dtype, const py::object& count_arg) {
+// `residual` (none: the plain kernel, and a 2-tuple): float32, one value per element of the count's whole
+// blocks; the feedback form then runs on it and the residual it left comes back as a third array.
+py::tuple peer_q8_quantize(int dev, const py::array& array, const std::string& dtype, const py::object& count_arg,
+                           const py::object& residual_arg) {
   const PeerTypes types = peer_types(dtype, "");
   check_dev(dev);
   const py::dtype want = types.in_bf16 ? py::dtype::of<uint16_t>() : py::dtype::of<float>();
@@ -535,26 +549,48 @@ py::tuple peer_q8_quantize(int dev, const py::array& array, const std::string& d
   if (count > PeerAllreduce::kMaxCount) throw std::invalid_argument("count <= 64 Mi elements");
   const py::array src = py::array::ensure(array, py::array::c_style);
   const size_t n_blocks = (count + kQ8Block - 1) / kQ8Block, in_bytes = n_blocks * kQ8Block * types.in_elem();
+  const bool ef = !residual_arg.is_none();
+  const size_t res_bytes = n_blocks * kQ8Block * sizeof(float);
+  py::array res_in;
+  if (ef) {
+    const py::array given = residual_arg.cast<py::array>();
+    if (given.ndim() != 1 || (size_t)given.size() != n_blocks * kQ8Block || !given.dtype().is(py::dtype::of<float>()))
+      throw std::invalid_argument("residual: a one-dimensional float32 array, one value per element of the count's whole blocks");
+    res_in = py::array::ensure(given, py::array::c_style);
+  }
   py::array_t<uint8_t> codes((py::ssize_t)(n_blocks * kQ8Block));
   py::array_t<int32_t> exps((py::ssize_t)n_blocks);
+  py::array_t<float> res_out((py::ssize_t)(ef ? n_blocks * kQ8Block : 0));
   std::vector<uint8_t> biased(n_blocks);
   const void* from = src.data();
+  const void* res_from = ef ? res_in.data() : nullptr;
   void* to = codes.mutable_data();
+  void* res_to = res_out.mutable_data();
   {
     py::gil_scoped_release nogil;
     DeviceGuard g(dev);
     DevBuf win(dev, in_bytes), packed(dev, q8_packed_vecs(n_blocks) * 16);
+    std::unique_ptr<DevBuf> residual;
     HIP_CHECK(hipMemset(win.p, 0x7b, in_bytes));
     HIP_CHECK(hipMemcpy(win.p, from, std::min((size_t)array.size() * types.in_elem(), in_bytes), hipMemcpyHostToDevice));
     const int grid = peer_reduce_grid(num_cus(dev), kBlocksPerCU, 1, in_bytes / 16);
-    launch_peer_q8_quantize(types.in_bf16, (const u32x4*)win.p, (u32x4*)packed.p, q8_exp_vec(n_blocks), 0, n_blocks, count, grid,
-                            nullptr);
+    if (ef) {
+      residual.reset(new DevBuf(dev, res_bytes));
+      HIP_CHECK(hipMemcpy(residual->p, res_from, res_bytes, hipMemcpyHostToDevice));
+      launch_peer_q8_quantize_ef(types.in_bf16, (const u32x4*)win.p, (u32x4*)packed.p, q8_exp_vec(n_blocks), 0, n_blocks, count,
+                                 (u32x4*)residual->p, grid, nullptr);
+    } else {
+      launch_peer_q8_quantize(types.in_bf16, (const u32x4*)win.p, (u32x4*)packed.p, q8_exp_vec(n_blocks), 0, n_blocks, count, grid,
+                              nullptr);
+    }
     HIP_CHECK(hipDeviceSynchronize());
     HIP_CHECK(hipMemcpy(to, packed.p, n_blocks * kQ8Block, hipMemcpyDeviceToHost));
     HIP_CHECK(hipMemcpy(biased.data(), (const char*)packed.p + q8_exp_vec(n_blocks) * 16, n_blocks, hipMemcpyDeviceToHost));
+    if (ef) HIP_CHECK(hipMemcpy(res_to, residual->p, res_bytes, hipMemcpyDeviceToHost));
   }
   int32_t* e = exps.mutable_data();
   for (size_t b = 0; b < n_blocks; ++b) e[b] = (int32_t)biased[b] - kQ8Bias;
+  if (ef) return py::make_tuple(codes, exps, res_out);
   return py::make_tuple(codes, exps);
 }
 

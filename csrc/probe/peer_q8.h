@@ -39,6 +39,13 @@
 // has no infinity), a magnitude of at least 248 * 2^120 as Inf.  Both phases then move 33 bytes per 32
 // elements over the links.
 //
+// Error feedback (peer_q8_quantize_ef_kernel; ops/peer_ref.py: q8_quantize_ef_ref decides): the rank keeps an
+// fp32 residual per element of its window, what its last packing dropped.  The feedback form packs
+// y = x + residual (one fp32 add, x itself where the residual is zero; then the count's mask) by the rule above and leaves y - float(code) * 2^e,
+// an exact difference, as the new residual: +0 where that is not finite (y NaN or Inf, or a code that
+// widens to 2^128) and past the count.  The residual is the rank's own: no peer reads it, it costs no link
+// byte, no launch and no barrier, and the plain form is the same code as without it.
+//
 // Conversions: v_cvt_pk_fp8_f32 and v_cvt_pk_f32_fp8 through their builtins, on values already scaled by
 // an exact fp32 multiply; the scaling forms (cvt_scalef32_*) are not used, so which way they apply their
 // scale operand plays no part here.  tests/test_gpu_peer_q8.py compares every code with the numpy rule.
@@ -78,14 +85,25 @@ __device__ __forceinline__ unsigned int q8_codes2(float a, float b) {
 // consecutive lanes that hold a block (bf16: 4 lanes of 8 elements; fp32: 8 lanes of 4): the block's amax
 // is log2(G) lane exchanges, with no memory and no other wave involved; every lane stores its own codes
 // (8 or 4 bytes), the first lane of a block the exponent byte.
-template <typename TI>
-__device__ __forceinline__ void q8_quantize_vec(const u32x4& r, size_t v, size_t count, u32x4* __restrict__ packed,
-                                                unsigned char* __restrict__ exps) {
+// EF, the feedback form: `res` holds the L residual floats of the lane's elements (zero for a vector wholly
+// past the count), added before the count's mask; the codes just made are widened as q8_widen widens them
+// and the new residual, what the packing dropped, goes to floats [v L, v L + L) of `residual` as vectors.
+template <typename TI, bool EF>
+__device__ __forceinline__ void q8_quantize_vec(const u32x4& r, const u32x4 (&res)[kPeerLanes<TI> / 4], size_t v, size_t count,
+                                                u32x4* __restrict__ packed, unsigned char* __restrict__ exps,
+                                                u32x4* __restrict__ residual) {
   constexpr int L = kPeerLanes<TI>;
   constexpr int G = kQ8Block / L;
   const size_t first = v * L;
   float f[L];
   peer_widen(r, f);
+  if constexpr (EF) {
+#pragma unroll
+    for (int j = 0; j < L; ++j) {
+      const float q = __uint_as_float(res[j / 4][j % 4]);
+      f[j] = q == 0.f ? f[j] : f[j] + q;  // x + 0 would make +0 of -0: a zero residual leaves the plain rule's codes
+    }
+  }
   if (first + L > count) {  // the vector the count ends in, and those after it: every other one skips the mask
 #pragma unroll
     for (int j = 0; j < L; ++j)
@@ -113,34 +131,80 @@ __device__ __forceinline__ void q8_quantize_vec(const u32x4& r, size_t v, size_t
     __builtin_nontemporal_store(w[0], reinterpret_cast<unsigned int*>(packed) + v);
   }
   if (v % G == 0) exps[v / G] = (unsigned char)(e + kQ8Bias);
+  if constexpr (EF) {
+    // The subtraction must see the rounded product: contracted into one fma, 256 * 2^120 would not be Inf.
+#pragma clang fp contract(off)
+    const float up = q8_pow2(e);
+#pragma unroll
+    for (int j = 0; j < L / 4; ++j) {
+      const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[j], false);
+      const f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[j], true);
+      const float dq[4] = {lo[0] * up, lo[1] * up, hi[0] * up, hi[1] * up};
+      u32x4 n;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const unsigned int d = __float_as_uint(f[4 * j + i] - dq[i]);
+        n[i] = (d & 0x7f800000u) == 0x7f800000u ? 0u : d;  // NaN or Inf in, or 2^128 out: nothing is carried
+      }
+      __builtin_nontemporal_store(n, residual + v * (L / 4) + j);
+    }
+  }
 }
 
 // Blocks [b0, b1) of the window to the same blocks of the rank's own packed buffer, one window vector
 // per lane and U of them per pass, a grid apart, all loaded before the first is converted.  b0 * G and
-// the grid's stride are multiples of G, so the lanes of a block take every branch together.
-template <typename TI>
-__global__ __launch_bounds__(gtk::kStreamBlock) void peer_q8_quantize_kernel(const u32x4* __restrict__ win,
-                                                                             u32x4* __restrict__ packed, size_t exp_vec,
-                                                                             size_t b0, size_t b1, size_t count) {
+// the grid's stride are multiples of G, so the lanes of a block take every branch together.  EF: the
+// residual vectors of those elements (two per bf16 window vector, one per fp32) are loaded with them and
+// rewritten; a vector wholly past the count reads neither and writes a zero residual.
+template <typename TI, bool EF>
+__device__ __forceinline__ void peer_q8_quantize_blocks(const u32x4* __restrict__ win, u32x4* __restrict__ packed, size_t exp_vec,
+                                                        size_t b0, size_t b1, size_t count, u32x4* __restrict__ residual) {
   constexpr int L = kPeerLanes<TI>;
   constexpr int G = kQ8Block / L;
+  constexpr int R = L / 4;  // residual vectors per window vector
   constexpr int U = 4;
   unsigned char* exps = reinterpret_cast<unsigned char*>(packed + exp_vec);
   const size_t end = b1 * G, stride = (size_t)gridDim.x * gtk::kStreamBlock;
   for (size_t base = b0 * G + (size_t)blockIdx.x * gtk::kStreamBlock + threadIdx.x; base < end; base += stride * U) {
     u32x4 r[U];
+    u32x4 q[U][R];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const size_t v = base + (size_t)u * stride;
       r[u] = u32x4{0u, 0u, 0u, 0u};
-      if (v < end && v * L < count) r[u] = __builtin_nontemporal_load(win + v);  // a vector wholly past the count is not read
+#pragma unroll
+      for (int j = 0; j < R; ++j) q[u][j] = u32x4{0u, 0u, 0u, 0u};
+      if (v < end && v * L < count) {  // a vector wholly past the count is not read
+        r[u] = __builtin_nontemporal_load(win + v);
+        if constexpr (EF) {
+#pragma unroll
+          for (int j = 0; j < R; ++j) q[u][j] = __builtin_nontemporal_load(residual + v * R + j);
+        }
+      }
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const size_t v = base + (size_t)u * stride;
-      if (v < end) q8_quantize_vec<TI>(r[u], v, count, packed, exps);
+      if (v < end) q8_quantize_vec<TI, EF>(r[u], q[u], v, count, packed, exps, residual);
     }
   }
+}
+
+template <typename TI>
+__global__ __launch_bounds__(gtk::kStreamBlock) void peer_q8_quantize_kernel(const u32x4* __restrict__ win,
+                                                                             u32x4* __restrict__ packed, size_t exp_vec,
+                                                                             size_t b0, size_t b1, size_t count) {
+  peer_q8_quantize_blocks<TI, false>(win, packed, exp_vec, b0, b1, count, nullptr);
+}
+
+// The feedback form: `residual` is the rank's own fp32 buffer, one float per element of the window, read
+// and rewritten in blocks [b0, b1) alone.
+template <typename TI>
+__global__ __launch_bounds__(gtk::kStreamBlock) void peer_q8_quantize_ef_kernel(const u32x4* __restrict__ win,
+                                                                                u32x4* __restrict__ packed, size_t exp_vec,
+                                                                                size_t b0, size_t b1, size_t count,
+                                                                                u32x4* __restrict__ residual) {
+  peer_q8_quantize_blocks<TI, true>(win, packed, exp_vec, b0, b1, count, residual);
 }
 
 // The 16 values of one code vector: float(code) * 2^e, `ebyte` being the block's stored exponent byte.

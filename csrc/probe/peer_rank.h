@@ -5,7 +5,10 @@
 // A rank owns a window (inputs, `capacity` bytes), an out (results, twice that: the wide form writes
 // two vectors per input vector), a packed buffer (the fp8 wire's form of the window, sized for a window
 // full of bf16: capacity / 64 blocks), a second packed buffer of that size (the fp8x2 wire's form of the rank's
-// slice of a sum, which its peers gather from) and one non-blocking stream on its device.  Ranks are threads of one
+// slice of a sum, which its peers gather from) and one non-blocking stream on its device.  A rank that packs with
+// error feedback also owns a residual (fp32, one value per element of a window full of bf16: twice the capacity),
+// allocated on its first feedback call; it is the rank's alone, never published and no part of open_peers.
+// Ranks are threads of one
 // process, so a peer's buffer is reached through its plain device address and, across devices,
 // hipDeviceEnablePeerAccess: no IPC call.  A PeerRank is used by one thread.  Nothing here waits on
 // the GPU for another rank: no event is shared between ranks and no kernel spins, so ordering between
@@ -73,6 +76,7 @@ class PeerRank {
   size_t capacity_bytes() const { return cap_; }
   size_t max_blocks() const { return cap_ / (kQ8Block * 2); }  // blocks of 32 bf16 elements the window holds
   size_t packed_bytes() const { return std::max<size_t>(16, q8_packed_vecs(max_blocks()) * 16); }
+  size_t residual_bytes() const { return residual_ ? 2 * cap_ : 0; }  // 0 until the first feedback call
   size_t launches() const { return launches_; }
   bool released() const { return released_; }
 
@@ -140,18 +144,60 @@ class PeerRank {
   }
 
   // The fp8 wire's first phase: blocks [b0, b1) of this rank's window (32 elements of `in_dtype` each,
-  // elements at or past `count` taken as zero) to the same blocks of its packed buffer.
-  void quantize(size_t b0, size_t b1, size_t count, const std::string& in_dtype) {
+  // elements at or past `count` taken as zero) to the same blocks of its packed buffer.  With
+  // `error_feedback` the rank's residual of those blocks is added first and rewritten with what the packing
+  // dropped (element i of the window has float i of the residual); the first such call allocates it, zeroed.
+  // One launch either way.
+  void quantize(size_t b0, size_t b1, size_t count, const std::string& in_dtype, bool error_feedback = false) {
     const PeerTypes t = peer_types(in_dtype, "");
     need_q8();
     if (b0 > b1 || b1 * kQ8Block * t.in_elem() > cap_) throw std::invalid_argument("quantize: blocks past the end of the window");
-    if (b1 > max_blocks()) throw std::invalid_argument("quantize: blocks past the end of the packed buffer");
+    if (b1 > max_blocks()) throw std::invalid_argument("quantize: blocks past the end of the packed buffer");  // and of the residual
     if (b0 == b1) return;
     const int grid = peer_reduce_grid(cus_, blocks_per_cu_, share_, (b1 - b0) * kQ8Block * t.in_elem() / 16);
     DeviceGuard g(dev_);
-    launch_peer_q8_quantize(t.in_bf16, reinterpret_cast<const u32x4*>(window_->p), reinterpret_cast<u32x4*>(packed_->p),
-                            q8_exp_vec(max_blocks()), b0, b1, count, grid, stream_);
+    if (error_feedback) {
+      need_residual();
+      launch_peer_q8_quantize_ef(t.in_bf16, reinterpret_cast<const u32x4*>(window_->p), reinterpret_cast<u32x4*>(packed_->p),
+                                 q8_exp_vec(max_blocks()), b0, b1, count, reinterpret_cast<u32x4*>(residual_->p), grid, stream_);
+    } else {
+      launch_peer_q8_quantize(t.in_bf16, reinterpret_cast<const u32x4*>(window_->p), reinterpret_cast<u32x4*>(packed_->p),
+                              q8_exp_vec(max_blocks()), b0, b1, count, grid, stream_);
+    }
     ++launches_;
+  }
+
+  // The residual back to zero: one memset on the stream, nothing if it was never allocated.
+  void reset_residual() {
+    live();
+    if (!residual_) return;
+    DeviceGuard g(dev_);
+    HIP_CHECK(hipMemsetAsync(residual_->p, 0, 2 * cap_, stream_));
+  }
+
+  // Floats [first_elem, first_elem + n) of the residual to `dst`, after everything on the stream; zeros
+  // while it is unallocated, which is what it then stands for.
+  void read_residual(float* dst, size_t first_elem, size_t n) {
+    live();
+    if (first_elem > cap_ / 2 || n > cap_ / 2 - first_elem) throw std::invalid_argument("read_residual: past the end of the residual");
+    DeviceGuard g(dev_);
+    if (!residual_)
+      std::fill(dst, dst + n, 0.f);
+    else if (n)
+      HIP_CHECK(hipMemcpyAsync(dst, static_cast<const float*>(residual_->p) + first_elem, n * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipStreamSynchronize(stream_));
+  }
+
+  // Host floats into the residual from `first_elem` on (a restored checkpoint; the tests' starting state),
+  // allocating it if need be.  On the rank's stream; returns once the host floats have been read.
+  void write_residual(const float* src, size_t n, size_t first_elem) {
+    live();
+    if (first_elem > cap_ / 2 || n > cap_ / 2 - first_elem) throw std::invalid_argument("write_residual: past the end of the residual");
+    if (!n) return;
+    DeviceGuard g(dev_);
+    need_residual();
+    HIP_CHECK(hipMemcpyAsync(static_cast<float*>(residual_->p) + first_elem, src, n * sizeof(float), hipMemcpyHostToDevice, stream_));
+    HIP_CHECK(hipStreamSynchronize(stream_));
   }
 
   // Blocks [b0, b1) of this rank's out (whole blocks of `out_dtype`) = scale x the sum over ranks of the
@@ -285,6 +331,17 @@ class PeerRank {
     if (!open_q8x2_) throw std::runtime_error("the fp8x2 phases need open_peers with the peers' second packed buffers");
   }
 
+  // The residual, allocated like the other buffers and zeroed on the stream, ahead of its first use there.
+  // The caller holds a DeviceGuard of dev_.
+  void need_residual() {
+    if (residual_) return;
+    {
+      std::lock_guard<std::mutex> lock(peer_rank_mutex());
+      residual_.reset(new DevBuf(dev_, 2 * cap_));
+    }
+    HIP_CHECK(hipMemsetAsync(residual_->p, 0, 2 * cap_, stream_));
+  }
+
   static void check_allocation(uintptr_t addr, int dev, size_t bytes) {
     void* p = reinterpret_cast<void*>(addr);
     hipPointerAttribute_t attr{};
@@ -325,12 +382,13 @@ class PeerRank {
     out_.reset();
     packed_.reset();
     packed_out_.reset();
+    residual_.reset();
   }
 
   int dev_, rank_, world_;
   size_t cap_;
   int blocks_per_cu_, cus_ = 1, share_ = 1;
-  std::unique_ptr<DevBuf> window_, out_, packed_, packed_out_;
+  std::unique_ptr<DevBuf> window_, out_, packed_, packed_out_, residual_;
   hipStream_t stream_ = nullptr;
   SrcSet windows_{}, packeds_{};
   std::vector<const u32x4*> outs_, packed_outs_;
@@ -354,7 +412,31 @@ void bind_peer_rank(py::module_& m) {
       .def("close_peers", &PeerRank::close_peers, nogil())
       .def("reduce", &PeerRank::reduce, py::arg("v0"), py::arg("v1"), py::arg("in_dtype"), py::arg("out_dtype"), py::arg("scale") = 1.0f,
            nogil())
-      .def("quantize", &PeerRank::quantize, py::arg("b0"), py::arg("b1"), py::arg("count"), py::arg("in_dtype"), nogil())
+      .def("quantize", &PeerRank::quantize, py::arg("b0"), py::arg("b1"), py::arg("count"), py::arg("in_dtype"),
+           py::arg("error_feedback") = false, nogil())
+      .def("reset_residual", &PeerRank::reset_residual, nogil())
+      .def("read_residual",
+           [](PeerRank& r, size_t first_elem, size_t n) {
+             if (r.released()) throw std::runtime_error("the PeerRank is released");
+             if (first_elem > r.capacity_bytes() / 2 || n > r.capacity_bytes() / 2 - first_elem)
+               throw std::invalid_argument("read_residual: past the end of the residual");
+             py::array_t<float> a((py::ssize_t)n);
+             float* p = a.mutable_data();
+             {
+               py::gil_scoped_release nogil;
+               r.read_residual(p, first_elem, n);
+             }
+             return a;
+           },
+           py::arg("first_elem"), py::arg("n"))
+      .def("write_residual",
+           [](PeerRank& r, const py::array_t<float, py::array::c_style | py::array::forcecast>& a, size_t first_elem) {
+             const float* p = a.data();
+             const size_t n = (size_t)a.size();
+             py::gil_scoped_release nogil;
+             r.write_residual(p, n, first_elem);
+           },
+           py::arg("floats"), py::arg("first_elem") = 0)
       .def("reduce_q8", &PeerRank::reduce_q8, py::arg("b0"), py::arg("b1"), py::arg("out_dtype"), py::arg("scale") = 1.0f, nogil())
       .def("repack_q8", &PeerRank::repack_q8, py::arg("b0"), py::arg("b1"), py::arg("scale") = 1.0f, nogil())
       .def("unpack_q8", &PeerRank::unpack_q8, py::arg("slices"), py::arg("out_dtype"), nogil())
@@ -389,6 +471,7 @@ void bind_peer_rank(py::module_& m) {
       .def_property_readonly("launches", &PeerRank::launches)
       .def_property_readonly("capacity_bytes", &PeerRank::capacity_bytes)
       .def_property_readonly("packed_bytes", &PeerRank::packed_bytes)
+      .def_property_readonly("residual_bytes", &PeerRank::residual_bytes)
       .def_property_readonly("released", &PeerRank::released);
 }
 

@@ -875,9 +875,12 @@ PYBIND11_MODULE(_probe, m) {
         "K7 on the caller's arrays (uint16 bit patterns for bf16, float32 for fp32): the k members' results, "
         "scale x sum, in out_dtype (none: dtype; fp32 of bf16 inputs is the wide reduce)");
   m.def("peer_q8_quantize", &peer_q8_quantize, py::arg("dev"), py::arg("array"), py::arg("dtype") = "bf16",
-        py::arg("count") = py::none(),
+        py::arg("count") = py::none(), py::arg("residual") = py::none(),
         "the fp8 wire's quantize kernel on one array: (codes uint8, block exponents int32) in logical order; "
-        "count (none: all): the elements that are data, the rest lies in the window after them");
+        "count (none: all): the elements that are data, the rest lies in the window after them; residual (float32, "
+        "one value per element of the count's whole blocks): the feedback form, and the new residual as a third array");
+  m.def("peer_reduce_grid", &peer_reduce_grid, py::arg("cus"), py::arg("blocks_per_cu"), py::arg("share"), py::arg("n_vec"),
+        "blocks of a K7 reduce or quantize of n_vec vectors on a device of `cus` CUs that `share` members split");
   bind_peer_rank(m);
   m.def("chase_latency", &chase_latency, py::arg("src_dev"), py::arg("exec_dev"), py::arg("ws_bytes") = (size_t)1 << 30,
         py::arg("stride") = (size_t)128, py::arg("hops") = 4096, py::arg("chains") = 1, py::arg("iters") = 5,

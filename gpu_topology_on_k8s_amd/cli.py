@@ -431,6 +431,10 @@ def cmd_validate(a) -> int:
     if a.wire == "fp8x2" and a.algo == "oneshot":
         print("gtk validate: error: --wire fp8x2 packs the gather phase of a twoshot: --algo twoshot or both", file=sys.stderr)
         return 2
+    if a.error_feedback and (a.wire not in ("fp8", "fp8x2") or a.ranks != "thread"):
+        print("gtk validate: error: --error-feedback belongs to --ranks thread with --wire fp8 or fp8x2: only a packed wire "
+              "drops anything to feed back", file=sys.stderr)
+        return 2
     if a.ranks == "thread":  # refused before anything native is loaded
         if a.backend != "peer":
             raise SystemExit("--ranks thread belongs to --backend peer")
@@ -456,9 +460,9 @@ def cmd_validate(a) -> int:
         if a.ranks == "thread":  # one thread per member through the peer communicator, not one driver call for all
             from .parallel.peer_comm import selftest, thread_sweep
 
-            st = selftest(devs, wire=a.wire)
+            st = selftest(devs, wire=a.wire, error_feedback=a.error_feedback)
             print(json.dumps({"selftest": True, "k": len(devs), "devices": devs, "ranks": "thread", **st}), flush=True)
-            selftest_wrong = st["wrong"] + st["q8_wrong"] + st.get("q8x2_wrong", 0)
+            selftest_wrong = st["wrong"] + st["q8_wrong"] + st.get("q8x2_wrong", 0) + st.get("ef_wrong", 0)
             pts = thread_sweep(devs, sizes, a.dtype, algo, a.iters, a.warmup, wire=a.wire)
             extra = {"backend": "peer", "algo": algo, "ranks": "thread", "selftest_wrong": selftest_wrong, "wire": a.wire}
         else:
@@ -632,6 +636,9 @@ def main(argv=None) -> int:
                    help="--backend peer: native = members read each other's inputs; fp8 = each member packs its input into "
                         "e4m3 codes with one power-of-two scale per 32 elements and the members read that (33 bytes per 32 elements); "
                         "fp8x2 = the two-shot alone, its gather phase packed the same way")
+    p.add_argument("--error-feedback", action="store_true",
+                   help="--ranks thread with --wire fp8|fp8x2: the self-test also issues the packed wires' cases with error "
+                        "feedback, three times each with the residual carried, against the chained CPU reference")
     p.add_argument("--ranks", default="driver", choices=["driver", "thread"],
                    help="--backend peer: driver = one in-process call drives every member (stream events); thread = one thread "
                         "per member through the peer communicator (a self-test, then host-timed all_reduce calls checked on the host)")

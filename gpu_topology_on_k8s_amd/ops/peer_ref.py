@@ -16,6 +16,11 @@ rank's input into OCP e4m3fn codes with one power-of-two scale per 32 elements, 
 :func:`allreduce_q8_ref` sums the dequantised values exactly as :func:`allreduce_ref` sums the inputs.
 :func:`allreduce_q8x2_ref` is the two-shot whose gather phase is packed too (``wire="fp8x2"``): the scaled fp32 sum
 goes through the same block rule once more, and every member takes its result from that packed form.
+
+Error feedback (:func:`q8_quantize_ef_ref`, :func:`allreduce_q8_ef_ref`, :func:`reduce_scatter_q8_ef_ref`): a
+sender adds what its last packing dropped, a float32 *residual* per element, to what it packs next, so over
+any number of calls the sum of what it sent differs from the sum of what it was given by the last residual
+alone.
 """
 from __future__ import annotations
 
@@ -25,7 +30,8 @@ import numpy as np
 
 __all__ = ["ELEM", "peer_slices", "bf16_round", "bf16_to_f32", "bits", "out_dtype_of", "allreduce_ref", "reduce_scatter_ref",
            "is_nan_bits", "mismatches", "Q8_BLOCK", "Q8_EXP_MIN", "Q8_EXP_MAX", "q8_blocks", "q8_slices", "q8_quantize_ref", "q8_dequantize_ref",
-           "allreduce_q8_ref", "reduce_scatter_q8_ref", "allreduce_q8x2_ref"]
+           "allreduce_q8_ref", "reduce_scatter_q8_ref", "allreduce_q8x2_ref", "q8_quantize_ef_ref", "allreduce_q8_ef_ref",
+           "reduce_scatter_q8_ef_ref"]
 
 ELEM = {"bf16": 2, "fp32": 4}  # bytes per element
 
@@ -242,3 +248,85 @@ def allreduce_q8x2_ref(inputs: Sequence[np.ndarray], dtype: str, out_dtype: Opti
     s = allreduce_q8_ref(inputs, dtype, "fp32", scale)
     back = q8_dequantize_ref(*q8_quantize_ref(s, "fp32"))[:s.shape[0]]
     return bf16_round(back) if out == "bf16" else back
+
+
+# -- error feedback -----------------------------------------------------------------------------
+def q8_quantize_ef_ref(x: np.ndarray, dtype: str, residual: np.ndarray,
+                       count: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """:func:`q8_quantize_ref` with error feedback: ``(codes, exps, new_residual)``.  ``residual`` is float32,
+    one value per element of the whole blocks the ``count`` (none: all of ``x``) covers, and so is ``new_residual``.
+
+    1. ``v`` is ``x`` widened to fp32, elements at or past ``count`` zero, as in :func:`q8_quantize_ref`.
+    2. ``y = fp32(v + residual)``, one IEEE add with subnormals kept; at or past ``count`` ``y = 0`` whatever
+       ``residual`` holds there.  Where ``residual`` is zero ``y`` is ``v`` itself: the add would turn an input of
+       ``-0`` into ``+0`` and its code ``0x80`` into ``0x00``, the one difference from the plain rule that a zero
+       residual could make.
+    3. ``codes, exps = q8_quantize_ref(y, "fp32")`` and ``dq = q8_dequantize_ref(codes, exps)``: the block
+       exponent, its clamp and the NaN/Inf coding are the unchanged rule's, applied to ``y``.
+    4. ``new_residual = fp32(y - dq)`` where that difference is finite (the subtraction is then exact), and
+       ``+0`` elsewhere: where ``y`` is NaN or Inf, where ``dq`` came out Inf (a magnitude of at least
+       ``248 * 2^120`` packed under ``e = 120``) and at or past ``count``.  One overflowing step must not poison
+       every later one.
+
+    With ``residual`` all zero the codes and exponents are :func:`q8_quantize_ref`'s.  Where the block
+    exponent is not clamped, ``|new_residual| <= amax(y) / 14`` of its block."""
+    if dtype not in ELEM:
+        raise ValueError(f"dtype must be bf16|fp32, got {dtype!r}")
+    v = bf16_to_f32(x) if dtype == "bf16" else np.ascontiguousarray(x, dtype=np.float32)
+    count = int(v.shape[0]) if count is None else int(count)
+    if not 0 <= count <= v.shape[0]:
+        raise ValueError("count past the end of x")
+    n = q8_blocks(count) * Q8_BLOCK
+    res = np.ascontiguousarray(residual)
+    if res.dtype != np.float32 or res.shape != (n,):
+        raise ValueError(f"residual: float32, one value per element of the {n // Q8_BLOCK} blocks covered")
+    y = np.zeros(n, np.float32)
+    with np.errstate(over="ignore", invalid="ignore"):  # Inf and NaN are results here, not faults
+        y[:count] = np.where(res[:count] == 0, v[:count], (v[:count] + res[:count]).astype(np.float32))
+        codes, exps = q8_quantize_ref(y, "fp32")
+        diff = (y - q8_dequantize_ref(codes, exps)).astype(np.float32)
+    return codes, exps, np.where(np.isfinite(diff), diff, np.float32(0)).astype(np.float32)
+
+
+def _q8_ef_contributions(inputs: Sequence[np.ndarray], residuals: Sequence[np.ndarray], dtype: str):
+    """Every member's dequantised packing with feedback, cut to the count, and its new residual."""
+    if not inputs:
+        raise ValueError("no inputs")
+    if len(residuals) != len(inputs):
+        raise ValueError("one residual per member")
+    count = int(np.asarray(inputs[0]).shape[0])
+    wide, new = [], []
+    for a, r in zip(inputs, residuals):
+        codes, exps, nr = q8_quantize_ef_ref(a, dtype, r)
+        wide.append(q8_dequantize_ref(codes, exps)[:count])
+        new.append(nr)
+    return wide, new
+
+
+def allreduce_q8_ef_ref(inputs: Sequence[np.ndarray], residuals: Sequence[np.ndarray], dtype: str, out_dtype: Optional[str] = None,
+                        scale: float = 1.0, wire: str = "fp8") -> Tuple[np.ndarray, List[np.ndarray]]:
+    """:func:`allreduce_q8_ref` (``wire="fp8"``) or :func:`allreduce_q8x2_ref` (``wire="fp8x2"``) with error
+    feedback: ``(result, new_residuals)``.  Member m's contribution is the dequantised packing of
+    :func:`q8_quantize_ef_ref` on ``inputs[m]`` and ``residuals[m]``; the sum, the scale, the rounding and,
+    for ``fp8x2``, the second packing are exactly those functions'.
+
+    Feedback covers the sender's packing only.  The second rounding of ``fp8x2``, phase 1 packing the sum
+    again, is not fed back: it is the slice owner's, and its error stays in the result."""
+    out = out_dtype_of(dtype, out_dtype)
+    if wire not in ("fp8", "fp8x2"):
+        raise ValueError(f'wire must be "fp8" or "fp8x2", got {wire!r}')
+    wide, new = _q8_ef_contributions(inputs, residuals, dtype)
+    acc = allreduce_ref(wide, "fp32", "fp32", scale)
+    if wire == "fp8x2":
+        acc = q8_dequantize_ref(*q8_quantize_ref(acc, "fp32"))[:acc.shape[0]]
+    return (bf16_round(acc) if out == "bf16" else acc), new
+
+
+def reduce_scatter_q8_ef_ref(inputs: Sequence[np.ndarray], residuals: Sequence[np.ndarray], dtype: str,
+                             out_dtype: Optional[str] = None, scale: float = 1.0) -> Tuple[List[np.ndarray], List[np.ndarray]]:
+    """:func:`reduce_scatter_q8_ref` with error feedback: ``(pieces, new_residuals)``.  The pieces concatenate
+    to :func:`allreduce_q8_ef_ref`'s result on the fp8 wire; every member packs its whole input, so the
+    residuals are that function's too.  Feedback covers the sender's packing only."""
+    full, new = allreduce_q8_ef_ref(inputs, residuals, dtype, out_dtype, scale)
+    count = int(full.shape[0])
+    return [full[min(count, a * Q8_BLOCK):min(count, b * Q8_BLOCK)] for a, b in q8_slices(q8_blocks(count), len(inputs))], new

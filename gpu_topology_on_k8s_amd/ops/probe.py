@@ -164,12 +164,20 @@ def peer_allreduce(devs: Sequence[int], count: int, dtype: str = "bf16", algo: s
                                     int(blocks_per_cu), wire, bool(dry_run)))
 
 
-def peer_q8_quantize(dev: int, array: np.ndarray, dtype: str = "bf16", count: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+def peer_q8_quantize(dev: int, array: np.ndarray, dtype: str = "bf16", count: Optional[int] = None,
+                     residual: Optional[np.ndarray] = None) -> Tuple[np.ndarray, ...]:
     """The fp8 wire's quantize kernel on one array: ``(codes uint8, block exponents int32)``, the bits
     ``ops.peer_ref.q8_quantize_ref`` gives.  ``count`` (none: all) is the number of elements that are data;
-    the array's later elements lie in the window after them, up to the end of the count's last block."""
-    codes, exps = _p().peer_q8_quantize(int(dev), array, dtype, None if count is None else int(count))
-    return codes, exps
+    the array's later elements lie in the window after them, up to the end of the count's last block.
+
+    ``residual`` (float32, one value per element of the count's whole blocks) selects the kernel's
+    error-feedback form: ``(codes, exps, new_residual)``, the bits of ``ops.peer_ref.q8_quantize_ef_ref``."""
+    n = None if count is None else int(count)
+    if residual is None:
+        codes, exps = _p().peer_q8_quantize(int(dev), array, dtype, n)
+        return codes, exps
+    codes, exps, new = _p().peer_q8_quantize(int(dev), array, dtype, n, np.ascontiguousarray(residual))
+    return codes, exps, new
 
 
 def peer_allreduce_arrays(devs: Sequence[int], inputs: Sequence[np.ndarray], dtype: str = "bf16", algo: str = "twoshot",

@@ -48,6 +48,25 @@ after synchronising its own phase 2.  The second rounding costs at most ``amax /
 scaled sum per element; an Inf in the sum comes out as NaN, since e4m3fn has no infinity, and a magnitude of
 at least ``248 * 2^120`` comes out Inf.
 
+``error_feedback=True`` (``all_reduce`` and ``reduce_scatter`` on ``wire="fp8"`` or ``"fp8x2"``) makes the wire fit
+for gradients that keep their value from call to call.  Every rank keeps a *residual*, fp32, one value per
+element of its window: what its last packing dropped.  The quantize adds it to the window before it packs
+and leaves ``y - dq`` behind (``ops/peer_ref.q8_quantize_ef_ref``), so over any number of calls the sum of what
+a rank has sent differs from the sum of what it was given by the last residual alone, at most ``amax / 13`` of
+its block; the plain wire's error grows with the number of calls.  The residual is read and written by its
+owner alone, in the quantize, before barrier A: it is never published and no peer ever opens it, so no new
+hazard exists, and a collective still has two barriers and the same number of launches.  It costs no link
+byte.  It is allocated on the first feedback call (twice the window's bytes); a communicator that never asks
+for feedback holds none.  Feedback covers the sender's packing only: the second rounding of ``fp8x2``, phase 1
+packing the sum again, is the slice owner's and stays in the result.
+
+The residual is positional: value i belongs to element i of the window, whatever the caller put there.  A
+caller who changes what the window holds (another tensor, another layout, another count's tail) calls
+:meth:`PeerComm.reset_error_feedback` first.  A call with ``error_feedback=False`` neither reads nor writes it.
+Because the quantize runs before the descriptors are compared, a mismatched feedback call would have advanced
+the residual with data that no one summed: when barrier A of a feedback call raises (``PeerCommMismatch``, or a
+timeout), the rank's residual is therefore reset to zero before the exception leaves.
+
 Two backends exist, both with the ranks as threads of one process:
 
 ``backend="host"``: numpy buffers, the phases computed by ``ops/peer_ref.py``, every access logged; two
@@ -77,11 +96,12 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ..ops.peer_ref import (ELEM as _ELEM, Q8_BLOCK, allreduce_q8_ref, allreduce_q8x2_ref, allreduce_ref, bf16_round, bits as _bits,
-                            out_dtype_of as _out_dtype, peer_slices, q8_blocks, q8_dequantize_ref, q8_quantize_ref, q8_slices)
+from ..ops.peer_ref import (ELEM as _ELEM, Q8_BLOCK, allreduce_q8_ef_ref, allreduce_q8_ref, allreduce_q8x2_ref, allreduce_ref, bf16_round,
+                            bits as _bits, out_dtype_of as _out_dtype, peer_slices, q8_blocks, q8_dequantize_ref, q8_quantize_ef_ref,
+                            q8_quantize_ref, q8_slices, reduce_scatter_q8_ef_ref)
 
 __all__ = ["PeerComm", "PeerCommError", "PeerCommTimeout", "PeerCommMismatch", "HostFabric", "MemoryStore",
-           "selftest_cases", "selftest_cases_q8", "selftest_cases_q8x2", "case_input", "run_case", "run_thread_ranks", "selftest", "thread_sweep", "timed_all_reduce", "parked_bytes",
+           "selftest_cases", "selftest_cases_q8", "selftest_cases_q8x2", "selftest_cases_ef", "case_input", "run_case", "run_thread_ranks", "selftest", "thread_sweep", "timed_all_reduce", "parked_bytes",
            "MAX_WORLD"]
 
 MAX_WORLD = 16  # kMaxSrc of csrc/probe/probe_common.h
@@ -168,7 +188,8 @@ class MemoryStore:
 
 class HostFabric:
     """The buffers of ``backend="host"`` (one window, one out and two packed buffers per rank, shared by
-    the ranks' threads) and the access log the conflict check reads."""
+    the ranks' threads; a rank's error-feedback residual, float32, made when it first asks for one) and the
+    access log the conflict check reads."""
 
     def __init__(self, world: int, capacity_bytes: int):
         self.world, self.capacity_bytes = world, capacity_bytes
@@ -176,6 +197,7 @@ class HostFabric:
         self.out = [np.zeros(2 * capacity_bytes, np.uint8) for _ in range(world)]
         self.packed = [np.zeros(_packed_bytes(capacity_bytes), np.uint8) for _ in range(world)]
         self.packed_out = [np.zeros(_packed_bytes(capacity_bytes), np.uint8) for _ in range(world)]
+        self.residual: List[Optional[np.ndarray]] = [None] * world  # capacity_bytes // 2 floats each, once made
         self.lock = threading.Lock()
         #: (accessor, owner, buffer, v0, v1, "r" | "w", the accessor's barrier count)
         self.log: List[Tuple[int, int, str, int, int, str, int]] = []
@@ -252,7 +274,27 @@ class _HostBackend:
         self.f.access(self.rank, p, name, 2 * nb + b0 // 16, 2 * nb + -(-b1 // 16), mode, self.epoch)
         return buf[Q8_BLOCK * b0:Q8_BLOCK * b1], buf[Q8_BLOCK * nb + b0:Q8_BLOCK * nb + b1]
 
-    def quantize(self, b0: int, b1: int, count: int, in_dtype: str) -> None:
+    def _residual(self, first: int, end: int, mode: str) -> np.ndarray:
+        """Floats ``[first, end)`` of this rank's own residual, made on first use, logged in vectors."""
+        if self.f.residual[self.rank] is None:
+            self.f.residual[self.rank] = np.zeros(self.f.capacity_bytes // 2, np.float32)
+        self.f.access(self.rank, self.rank, "residual", first * 4 // 16, -(-end * 4 // 16), mode, self.epoch)
+        return self.f.residual[self.rank][first:end]
+
+    @property
+    def residual_bytes(self) -> int:
+        return 0 if self.f.residual[self.rank] is None else 2 * self.f.capacity_bytes
+
+    def reset_residual(self) -> None:
+        if self.f.residual[self.rank] is not None:
+            self._residual(0, self.f.capacity_bytes // 2, "w")[:] = 0
+
+    def read_residual(self, first: int, n: int) -> np.ndarray:
+        if self.f.residual[self.rank] is None:
+            return np.zeros(n, np.float32)
+        return self._residual(first, first + n, "r").copy()
+
+    def quantize(self, b0: int, b1: int, count: int, in_dtype: str, error_feedback: bool = False) -> None:
         e = _ELEM[in_dtype]
         if b0 > b1 or b1 * Q8_BLOCK * e > self.f.capacity_bytes:
             raise ValueError("quantize: blocks past the end of the window")
@@ -264,7 +306,13 @@ class _HostBackend:
         n = max(0, min(int(count), b1 * Q8_BLOCK) - first)  # the elements of the range before the count: no others are read
         x = np.zeros((b1 - b0) * Q8_BLOCK, _NP[in_dtype])
         x[:n] = self._win(self.rank, first * e // 16, -(-(first + n) * e // 16), "r").view(_NP[in_dtype])[:n]
-        codes, exps = q8_quantize_ref(x, in_dtype)
+        if error_feedback:
+            res = np.zeros(x.size, np.float32)  # past the count the residual is not read, and comes back zero
+            res[:n] = self._residual(first, first + n, "r")
+            codes, exps, new = q8_quantize_ef_ref(x, in_dtype, res)
+            self._residual(first, b1 * Q8_BLOCK, "w")[:] = new
+        else:
+            codes, exps = q8_quantize_ref(x, in_dtype)
         c, x8 = self._packed(self.rank, b0, b1, "w")
         c[:], x8[:] = codes, (exps + _Q8_BIAS).astype(np.uint8)
 
@@ -346,9 +394,10 @@ _PARKED_LOCK = threading.Lock()
 
 def parked_bytes() -> int:
     """Device memory held by ranks of broken ``backend="device"`` communicators that were closed but
-    not freed, in bytes (a window, an out of twice its size and two packed buffers per rank)."""
+    not freed, in bytes (a window, an out of twice its size, two packed buffers and, where the rank had asked
+    for error feedback, its residual per rank)."""
     with _PARKED_LOCK:
-        return sum(3 * int(r.capacity_bytes) + 2 * int(r.packed_bytes) for r in _PARKED)
+        return sum(3 * int(r.capacity_bytes) + 2 * int(r.packed_bytes) + int(getattr(r, "residual_bytes", 0)) for r in _PARKED)
 
 
 class _DeviceBackend:
@@ -399,8 +448,18 @@ class _DeviceBackend:
     def reduce(self, v0: int, v1: int, in_dtype: str, out_dtype: str, scale: float) -> None:
         self.r.reduce(v0, v1, in_dtype, out_dtype, scale)
 
-    def quantize(self, b0: int, b1: int, count: int, in_dtype: str) -> None:
-        self.r.quantize(b0, b1, count, in_dtype)
+    def quantize(self, b0: int, b1: int, count: int, in_dtype: str, error_feedback: bool = False) -> None:
+        self.r.quantize(b0, b1, count, in_dtype, bool(error_feedback))
+
+    @property
+    def residual_bytes(self) -> int:
+        return int(self.r.residual_bytes)
+
+    def reset_residual(self) -> None:
+        self.r.reset_residual()
+
+    def read_residual(self, first: int, n: int) -> np.ndarray:
+        return self.r.read_residual(first, n)
 
     def reduce_q8(self, b0: int, b1: int, out_dtype: str, scale: float) -> None:
         self.r.reduce_q8(b0, b1, out_dtype, scale)
@@ -552,15 +611,23 @@ class PeerComm:
         may read any window and overwrite my out."""
         desc = {**desc, "seq": self._seq}
         self._seq += 1
-        self._b.synchronize()
-        mine = json.dumps(desc, sort_keys=True)
-        keys = [f"{self._prefix}/desc/{desc['seq']}/{p}" for p in range(self.world)]
-        self._stale[1].append(keys[self.rank])
-        self._store_call(lambda: self._store.set(keys[self.rank], mine), "publishing the call descriptor failed")
-        self._barrier()
-        theirs = self._store_call(lambda: [bytes(self._store.get(k)).decode() for k in keys], "reading the call descriptors failed")
-        if any(t != mine for t in theirs):
-            raise PeerCommMismatch(f"rank {self.rank}: the ranks disagree on collective {desc['seq']}: " + " | ".join(theirs))
+        try:
+            self._b.synchronize()
+            mine = json.dumps(desc, sort_keys=True)
+            keys = [f"{self._prefix}/desc/{desc['seq']}/{p}" for p in range(self.world)]
+            self._stale[1].append(keys[self.rank])
+            self._store_call(lambda: self._store.set(keys[self.rank], mine), "publishing the call descriptor failed")
+            self._barrier()
+            theirs = self._store_call(lambda: [bytes(self._store.get(k)).decode() for k in keys], "reading the call descriptors failed")
+            if any(t != mine for t in theirs):
+                raise PeerCommMismatch(f"rank {self.rank}: the ranks disagree on collective {desc['seq']}: " + " | ".join(theirs))
+        except BaseException:
+            if desc.get("ef"):  # the quantize has advanced the residual with data that no one will sum
+                try:
+                    self._b.reset_residual()
+                except Exception:  # the error that brought us here is the one to report
+                    pass
+            raise
 
     def _leave(self) -> None:
         """Barrier B.  One-shot, reduce-scatter and all-gather: nobody is still reading any window, so
@@ -571,9 +638,10 @@ class PeerComm:
 
     # -- collectives --------------------------------------------------------------------------
     def _reduce_args(self, op: str, count: int, dtype: str, algo: str, out_dtype: Optional[str], scale: float,
-                     wire: Optional[str] = None):
+                     wire: Optional[str] = None, error_feedback: bool = False):
         """The checked arguments of a reduce: its units (vectors of the window; blocks of 32 elements on the
-        fp8 wire), the output dtype, the scale as the kernel gets it, and the call's descriptor."""
+        fp8 wire), the output dtype, the scale as the kernel gets it, and the call's descriptor (``"ef"`` in it
+        only when feedback is set, so the descriptors of every other call are what they were)."""
         self._check()
         out = _out_dtype(dtype, out_dtype)
         if algo not in ALGOS:
@@ -582,6 +650,8 @@ class PeerComm:
             raise ValueError(f'wire must be None, "native", "fp8" or "fp8x2", got {wire!r}')
         if wire == "fp8x2" and (op != "all_reduce" or algo != "twoshot"):
             raise ValueError('wire="fp8x2" packs the gather phase of all_reduce(algo="twoshot"): nothing else has one')
+        if error_feedback and wire not in ("fp8", "fp8x2"):
+            raise ValueError('error_feedback=True belongs to wire="fp8" or "fp8x2": the native wire drops nothing')
         if count < 1:
             raise ValueError("count >= 1")
         scale = float(np.float32(scale))
@@ -591,21 +661,23 @@ class PeerComm:
             if n * Q8_BLOCK * _ELEM[dtype] > self.capacity_bytes:
                 raise ValueError(f"{count} {dtype} elements, rounded up to blocks of {Q8_BLOCK}, exceed the window of "
                                  f"{self.capacity_bytes} bytes")
-            return n, out, scale, {**desc, "wire": wire}
+            return n, out, scale, {**desc, "wire": wire, **({"ef": True} if error_feedback else {})}
         n = _n_vec(count, dtype)
         if n * 16 > self.capacity_bytes:
             raise ValueError(f"{count} {dtype} elements exceed the window of {self.capacity_bytes} bytes")
         return n, out, scale, desc
 
     def all_reduce(self, count: int, dtype: str = "bf16", algo: str = "twoshot", out_dtype: Optional[str] = None,
-                   scale: float = 1.0, wire: Optional[str] = None) -> None:
+                   scale: float = 1.0, wire: Optional[str] = None, error_feedback: bool = False) -> None:
         """out[0, count) of every rank = ``scale`` x the sum over ranks of window[0, count), in ``out_dtype``.
         ``wire="fp8"``: of the windows' packed forms; ``wire="fp8x2"`` (two-shot only): the same, packed once more
-        for the gather (see the module docstring)."""
-        n, out, scale, desc = self._reduce_args("all_reduce", count, dtype, algo, out_dtype, scale, wire)
+        for the gather (see the module docstring).  ``error_feedback=True`` (those two wires; ``ValueError`` on the
+        native one, before any barrier or launch): this rank's residual is added to its window before the packing
+        and keeps what the packing dropped."""
+        n, out, scale, desc = self._reduce_args("all_reduce", count, dtype, algo, out_dtype, scale, wire, error_feedback)
         if wire == "fp8x2":
             plan = q8_slices(n, self.world)
-            self._b.quantize(0, n, count, dtype)
+            self._b.quantize(0, n, count, dtype, error_feedback)
             self._enter(desc)
             self._b.repack_q8(*plan[self.rank], scale)
             self._leave()
@@ -616,7 +688,7 @@ class PeerComm:
         if wire == "fp8":
             per = Q8_BLOCK * _ELEM[out] // 16  # output vectors per block
             plan = q8_slices(n, self.world)
-            self._b.quantize(0, n, count, dtype)
+            self._b.quantize(0, n, count, dtype, error_feedback)
             self._enter(desc)
             a, b = (0, n) if algo == "oneshot" else plan[self.rank]
             self._b.reduce_q8(a, b, out, scale)
@@ -641,14 +713,15 @@ class PeerComm:
         self._b.synchronize()
 
     def reduce_scatter(self, count: int, dtype: str = "bf16", out_dtype: Optional[str] = None, scale: float = 1.0,
-                       wire: Optional[str] = None) -> Tuple[int, int]:
+                       wire: Optional[str] = None, error_feedback: bool = False) -> Tuple[int, int]:
         """Rank r reduces slice r of ``peer_slices`` only (``wire="fp8"``: of ``q8_slices``, over blocks of the
         packed forms).  Returns the ``(first, n)`` elements of out, in ``out_dtype``, that hold this rank's
-        piece (``n`` may be 0)."""
-        n, out, scale, desc = self._reduce_args("reduce_scatter", count, dtype, "oneshot", out_dtype, scale, wire)
+        piece (``n`` may be 0).  ``error_feedback=True`` (``wire="fp8"`` only): as in :meth:`all_reduce`; every
+        rank packs, and feeds back, its whole window."""
+        n, out, scale, desc = self._reduce_args("reduce_scatter", count, dtype, "oneshot", out_dtype, scale, wire, error_feedback)
         if wire == "fp8":
             a, b = q8_slices(n, self.world)[self.rank]
-            self._b.quantize(0, n, count, dtype)
+            self._b.quantize(0, n, count, dtype, error_feedback)
             self._enter(desc)
             self._b.reduce_q8(a, b, out, scale)
             self._leave()
@@ -697,6 +770,25 @@ class PeerComm:
         if dtype not in _ELEM or first < 0 or n < 0 or (first + n) * _ELEM[dtype] > 2 * self.capacity_bytes:
             raise ValueError("read: bad dtype, or past the end of out")
         return self._b.read_host(first, n, dtype)
+
+    def reset_error_feedback(self) -> None:
+        """This rank's residual back to zero (nothing, if it never asked for feedback).  To be called whenever
+        the window is about to hold something else than the calls so far fed back on."""
+        self._check()
+        self._b.reset_residual()
+
+    def residual(self, first: int, n: int) -> np.ndarray:
+        """Values ``[first, first + n)`` of this rank's residual as a float32 host array, value i belonging to
+        element i of the window; zeros before the first feedback call."""
+        self._check()
+        if first < 0 or n < 0 or (first + n) * 4 > 2 * self.capacity_bytes:
+            raise ValueError("residual: past the end of the residual")
+        return self._b.read_residual(first, n)
+
+    @property
+    def residual_bytes(self) -> int:
+        """Bytes of this rank's residual buffer: 0 until its first feedback call, then twice the window's."""
+        return self._b.residual_bytes
 
     def synchronize(self) -> None:
         self._b.synchronize()
@@ -789,13 +881,35 @@ def case_input(case_index: int, issue: int, rank: int, count: int, dtype: str) -
     return bf16_round(x) if dtype == "bf16" else x
 
 
-def run_case(comm: PeerComm, case: Dict[str, object], inputs: Sequence[np.ndarray]) -> Tuple[np.ndarray, np.ndarray]:
+def run_case(comm: PeerComm, case: Dict[str, object], inputs: Sequence[np.ndarray],
+             residuals: Optional[List[np.ndarray]] = None) -> Tuple[np.ndarray, np.ndarray]:
     """Issues one case on ``comm`` with ``inputs[comm.rank]`` as this rank's data; returns (got, reference),
-    both computed by this rank, the reference from every rank's input."""
+    both computed by this rank, the reference from every rank's input.
+
+    A case with ``"ef": True`` is issued with error feedback.  ``residuals`` is then the reference's residual
+    of every rank before this issue (float32, the count's whole blocks; none: zeros, a communicator just
+    reset), and the list is given the residuals after it, so issues chain: ``comm.residual(0, n)`` must equal
+    ``residuals[comm.rank]`` afterwards."""
     from ..ops.peer_ref import reduce_scatter_q8_ref, reduce_scatter_ref
 
     op, count, dtype, out = case["op"], int(case["count"]), case["dtype"], case["out_dtype"]
     k, r = comm.world, comm.rank
+    if case.get("ef"):
+        n = q8_blocks(count) * Q8_BLOCK
+        before = [np.zeros(n, np.float32) for _ in range(k)] if not residuals else list(residuals)
+        comm.write(inputs[r])
+        if op == "all_reduce":
+            comm.all_reduce(count, dtype, case["algo"], out, case["scale"], wire=case["wire"], error_feedback=True)
+            got = comm.read(0, count, out)
+            ref, after = allreduce_q8_ef_ref(inputs, before, dtype, out, case["scale"], wire=case["wire"])
+        else:
+            first, m = comm.reduce_scatter(count, dtype, out, case["scale"], wire="fp8", error_feedback=True)
+            got = comm.read(first, m, out)
+            pieces, after = reduce_scatter_q8_ef_ref(inputs, before, dtype, out, case["scale"])
+            ref = pieces[r]
+        if residuals is not None:
+            residuals[:] = after
+        return got, ref
     if case.get("wire") == "fp8x2":
         comm.write(inputs[r])
         comm.all_reduce(count, dtype, case["algo"], out, case["scale"], wire="fp8x2")
@@ -966,8 +1080,13 @@ def _case_capacity(k: int, cases: Sequence[Dict[str, object]]) -> int:
     return max(16, max(vecs(c) for c in cases) * 16)
 
 
+def selftest_cases_ef(k: int, counts: Optional[Sequence[int]] = None) -> List[Dict[str, object]]:
+    """The error-feedback cases: those of :func:`selftest_cases_q8` and :func:`selftest_cases_q8x2`, each with ``"ef": True``."""
+    return [{**c, "ef": True} for c in selftest_cases_q8(k, counts) + selftest_cases_q8x2(k, counts)]
+
+
 def selftest(devices: Sequence[int], counts: Optional[Sequence[int]] = None, timeout_s: float = 60.0,
-             wire: Optional[str] = None) -> Dict[str, object]:
+             wire: Optional[str] = None, error_feedback: bool = False) -> Dict[str, object]:
     """Every case of :func:`selftest_cases`, each issued twice in a row with different inputs, on
     thread ranks over ``devices`` (:func:`run_thread_ranks`), compared bit for bit with ``ops/peer_ref.py``.
 
@@ -978,13 +1097,20 @@ def selftest(devices: Sequence[int], counts: Optional[Sequence[int]] = None, tim
     none) run after them on the same communicators and are reported as ``q8_cases``, ``q8_collectives``,
     ``q8_wrong`` and ``q8_launches``.  ``wire="fp8x2"`` adds the cases of :func:`selftest_cases_q8x2` after those,
     reported as ``q8x2_cases``, ``q8x2_collectives``, ``q8x2_wrong`` and ``q8x2_launches``.
-    ``barriers_per_collective`` covers every set."""
+    ``barriers_per_collective`` covers every set.
+
+    ``error_feedback=True`` adds the cases of :func:`selftest_cases_ef` (both packed wires) after all of those.  Each is
+    issued three times in a row on the one communicator with different inputs and the residual carried from
+    issue to issue; the residual is reset before each case.  Every result, and after every issue the rank's
+    whole residual, is compared bit for bit with the chained reference.  Reported as ``ef_cases``,
+    ``ef_collectives``, ``ef_wrong`` and ``ef_launches``."""
     if wire not in WIRES:
         raise ValueError(f'wire must be None, "native", "fp8" or "fp8x2", got {wire!r}')
     k = len(devices)
     native = selftest_cases(k, counts)
     q8 = selftest_cases_q8(k, counts)
-    cases = native + q8 + (selftest_cases_q8x2(k, counts) if wire == "fp8x2" else [])
+    plain = native + q8 + (selftest_cases_q8x2(k, counts) if wire == "fp8x2" else [])
+    cases = plain + (selftest_cases_ef(k, counts) if error_feedback else [])
     once = _Once()  # every rank's inputs of (case, issue), made by the first rank that asks
 
     def inputs(ci: int, issue: int) -> List[np.ndarray]:
@@ -994,16 +1120,23 @@ def selftest(devices: Sequence[int], counts: Optional[Sequence[int]] = None, tim
     def body(comm: PeerComm):
         wrong, barriers, marks = set(), set(), {}
         for ci, case in enumerate(cases):
-            if ci in (len(native), len(native) + len(q8)):
+            if ci in (len(native), len(native) + len(q8), len(plain)):
                 marks[ci] = comm.launches
-            for issue in range(2):
+            fed = bool(case.get("ef"))
+            residuals: List[np.ndarray] = []
+            if fed:
+                comm.reset_error_feedback()
+            for issue in range(3 if fed else 2):
                 before = comm.barriers
-                got, ref = run_case(comm, case, inputs(ci, issue))
+                got, ref = run_case(comm, case, inputs(ci, issue), residuals if fed else None)
                 barriers.add(comm.barriers - before)
                 if got.dtype != ref.dtype or got.shape != ref.shape or not np.array_equal(_bits(got), _bits(ref)):
                     wrong.add((ci, issue))
-        first_q8, end_q8 = marks[len(native)], marks.get(len(native) + len(q8), comm.launches)
-        return wrong, barriers, first_q8, end_q8 - first_q8, comm.launches - end_q8
+                elif fed and not np.array_equal(_bits(comm.residual(0, residuals[comm.rank].size)), _bits(residuals[comm.rank])):
+                    wrong.add((ci, issue))
+        end = marks.get(len(plain), comm.launches)
+        first_q8, end_q8 = marks[len(native)], marks.get(len(native) + len(q8), end)
+        return wrong, barriers, first_q8, end_q8 - first_q8, end - end_q8, comm.launches - end
 
     res = run_thread_ranks(devices, body, _case_capacity(k, cases), timeout_s=timeout_s)
     bad = set().union(*(r[0] for r in res))
@@ -1013,7 +1146,11 @@ def selftest(devices: Sequence[int], counts: Optional[Sequence[int]] = None, tim
            "q8_cases": nq, "q8_collectives": 2 * nq, "q8_wrong": sum(n <= ci < n + nq for ci, _ in bad),
            "q8_launches": sum(r[3] for r in res)}
     if wire == "fp8x2":
-        nx = len(cases) - n - nq
-        rep.update({"q8x2_cases": nx, "q8x2_collectives": 2 * nx, "q8x2_wrong": sum(ci >= n + nq for ci, _ in bad),
+        nx = len(plain) - n - nq
+        rep.update({"q8x2_cases": nx, "q8x2_collectives": 2 * nx, "q8x2_wrong": sum(n + nq <= ci < len(plain) for ci, _ in bad),
                     "q8x2_launches": sum(r[4] for r in res)})
+    if error_feedback:
+        ne = len(cases) - len(plain)
+        rep.update({"ef_cases": ne, "ef_collectives": 3 * ne, "ef_wrong": sum(ci >= len(plain) for ci, _ in bad),
+                    "ef_launches": sum(r[5] for r in res)})
     return rep
