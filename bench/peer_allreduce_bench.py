@@ -2,7 +2,8 @@
 """K7 peer all-reduce next to its comparators, on given members and sizes, as one JSON document:
 
     python bench/peer_allreduce_bench.py [--members 0,0,0,0] [--sizes-mib 1,4,16,64,256,1024]
-                                         [--dtype bf16] [--iters 5] [--wire native|fp8|both|fp8x2|all] [--out FILE] [--md FILE]
+                                         [--dtype bf16] [--iters 5] [--wire native|fp8|both|fp8x2|all] [--push [--reps 3]]
+                                         [--out FILE] [--md FILE]
 
 Per size N (bytes per member):
   * the peer all-reduce under both algorithms (algBW, busBW, and the bytes each member moves:
@@ -17,7 +18,11 @@ and the rate each reaches alone on member 0.
 ``--wire fp8x2`` measures the two-shot whose gather phase is packed too (``twoshot_fp8x2``: quantize, repack,
 unpack), and ``--wire all`` the two-shot on the native wire, then on ``fp8``, then on ``fp8x2`` at every size,
 interleaved in one process, with the three kernels of ``fp8x2`` alone on member 0.
-Members that repeat a device give HBM rates of that one GPU, not xGMI rates.
+``--push`` measures something else: the push algorithm (one launch per member stores its slice of the sum into
+every member's out) against the two-shot, on the native and on the fp8 wire, the two alternated ``--reps`` times
+at every size in one process and the quicker repetition of each reported (``twoshot``, ``push``, ``twoshot_fp8``,
+``push_fp8``).  No K6 or RCCL run is made.
+Members that repeat a device give HBM rates of that one GPU, not xGMI rates: no store of a push then crosses a link.
 """
 import argparse
 import json
@@ -42,9 +47,13 @@ def member_bytes(algo: str, k: int, n: int, wire: str = "native", elem: int = 2,
     P / k; the unpack reads all k slices, P, and writes the whole result, n x ``out_elem`` / ``elem``
     (``out_elem`` 0: the input's)."""
     if wire == "native":
+        if algo == "push":  # slice m of every input in, slice m of every out written: n / k x k each way
+            return {"read": n, "written": n}
         return {"read": k * n if algo == "oneshot" else (2 * k - 1) * n // k, "written": n}
     packed = n // elem * 33 // 32
     quantize = {"read": n, "written": packed}
+    if algo == "push":  # the sum reads slice m of every packed buffer and writes slice m of every out
+        return {"read": n + packed, "written": packed + n, "quantize": quantize, "sum": {"read": packed, "written": n}}
     if wire == "fp8x2":
         if algo != "twoshot":
             raise ValueError("the fp8x2 wire is a two-shot")
@@ -115,6 +124,47 @@ def measure(devs, sizes, dtype, iters, warmup, wire="native"):
             "wire": wire, "sizes": rows, "twoshot_faster_from_bytes": crossover}
 
 
+PUSH_PAIRS = (("twoshot", "native"), ("push", "native"), ("twoshot", "fp8"), ("push", "fp8"))
+
+
+def measure_push(devs, sizes, dtype, iters, warmup, reps):
+    """Push against two-shot on both wires: per size the four points in the order of PUSH_PAIRS, ``reps`` times
+    over, so the two algorithms alternate; the quicker repetition of each is the point reported."""
+    k = len(devs)
+    rows = []
+    for n in sizes:
+        runs = {key(a, w): [] for a, w in PUSH_PAIRS}
+        for _ in range(reps):
+            for a, w in PUSH_PAIRS:
+                runs[key(a, w)].append(point(devs, n, dtype, a, iters, warmup, w))
+        row = {"bytes": n}
+        for name, pts in runs.items():
+            best = min(pts, key=lambda p: p["time_us"])
+            row[name] = {**best, "time_us_reps": [p["time_us"] for p in pts], "wrong": sum(p["wrong"] for p in pts)}
+        for sfx in ("", "_fp8"):
+            row["push_over_twoshot" + sfx] = row["push" + sfx]["time_us"] / row["twoshot" + sfx]["time_us"]
+        rows.append(row)
+        print(json.dumps(row), file=sys.stderr, flush=True)
+    return {"members": list(devs), "k": k, "distinct_devices": len(set(devs)) == k, "dtype": dtype, "iters": iters, "warmup": warmup,
+            "reps": reps, "push": True, "derived_traffic_ratio": (3 - 1 / k) / 2, "sizes": rows}
+
+
+def markdown_push(res) -> str:
+    mib = lambda b: f"{b / 2**20:.1f}"  # noqa: E731
+    out = [f"### push against two-shot, driver, members {res['members']} (k = {res['k']}), {res['dtype']}, {res['iters']} timed rounds, "
+           f"best of {res['reps']} alternated repetitions", "",
+           "| N per member MiB | wire | twoshot us | push us | push / twoshot time | twoshot / push time | twoshot MiB read + written | "
+           "push MiB read + written | wrong |", "|---|---|---|---|---|---|---|---|---|"]
+    for r in res["sizes"]:
+        for sfx, wire in (("", "native"), ("_fp8", "fp8")):
+            t, p = r["twoshot" + sfx], r["push" + sfx]
+            out.append(f"| {mib(r['bytes'])} | {wire} | {t['time_us']:.1f} | {p['time_us']:.1f} | {p['time_us'] / t['time_us']:.2f} "
+                       f"| {t['time_us'] / p['time_us']:.2f} | {mib(t['member_read_bytes'])} + {mib(t['member_written_bytes'])} "
+                       f"| {mib(p['member_read_bytes'])} + {mib(p['member_written_bytes'])} | {t['wrong'] + p['wrong']} |")
+    out += ["", f"Derived traffic of one member on the native wire, two-shot over push: (3 - 1/k) / 2 = {res['derived_traffic_ratio']:.3f}.", ""]
+    return "\n".join(out)
+
+
 def markdown_fp8(res) -> str:
     """The fp8 wire next to the native one: one line per size and algorithm."""
     mib = lambda b: f"{b / 2**20:.1f}"  # noqa: E731
@@ -161,6 +211,8 @@ def markdown_fp8x2(res) -> str:
 
 
 def markdown(res) -> str:
+    if res.get("push"):
+        return markdown_push(res)
     if res["wire"] == "fp8":
         return markdown_fp8(res)
     if res["wire"] in ("fp8x2", "all"):
@@ -191,6 +243,8 @@ def main():
     ap.add_argument("--wire", default="native", choices=["native", "fp8", "both", "fp8x2", "all"],
                     help="fp8: the block-scaled e4m3 wire alone; both: it next to the native wire, interleaved; fp8x2: the "
                          "two-shot with its gather phase packed too; all: the two-shot on native, fp8 and fp8x2, interleaved")
+    ap.add_argument("--push", action="store_true", help="the push algorithm against the two-shot on the native and the fp8 wire, alternated")
+    ap.add_argument("--reps", type=int, default=3, help="--push: alternated repetitions of each measurement")
     ap.add_argument("--out", default="", help="also write the JSON document here")
     ap.add_argument("--md", default="", help="also write the tables as Markdown here")
     a = ap.parse_args()
@@ -198,7 +252,8 @@ def main():
     sizes = [int(float(x) * (1 << 20)) for x in a.sizes_mib.split(",")]
     probe.warmup(groups[0][0], 100.0)
     doc = {"device": probe.device_props(groups[0][0])["name"], "rates": "GB/s (1e9 bytes/s)",
-           "runs": [measure(g, sizes, a.dtype, a.iters, a.warmup, a.wire) for g in groups]}
+           "runs": [measure_push(g, sizes, a.dtype, a.iters, a.warmup, max(1, a.reps)) if a.push else
+                    measure(g, sizes, a.dtype, a.iters, a.warmup, a.wire) for g in groups]}
     text = json.dumps(doc)
     print(text)
     for path, body in ((a.out, text + "\n"), (a.md, "\n".join(markdown(r) for r in doc["runs"]))):
@@ -206,7 +261,7 @@ def main():
             os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
             with open(path, "w") as f:
                 f.write(body)
-    measured = [al + sfx for al in probe.PEER_ALGOS for sfx in ("", "_fp8", "_fp8x2")]
+    measured = [al + sfx for al in probe.PEER_ALGOS + (probe.PEER_PUSH,) for sfx in ("", "_fp8", "_fp8x2")]
     return 1 if any(r[al]["wrong"] for run in doc["runs"] for r in run["sizes"] for al in measured if al in r) else 0
 
 

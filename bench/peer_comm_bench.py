@@ -2,7 +2,7 @@
 """The peer communicator's thread-rank all_reduce next to the in-process driver's, as one JSON document:
 
     python bench/peer_comm_bench.py [--members 0,0,0,0] [--sizes-mib 1,4,16,64,256] [--dtype bf16]
-                                    [--iters 20] [--warmup 2] [--wire native|fp8|fp8x2] [--error-feedback]
+                                    [--iters 20] [--warmup 2] [--wire native|fp8|fp8x2] [--error-feedback] [--push]
                                     [--out FILE] [--md FILE]
 
 Both run the same K7 kernels on the same members at the same count, in one process:
@@ -21,6 +21,12 @@ window first and the ranks read the packed forms; ``--wire fp8x2`` the two-shot 
 with and without error feedback, the two alternated ``--reps`` times in one process, the quicker repetition of
 each reported.  The feedback form's quantize reads and writes the rank's fp32 residual next to the window; the
 link bytes, the launches and the barriers are the plain call's.  No driver run is made.
+
+``--push`` measures the push algorithm (``all_reduce(algo="push")``: one launch stores the rank's slice of the sum
+into every rank's out; two stream synchronisations per call where the two-shot has three) against the two-shot
+on thread ranks, on the native and on the fp8 wire, the two alternated ``--reps`` times in one process, the
+quicker repetition of each reported.  Up to ``--check-max-mib`` the push result is compared with the host
+reference; at every size it is compared bit for bit with the two-shot's.  No driver run is made.
 """
 import argparse
 import json
@@ -85,6 +91,69 @@ def measure(devs, sizes, dtype, iters, warmup, reps, wire="native"):
         print(json.dumps(row), file=sys.stderr, flush=True)
     return {"members": list(devs), "k": k, "distinct_devices": len(set(devs)) == k, "dtype": dtype, "iters": iters, "warmup": warmup,
             "reps": reps, "wire": wire, "sizes": out}
+
+
+def measure_push(devs, sizes, dtype, iters, warmup, reps, check_max_bytes):
+    """Host seconds per ``all_reduce`` call of the two-shot and of the push on thread ranks, alternated, on both wires."""
+    k, elem = len(devs), ELEM[dtype]
+    counts = [max(1, n // elem) for n in sizes]
+    once = pc._Once()
+
+    def body(comm):
+        rows = []
+        for count in counts:
+            xs = once.get(("in", count), lambda: [pc.case_input(0, 0, p, count, dtype) for p in range(k)], lambda o: o[1] == count)
+            comm.write(xs[comm.rank])
+            for wire in ("native", "fp8"):
+                checked = count * elem <= check_max_bytes
+                ref = once.get(("ref", count, wire), lambda: pc._WIRE_REF[wire](xs, dtype), lambda o: o[1] == count) if checked else None
+                for r in range(reps):
+                    two, two_barriers = pc.timed_all_reduce(comm, count, dtype, "twoshot", iters, warmup, wire)
+                    kept = comm.read(0, count, dtype) if r == 0 else None
+                    comm.barrier()  # no rank checks a result, holding the interpreter, while another still reads its clock
+                    push, push_barriers = pc.timed_all_reduce(comm, count, dtype, "push", iters, warmup, wire)
+                    wrong = differ = 0
+                    if r == 0:
+                        got = comm.read(0, count, dtype)
+                        differ = int(np.count_nonzero(pc._bits(got) != pc._bits(kept)))
+                        wrong = int(np.count_nonzero(pc._bits(got) != pc._bits(ref))) if checked else 0
+                    comm.barrier()
+                    rows.append((count, wire, r, two, push, two_barriers, push_barriers, wrong, differ, checked))
+        return rows
+
+    res = pc.run_thread_ranks(devs, body, q8_blocks(max(counts)) * Q8_BLOCK * elem, timeout_s=300.0, join_s=3000.0)
+    out = []
+    for count in counts:
+        row = {"bytes": count * elem, "count": count}
+        for wire in ("native", "fp8"):
+            mine = [[r for r in rank_rows if r[:2] == (count, wire)] for rank_rows in res]
+            two = [max(rows[r][3] for rows in mine) * 1e6 for r in range(reps)]  # the slowest rank of each repetition
+            push = [max(rows[r][4] for rows in mine) * 1e6 for r in range(reps)]
+            bt, bp = min(range(reps), key=lambda i: two[i]), min(range(reps), key=lambda i: push[i])
+            row[wire] = {"twoshot_time_us": two[bt], "push_time_us": push[bp], "push_over_twoshot": push[bp] / two[bt],
+                         "twoshot_barrier_us": sum(rows[bt][5] for rows in mine) / k * 1e6,
+                         "push_barrier_us": sum(rows[bp][6] for rows in mine) / k * 1e6,
+                         "twoshot_time_us_reps": two, "push_time_us_reps": push, "checked_against_reference": bool(mine[0][0][9]),
+                         "push_wrong": sum(r[7] for rows in mine for r in rows), "push_differs_from_twoshot": sum(r[8] for rows in mine for r in rows)}
+        out.append(row)
+        print(json.dumps(row), file=sys.stderr, flush=True)
+    return {"members": list(devs), "k": k, "distinct_devices": len(set(devs)) == k, "dtype": dtype, "iters": iters, "warmup": warmup,
+            "reps": reps, "push": True, "sizes": out}
+
+
+def markdown_push(res) -> str:
+    out = [f"### push against two-shot, thread ranks, members {res['members']} (k = {res['k']}), {res['dtype']}, {res['iters']} timed calls, "
+           f"best of {res['reps']} alternated repetitions", "",
+           "| N per member | wire | twoshot us / call | of it in barriers | push us / call | of it in barriers | push / twoshot | wrong | differs from twoshot |",
+           "|---|---|---|---|---|---|---|---|---|"]
+    for r in res["sizes"]:
+        for wire in ("native", "fp8"):
+            a = r[wire]
+            out.append(f"| {r['bytes'] / 2**20:.1f} MiB | {wire} | {a['twoshot_time_us']:.1f} | {a['twoshot_barrier_us']:.1f} | {a['push_time_us']:.1f} "
+                       f"| {a['push_barrier_us']:.1f} | {a['push_over_twoshot']:.2f} | {a['push_wrong'] if a['checked_against_reference'] else 'n/a'} "
+                       f"| {a['push_differs_from_twoshot']} |")
+    out.append("")
+    return "\n".join(out)
 
 
 EF_CALLS = ("reduce_scatter", "twoshot")
@@ -191,6 +260,8 @@ def main():
                     help="fp8: the block-scaled e4m3 wire of csrc/probe/peer_q8.h; fp8x2: the two-shot with its gather phase packed too")
     ap.add_argument("--error-feedback", action="store_true",
                     help="thread ranks alone: the fp8 reduce_scatter and two-shot all_reduce without and with error feedback, alternated")
+    ap.add_argument("--push", action="store_true", help="thread ranks alone: the push all_reduce against the two-shot on the native and the fp8 wire, alternated")
+    ap.add_argument("--check-max-mib", type=float, default=64.0, help="--push: the largest size whose result is compared with the host reference")
     ap.add_argument("--reps", type=int, default=2, help="alternated repetitions of each measurement")
     ap.add_argument("--out", default="", help="also write the JSON document here")
     ap.add_argument("--md", default="", help="also write the tables as Markdown here")
@@ -198,6 +269,18 @@ def main():
     groups = [[int(x) for x in m.split(",")] for m in (a.members or ["0,0,0,0"])]
     sizes = [int(float(x) * (1 << 20)) for x in a.sizes_mib.split(",")]
     probe.warmup(groups[0][0], 100.0)
+    if a.push:
+        doc = {"device": probe.device_props(groups[0][0])["name"],
+               "runs": [measure_push(g, sizes, a.dtype, a.iters, a.warmup, max(1, a.reps), int(a.check_max_mib * (1 << 20))) for g in groups]}
+        text = json.dumps(doc)
+        print(text)
+        for path, body in ((a.out, text + "\n"), (a.md, "\n".join(markdown_push(r) for r in doc["runs"]))):
+            if path:
+                os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+                with open(path, "w") as f:
+                    f.write(body)
+        return 1 if any(r[w][key] for run in doc["runs"] for r in run["sizes"] for w in ("native", "fp8")
+                        for key in ("push_wrong", "push_differs_from_twoshot")) else 0
     if a.error_feedback:
         if a.wire == "fp8x2":
             ap.error("--error-feedback compares the calls of the fp8 wire")

@@ -14,6 +14,9 @@
 // that reaches 0x7F7F8000 rounds to a bf16 Inf.  Which NaN comes out (sign, payload) is the hardware's
 // choice, the same on every member; tests/test_gpu_peer_nonfinite.py compares the rest bit for bit.
 //
+// The push form (peer_reduce_push_kernel) is the same body with another sink for the stores: every result
+// vector goes to every member's `out`, so what is said above about the bits holds for it unchanged.
+//
 // No kernel here waits for another running kernel: the all-reduce's cross-member ordering is stream
 // events between launches (the host driver in peer_driver.h), visibility rests on kernel boundaries.
 #pragma once
@@ -52,34 +55,63 @@ __device__ __forceinline__ u32x4 peer_narrow(const float (&f)[8]) {
   return v;
 }
 
+// Where a position's rounded result goes: `sink(v, dst, o)` stores the N vectors v[] at vector offsets
+// o, o + 1, ... of `dst`, the launch's first (PeerOneDst: only) destination, non-temporally.  PeerPushDst is the push form:
+// after `dst`, which is dsts.p[0], the same vectors go to dsts.p[d] + o for every 0 < d < k, in the set's order
+// (the host chooses it) and destination by destination, so the adjacent vectors of one position reach each
+// destination back to back; KB is the member bucket as in peer_reduce_vecs, so p[] is indexed by constants only.
+struct PeerOneDst {
+  template <int N>
+  __device__ __forceinline__ void operator()(const u32x4 (&v)[N], u32x4* __restrict__ dst, size_t o) const {
+#pragma unroll
+    for (int j = 0; j < N; ++j) __builtin_nontemporal_store(v[j], dst + o + j);
+  }
+};
+template <int KB>
+struct PeerPushDst {
+  const DstSet& dsts;
+  int k;
+  template <int N>
+  __device__ __forceinline__ void operator()(const u32x4 (&v)[N], u32x4* __restrict__ dst, size_t o) const {
+#pragma unroll
+    for (int j = 0; j < N; ++j) __builtin_nontemporal_store(v[j], dst + o + j);
+#pragma unroll
+    for (int d = 1; d < KB; ++d)
+      if (d < k) {
+#pragma unroll
+        for (int j = 0; j < N; ++j) __builtin_nontemporal_store(v[j], dsts.p[d] + o + j);
+      }
+  }
+};
+
 // One position's result: `scale` applied to the fp32 sum, then a bf16 output rounds once and stores one
 // vector at `o`; an fp32 output of bf16 inputs (the wide form) stores two, at 2 * o and 2 * o + 1, so its
 // offsets and slice bounds are twice the input's.  scale == 1.0f changes no bit of the sum.
-template <typename TO, int L>
-__device__ __forceinline__ void peer_store(float (&acc)[L], float scale, u32x4* __restrict__ dst, size_t o) {
+template <typename TO, int L, typename Sink>
+__device__ __forceinline__ void peer_store(float (&acc)[L], float scale, const Sink& sink, u32x4* __restrict__ dst, size_t o) {
 #pragma unroll
   for (int j = 0; j < L; ++j) acc[j] = acc[j] * scale;
   if constexpr (L == kPeerLanes<TO>) {
-    __builtin_nontemporal_store(peer_narrow(acc), dst + o);
+    const u32x4 v[1] = {peer_narrow(acc)};
+    sink(v, dst, o);
   } else {
     static_assert(L == 8 && kPeerLanes<TO> == 4, "the wide form is bf16 in, fp32 out");
-    u32x4 lo, hi;
+    u32x4 v[2];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      lo[j] = __float_as_uint(acc[j]);
-      hi[j] = __float_as_uint(acc[4 + j]);
+      v[0][j] = __float_as_uint(acc[j]);
+      v[1][j] = __float_as_uint(acc[4 + j]);
     }
-    __builtin_nontemporal_store(lo, dst + 2 * o);
-    __builtin_nontemporal_store(hi, dst + 2 * o + 1);
+    sink(v, dst, 2 * o);
   }
 }
 
 // U vectors per lane, `stride` apart from `i`: the k x U loads (member-major, all in flight before the
 // first add), then per position the sum in member order, one multiply by `scale`, one rounding and the
 // store.  TI / TO are the input and output element types.  KB is the member bucket the registers are
-// sized for (k <= KB): r[] is indexed by constants only.
-template <typename TI, typename TO, int KB, int U>
-__device__ __forceinline__ void peer_reduce_vecs(const SrcSet& srcs, int k, u32x4* __restrict__ dst, size_t i,
+// sized for (k <= KB): r[] is indexed by constants only.  `sink` takes the stores (PeerOneDst, PeerPushDst).
+template <typename TI, typename TO, int KB, int U, typename Sink>
+__device__ __forceinline__ void peer_reduce_vecs(const SrcSet& srcs, int k, const Sink& sink, u32x4* __restrict__ dst, size_t i,
                                                  size_t stride, float scale) {
   u32x4 r[KB][U];
 #pragma unroll
@@ -100,27 +132,44 @@ __device__ __forceinline__ void peer_reduce_vecs(const SrcSet& srcs, int k, u32x
 #pragma unroll
         for (int j = 0; j < kPeerLanes<TI>; ++j) acc[j] = acc[j] + x[j];
       }
-    peer_store<TO>(acc, scale, dst, i + (size_t)u * stride);
+    peer_store<TO>(acc, scale, sink, dst, i + (size_t)u * stride);
   }
 }
 
-// dst[v0, v1) = scale * sum over members m < k of srcs.p[m][v0, v1), vectors of the input type TI
-// (float, or bf16 as raw u16); the wide form (bf16 in, float out) writes dst[2 * v0, 2 * v1).  Whole
+// dst[v0, v1), and the same vectors of what else the sink stores to, = scale * sum over members m < k of
+// srcs.p[m][v0, v1), vectors of the input type TI (float, or bf16 as raw u16); the wide form (bf16 in, float
+// out) writes [2 * v0, 2 * v1).  Whole
 // tiles (kStreamBlock x U vectors) are cut into one contiguous run per block, as gtk::stream_slices
 // does; what is left of the range, under one tile, goes one vector per lane over the whole grid.
-template <typename TI, typename TO, int KB, int U>
-__global__ __launch_bounds__(gtk::kStreamBlock) void peer_reduce_kernel(SrcSet srcs, int k, size_t v0, size_t v1,
-                                                                        u32x4* __restrict__ dst, float scale) {
+template <typename TI, typename TO, int KB, int U, typename Sink>
+__device__ __forceinline__ void peer_reduce_range(const SrcSet& srcs, int k, size_t v0, size_t v1, const Sink& sink,
+                                                  u32x4* __restrict__ dst, float scale) {
   const size_t tile = (size_t)gtk::kStreamBlock * U;
   const size_t n_tiles = (v1 - v0) / tile;
   const size_t per = (n_tiles + gridDim.x - 1) / gridDim.x;
   const size_t t0 = (size_t)blockIdx.x * per;
   const size_t t1 = std::min(n_tiles, t0 + per);
   for (size_t t = t0; t < t1; ++t)
-    peer_reduce_vecs<TI, TO, KB, U>(srcs, k, dst, v0 + t * tile + threadIdx.x, gtk::kStreamBlock, scale);
+    peer_reduce_vecs<TI, TO, KB, U>(srcs, k, sink, dst, v0 + t * tile + threadIdx.x, gtk::kStreamBlock, scale);
   for (size_t i = v0 + n_tiles * tile + (size_t)blockIdx.x * gtk::kStreamBlock + threadIdx.x; i < v1;
        i += (size_t)gridDim.x * gtk::kStreamBlock)
-    peer_reduce_vecs<TI, TO, KB, 1>(srcs, k, dst, i, 0, scale);
+    peer_reduce_vecs<TI, TO, KB, 1>(srcs, k, sink, dst, i, 0, scale);
+}
+
+// The reduce into the launching member's own `dst`.
+template <typename TI, typename TO, int KB, int U>
+__global__ __launch_bounds__(gtk::kStreamBlock) void peer_reduce_kernel(SrcSet srcs, int k, size_t v0, size_t v1,
+                                                                        u32x4* __restrict__ dst, float scale) {
+  peer_reduce_range<TI, TO, KB, U>(srcs, k, v0, v1, PeerOneDst{}, dst, scale);
+}
+
+// The push form: the same range, sum and rounding, every result vector stored to the same offset of every
+// dsts.p[d], d < k: all members' `out`, the launching member's among them.  No member reads an `out`, and
+// vectors [v0, v1) of every `out` are written by this launch alone, so a round needs no second phase.
+template <typename TI, typename TO, int KB, int U>
+__global__ __launch_bounds__(gtk::kStreamBlock) void peer_reduce_push_kernel(SrcSet srcs, DstSet dsts, int k, size_t v0,
+                                                                             size_t v1, float scale) {
+  peer_reduce_range<TI, TO, KB, U>(srcs, k, v0, v1, PeerPushDst<KB>{dsts, k}, dsts.p[0], scale);
 }
 
 // Slice i of an all-gather: `count` vectors from vector `first` of p[i], to the same offset of dst.

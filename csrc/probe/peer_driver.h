@@ -9,9 +9,15 @@
 //            one launch, no dependency between members.
 //   twoshot: phase 1, member m reduces slice m of every `in` into slice m of its `out`; phase 2, it
 //            copies slice p from out[p] for every p != m.  Ingress per member 2(k-1)/k x N.
+//   push:    member m reduces slice m of every `in` and stores the result into slice m of every member's
+//            `out` (peer_reduce_push_kernel), its own first and the others in ring order: (k-1)/k x N read
+//            in and (k-1)/k x N written out per member, one launch, no second phase, the two-shot's bits.
 // Members are ordered by stream events alone (no kernel waits for a running kernel): e1[m] follows
 // m's phase 1 and every member's phase 2 waits for all of them; e2[m] follows m's phase 2 and every
 // member's next phase 1 waits for all of them, since phase 2 of p reads the slice m then overwrites.
+// A push takes none of those events: slice m of every `out` is written by member m alone, on m's stream,
+// and no kernel of a round reads an `out`, so consecutive rounds of a member are ordered by its stream.
+// On the fp8 wire it takes the one-shot's: eq before the sum, e1 before the next quantize.
 //   wire fp8: a round starts with every member packing its own `in` into its own packed buffer
 //            (peer_q8.h), phase 1 reads the packed buffers, blocks of 32 elements in place of vectors,
 //            and phase 2 is unchanged.  eq[m] follows m's quantize and every member's phase 1 waits for
@@ -87,6 +93,40 @@ void launch_peer_reduce(PeerTypes t, const SrcSet& set, int k, size_t v0, size_t
     launch_peer_reduce<uint16_t, float>(set, k, v0, v1, dst, scale, grid, s);
 }
 
+// The push form: the reduce's buckets and U, the stores of every position going to every dsts.p[d], d < k.
+template <typename TI, typename TO>
+void launch_peer_reduce_push(const SrcSet& set, const DstSet& dsts, int k, size_t v0, size_t v1, float scale, int grid, hipStream_t s) {
+  const dim3 g(grid), b(kBlock);
+  if (k <= 2)
+    peer_reduce_push_kernel<TI, TO, 2, 4><<<g, b, 0, s>>>(set, dsts, k, v0, v1, scale);
+  else if (k <= 4)
+    peer_reduce_push_kernel<TI, TO, 4, 4><<<g, b, 0, s>>>(set, dsts, k, v0, v1, scale);
+  else if (k <= 8)
+    peer_reduce_push_kernel<TI, TO, 8, 2><<<g, b, 0, s>>>(set, dsts, k, v0, v1, scale);
+  else
+    peer_reduce_push_kernel<TI, TO, 16, 1><<<g, b, 0, s>>>(set, dsts, k, v0, v1, scale);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_peer_reduce_push(PeerTypes t, const SrcSet& set, const DstSet& dsts, int k, size_t v0, size_t v1, float scale, int grid,
+                             hipStream_t s) {
+  if (!t.in_bf16)
+    launch_peer_reduce_push<float, float>(set, dsts, k, v0, v1, scale, grid, s);
+  else if (t.out_bf16)
+    launch_peer_reduce_push<uint16_t, uint16_t>(set, dsts, k, v0, v1, scale, grid, s);
+  else
+    launch_peer_reduce_push<uint16_t, float>(set, dsts, k, v0, v1, scale, grid, s);
+}
+
+// The destinations of member m's push: every member's `out`, m's own first and the others in ring order
+// after it, so the k members of a round do not all store to member 0 first.
+DstSet peer_push_dsts(const std::vector<u32x4*>& outs, int m) {
+  DstSet d{};
+  const int k = (int)outs.size();
+  for (int j = 0; j < k; ++j) d.p[j] = outs[(m + j) % k];
+  return d;
+}
+
 // The fp8 wire's two launches.  The sum keeps the reduce's member buckets and U: k x U code vectors and as
 // many exponent words per lane, 80 VGPRs of loads, and sixteen accumulators.
 template <typename TO>
@@ -110,6 +150,29 @@ void launch_peer_q8_sum(bool out_bf16, const SrcSet& packed, int k, size_t exp_v
     launch_peer_q8_sum<uint16_t>(packed, k, exp_vec, b0, b1, dst, scale, grid, s);
   else
     launch_peer_q8_sum<float>(packed, k, exp_vec, b0, b1, dst, scale, grid, s);
+}
+
+template <typename TO>
+void launch_peer_q8_sum_push(const SrcSet& packed, const DstSet& dsts, int k, size_t exp_vec, size_t b0, size_t b1, float scale,
+                             int grid, hipStream_t s) {
+  const dim3 g(grid), b(kBlock);
+  if (k <= 2)
+    peer_q8_sum_push_kernel<TO, 2, 4><<<g, b, 0, s>>>(packed, dsts, k, exp_vec, b0, b1, scale);
+  else if (k <= 4)
+    peer_q8_sum_push_kernel<TO, 4, 4><<<g, b, 0, s>>>(packed, dsts, k, exp_vec, b0, b1, scale);
+  else if (k <= 8)
+    peer_q8_sum_push_kernel<TO, 8, 2><<<g, b, 0, s>>>(packed, dsts, k, exp_vec, b0, b1, scale);
+  else
+    peer_q8_sum_push_kernel<TO, 16, 1><<<g, b, 0, s>>>(packed, dsts, k, exp_vec, b0, b1, scale);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_peer_q8_sum_push(bool out_bf16, const SrcSet& packed, const DstSet& dsts, int k, size_t exp_vec, size_t b0, size_t b1,
+                             float scale, int grid, hipStream_t s) {
+  if (out_bf16)
+    launch_peer_q8_sum_push<uint16_t>(packed, dsts, k, exp_vec, b0, b1, scale, grid, s);
+  else
+    launch_peer_q8_sum_push<float>(packed, dsts, k, exp_vec, b0, b1, scale, grid, s);
 }
 
 void launch_peer_q8_quantize(bool in_bf16, const u32x4* win, u32x4* packed, size_t exp_vec, size_t b0, size_t b1, size_t count,
@@ -166,6 +229,8 @@ PeerWire peer_wire(const std::string& wire, const std::string& algo) {
   if (wire != "native" && wire != "fp8" && wire != "fp8x2") throw std::invalid_argument("wire must be native|fp8|fp8x2");
   if (wire == "fp8x2" && algo == "oneshot")
     throw std::invalid_argument("wire fp8x2 packs the gather phase of a twoshot: a oneshot has none");
+  if (wire == "fp8x2" && algo == "push")
+    throw std::invalid_argument("wire fp8x2 packs the gather phase of a twoshot: a push has none");
   return PeerWire{wire != "native", wire == "fp8x2"};
 }
 
@@ -201,6 +266,7 @@ struct PeerAllreduce {
   std::vector<int> devs;
   int k = 0, nsets = 1;
   bool twoshot = false;
+  bool push = false;                // phase 1 stores slice m of the sum into every member's `out`; no phase 2
   PeerTypes types;
   float scale = 1.0f;
   bool fp8 = false;                 // the wire: members read each other's packed buffers, not their `in`
@@ -212,8 +278,9 @@ struct PeerAllreduce {
   std::vector<std::unique_ptr<DevBuf>> packed;      // fp8: packed[m], member m's `in` of the current round
   std::vector<std::unique_ptr<DevBuf>> packed_out;  // fp8x2: packed_out[m], slice m of the round's sum, packed by m
   SrcSet srcs[2]{}, packs{};
+  std::vector<DstSet> push_dsts;    // push: member m's destinations, every `out` from its own on
   SliceSet unpack_set{};            // fp8x2: every member's phase 2, slice p (blocks) of packed_out[p] for every p
-  std::vector<PeerSlice> plan;      // phase 1 of a two-shot: vectors of an `in`; fp8: blocks
+  std::vector<PeerSlice> plan;      // phase 1 of a two-shot or a push: vectors of an `in`; fp8: blocks
   std::vector<SliceSet> gather;  // member m's phase 2: slice p of out[p], every p != m
   std::vector<int> reduce_grid, gather_grid_, quantize_grid;
   MemberStreams ts;
@@ -225,18 +292,19 @@ struct PeerAllreduce {
     if (devs.size() < 2 || devs.size() > (size_t)kMaxSrc) throw std::invalid_argument("2..16 members");
     check_devs(devs);
     if (count < 1) throw std::invalid_argument("count >= 1");
-    if (algo != "oneshot" && algo != "twoshot") throw std::invalid_argument("algo must be oneshot|twoshot");
+    if (algo != "oneshot" && algo != "twoshot" && algo != "push") throw std::invalid_argument("algo must be oneshot|twoshot|push");
   }
 
   PeerAllreduce(const std::vector<int>& devs_, size_t count_, PeerTypes types_, const std::string& algo, int nsets_,
                 int blocks_per_cu, float scale_ = 1.0f, PeerWire wire = PeerWire{})
-      : devs(devs_), k((int)devs_.size()), nsets(nsets_), twoshot(algo == "twoshot"), types(types_), scale(scale_), fp8(wire.fp8),
+      : devs(devs_), k((int)devs_.size()), nsets(nsets_), twoshot(algo == "twoshot"), push(algo == "push"), types(types_), scale(scale_), fp8(wire.fp8),
         x2(wire.x2), count(count_), n_vec((count_ * types_.in_elem() + 15) / 16), n_blocks((count_ + kQ8Block - 1) / kQ8Block),
         plan(peer_slices(wire.fp8 ? n_blocks : n_vec, k)), gather(k), reduce_grid(k), gather_grid_(k), quantize_grid(k),
         e1(k, nullptr), e2(k, nullptr), eq(k, nullptr) {
     for (int m = 0; m < k; ++m)
       for (int p = 0; p < k; ++p) enable_peer(devs[m], devs[p]);
     std::vector<const u32x4*> outs(k);
+    std::vector<u32x4*> outs_w(k);
     std::vector<PeerSlice> out_plan(k);  // slices of the output type
     // output vectors per unit of the plan, and of a whole `out`
     const size_t per_unit = fp8 ? kQ8Block * types.out_elem() / 16 : types.ratio();
@@ -258,12 +326,14 @@ struct PeerAllreduce {
       }
       out.emplace_back(new DevBuf(devs[m], out_vec * 16));
       outs[m] = reinterpret_cast<const u32x4*>(out[m]->p);
+      outs_w[m] = reinterpret_cast<u32x4*>(out[m]->p);
       out_plan[m] = PeerSlice{plan[m].first * per_unit, plan[m].count * per_unit};
     }
+    for (int m = 0; push && m < k; ++m) push_dsts.push_back(peer_push_dsts(outs_w, m));
     try {
       for (int m = 0; m < k; ++m) {
         const int share = device_share(devs, devs[m]);  // as in K6
-        const size_t units = twoshot ? plan[m].count : (fp8 ? n_blocks : n_vec);
+        const size_t units = twoshot || push ? plan[m].count : (fp8 ? n_blocks : n_vec);
         reduce_grid[m] = peer_reduce_grid(num_cus(devs[m]), blocks_per_cu, share, fp8 ? 2 * units : units);
         quantize_grid[m] = peer_reduce_grid(num_cus(devs[m]), blocks_per_cu, share, n_blocks * 64 / types.in_elem());
         gather_grid_[m] = gather_grid(devs[m], blocks_per_cu, x2 ? k : k - 1, share);
@@ -289,7 +359,11 @@ struct PeerAllreduce {
   void reduce(int m, int set, size_t v0, size_t v1) {
     if (v0 == v1 || dry) return;
     u32x4* dst = reinterpret_cast<u32x4*>(out[m]->p);
-    if (x2)
+    if (push && fp8)
+      launch_peer_q8_sum_push(types.out_bf16, packs, push_dsts[m], k, q8_exp_vec(n_blocks), v0, v1, scale, reduce_grid[m], ts[m]->s);
+    else if (push)
+      launch_peer_reduce_push(types, srcs[set], push_dsts[m], k, v0, v1, scale, reduce_grid[m], ts[m]->s);
+    else if (x2)
       launch_peer_q8_repack(packs, k, q8_exp_vec(n_blocks), v0, v1, reinterpret_cast<u32x4*>(packed_out[m]->p), scale,
                             reduce_grid[m], ts[m]->s);
     else if (fp8)
@@ -330,6 +404,11 @@ struct PeerAllreduce {
     for (int m = 0; m < k; ++m) {
       DeviceGuard g(devs[m]);
       if (fp8) wait_others(m, eq);
+      if (push) {  // slice m of every `out` is this member's alone and nothing reads an `out`: no event of its own
+        reduce(m, set, plan[m].first, plan[m].first + plan[m].count);
+        if (fp8) HIP_CHECK(hipEventRecord(e1[m], ts[m]->s));
+        continue;
+      }
       if (!twoshot) {
         reduce(m, set, 0, fp8 ? n_blocks : n_vec);
         if (fp8) HIP_CHECK(hipEventRecord(e1[m], ts[m]->s));
@@ -437,7 +516,8 @@ py::dict peer_allreduce(const std::vector<int>& devs, size_t count, const std::s
       // member 0's kernels alone on an idle device, after the check: the same set as the last round,
       // so `out` (fp8x2: its slice of the second packed buffer, then `out`) is rewritten with the same bits
       const int set = (total - 1) % ar.nsets;
-      const size_t a = ar.twoshot ? ar.plan[0].first : 0, b = ar.twoshot ? a + ar.plan[0].count : ar.n_blocks;
+      const bool sliced = ar.twoshot || ar.push;
+      const size_t a = sliced ? ar.plan[0].first : 0, b = sliced ? a + ar.plan[0].count : ar.n_blocks;
       DeviceGuard g(devs[0]);
       ar.ts[0]->begin();
       for (int i = 0; i < iters; ++i) ar.quantize(0, set);

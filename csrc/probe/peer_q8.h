@@ -221,26 +221,29 @@ __device__ __forceinline__ void q8_widen(const u32x4& c, unsigned int ebyte, flo
   }
 }
 
-// The 16 results of code vector v: two vectors of a bf16 out at 2 v, four of an fp32 out at 4 v.
-template <typename TO>
-__device__ __forceinline__ void q8_store(const float (&acc)[16], u32x4* __restrict__ dst, size_t v) {
+// The 16 results of code vector v: two vectors of a bf16 out at 2 v, four of an fp32 out at 4 v, of `dst`
+// through `sink` (PeerOneDst or PeerPushDst of peer_allreduce.h).
+template <typename TO, typename Sink>
+__device__ __forceinline__ void q8_store(const float (&acc)[16], const Sink& sink, u32x4* __restrict__ dst, size_t v) {
   constexpr int L = kPeerLanes<TO>;
+  u32x4 out[16 / L];
 #pragma unroll
   for (int p = 0; p < 16 / L; ++p) {
     float part[L];
 #pragma unroll
     for (int j = 0; j < L; ++j) part[j] = acc[p * L + j];
-    __builtin_nontemporal_store(peer_narrow(part), dst + v * (16 / L) + p);
+    out[p] = peer_narrow(part);
   }
+  sink(out, dst, v * (16 / L));
 }
 
 // peer_reduce_vecs on the packed form: U code vectors per lane, `stride` apart from `i`; the k x U code
 // loads and the k x U exponent words (member-major, all in flight before the first add), then per
 // position the sum in member order, one multiply by `scale`, one rounding and the stores.  r[][] and
 // x[][] are indexed by constants only.
-template <typename TO, int KB, int U>
-__device__ __forceinline__ void peer_q8_sum_vecs(const SrcSet& srcs, int k, size_t exp_vec, u32x4* __restrict__ dst, size_t i,
-                                                 size_t stride, float scale) {
+template <typename TO, int KB, int U, typename Sink>
+__device__ __forceinline__ void peer_q8_sum_vecs(const SrcSet& srcs, int k, size_t exp_vec, const Sink& sink, u32x4* __restrict__ dst,
+                                                 size_t i, size_t stride, float scale) {
   u32x4 r[KB][U];
   unsigned int x[KB][U];
 #pragma unroll
@@ -269,17 +272,18 @@ __device__ __forceinline__ void peer_q8_sum_vecs(const SrcSet& srcs, int k, size
       }
 #pragma unroll
     for (int j = 0; j < 16; ++j) acc[j] = acc[j] * scale;
-    q8_store<TO>(acc, dst, v);
+    q8_store<TO>(acc, sink, dst, v);
   }
 }
 
-// Blocks [b0, b1) of dst (whole blocks of the output type TO: float, or bf16 as raw u16) = scale * the
+// Blocks [b0, b1) of dst, and of what else the sink stores to (whole blocks of the output type TO: float, or
+// bf16 as raw u16) = scale * the
 // sum over members m < k of the dequantised blocks [b0, b1) of srcs.p[m], every member's packed buffer.
 // The range is code vectors [2 b0, 2 b1), cut as peer_reduce_kernel cuts its vectors: whole tiles in one
 // contiguous run per block, the rest one vector per lane over the whole grid.
-template <typename TO, int KB, int U>
-__global__ __launch_bounds__(gtk::kStreamBlock) void peer_q8_sum_kernel(SrcSet srcs, int k, size_t exp_vec, size_t b0,
-                                                                        size_t b1, u32x4* __restrict__ dst, float scale) {
+template <typename TO, int KB, int U, typename Sink>
+__device__ __forceinline__ void peer_q8_sum_range(const SrcSet& srcs, int k, size_t exp_vec, size_t b0, size_t b1, const Sink& sink,
+                                                  u32x4* __restrict__ dst, float scale) {
   const size_t v0 = 2 * b0, v1 = 2 * b1;
   const size_t tile = (size_t)gtk::kStreamBlock * U;
   const size_t n_tiles = (v1 - v0) / tile;
@@ -287,10 +291,25 @@ __global__ __launch_bounds__(gtk::kStreamBlock) void peer_q8_sum_kernel(SrcSet s
   const size_t t0 = (size_t)blockIdx.x * per;
   const size_t t1 = std::min(n_tiles, t0 + per);
   for (size_t t = t0; t < t1; ++t)
-    peer_q8_sum_vecs<TO, KB, U>(srcs, k, exp_vec, dst, v0 + t * tile + threadIdx.x, gtk::kStreamBlock, scale);
+    peer_q8_sum_vecs<TO, KB, U>(srcs, k, exp_vec, sink, dst, v0 + t * tile + threadIdx.x, gtk::kStreamBlock, scale);
   for (size_t i = v0 + n_tiles * tile + (size_t)blockIdx.x * gtk::kStreamBlock + threadIdx.x; i < v1;
        i += (size_t)gridDim.x * gtk::kStreamBlock)
-    peer_q8_sum_vecs<TO, KB, 1>(srcs, k, exp_vec, dst, i, 0, scale);
+    peer_q8_sum_vecs<TO, KB, 1>(srcs, k, exp_vec, sink, dst, i, 0, scale);
+}
+
+// The sum into the launching member's own `dst`.
+template <typename TO, int KB, int U>
+__global__ __launch_bounds__(gtk::kStreamBlock) void peer_q8_sum_kernel(SrcSet srcs, int k, size_t exp_vec, size_t b0,
+                                                                        size_t b1, u32x4* __restrict__ dst, float scale) {
+  peer_q8_sum_range<TO, KB, U>(srcs, k, exp_vec, b0, b1, PeerOneDst{}, dst, scale);
+}
+
+// The push form of the sum: the same blocks, sum and rounding, every result vector stored to the same
+// offset of every dsts.p[d], d < k (every member's `out`), as peer_reduce_push_kernel does.
+template <typename TO, int KB, int U>
+__global__ __launch_bounds__(gtk::kStreamBlock) void peer_q8_sum_push_kernel(SrcSet srcs, DstSet dsts, int k, size_t exp_vec,
+                                                                             size_t b0, size_t b1, float scale) {
+  peer_q8_sum_range<TO, KB, U>(srcs, k, exp_vec, b0, b1, PeerPushDst<KB>{dsts, k}, dsts.p[0], scale);
 }
 
 // peer_q8_sum_vecs up to the multiply by `scale` (k x U code vectors and exponent words in flight, the sum
@@ -400,7 +419,7 @@ __global__ __launch_bounds__(gtk::kStreamBlock) void peer_q8_unpack_kernel(Slice
       if (v < v1) {
         float f[16];
         q8_widen(r[u], (x[u] >> (8u * (unsigned int)((v >> 1) & 3))) & 0xffu, f);
-        q8_store<TO>(f, dst, v);
+        q8_store<TO>(f, PeerOneDst{}, dst, v);
       }
     }
   }

@@ -1,6 +1,7 @@
 // One rank's device state for the peer communicator (parallel/peer_comm.py, backend="device").
 // Host code only: it launches the K7 kernels of peer_allreduce.h and peer_q8.h through the launch plan of
-// peer_driver.h, as PeerAllreduce does, and adds no kernel and no instantiation.
+// peer_driver.h, as PeerAllreduce does, and adds no kernel and no instantiation.  The push launches
+// (reduce_push, reduce_q8_push) store into the peers' outs, which is why those are held mutable.
 //
 // A rank owns a window (inputs, `capacity` bytes), an out (results, twice that: the wide form writes
 // two vectors per input vector), a packed buffer (the fp8 wire's form of the window, sized for a window
@@ -82,7 +83,8 @@ class PeerRank {
 
   // Every rank's device and buffer addresses, this rank's own included (and checked to be its own).
   // A peer's address must be the base of a device allocation of this process on the device it names,
-  // at least as large as this rank's buffers: the kernels index a peer's buffer as they index their own.
+  // at least as large as this rank's buffers: the kernels index a peer's buffer as they index their own,
+  // and a push (reduce_push, reduce_q8_push) stores into the peers' outs.
   // `packeds` is optional: without the peers' packed buffers the fp8 phases stay unavailable; so is
   // `packed_outs`, the peers' second packed buffers, without which the fp8x2 phases stay unavailable.
   void open_peers(const std::vector<int>& devices, const std::vector<uintptr_t>& windows, const std::vector<uintptr_t>& outs,
@@ -113,7 +115,7 @@ class PeerRank {
     packed_outs_.assign(k, nullptr);
     for (size_t p = 0; p < k; ++p) {
       windows_.p[p] = reinterpret_cast<const u32x4*>(windows[p]);
-      outs_[p] = reinterpret_cast<const u32x4*>(outs[p]);
+      outs_[p] = reinterpret_cast<u32x4*>(outs[p]);
       packeds_.p[p] = packeds ? reinterpret_cast<const u32x4*>((*packeds)[p]) : nullptr;
       if (packed_outs) packed_outs_[p] = reinterpret_cast<const u32x4*>((*packed_outs)[p]);
     }
@@ -140,6 +142,21 @@ class PeerRank {
     const int grid = peer_reduce_grid(cus_, blocks_per_cu_, share_, v1 - v0);
     DeviceGuard g(dev_);
     launch_peer_reduce(t, windows_, world_, v0, v1, reinterpret_cast<u32x4*>(out_->p), scale, grid, stream_);
+    ++launches_;
+  }
+
+  // The push form of reduce: the same sum of window[v0, v1) of every rank, stored to vectors [v0, v1) of
+  // every rank's out (the wide form: [2 * v0, 2 * v1)), this rank's own first and the others in ring order.
+  // One launch.  The caller gives every rank a range of its own: the ranges of one epoch must not overlap.
+  void reduce_push(size_t v0, size_t v1, const std::string& in_dtype, const std::string& out_dtype, float scale) {
+    const PeerTypes t = peer_types(in_dtype, out_dtype);
+    need_peers();
+    if (v0 > v1 || v1 > cap_ / 16) throw std::invalid_argument("reduce_push: vectors past the end of the window");
+    if (v1 * t.ratio() > 2 * cap_ / 16) throw std::invalid_argument("reduce_push: vectors past the end of out");
+    if (v0 == v1) return;
+    const int grid = peer_reduce_grid(cus_, blocks_per_cu_, share_, v1 - v0);
+    DeviceGuard g(dev_);
+    launch_peer_reduce_push(t, windows_, peer_push_dsts(outs_, rank_), world_, v0, v1, scale, grid, stream_);
     ++launches_;
   }
 
@@ -215,6 +232,20 @@ class PeerRank {
     ++launches_;
   }
 
+  // The push form of reduce_q8: the same sum, stored to blocks [b0, b1) of every rank's out, in reduce_push's order.
+  void reduce_q8_push(size_t b0, size_t b1, const std::string& out_dtype, float scale) {
+    const PeerTypes t = peer_types("bf16", out_dtype);  // as reduce_q8
+    need_q8();
+    if (b0 > b1 || b1 > max_blocks()) throw std::invalid_argument("reduce_q8_push: blocks past the end of the packed buffer");
+    if (b1 * kQ8Block * t.out_elem() > 2 * cap_) throw std::invalid_argument("reduce_q8_push: blocks past the end of out");
+    if (b0 == b1) return;
+    const int grid = peer_reduce_grid(cus_, blocks_per_cu_, share_, 2 * (b1 - b0));
+    DeviceGuard g(dev_);
+    launch_peer_q8_sum_push(t.out_bf16, packeds_, peer_push_dsts(outs_, rank_), world_, q8_exp_vec(max_blocks()), b0, b1, scale, grid,
+                            stream_);
+    ++launches_;
+  }
+
   // Phase 1 of the fp8x2 two-shot: blocks [b0, b1) of this rank's second packed buffer = the packed form of
   // scale x the sum over ranks of the same blocks of their packed buffers.
   void repack_q8(size_t b0, size_t b1, float scale) {
@@ -261,7 +292,7 @@ class PeerRank {
       if (a > b || b > 2 * cap_ / 16) throw std::invalid_argument("gather: slice past the end of out");
       plan[p] = PeerSlice{a, b - a};
     }
-    launch_gather(peer_gather_slices(outs_, plan, rank_), world_ - 1);
+    launch_gather(peer_gather_slices(std::vector<const u32x4*>(outs_.begin(), outs_.end()), plan, rank_), world_ - 1);
   }
 
   // All-gather: vectors [p * n_vec, (p + 1) * n_vec) of rank p's window to the same vectors of this
@@ -391,7 +422,8 @@ class PeerRank {
   std::unique_ptr<DevBuf> window_, out_, packed_, packed_out_, residual_;
   hipStream_t stream_ = nullptr;
   SrcSet windows_{}, packeds_{};
-  std::vector<const u32x4*> outs_, packed_outs_;
+  std::vector<u32x4*> outs_;  // mutable: a push stores into every rank's out
+  std::vector<const u32x4*> packed_outs_;
   bool open_ = false, open_q8_ = false, open_q8x2_ = false, released_ = false;
   size_t launches_ = 0;
 };
@@ -438,6 +470,10 @@ void bind_peer_rank(py::module_& m) {
            },
            py::arg("floats"), py::arg("first_elem") = 0)
       .def("reduce_q8", &PeerRank::reduce_q8, py::arg("b0"), py::arg("b1"), py::arg("out_dtype"), py::arg("scale") = 1.0f, nogil())
+      .def("reduce_push", &PeerRank::reduce_push, py::arg("v0"), py::arg("v1"), py::arg("in_dtype"), py::arg("out_dtype"),
+           py::arg("scale") = 1.0f, nogil())
+      .def("reduce_q8_push", &PeerRank::reduce_q8_push, py::arg("b0"), py::arg("b1"), py::arg("out_dtype"), py::arg("scale") = 1.0f,
+           nogil())
       .def("repack_q8", &PeerRank::repack_q8, py::arg("b0"), py::arg("b1"), py::arg("scale") = 1.0f, nogil())
       .def("unpack_q8", &PeerRank::unpack_q8, py::arg("slices"), py::arg("out_dtype"), nogil())
       .def("gather", &PeerRank::gather, py::arg("slices"), nogil())

@@ -21,7 +21,8 @@
 //                  against a CPU sum; the repository's own collective, next to RCCL's.  On the fp8 wire
 //                  (peer_q8.h) every member packs its input into block-scaled e4m3 first and the members
 //                  read that, 33 bytes per 32 elements, with the same fixed order and exactness; on the
-//                  fp8x2 wire a two-shot packs its sums again and gathers the packed form too.  PeerRank
+//                  fp8x2 wire a two-shot packs its sums again and gathers the packed form too; the push
+//                  algorithm stores each member's slice of the sum into every member's out in one launch.  PeerRank
 //                  (peer_rank.h) launches the same kernels for one rank of the peer communicator.
 //   K8 latency   : one wave follows a chain of dependent loads through a buffer of another device
 //                  (chase_latency.h): nanoseconds per access over the link, next to K1's GB/s.
@@ -868,7 +869,8 @@ PYBIND11_MODULE(_probe, m) {
         py::arg("wire") = "native", py::arg("dry_run") = false,
         "K7: timed all-reduce (sum) of device-made inputs over peer pointers; every member's result checked; "
         "wire=\"fp8\": members read each other's block-scaled e4m3 form (peer_q8.h); wire=\"fp8x2\" (twoshot): the "
-        "gather phase reads packed sums too; dry_run (tests only): everything but the kernels of the rounds");
+        "gather phase reads packed sums too; algo=\"push\": one launch per member stores its slice of the sum into every "
+        "member's out (native and fp8 wires); dry_run (tests only): everything but the kernels of the rounds");
   m.def("peer_allreduce_arrays", &peer_allreduce_arrays, py::arg("devs"), py::arg("inputs"), py::arg("dtype") = "bf16",
         py::arg("algo") = "twoshot", py::arg("rounds") = 1, py::arg("out_dtype") = py::none(), py::arg("scale") = 1.0f,
         py::arg("wire") = "native",

@@ -47,6 +47,10 @@ constexpr int kMaxSrc = 16;
 struct SrcSet {
   const u32x4* p[kMaxSrc];
 };
+// The destinations of one push reduce (K7): every member's `out`, in the order a lane stores to them.
+struct DstSet {
+  u32x4* p[kMaxSrc];
+};
 
 __global__ __launch_bounds__(kBlock) void fill_pattern_kernel(unsigned int* __restrict__ p, size_t n_words,
                                                               unsigned int seed) {

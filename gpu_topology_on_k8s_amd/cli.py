@@ -428,7 +428,7 @@ def cmd_validate(a) -> int:
     if a.wire != "native" and a.backend != "peer":  # misuse, like an unknown choice: usage error
         print(f"gtk validate: error: --wire {a.wire} belongs to --backend peer", file=sys.stderr)
         return 2
-    if a.wire == "fp8x2" and a.algo == "oneshot":
+    if a.wire == "fp8x2" and a.algo in ("oneshot", "push"):
         print("gtk validate: error: --wire fp8x2 packs the gather phase of a twoshot: --algo twoshot or both", file=sys.stderr)
         return 2
     if a.error_feedback and (a.wire not in ("fp8", "fp8x2") or a.ranks != "thread"):
@@ -460,9 +460,9 @@ def cmd_validate(a) -> int:
         if a.ranks == "thread":  # one thread per member through the peer communicator, not one driver call for all
             from .parallel.peer_comm import selftest, thread_sweep
 
-            st = selftest(devs, wire=a.wire, error_feedback=a.error_feedback)
+            st = selftest(devs, wire=a.wire, error_feedback=a.error_feedback, push=a.algo in ("push", "all"))
             print(json.dumps({"selftest": True, "k": len(devs), "devices": devs, "ranks": "thread", **st}), flush=True)
-            selftest_wrong = st["wrong"] + st["q8_wrong"] + st.get("q8x2_wrong", 0) + st.get("ef_wrong", 0)
+            selftest_wrong = st["wrong"] + st["q8_wrong"] + st.get("q8x2_wrong", 0) + st.get("ef_wrong", 0) + st.get("push_wrong", 0)
             pts = thread_sweep(devs, sizes, a.dtype, algo, a.iters, a.warmup, wire=a.wire)
             extra = {"backend": "peer", "algo": algo, "ranks": "thread", "selftest_wrong": selftest_wrong, "wire": a.wire}
         else:
@@ -631,7 +631,9 @@ def main(argv=None) -> int:
     p.add_argument("--cpu-bind", default="env", choices=["env", "off"], help="pin to GTK_CPUSET (the pod's cores) or not")
     p.add_argument("--backend", default="rccl", choices=["rccl", "peer"],
                    help="rccl: librccl's all-reduce; peer: this repository's K7 kernels over peer pointers (no RCCL; bf16|fp32)")
-    p.add_argument("--algo", default="both", choices=["oneshot", "twoshot", "both"], help="--backend peer: K7 algorithm(s)")
+    p.add_argument("--algo", default="both", choices=["oneshot", "twoshot", "both", "push", "all"],
+                   help="--backend peer: K7 algorithm(s); both = oneshot and twoshot, all = those and push (push: one launch "
+                        "stores each member's slice of the sum into every member's out)")
     p.add_argument("--wire", default="native", choices=["native", "fp8", "fp8x2"],
                    help="--backend peer: native = members read each other's inputs; fp8 = each member packs its input into "
                         "e4m3 codes with one power-of-two scale per 32 elements and the members read that (33 bytes per 32 elements); "

@@ -1,5 +1,6 @@
 """Python front-end of the HIP/CDNA4 link probe (``csrc/probe/probe.hip`` and the headers it
-includes: ``probe_common.h``, K7's ``peer_allreduce.h`` / ``peer_q8.h`` / ``peer_driver.h``, K8's ``chase_latency.h``).
+includes: ``probe_common.h``, K7's ``peer_allreduce.h`` / ``peer_q8.h`` / ``peer_driver.h``, K8's ``chase_latency.h``).  K7 has three algorithms:
+``oneshot`` and ``twoshot`` only read over the links, ``push`` (:data:`PEER_PUSH`, opt-in) also stores over them.
 
 Seeds the link-cost matrix at node start (BASELINE.json north_star):
 
@@ -33,7 +34,7 @@ log = logging.getLogger(__name__)
 
 __all__ = ["device_count", "device_props", "warmup", "copy_bw", "gather_bw", "measure_matrix", "measure_ingress",
            "probe_topology", "probe_in_child", "ingress_bound", "ring_peers", "ring_bw", "measure_ring", "ring_in_child",
-           "peer_allreduce", "peer_allreduce_arrays", "peer_q8_quantize", "peer_sweep", "PEER_ALGOS", "PROBE_PRESETS",
+           "peer_allreduce", "peer_allreduce_arrays", "peer_q8_quantize", "peer_sweep", "PEER_ALGOS", "PEER_PUSH", "PROBE_PRESETS",
            "chase_latency", "measure_latency", "LATENCY_PRESETS"]
 
 #: bytes per transfer / timed iterations / repeats of every pair (the link's median is published, its
@@ -145,6 +146,11 @@ def ring_in_child(devs: Sequence[int], preset: str = "quick", timeout: float = 1
 #: measured, so ``peer_sweep(..., algo="both")`` reports it per size instead of assuming a cutoff.
 PEER_ALGOS = ("oneshot", "twoshot")
 
+#: K7's third algorithm, opt-in (``algo="push"``, or ``"all"`` in :func:`peer_sweep`): member m sums slice m of every
+#: input and stores the result into slice m of every member's ``out``, in one launch with no second phase.  It moves
+#: the two-shot's bytes per link, half of them as remote stores, and gives the two-shot's bits.
+PEER_PUSH = "push"
+
 
 def peer_allreduce(devs: Sequence[int], count: int, dtype: str = "bf16", algo: str = "twoshot", iters: int = 3,
                    warmup_iters: int = 1, blocks_per_cu: int = 8, wire: str = "native",
@@ -159,7 +165,11 @@ def peer_allreduce(devs: Sequence[int], count: int, dtype: str = "bf16", algo: s
     kernels timed alone.  ``wire="fp8x2"`` (``algo="twoshot"`` only, ``ValueError`` otherwise): phase 1 packs its sums
     again and phase 2 unpacks every member's slice, so both phases move packed bytes; the device-made inputs
     are then values in {-1, 0}, whose sums survive the second packing, and ``gather_us`` is member 0's unpack
-    kernel timed alone."""
+    kernel timed alone.
+
+    ``algo="push"`` (:data:`PEER_PUSH`): one launch per member writes its slice of the sum into every member's
+    ``out``; on the native wire the members then need no event between them, on ``wire="fp8"`` they keep the
+    one-shot's.  ``wire="fp8x2"`` with it is a ``ValueError``: a push has no gather phase to pack."""
     return dict(_p().peer_allreduce([int(d) for d in devs], int(count), dtype, algo, int(iters), int(warmup_iters),
                                     int(blocks_per_cu), wire, bool(dry_run)))
 
@@ -188,25 +198,27 @@ def peer_allreduce_arrays(devs: Sequence[int], inputs: Sequence[np.ndarray], dty
     ``out_dtype="fp32"`` of ``bf16`` inputs is the wide reduce (bf16 read, fp32 summed and written);
     ``scale`` multiplies the fp32 sum once before the one rounding (``1 / k`` for a mean).  With
     ``wire="fp8"`` the bits are ``ops.peer_ref.allreduce_q8_ref``'s, with ``wire="fp8x2"`` (``algo="twoshot"`` only)
-    ``ops.peer_ref.allreduce_q8x2_ref``'s."""
+    ``ops.peer_ref.allreduce_q8x2_ref``'s.  ``algo="push"`` gives the bits of ``"twoshot"`` on the native and the
+    ``"fp8"`` wire."""
     return list(_p().peer_allreduce_arrays([int(d) for d in devs], list(inputs), dtype, algo, int(rounds), out_dtype,
                                            float(scale), wire))
 
 
 def peer_sweep(devs: Sequence[int], sizes: Sequence[int], dtype: str = "bf16", algo: str = "both", iters: int = 3,
                warmup_iters: int = 1, wire: str = "native") -> List[Dict[str, object]]:
-    """K7 at every size (bytes) under ``algo`` (``oneshot``, ``twoshot`` or ``both``) on ``wire``: one dict per
-    size and algorithm, in size order, with ``fastest`` marking the quicker algorithm of each size.
-    ``wire="fp8x2"`` belongs to ``algo="twoshot"``."""
-    if algo != "both" and algo not in PEER_ALGOS:
-        raise ValueError(f"algo must be oneshot|twoshot|both, got {algo!r}")
+    """K7 at every size (bytes) under ``algo`` (``oneshot``, ``twoshot``, ``push``, ``both`` for the first two or
+    ``all`` for the three) on ``wire``: one dict per size and algorithm, in size order, with ``fastest`` marking the
+    quickest algorithm of each size.  ``wire="fp8x2"`` belongs to ``algo="twoshot"``."""
+    if algo not in ("both", "all", PEER_PUSH) and algo not in PEER_ALGOS:
+        raise ValueError(f"algo must be oneshot|twoshot|push|both|all, got {algo!r}")
+    algos = PEER_ALGOS if algo == "both" else PEER_ALGOS + (PEER_PUSH,) if algo == "all" else (algo,)
     elem = ELEM.get(dtype)
     if elem is None:
         raise ValueError(f"dtype must be bf16|fp32, got {dtype!r}")
     out: List[Dict[str, object]] = []
     for nbytes in sizes:
         pts = [peer_allreduce(devs, max(1, int(nbytes) // elem), dtype, a, iters, warmup_iters, wire=wire)
-               for a in (PEER_ALGOS if algo == "both" else (algo,))]
+               for a in algos]
         best = min(pts, key=lambda p: p["time_us"])
         for p in pts:
             p["fastest"] = p is best

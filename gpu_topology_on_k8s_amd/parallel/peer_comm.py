@@ -15,6 +15,21 @@ the host (``PeerCommTimeout``).  Every collective is
 and never more than those two barriers.  The price is that every collective is host-synchronous: two
 store round trips and two (two-shot: three) stream synchronisations per call.
 
+``algo="push"`` (``all_reduce``) is the two-shot without its second phase: rank r sums slice r of every window
+and stores the result into slice r of **every** rank's out, its own first and the others in ring order
+(``peer_reduce_push_kernel``), so a call is
+
+    barrier A -> push -> synchronize -> barrier B
+
+one launch and two stream synchronisations, with the two-shot's link bytes and the two-shot's bits.  A rank's
+out is now written by its peers, between barrier A and barrier B of a push, and that is the one new hazard.
+Every reader of that out has synchronised before it entered barrier A: the rank's own ``read``, and a
+peer's two-shot phase 2 of the previous collective, which that peer synchronises before it returns.  The
+writers of one push never overlap, slice r being rank r's alone.  The pushed slices are final once every rank
+has synchronised and passed barrier B, so ``read`` after the call sees them, and the next writer of any out,
+whatever the collective, comes after the next barrier A.  On ``wire="fp8"`` the sum reads the packed buffers
+and the quantize stays before barrier A; ``wire="fp8x2"`` is refused, a push having no gather phase to pack.
+
 ``wire="fp8"`` (``all_reduce``, ``reduce_scatter``) adds a third buffer per rank, *packed*: the rank's
 window as e4m3 codes with one power-of-two scale per 32 elements (``csrc/probe/peer_q8.h``,
 ``ops/peer_ref.q8_quantize_ref``), 33 bytes per 32 elements.  Peers read that instead of the window, and a
@@ -101,13 +116,14 @@ from ..ops.peer_ref import (ELEM as _ELEM, Q8_BLOCK, allreduce_q8_ef_ref, allred
                             q8_quantize_ref, q8_slices, reduce_scatter_q8_ef_ref)
 
 __all__ = ["PeerComm", "PeerCommError", "PeerCommTimeout", "PeerCommMismatch", "HostFabric", "MemoryStore",
-           "selftest_cases", "selftest_cases_q8", "selftest_cases_q8x2", "selftest_cases_ef", "case_input", "run_case", "run_thread_ranks", "selftest", "thread_sweep", "timed_all_reduce", "parked_bytes",
+           "selftest_cases", "selftest_cases_q8", "selftest_cases_q8x2", "selftest_cases_ef", "selftest_cases_push", "case_input", "run_case", "run_thread_ranks", "selftest", "thread_sweep", "timed_all_reduce", "parked_bytes",
            "MAX_WORLD"]
 
 MAX_WORLD = 16  # kMaxSrc of csrc/probe/probe_common.h
 BACKENDS = ("host", "device")
 _NP = {"bf16": np.uint16, "fp32": np.float32}
 ALGOS = ("oneshot", "twoshot")
+PUSH = "push"  # all_reduce alone, opt-in: rank r stores slice r of the sum into every rank's out
 WIRES = (None, "native", "fp8", "fp8x2")  # None and "native" are the same call: the windows as they are
 _WIRE_REF = {None: allreduce_ref, "native": allreduce_ref, "fp8": allreduce_q8_ref, "fp8x2": allreduce_q8x2_ref}
 _Q8_BIAS = 127  # a block's stored exponent byte is e + 127, as in csrc/probe/peer_q8.h
@@ -225,7 +241,7 @@ class HostFabric:
 
 
 class _HostBackend:
-    """One rank's phase calls (reduce, quantize, reduce_q8, repack_q8, unpack_q8, gather, gather_windows, host copies) on a
+    """One rank's phase calls (reduce, reduce_push, quantize, reduce_q8, reduce_q8_push, repack_q8, unpack_q8, gather, gather_windows, host copies) on a
     :class:`HostFabric`, computed by ``ops/peer_ref.py``."""
 
     def __init__(self, rank: int, world: int, fabric: HostFabric):
@@ -264,6 +280,17 @@ class _HostBackend:
         xs = [self._win(p, v0, v1, "r").view(_NP[in_dtype]).copy() for p in range(self.world)]
         ratio = _ELEM[out_dtype] // _ELEM[in_dtype]
         self._out(self.rank, v0 * ratio, v1 * ratio, "w")[:] = allreduce_ref(xs, in_dtype, out_dtype, scale).view(np.uint8)
+
+    def reduce_push(self, v0: int, v1: int, in_dtype: str, out_dtype: str, scale: float) -> None:
+        with self.f.lock:
+            self.f.launches += 1
+        if v0 == v1:
+            return
+        xs = [self._win(p, v0, v1, "r").view(_NP[in_dtype]).copy() for p in range(self.world)]
+        ratio = _ELEM[out_dtype] // _ELEM[in_dtype]
+        res = allreduce_ref(xs, in_dtype, out_dtype, scale).view(np.uint8)
+        for j in range(self.world):  # every owner's out, this rank's first: a peer write is logged like any other
+            self._out((self.rank + j) % self.world, v0 * ratio, v1 * ratio, "w")[:] = res
 
     def _packed(self, p: int, b0: int, b1: int, mode: str, name: str = "packed") -> Tuple[np.ndarray, np.ndarray]:
         """Blocks ``[b0, b1)`` of rank p's packed buffer ``name`` (``packed`` or ``packed_out``): its code bytes and
@@ -327,6 +354,19 @@ class _HostBackend:
         acc = self._sum_q8(b0, b1, scale)
         res = bf16_round(acc) if out_dtype == "bf16" else acc
         self._out(self.rank, b0 * Q8_BLOCK * e // 16, b1 * Q8_BLOCK * e // 16, "w")[:] = res.view(np.uint8)
+
+    def reduce_q8_push(self, b0: int, b1: int, out_dtype: str, scale: float) -> None:
+        e = _ELEM[out_dtype]
+        if b0 > b1 or b1 > _max_blocks(self.f.capacity_bytes) or b1 * Q8_BLOCK * e > 2 * self.f.capacity_bytes:
+            raise ValueError("reduce_q8_push: blocks past the end of the packed buffer or of out")
+        with self.f.lock:
+            self.f.launches += 1
+        if b0 == b1:
+            return
+        acc = self._sum_q8(b0, b1, scale)
+        res = (bf16_round(acc) if out_dtype == "bf16" else acc).view(np.uint8)
+        for j in range(self.world):
+            self._out((self.rank + j) % self.world, b0 * Q8_BLOCK * e // 16, b1 * Q8_BLOCK * e // 16, "w")[:] = res
 
     def _sum_q8(self, b0: int, b1: int, scale: float) -> np.ndarray:
         """``scale`` x the fp32 sum in rank order of blocks ``[b0, b1)`` of every rank's packed buffer."""
@@ -448,6 +488,9 @@ class _DeviceBackend:
     def reduce(self, v0: int, v1: int, in_dtype: str, out_dtype: str, scale: float) -> None:
         self.r.reduce(v0, v1, in_dtype, out_dtype, scale)
 
+    def reduce_push(self, v0: int, v1: int, in_dtype: str, out_dtype: str, scale: float) -> None:
+        self.r.reduce_push(v0, v1, in_dtype, out_dtype, scale)
+
     def quantize(self, b0: int, b1: int, count: int, in_dtype: str, error_feedback: bool = False) -> None:
         self.r.quantize(b0, b1, count, in_dtype, bool(error_feedback))
 
@@ -463,6 +506,9 @@ class _DeviceBackend:
 
     def reduce_q8(self, b0: int, b1: int, out_dtype: str, scale: float) -> None:
         self.r.reduce_q8(b0, b1, out_dtype, scale)
+
+    def reduce_q8_push(self, b0: int, b1: int, out_dtype: str, scale: float) -> None:
+        self.r.reduce_q8_push(b0, b1, out_dtype, scale)
 
     def repack_q8(self, b0: int, b1: int, scale: float) -> None:
         self.r.repack_q8(b0, b1, scale)
@@ -608,7 +654,8 @@ class PeerComm:
 
         Hazards it covers: every rank's window is written (each rank synchronised its stream before
         it arrived), and last round's readers of my out (phase 2 of a two-shot) are done, so phase 1
-        may read any window and overwrite my out."""
+        may read any window and overwrite my out, and a push may overwrite its slice of every rank's out:
+        the owner's own ``read`` of it is synchronous and lies before the owner's arrival too."""
         desc = {**desc, "seq": self._seq}
         self._seq += 1
         try:
@@ -632,7 +679,8 @@ class PeerComm:
     def _leave(self) -> None:
         """Barrier B.  One-shot, reduce-scatter and all-gather: nobody is still reading any window, so
         the caller may refill its own.  Two-shot: every slice of out that phase 2 is about to read is
-        final (and, again, no window is still being read)."""
+        final (and, again, no window is still being read).  Push: every rank's stores into every out are
+        complete, so each rank may read its own."""
         self._b.synchronize()
         self._barrier()
 
@@ -644,12 +692,13 @@ class PeerComm:
         only when feedback is set, so the descriptors of every other call are what they were)."""
         self._check()
         out = _out_dtype(dtype, out_dtype)
-        if algo not in ALGOS:
-            raise ValueError(f"algo must be oneshot|twoshot, got {algo!r}")
+        if algo not in ALGOS and not (algo == PUSH and op == "all_reduce"):
+            raise ValueError(f"algo must be oneshot|twoshot|push, got {algo!r}")
         if wire not in WIRES:
             raise ValueError(f'wire must be None, "native", "fp8" or "fp8x2", got {wire!r}')
         if wire == "fp8x2" and (op != "all_reduce" or algo != "twoshot"):
-            raise ValueError('wire="fp8x2" packs the gather phase of all_reduce(algo="twoshot"): nothing else has one')
+            raise ValueError('wire="fp8x2" packs the gather phase of all_reduce(algo="twoshot"): nothing else has one, '
+                             'a push least of all')
         if error_feedback and wire not in ("fp8", "fp8x2"):
             raise ValueError('error_feedback=True belongs to wire="fp8" or "fp8x2": the native wire drops nothing')
         if count < 1:
@@ -673,7 +722,8 @@ class PeerComm:
         ``wire="fp8"``: of the windows' packed forms; ``wire="fp8x2"`` (two-shot only): the same, packed once more
         for the gather (see the module docstring).  ``error_feedback=True`` (those two wires; ``ValueError`` on the
         native one, before any barrier or launch): this rank's residual is added to its window before the packing
-        and keeps what the packing dropped."""
+        and keeps what the packing dropped.  ``algo="push"``: one launch, this rank's slice of the sum stored into
+        every rank's out (native and ``"fp8"`` wires; ``"fp8x2"`` is a ``ValueError`` before any barrier or launch)."""
         n, out, scale, desc = self._reduce_args("all_reduce", count, dtype, algo, out_dtype, scale, wire, error_feedback)
         if wire == "fp8x2":
             plan = q8_slices(n, self.world)
@@ -690,6 +740,10 @@ class PeerComm:
             plan = q8_slices(n, self.world)
             self._b.quantize(0, n, count, dtype, error_feedback)
             self._enter(desc)
+            if algo == PUSH:
+                self._b.reduce_q8_push(*plan[self.rank], out, scale)
+                self._leave()
+                return
             a, b = (0, n) if algo == "oneshot" else plan[self.rank]
             self._b.reduce_q8(a, b, out, scale)
             self._leave()
@@ -705,6 +759,10 @@ class PeerComm:
             self._leave()
             return
         a, b = plan[self.rank]
+        if algo == PUSH:  # my slice of the sum into every rank's out; after barrier B every out is whole
+            self._b.reduce_push(a, b, dtype, out, scale)
+            self._leave()
+            return
         self._b.reduce(a, b, dtype, out, scale)
         self._leave()
         # phase 2 needs no barrier after it: the other ranks may still read my slice of out when I return,
@@ -874,6 +932,21 @@ def selftest_cases_q8x2(k: int, counts: Optional[Sequence[int]] = None) -> List[
             for dtype, out, scale in (("bf16", "bf16", 1.0), ("fp32", "fp32", 1.0), ("bf16", "fp32", 1.0 / k))]
 
 
+def selftest_cases_push(k: int, counts: Optional[Sequence[int]] = None) -> List[Dict[str, object]]:
+    """The push ``all_reduce``'s cases: the three dtype pairs (the wide one with ``scale = 1 / k``) on the native wire at
+    every count of :func:`selftest_counts`, then bf16 -> bf16 and bf16 -> fp32 on the fp8 wire at every count of
+    :func:`selftest_counts_q8`; ``counts``, when given, serves both."""
+    cases: List[Dict[str, object]] = []
+    for count in (selftest_counts(k) if counts is None else counts):
+        for dtype, out, scale in (("bf16", "bf16", 1.0), ("fp32", "fp32", 1.0), ("bf16", "fp32", 1.0 / k)):
+            cases.append({"op": "all_reduce", "count": count, "dtype": dtype, "out_dtype": out, "algo": PUSH, "scale": scale})
+    for count in (selftest_counts_q8(k) if counts is None else counts):
+        for dtype, out, scale in (("bf16", "bf16", 1.0), ("bf16", "fp32", 1.0 / k)):
+            cases.append({"op": "all_reduce", "count": count, "dtype": dtype, "out_dtype": out, "algo": PUSH, "scale": scale,
+                          "wire": "fp8"})
+    return cases
+
+
 def case_input(case_index: int, issue: int, rank: int, count: int, dtype: str) -> np.ndarray:
     """Rank ``rank``'s N(0, 1) input of the ``issue``-th issue of case ``case_index``; any rank can make any rank's."""
     rng = np.random.default_rng([case_index, issue, rank, count])
@@ -1019,7 +1092,7 @@ def timed_all_reduce(comm: PeerComm, count: int, dtype: str, algo: str, iters: i
 def thread_sweep(devices: Sequence[int], sizes: Sequence[int], dtype: str = "bf16", algo: str = "both", iters: int = 3,
                  warmup_iters: int = 1, timeout_s: float = 60.0, wire: Optional[str] = None) -> List[Dict[str, object]]:
     """``all_reduce`` on thread ranks over ``devices`` at every size (bytes) under ``algo`` (``oneshot``,
-    ``twoshot`` or ``both``): one dict per size and algorithm, in size order, with the keys of
+    ``twoshot``, ``push``, ``both`` for the first two or ``all`` for the three): one dict per size and algorithm, in size order, with the keys of
     ``ops.probe.peer_sweep`` and ``barrier_us``.
 
     At each point every rank writes a seeded input, makes ``warmup_iters + iters`` calls and reads the
@@ -1028,19 +1101,19 @@ def thread_sweep(devices: Sequence[int], sizes: Sequence[int], dtype: str = "bf1
     per call spent inside the call's two barriers.  ``wrong`` counts, over all ranks, the elements
     whose bits differ from ``allreduce_ref`` (``wire="fp8"``: from ``allreduce_q8_ref``, ``wire="fp8x2"``: from
     ``allreduce_q8x2_ref``, and the rows carry ``"wire"``; ``"fp8x2"`` runs the two-shot alone, so ``algo`` must be
-    ``twoshot`` or ``both``); the check runs on the host, so sizes should stay moderate."""
-    if algo != "both" and algo not in ALGOS:
-        raise ValueError(f"algo must be oneshot|twoshot|both, got {algo!r}")
+    ``twoshot``, ``both`` or ``all``); the check runs on the host, so sizes should stay moderate."""
+    if algo not in ("both", "all", PUSH) and algo not in ALGOS:
+        raise ValueError(f"algo must be oneshot|twoshot|push|both|all, got {algo!r}")
     if dtype not in _ELEM:
         raise ValueError(f"dtype must be bf16|fp32, got {dtype!r}")
     if iters < 1 or warmup_iters < 0:
         raise ValueError("iters >= 1, warmup_iters >= 0")
     if wire not in WIRES:
         raise ValueError(f'wire must be None, "native", "fp8" or "fp8x2", got {wire!r}')
-    if wire == "fp8x2" and algo == "oneshot":
-        raise ValueError('wire="fp8x2" packs the gather phase of a twoshot: algo must be twoshot or both')
+    if wire == "fp8x2" and algo in ("oneshot", PUSH):
+        raise ValueError('wire="fp8x2" packs the gather phase of a twoshot: algo must be twoshot, both or all')
     fp8 = wire in ("fp8", "fp8x2")
-    algos = ("twoshot",) if wire == "fp8x2" else ALGOS if algo == "both" else (algo,)
+    algos = ("twoshot",) if wire == "fp8x2" else ALGOS if algo == "both" else ALGOS + (PUSH,) if algo == "all" else (algo,)
     k, elem = len(devices), _ELEM[dtype]
     points = [(max(1, int(nbytes) // elem), a) for nbytes in sizes for a in algos]
     if not points:
@@ -1086,7 +1159,7 @@ def selftest_cases_ef(k: int, counts: Optional[Sequence[int]] = None) -> List[Di
 
 
 def selftest(devices: Sequence[int], counts: Optional[Sequence[int]] = None, timeout_s: float = 60.0,
-             wire: Optional[str] = None, error_feedback: bool = False) -> Dict[str, object]:
+             wire: Optional[str] = None, error_feedback: bool = False, push: bool = False) -> Dict[str, object]:
     """Every case of :func:`selftest_cases`, each issued twice in a row with different inputs, on
     thread ranks over ``devices`` (:func:`run_thread_ranks`), compared bit for bit with ``ops/peer_ref.py``.
 
@@ -1103,14 +1176,18 @@ def selftest(devices: Sequence[int], counts: Optional[Sequence[int]] = None, tim
     issued three times in a row on the one communicator with different inputs and the residual carried from
     issue to issue; the residual is reset before each case.  Every result, and after every issue the rank's
     whole residual, is compared bit for bit with the chained reference.  Reported as ``ef_cases``,
-    ``ef_collectives``, ``ef_wrong`` and ``ef_launches``."""
+    ``ef_collectives``, ``ef_wrong`` and ``ef_launches``.
+
+    ``push=True`` adds the cases of :func:`selftest_cases_push` after every other set, each issued twice like the plain
+    ones; reported as ``push_cases``, ``push_collectives``, ``push_wrong`` and ``push_launches``."""
     if wire not in WIRES:
         raise ValueError(f'wire must be None, "native", "fp8" or "fp8x2", got {wire!r}')
     k = len(devices)
     native = selftest_cases(k, counts)
     q8 = selftest_cases_q8(k, counts)
     plain = native + q8 + (selftest_cases_q8x2(k, counts) if wire == "fp8x2" else [])
-    cases = plain + (selftest_cases_ef(k, counts) if error_feedback else [])
+    fed_end = len(plain) + (len(selftest_cases_ef(k, counts)) if error_feedback else 0)
+    cases = plain + (selftest_cases_ef(k, counts) if error_feedback else []) + (selftest_cases_push(k, counts) if push else [])
     once = _Once()  # every rank's inputs of (case, issue), made by the first rank that asks
 
     def inputs(ci: int, issue: int) -> List[np.ndarray]:
@@ -1120,7 +1197,7 @@ def selftest(devices: Sequence[int], counts: Optional[Sequence[int]] = None, tim
     def body(comm: PeerComm):
         wrong, barriers, marks = set(), set(), {}
         for ci, case in enumerate(cases):
-            if ci in (len(native), len(native) + len(q8), len(plain)):
+            if ci in (len(native), len(native) + len(q8), len(plain), fed_end):
                 marks[ci] = comm.launches
             fed = bool(case.get("ef"))
             residuals: List[np.ndarray] = []
@@ -1134,9 +1211,10 @@ def selftest(devices: Sequence[int], counts: Optional[Sequence[int]] = None, tim
                     wrong.add((ci, issue))
                 elif fed and not np.array_equal(_bits(comm.residual(0, residuals[comm.rank].size)), _bits(residuals[comm.rank])):
                     wrong.add((ci, issue))
-        end = marks.get(len(plain), comm.launches)
+        end_fed = marks.get(fed_end, comm.launches)  # where the push cases start
+        end = marks.get(len(plain), end_fed)
         first_q8, end_q8 = marks[len(native)], marks.get(len(native) + len(q8), end)
-        return wrong, barriers, first_q8, end_q8 - first_q8, end - end_q8, comm.launches - end
+        return wrong, barriers, first_q8, end_q8 - first_q8, end - end_q8, end_fed - end, comm.launches - end_fed
 
     res = run_thread_ranks(devices, body, _case_capacity(k, cases), timeout_s=timeout_s)
     bad = set().union(*(r[0] for r in res))
@@ -1150,7 +1228,11 @@ def selftest(devices: Sequence[int], counts: Optional[Sequence[int]] = None, tim
         rep.update({"q8x2_cases": nx, "q8x2_collectives": 2 * nx, "q8x2_wrong": sum(n + nq <= ci < len(plain) for ci, _ in bad),
                     "q8x2_launches": sum(r[4] for r in res)})
     if error_feedback:
-        ne = len(cases) - len(plain)
-        rep.update({"ef_cases": ne, "ef_collectives": 3 * ne, "ef_wrong": sum(ci >= len(plain) for ci, _ in bad),
+        ne = fed_end - len(plain)
+        rep.update({"ef_cases": ne, "ef_collectives": 3 * ne, "ef_wrong": sum(len(plain) <= ci < fed_end for ci, _ in bad),
                     "ef_launches": sum(r[5] for r in res)})
+    if push:
+        npush = len(cases) - fed_end
+        rep.update({"push_cases": npush, "push_collectives": 2 * npush, "push_wrong": sum(ci >= fed_end for ci, _ in bad),
+                    "push_launches": sum(r[6] for r in res)})
     return rep

@@ -4,7 +4,8 @@ catch it (a mutation-testing pass; README "Mutation testing of the control plane
 
     python tools/mutants.py                  # every group
     python tools/mutants.py --only ledger    # one group (ledger, cache, plugin, informer, rbac, numa, cordon, objective, dp, guard,
-                                             # banding, gaia, repartition, extender, contract, peer_ref)
+                                             # banding, gaia, repartition, extender, contract, peer_ref:
+                                             # the K7 references and the peer communicator's push)
 
 Each mutant replaces one line (or a few) of a source file, runs the group's tests with pytest-xdist,
 and restores the file whatever happens.  ``CAUGHT`` = some test failed, ``SURVIVED`` = the tests did
@@ -51,6 +52,7 @@ KUBELET = "gpu_topology_on_k8s_amd/deviceplugin/kubelet.py"
 CORE = "gpu_topology_on_k8s_amd/placement/core.py"
 ENGINE = "csrc/placement/engine.cpp"
 PEER_REF = "gpu_topology_on_k8s_amd/ops/peer_ref.py"
+PEER_COMM = "gpu_topology_on_k8s_amd/parallel/peer_comm.py"
 
 MUTANTS: List[Mutant] = [
     # allocation ledger (cross-extender bind safety)
@@ -239,6 +241,11 @@ MUTANTS: List[Mutant] = [
     Mutant("peer_ref", PEER_REF, "    code = np.where(special, 0x7F, np.minimum(code, 0x7E))  # no finite element reaches the minimum",
            "    code = np.minimum(code, 0x7E)"),
     Mutant("peer_ref", PEER_REF, "    e = np.where(np.isinf(amax), Q8_EXP_MAX, e).astype(np.int32)", "    e = e.astype(np.int32)"),
+    # the push all-reduce of the peer communicator (host backend): a destination left out, barrier B left out
+    Mutant("peer_ref", PEER_COMM, "        for j in range(self.world):  # every owner's out, this rank's first: a peer write is logged like any other",
+           "        for j in range(self.world - 1):"),
+    Mutant("peer_ref", PEER_COMM, "            self._b.reduce_push(a, b, dtype, out, scale)\n            self._leave()",
+           "            self._b.reduce_push(a, b, dtype, out, scale)\n            self._b.synchronize()"),
 ]
 
 TESTS = {
@@ -263,7 +270,7 @@ TESTS = {
     "extender": ["tests/test_shares.py", "tests/test_extender.py", "tests/test_cluster_features.py"],
     "contract": ["tests/test_k8s.py", "tests/test_extender.py", "tests/test_extender_fuzz.py", "tests/test_extender_ledger.py",
                  "tests/test_deviceplugin.py", "tests/test_cluster_features.py"],
-    "peer_ref": ["tests/test_peer_nonfinite_cpu.py"],
+    "peer_ref": ["tests/test_peer_nonfinite_cpu.py", "tests/test_peer_push_cpu.py"],
 }
 
 GUARD_TARGETS = "vgpu_guard,vgpu_selftest_asan,vgpu_selftest_tsan"
