@@ -2,7 +2,7 @@
 """The peer communicator's thread-rank all_reduce next to the in-process driver's, as one JSON document:
 
     python bench/peer_comm_bench.py [--members 0,0,0,0] [--sizes-mib 1,4,16,64,256] [--dtype bf16]
-                                    [--iters 20] [--warmup 2] [--wire native|fp8|fp8x2] [--error-feedback] [--push]
+                                    [--iters 20] [--warmup 2] [--wire native|fp8|fp8x2] [--error-feedback] [--push] [--zero1]
                                     [--out FILE] [--md FILE]
 
 Both run the same K7 kernels on the same members at the same count, in one process:
@@ -27,6 +27,14 @@ into every rank's out; two stream synchronisations per call where the two-shot h
 on thread ranks, on the native and on the fp8 wire, the two alternated ``--reps`` times in one process, the
 quicker repetition of each reported.  Up to ``--check-max-mib`` the push result is compared with the host
 reference; at every size it is compared bit for bit with the two-shot's.  No driver run is made.
+
+``--zero1`` measures the ZeRO-1 step (``PeerComm.zero1_step``: one launch sums the rank's slice of every window, applies
+AdamW to the rank's own fp32 state and stores the new bf16 weights into every rank's out) against the same communication
+with no optimizer at all: ``reduce_scatter(out_dtype="fp32")`` followed by ``all_gather`` of count / k bf16 elements, two
+launches and four barriers.  The two are alternated ``--reps`` times in one process on thread ranks, on the native and on
+the fp8 wire, the quicker repetition of each reported; the number of interest is how far the fused step exceeds the bare
+communication, if at all.  After the timed steps every rank's weights must be rank 0's and its own master rounded once,
+and up to ``--check-max-mib`` the first step is compared with the host reference at the GPU tests' tolerances.
 """
 import argparse
 import json
@@ -156,6 +164,113 @@ def markdown_push(res) -> str:
     return "\n".join(out)
 
 
+ZERO1_HP = dict(lr=1e-3, beta1=0.9, beta2=0.95, eps=1e-8, weight_decay=0.1)
+
+
+def measure_zero1(devs, sizes, iters, warmup, reps, check_max_bytes):
+    """Host seconds per call of the fused ZeRO-1 step and of reduce_scatter (fp32 out) + all_gather (count / k bf16), alternated."""
+    import time
+
+    from gpu_topology_on_k8s_amd.ops.peer_ref import bf16_round, bf16_to_f32, zero1_slices, zero1_step_ref
+
+    k = len(devs)
+    counts = [max(1, n // 2) for n in sizes]
+    once = pc._Once()
+    scale = float(np.float32(1.0 / k))
+
+    def start(w0, plan):  # what zero1_init makes of the weights: every rank's master widened, m and v zero
+        out = []
+        for p, q in plan:
+            master = np.zeros(q - p, np.float32)
+            master[:max(0, min(q, w0.size) - p)] = bf16_to_f32(w0[p:q])
+            out.append((master, np.zeros(q - p, np.float32), np.zeros(q - p, np.float32)))
+        return out
+
+    def timed(comm, call):
+        for i in range(warmup):
+            call(i)
+        comm.barrier()
+        t0 = time.perf_counter()
+        for i in range(iters):
+            call(warmup + i)
+        secs = (time.perf_counter() - t0) / iters
+        comm.barrier()  # no rank goes on to check its result, holding the interpreter, while another still reads its clock
+        return secs
+
+    def body(comm):
+        rows = []
+        for count in counts:
+            xs = once.get(("in", count), lambda: [pc.case_input(0, 0, p, count, "bf16") for p in range(k)], lambda o: o[1] == count)
+            w0 = once.get(("w", count), lambda: pc.case_input(1, 0, 0, count, "bf16"), lambda o: o[1] == count)
+            per = -(-count // k)  # elements every rank contributes to the all-gather of the weights
+            for wire in ("native", "fp8"):
+                checked = count * 2 <= check_max_bytes
+                plan = zero1_slices(count, k, wire)
+                a, b = plan[comm.rank]
+                comm.write(xs[comm.rank])
+                comm.zero1_init(count, w0, wire)
+                wrong = 0
+                if checked:  # the first step against the host reference
+                    ref = once.get(("ref", count, wire), lambda: zero1_step_ref(xs, start(w0, plan), "bf16", scale,
+                                                                                 pc.zero1_hyper(step=1, **ZERO1_HP), wire), lambda o: o[1] == count)
+                    comm.zero1_step(step=1, **ZERO1_HP)
+                    wrong = sum(int(np.count_nonzero(~np.isclose(g, r, rtol=1e-5, atol=tol)))
+                                for g, r, tol in zip(comm.zero1_state(), ref[0][comm.rank], (1e-6, 1e-6, 1e-7)))
+                    comm.zero1_init(count, w0, wire)
+                for r in range(reps):
+                    fused = timed(comm, lambda i: comm.zero1_step(step=i + 1, **ZERO1_HP))
+                    out = comm.read(0, count, "bf16")
+                    unrounded = int(np.count_nonzero(out[min(count, a):min(count, b)] != bf16_round(comm.zero1_state()[0])[:max(0, min(count, b) - a)]))
+                    comm.barrier()
+
+                    def bare(i):
+                        comm.reduce_scatter(count, "bf16", "fp32", scale, wire=None if wire == "native" else wire)
+                        comm.all_gather(per, "bf16")
+
+                    comm.write(xs[comm.rank])
+                    two = timed(comm, bare)
+                    rows.append((count, wire, r, fused, two, wrong if r == 0 else 0, unrounded, out if r == 0 else None, checked))
+                    comm.zero1_init(count, w0, wire)  # the same trajectory for every repetition
+        return rows
+
+    cap = max(q8_blocks(max(counts)) * Q8_BLOCK * 2, 16 * k * -(-(-(-max(counts) // k)) * 2 // 16))
+    res = pc.run_thread_ranks(devs, body, cap, timeout_s=300.0, join_s=3000.0)
+    out = []
+    for count in counts:
+        row = {"bytes": count * 2, "count": count}
+        for wire in ("native", "fp8"):
+            mine = [[r for r in rank_rows if r[:2] == (count, wire)] for rank_rows in res]
+            fused = [max(rows[r][3] for rows in mine) * 1e6 for r in range(reps)]  # the slowest rank of each repetition
+            two = [max(rows[r][4] for rows in mine) * 1e6 for r in range(reps)]
+            row[wire] = {"fused_step_time_us": min(fused), "reduce_scatter_all_gather_time_us": min(two),
+                         "fused_over_bare_communication": min(fused) / min(two), "fused_step_time_us_reps": fused,
+                         "reduce_scatter_all_gather_time_us_reps": two, "checked_against_reference": bool(mine[0][0][8]),
+                         "state_outside_tolerance": sum(r[5] for rows in mine for r in rows),
+                         "weights_not_the_rounded_master": sum(r[6] for rows in mine for r in rows),
+                         "weights_differ_between_ranks": sum(int(np.count_nonzero(rows[0][7] != mine[0][0][7])) for rows in mine)}
+        out.append(row)
+        print(json.dumps(row), file=sys.stderr, flush=True)
+    return {"members": list(devs), "k": k, "distinct_devices": len(set(devs)) == k, "dtype": "bf16", "iters": iters, "warmup": warmup,
+            "reps": reps, "zero1": True, "hyper": ZERO1_HP, "sizes": out}
+
+
+ZERO1_CHECKS = ("state_outside_tolerance", "weights_not_the_rounded_master", "weights_differ_between_ranks")
+
+
+def markdown_zero1(res) -> str:
+    out = [f"### ZeRO-1 step against reduce_scatter (fp32 out) + all_gather, thread ranks, members {res['members']} (k = {res['k']}), "
+           f"{res['iters']} timed calls, best of {res['reps']} alternated repetitions", "",
+           "| gradient per member | wire | fused step us / call | reduce_scatter + all_gather us / call | fused / bare communication | failed checks |",
+           "|---|---|---|---|---|---|"]
+    for r in res["sizes"]:
+        for wire in ("native", "fp8"):
+            a = r[wire]
+            out.append(f"| {r['bytes'] / 2**20:.1f} MiB | {wire} | {a['fused_step_time_us']:.1f} | {a['reduce_scatter_all_gather_time_us']:.1f} "
+                       f"| {a['fused_over_bare_communication']:.2f} | {sum(a[c] for c in ZERO1_CHECKS)} |")
+    out.append("")
+    return "\n".join(out)
+
+
 EF_CALLS = ("reduce_scatter", "twoshot")
 
 
@@ -261,7 +376,9 @@ def main():
     ap.add_argument("--error-feedback", action="store_true",
                     help="thread ranks alone: the fp8 reduce_scatter and two-shot all_reduce without and with error feedback, alternated")
     ap.add_argument("--push", action="store_true", help="thread ranks alone: the push all_reduce against the two-shot on the native and the fp8 wire, alternated")
-    ap.add_argument("--check-max-mib", type=float, default=64.0, help="--push: the largest size whose result is compared with the host reference")
+    ap.add_argument("--zero1", action="store_true",
+                    help="thread ranks alone: the fused ZeRO-1 step against reduce_scatter (fp32 out) + all_gather, on the native and the fp8 wire, alternated")
+    ap.add_argument("--check-max-mib", type=float, default=64.0, help="--push, --zero1: the largest size whose result is compared with the host reference")
     ap.add_argument("--reps", type=int, default=2, help="alternated repetitions of each measurement")
     ap.add_argument("--out", default="", help="also write the JSON document here")
     ap.add_argument("--md", default="", help="also write the tables as Markdown here")
@@ -269,6 +386,17 @@ def main():
     groups = [[int(x) for x in m.split(",")] for m in (a.members or ["0,0,0,0"])]
     sizes = [int(float(x) * (1 << 20)) for x in a.sizes_mib.split(",")]
     probe.warmup(groups[0][0], 100.0)
+    if a.zero1:
+        doc = {"device": probe.device_props(groups[0][0])["name"],
+               "runs": [measure_zero1(g, sizes, a.iters, a.warmup, max(1, a.reps), int(a.check_max_mib * (1 << 20))) for g in groups]}
+        text = json.dumps(doc)
+        print(text)
+        for path, body in ((a.out, text + "\n"), (a.md, "\n".join(markdown_zero1(r) for r in doc["runs"]))):
+            if path:
+                os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+                with open(path, "w") as f:
+                    f.write(body)
+        return 1 if any(r[w][key] for run in doc["runs"] for r in run["sizes"] for w in ("native", "fp8") for key in ZERO1_CHECKS) else 0
     if a.push:
         doc = {"device": probe.device_props(groups[0][0])["name"],
                "runs": [measure_push(g, sizes, a.dtype, a.iters, a.warmup, max(1, a.reps), int(a.check_max_mib * (1 << 20))) for g in groups]}

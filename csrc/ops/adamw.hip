@@ -25,6 +25,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "../common/adamw_update.h"  // Hyper and adam8_update, the update body every kernel here instantiates
 #include "tile_t.h"
 
 namespace gtk_adamw {
@@ -39,10 +40,6 @@ __device__ __forceinline__ float block_sum(float s) {
   __syncthreads();
   return red[0] + red[1] + red[2] + red[3];
 }
-
-struct Hyper {
-  float lr, b1, b2, eps, wd, gs, bc1, bc2;
-};
 
 // hp (host form) = [lr, beta1, beta2, eps, weight_decay, grad_scale, bias_c1, bias_c2]: a device
 //   tensor, so a captured graph replays with updated hyper-parameters.
@@ -119,15 +116,7 @@ __device__ __forceinline__ u16x8 adam8_store(float* __restrict__ master, float* 
     mm[j] = in.m0[j], mm[j + 4] = in.m1[j];
     vv[j] = in.v0[j], vv[j + 4] = in.v1[j];
   }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {  // the AdamW update: every kernel's bits come from these expressions
-    const float gr = in.gf[j] * h.gs;
-    mm[j] = h.b1 * mm[j] + (1.f - h.b1) * gr;
-    vv[j] = h.b2 * vv[j] + (1.f - h.b2) * gr * gr;
-    const float upd = (mm[j] / h.bc1) / (sqrtf(vv[j] / h.bc2) + h.eps);
-    p[j] = p[j] - h.lr * (upd + h.wd * p[j]);
-    wo[j] = f2bf(p[j]);
-  }
+  adam8_update(p, mm, vv, in.gf, h, wo);
   f32x4 p0, p1, m0, m1, v0, v1;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {

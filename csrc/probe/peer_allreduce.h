@@ -15,7 +15,9 @@
 // choice, the same on every member; tests/test_gpu_peer_nonfinite.py compares the rest bit for bit.
 //
 // The push form (peer_reduce_push_kernel) is the same body with another sink for the stores: every result
-// vector goes to every member's `out`, so what is said above about the bits holds for it unchanged.
+// vector goes to every member's `out`, so what is said above about the bits holds for it unchanged.  What
+// follows a position's sum is an epilogue (PeerStoreEpi: scale, round, store); the ZeRO-1 step of peer_zero1.h
+// is the same loads, sum and walk with the AdamW update as the epilogue.
 //
 // No kernel here waits for another running kernel: the all-reduce's cross-member ordering is stream
 // events between launches (the host driver in peer_driver.h), visibility rests on kernel boundaries.
@@ -106,20 +108,45 @@ __device__ __forceinline__ void peer_store(float (&acc)[L], float scale, const S
   }
 }
 
+// What follows a position's sum is an epilogue, `epi`:
+//   typename Epi::template Pre<U>   what it holds of its own per lane for U positions (PeerStoreEpi: nothing);
+//   epi.load(pre, u, o)             issues position u's own loads, at unit offset o, next to the members' loads;
+//   epi(pre, u, acc, dst, o)        takes the position's fp32 sum, not yet scaled, and stores what becomes of it;
+//                                   `dst` is the launch's first destination, handed down as a __restrict__
+//                                   parameter so that the members' loads may pass the stores to it.
+// PeerStoreEpi is the reduce itself: peer_store through a sink into `dst`, element type TO.  The fp8 wire's sum
+// (peer_q8.h) runs the same epilogues on sixteen sums per position, and peer_zero1.h has the AdamW one.
+template <typename TO, typename Sink>
+struct PeerStoreEpi {
+  Sink sink;
+  float scale;
+  template <int U>
+  struct Pre {};
+  template <int U>
+  __device__ __forceinline__ void load(Pre<U>&, int, size_t) const {}
+  template <int U, int L>
+  __device__ __forceinline__ void operator()(const Pre<U>&, int, float (&acc)[L], u32x4* __restrict__ dst, size_t o) const {
+    peer_store<TO>(acc, scale, sink, dst, o);
+  }
+};
+
 // U vectors per lane, `stride` apart from `i`: the k x U loads (member-major, all in flight before the
-// first add), then per position the sum in member order, one multiply by `scale`, one rounding and the
-// store.  TI / TO are the input and output element types.  KB is the member bucket the registers are
-// sized for (k <= KB): r[] is indexed by constants only.  `sink` takes the stores (PeerOneDst, PeerPushDst).
-template <typename TI, typename TO, int KB, int U, typename Sink>
-__device__ __forceinline__ void peer_reduce_vecs(const SrcSet& srcs, int k, const Sink& sink, u32x4* __restrict__ dst, size_t i,
-                                                 size_t stride, float scale) {
+// first add) and the epilogue's own, then per position the sum in member order and the epilogue: for the
+// reduce one multiply by `scale`, one rounding and the store.  TI is the input element type.  KB is the
+// member bucket the registers are sized for (k <= KB): r[] is indexed by constants only.
+template <typename TI, int KB, int U, typename Epi>
+__device__ __forceinline__ void peer_reduce_vecs(const SrcSet& srcs, int k, const Epi& epi, u32x4* __restrict__ dst, size_t i,
+                                                 size_t stride) {
   u32x4 r[KB][U];
+  typename Epi::template Pre<U> pre;
 #pragma unroll
   for (int m = 0; m < KB; ++m)
     if (m < k) {
 #pragma unroll
       for (int u = 0; u < U; ++u) r[m][u] = __builtin_nontemporal_load(srcs.p[m] + i + (size_t)u * stride);
     }
+#pragma unroll
+  for (int u = 0; u < U; ++u) epi.load(pre, u, i + (size_t)u * stride);
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     float acc[kPeerLanes<TI>];
@@ -132,35 +159,34 @@ __device__ __forceinline__ void peer_reduce_vecs(const SrcSet& srcs, int k, cons
 #pragma unroll
         for (int j = 0; j < kPeerLanes<TI>; ++j) acc[j] = acc[j] + x[j];
       }
-    peer_store<TO>(acc, scale, sink, dst, i + (size_t)u * stride);
+    epi(pre, u, acc, dst, i + (size_t)u * stride);
   }
 }
 
-// dst[v0, v1), and the same vectors of what else the sink stores to, = scale * sum over members m < k of
-// srcs.p[m][v0, v1), vectors of the input type TI (float, or bf16 as raw u16); the wide form (bf16 in, float
-// out) writes [2 * v0, 2 * v1).  Whole
+// The epilogue of the sum over members m < k of srcs.p[m][v0, v1), vectors of the input type TI (float, or
+// bf16 as raw u16), position by position.  With PeerStoreEpi: dst[v0, v1), and the same vectors of what else
+// the sink stores to, = scale * that sum; the wide form (bf16 in, float out) writes [2 * v0, 2 * v1).  Whole
 // tiles (kStreamBlock x U vectors) are cut into one contiguous run per block, as gtk::stream_slices
 // does; what is left of the range, under one tile, goes one vector per lane over the whole grid.
-template <typename TI, typename TO, int KB, int U, typename Sink>
-__device__ __forceinline__ void peer_reduce_range(const SrcSet& srcs, int k, size_t v0, size_t v1, const Sink& sink,
-                                                  u32x4* __restrict__ dst, float scale) {
+template <typename TI, int KB, int U, typename Epi>
+__device__ __forceinline__ void peer_reduce_range(const SrcSet& srcs, int k, size_t v0, size_t v1, const Epi& epi,
+                                                  u32x4* __restrict__ dst) {
   const size_t tile = (size_t)gtk::kStreamBlock * U;
   const size_t n_tiles = (v1 - v0) / tile;
   const size_t per = (n_tiles + gridDim.x - 1) / gridDim.x;
   const size_t t0 = (size_t)blockIdx.x * per;
   const size_t t1 = std::min(n_tiles, t0 + per);
-  for (size_t t = t0; t < t1; ++t)
-    peer_reduce_vecs<TI, TO, KB, U>(srcs, k, sink, dst, v0 + t * tile + threadIdx.x, gtk::kStreamBlock, scale);
+  for (size_t t = t0; t < t1; ++t) peer_reduce_vecs<TI, KB, U>(srcs, k, epi, dst, v0 + t * tile + threadIdx.x, gtk::kStreamBlock);
   for (size_t i = v0 + n_tiles * tile + (size_t)blockIdx.x * gtk::kStreamBlock + threadIdx.x; i < v1;
        i += (size_t)gridDim.x * gtk::kStreamBlock)
-    peer_reduce_vecs<TI, TO, KB, 1>(srcs, k, sink, dst, i, 0, scale);
+    peer_reduce_vecs<TI, KB, 1>(srcs, k, epi, dst, i, 0);
 }
 
 // The reduce into the launching member's own `dst`.
 template <typename TI, typename TO, int KB, int U>
 __global__ __launch_bounds__(gtk::kStreamBlock) void peer_reduce_kernel(SrcSet srcs, int k, size_t v0, size_t v1,
                                                                         u32x4* __restrict__ dst, float scale) {
-  peer_reduce_range<TI, TO, KB, U>(srcs, k, v0, v1, PeerOneDst{}, dst, scale);
+  peer_reduce_range<TI, KB, U>(srcs, k, v0, v1, PeerStoreEpi<TO, PeerOneDst>{PeerOneDst{}, scale}, dst);
 }
 
 // The push form: the same range, sum and rounding, every result vector stored to the same offset of every
@@ -169,7 +195,7 @@ __global__ __launch_bounds__(gtk::kStreamBlock) void peer_reduce_kernel(SrcSet s
 template <typename TI, typename TO, int KB, int U>
 __global__ __launch_bounds__(gtk::kStreamBlock) void peer_reduce_push_kernel(SrcSet srcs, DstSet dsts, int k, size_t v0,
                                                                              size_t v1, float scale) {
-  peer_reduce_range<TI, TO, KB, U>(srcs, k, v0, v1, PeerPushDst<KB>{dsts, k}, dsts.p[0], scale);
+  peer_reduce_range<TI, KB, U>(srcs, k, v0, v1, PeerStoreEpi<TO, PeerPushDst<KB>>{PeerPushDst<KB>{dsts, k}, scale}, dsts.p[0]);
 }
 
 // Slice i of an all-gather: `count` vectors from vector `first` of p[i], to the same offset of dst.

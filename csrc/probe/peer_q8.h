@@ -237,15 +237,34 @@ __device__ __forceinline__ void q8_store(const float (&acc)[16], const Sink& sin
   sink(out, dst, v * (16 / L));
 }
 
+// The reduce's epilogue (PeerStoreEpi of peer_allreduce.h) for the sixteen sums of a code vector: one multiply
+// by `scale`, one rounding and the stores of q8_store.
+template <typename TO, typename Sink>
+struct PeerQ8StoreEpi {
+  Sink sink;
+  float scale;
+  template <int U>
+  struct Pre {};
+  template <int U>
+  __device__ __forceinline__ void load(Pre<U>&, int, size_t) const {}
+  template <int U>
+  __device__ __forceinline__ void operator()(const Pre<U>&, int, float (&acc)[16], u32x4* __restrict__ dst, size_t v) const {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) acc[j] = acc[j] * scale;
+    q8_store<TO>(acc, sink, dst, v);
+  }
+};
+
 // peer_reduce_vecs on the packed form: U code vectors per lane, `stride` apart from `i`; the k x U code
-// loads and the k x U exponent words (member-major, all in flight before the first add), then per
-// position the sum in member order, one multiply by `scale`, one rounding and the stores.  r[][] and
-// x[][] are indexed by constants only.
-template <typename TO, int KB, int U, typename Sink>
-__device__ __forceinline__ void peer_q8_sum_vecs(const SrcSet& srcs, int k, size_t exp_vec, const Sink& sink, u32x4* __restrict__ dst,
-                                                 size_t i, size_t stride, float scale) {
+// loads and the k x U exponent words (member-major, all in flight before the first add) and the epilogue's
+// own, then per position the sum in member order and the epilogue: for the reduce one multiply by `scale`,
+// one rounding and the stores.  r[][] and x[][] are indexed by constants only.
+template <int KB, int U, typename Epi>
+__device__ __forceinline__ void peer_q8_sum_vecs(const SrcSet& srcs, int k, size_t exp_vec, const Epi& epi, u32x4* __restrict__ dst,
+                                                 size_t i, size_t stride) {
   u32x4 r[KB][U];
   unsigned int x[KB][U];
+  typename Epi::template Pre<U> pre;
 #pragma unroll
   for (int m = 0; m < KB; ++m)
     if (m < k) {
@@ -256,6 +275,8 @@ __device__ __forceinline__ void peer_q8_sum_vecs(const SrcSet& srcs, int k, size
         x[m][u] = __builtin_nontemporal_load(reinterpret_cast<const unsigned int*>(srcs.p[m] + exp_vec) + (v >> 3));
       }
     }
+#pragma unroll
+  for (int u = 0; u < U; ++u) epi.load(pre, u, i + (size_t)u * stride);
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     const size_t v = i + (size_t)u * stride;
@@ -270,20 +291,18 @@ __device__ __forceinline__ void peer_q8_sum_vecs(const SrcSet& srcs, int k, size
 #pragma unroll
         for (int j = 0; j < 16; ++j) acc[j] = acc[j] + y[j];
       }
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc[j] = acc[j] * scale;
-    q8_store<TO>(acc, sink, dst, v);
+    epi(pre, u, acc, dst, v);
   }
 }
 
-// Blocks [b0, b1) of dst, and of what else the sink stores to (whole blocks of the output type TO: float, or
-// bf16 as raw u16) = scale * the
-// sum over members m < k of the dequantised blocks [b0, b1) of srcs.p[m], every member's packed buffer.
+// The epilogue of the sum over members m < k of the dequantised blocks [b0, b1) of srcs.p[m], every member's
+// packed buffer, code vector by code vector.  With PeerQ8StoreEpi: blocks [b0, b1) of dst, and of what else the
+// sink stores to (whole blocks of the output type TO: float, or bf16 as raw u16) = scale * that sum.
 // The range is code vectors [2 b0, 2 b1), cut as peer_reduce_kernel cuts its vectors: whole tiles in one
 // contiguous run per block, the rest one vector per lane over the whole grid.
-template <typename TO, int KB, int U, typename Sink>
-__device__ __forceinline__ void peer_q8_sum_range(const SrcSet& srcs, int k, size_t exp_vec, size_t b0, size_t b1, const Sink& sink,
-                                                  u32x4* __restrict__ dst, float scale) {
+template <int KB, int U, typename Epi>
+__device__ __forceinline__ void peer_q8_sum_range(const SrcSet& srcs, int k, size_t exp_vec, size_t b0, size_t b1, const Epi& epi,
+                                                  u32x4* __restrict__ dst) {
   const size_t v0 = 2 * b0, v1 = 2 * b1;
   const size_t tile = (size_t)gtk::kStreamBlock * U;
   const size_t n_tiles = (v1 - v0) / tile;
@@ -291,17 +310,17 @@ __device__ __forceinline__ void peer_q8_sum_range(const SrcSet& srcs, int k, siz
   const size_t t0 = (size_t)blockIdx.x * per;
   const size_t t1 = std::min(n_tiles, t0 + per);
   for (size_t t = t0; t < t1; ++t)
-    peer_q8_sum_vecs<TO, KB, U>(srcs, k, exp_vec, sink, dst, v0 + t * tile + threadIdx.x, gtk::kStreamBlock, scale);
+    peer_q8_sum_vecs<KB, U>(srcs, k, exp_vec, epi, dst, v0 + t * tile + threadIdx.x, gtk::kStreamBlock);
   for (size_t i = v0 + n_tiles * tile + (size_t)blockIdx.x * gtk::kStreamBlock + threadIdx.x; i < v1;
        i += (size_t)gridDim.x * gtk::kStreamBlock)
-    peer_q8_sum_vecs<TO, KB, 1>(srcs, k, exp_vec, sink, dst, i, 0, scale);
+    peer_q8_sum_vecs<KB, 1>(srcs, k, exp_vec, epi, dst, i, 0);
 }
 
 // The sum into the launching member's own `dst`.
 template <typename TO, int KB, int U>
 __global__ __launch_bounds__(gtk::kStreamBlock) void peer_q8_sum_kernel(SrcSet srcs, int k, size_t exp_vec, size_t b0,
                                                                         size_t b1, u32x4* __restrict__ dst, float scale) {
-  peer_q8_sum_range<TO, KB, U>(srcs, k, exp_vec, b0, b1, PeerOneDst{}, dst, scale);
+  peer_q8_sum_range<KB, U>(srcs, k, exp_vec, b0, b1, PeerQ8StoreEpi<TO, PeerOneDst>{PeerOneDst{}, scale}, dst);
 }
 
 // The push form of the sum: the same blocks, sum and rounding, every result vector stored to the same
@@ -309,7 +328,7 @@ __global__ __launch_bounds__(gtk::kStreamBlock) void peer_q8_sum_kernel(SrcSet s
 template <typename TO, int KB, int U>
 __global__ __launch_bounds__(gtk::kStreamBlock) void peer_q8_sum_push_kernel(SrcSet srcs, DstSet dsts, int k, size_t exp_vec,
                                                                              size_t b0, size_t b1, float scale) {
-  peer_q8_sum_range<TO, KB, U>(srcs, k, exp_vec, b0, b1, PeerPushDst<KB>{dsts, k}, dsts.p[0], scale);
+  peer_q8_sum_range<KB, U>(srcs, k, exp_vec, b0, b1, PeerQ8StoreEpi<TO, PeerPushDst<KB>>{PeerPushDst<KB>{dsts, k}, scale}, dsts.p[0]);
 }
 
 // peer_q8_sum_vecs up to the multiply by `scale` (k x U code vectors and exponent words in flight, the sum

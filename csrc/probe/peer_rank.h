@@ -1,7 +1,8 @@
 // One rank's device state for the peer communicator (parallel/peer_comm.py, backend="device").
 // Host code only: it launches the K7 kernels of peer_allreduce.h and peer_q8.h through the launch plan of
-// peer_driver.h, as PeerAllreduce does, and adds no kernel and no instantiation.  The push launches
-// (reduce_push, reduce_q8_push) store into the peers' outs, which is why those are held mutable.
+// peer_driver.h, as PeerAllreduce does, and the ZeRO-1 kernels of peer_zero1.h, and adds no kernel of its own.
+// The push launches (reduce_push, reduce_q8_push, reduce_adamw_push, reduce_q8_adamw_push) store into the
+// peers' outs, which is why those are held mutable.
 //
 // A rank owns a window (inputs, `capacity` bytes), an out (results, twice that: the wide form writes
 // two vectors per input vector), a packed buffer (the fp8 wire's form of the window, sized for a window
@@ -9,6 +10,8 @@
 // slice of a sum, which its peers gather from) and one non-blocking stream on its device.  A rank that packs with
 // error feedback also owns a residual (fp32, one value per element of a window full of bf16: twice the capacity),
 // allocated on its first feedback call; it is the rank's alone, never published and no part of open_peers.
+// The same holds for the ZeRO-1 optimizer state (zero1_alloc): master, m and v, fp32, of the rank's slice of the
+// parameters alone, read and written by the rank's own fused step (reduce_adamw_push, reduce_q8_adamw_push).
 // Ranks are threads of one
 // process, so a peer's buffer is reached through its plain device address and, across devices,
 // hipDeviceEnablePeerAccess: no IPC call.  A PeerRank is used by one thread.  Nothing here waits on
@@ -16,9 +19,11 @@
 // ranks is the caller's (synchronize(), then a host barrier).  Every HIP call is made with the GIL
 // released, since a rank blocked in hipStreamSynchronize must not keep another from its barrier.
 #pragma once
+#include <array>
 #include <mutex>
 
 #include "peer_driver.h"
+#include "peer_zero1.h"
 
 namespace {
 
@@ -78,6 +83,8 @@ class PeerRank {
   size_t max_blocks() const { return cap_ / (kQ8Block * 2); }  // blocks of 32 bf16 elements the window holds
   size_t packed_bytes() const { return std::max<size_t>(16, q8_packed_vecs(max_blocks()) * 16); }
   size_t residual_bytes() const { return residual_ ? 2 * cap_ : 0; }  // 0 until the first feedback call
+  size_t zero1_elems() const { return zero1_n_; }  // floats of each of master, m and v; 0 until zero1_alloc
+  size_t zero1_bytes() const { return 3 * zero1_n_ * sizeof(float); }
   size_t launches() const { return launches_; }
   bool released() const { return released_; }
 
@@ -215,6 +222,72 @@ class PeerRank {
     need_residual();
     HIP_CHECK(hipMemcpyAsync(static_cast<float*>(residual_->p) + first_elem, src, n * sizeof(float), hipMemcpyHostToDevice, stream_));
     HIP_CHECK(hipStreamSynchronize(stream_));
+  }
+
+  // The ZeRO-1 optimizer state of this rank's slice: master, m and v, `n_elems` floats each (whole vectors of
+  // eight; 0 frees it), zero-filled on the stream.  A second call replaces what the first allocated.
+  void zero1_alloc(size_t n_elems) {
+    live();
+    if (n_elems % 8) throw std::invalid_argument("zero1_alloc: whole vectors of 8 elements");
+    if (n_elems > cap_ / 2) throw std::invalid_argument("zero1_alloc: more elements than a window full of bf16");
+    DeviceGuard g(dev_);
+    HIP_CHECK(hipStreamSynchronize(stream_));  // no launch still uses the state this call frees
+    {
+      std::lock_guard<std::mutex> lock(peer_rank_mutex());
+      zero1_.reset();
+      zero1_n_ = 0;
+      if (n_elems) zero1_.reset(new DevBuf(dev_, 3 * n_elems * sizeof(float)));
+    }
+    zero1_n_ = n_elems;
+    if (n_elems) HIP_CHECK(hipMemsetAsync(zero1_->p, 0, 3 * n_elems * sizeof(float), stream_));
+  }
+
+  // Host floats into floats [first, first + n) of master (which = 0), m (1) or v (2): the initial weights, a
+  // restored checkpoint.  On the rank's stream; returns once the host floats have been read.
+  void zero1_write_state(int which, const float* src, size_t first, size_t n) {
+    float* dst = zero1_ptr(which, first, n, "zero1_write_state");
+    if (!n) return;
+    DeviceGuard g(dev_);
+    HIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyHostToDevice, stream_));
+    HIP_CHECK(hipStreamSynchronize(stream_));
+  }
+
+  // Floats [first, first + n) of master, m or v to `dst`, after everything on the stream.
+  void zero1_read_state(int which, float* dst, size_t first, size_t n) {
+    const float* src = zero1_ptr(which, first, n, "zero1_read_state");
+    DeviceGuard g(dev_);
+    if (n) HIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipStreamSynchronize(stream_));
+  }
+
+  // The ZeRO-1 step on the native wire: scale x the sum over ranks of vectors [v0, v1) of their bf16 windows is
+  // the gradient of state floats [0, 8 (v1 - v0)); AdamW with `hyper` (the host form's eight: lr, beta1, beta2,
+  // eps, weight_decay, grad_scale, bias_c1, bias_c2) updates them, and the new bf16 weights go to vectors
+  // [v0, v1) of every rank's out, in reduce_push's order.  One launch; ranges of one epoch must not overlap.
+  void reduce_adamw_push(size_t v0, size_t v1, float scale, const std::array<float, 8>& hyper) {
+    need_peers();
+    if (v0 > v1 || v1 > cap_ / 16) throw std::invalid_argument("reduce_adamw_push: vectors past the end of the window");
+    if (8 * (v1 - v0) > zero1_n_) throw std::invalid_argument("reduce_adamw_push: more vectors than zero1_alloc made state for");
+    if (v0 == v1) return;
+    const int grid = peer_reduce_grid(cus_, blocks_per_cu_, share_, v1 - v0);
+    DeviceGuard g(dev_);
+    launch_peer_reduce_adamw_push(windows_, peer_push_dsts(outs_, rank_), world_, v0, v1, scale, zero1_state(0), zero1_state(1),
+                                  zero1_state(2), zero1_hyper(hyper), grid, stream_);
+    ++launches_;
+  }
+
+  // The same step on the fp8 wire: blocks [b0, b1) of every rank's packed buffer, state floats
+  // [0, 32 (b1 - b0)), the weights to blocks [b0, b1) of every rank's out.
+  void reduce_q8_adamw_push(size_t b0, size_t b1, float scale, const std::array<float, 8>& hyper) {
+    need_q8();
+    if (b0 > b1 || b1 > max_blocks()) throw std::invalid_argument("reduce_q8_adamw_push: blocks past the end of the packed buffer");
+    if (kQ8Block * (b1 - b0) > zero1_n_) throw std::invalid_argument("reduce_q8_adamw_push: more blocks than zero1_alloc made state for");
+    if (b0 == b1) return;
+    const int grid = peer_reduce_grid(cus_, blocks_per_cu_, share_, 2 * (b1 - b0));
+    DeviceGuard g(dev_);
+    launch_peer_q8_sum_adamw_push(packeds_, peer_push_dsts(outs_, rank_), world_, q8_exp_vec(max_blocks()), b0, b1, scale, zero1_state(0),
+                                  zero1_state(1), zero1_state(2), zero1_hyper(hyper), grid, stream_);
+    ++launches_;
   }
 
   // Blocks [b0, b1) of this rank's out (whole blocks of `out_dtype`) = scale x the sum over ranks of the
@@ -373,6 +446,17 @@ class PeerRank {
     HIP_CHECK(hipMemsetAsync(residual_->p, 0, 2 * cap_, stream_));
   }
 
+  float* zero1_state(int which) const { return static_cast<float*>(zero1_->p) + (size_t)which * zero1_n_; }
+  float* zero1_ptr(int which, size_t first, size_t n, const char* what) const {
+    live();
+    if (which < 0 || which > 2) throw std::invalid_argument(std::string(what) + ": which is 0 (master), 1 (m) or 2 (v)");
+    if (first > zero1_n_ || n > zero1_n_ - first) throw std::invalid_argument(std::string(what) + ": past the end of the state");
+    return zero1_ ? zero1_state(which) + first : nullptr;
+  }
+  static gtk_adamw::Hyper zero1_hyper(const std::array<float, 8>& a) {
+    return gtk_adamw::Hyper{a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7]};
+  }
+
   static void check_allocation(uintptr_t addr, int dev, size_t bytes) {
     void* p = reinterpret_cast<void*>(addr);
     hipPointerAttribute_t attr{};
@@ -414,12 +498,16 @@ class PeerRank {
     packed_.reset();
     packed_out_.reset();
     residual_.reset();
+    zero1_.reset();
+    zero1_n_ = 0;
   }
 
   int dev_, rank_, world_;
   size_t cap_;
   int blocks_per_cu_, cus_ = 1, share_ = 1;
   std::unique_ptr<DevBuf> window_, out_, packed_, packed_out_, residual_;
+  std::unique_ptr<DevBuf> zero1_;  // master, m and v, zero1_n_ floats each, in that order
+  size_t zero1_n_ = 0;
   hipStream_t stream_ = nullptr;
   SrcSet windows_{}, packeds_{};
   std::vector<u32x4*> outs_;  // mutable: a push stores into every rank's out
@@ -474,6 +562,32 @@ void bind_peer_rank(py::module_& m) {
            py::arg("scale") = 1.0f, nogil())
       .def("reduce_q8_push", &PeerRank::reduce_q8_push, py::arg("b0"), py::arg("b1"), py::arg("out_dtype"), py::arg("scale") = 1.0f,
            nogil())
+      .def("zero1_alloc", &PeerRank::zero1_alloc, py::arg("n_elems"), nogil())
+      .def("zero1_write_state",
+           [](PeerRank& r, int which, const py::array_t<float, py::array::c_style | py::array::forcecast>& a, size_t first) {
+             const float* p = a.data();
+             const size_t n = (size_t)a.size();
+             py::gil_scoped_release nogil;
+             r.zero1_write_state(which, p, first, n);
+           },
+           py::arg("which"), py::arg("floats"), py::arg("first") = 0)
+      .def("zero1_read_state",
+           [](PeerRank& r, int which, size_t first, size_t n) {
+             if (r.released()) throw std::runtime_error("the PeerRank is released");
+             if (first > r.zero1_elems() || n > r.zero1_elems() - first)
+               throw std::invalid_argument("zero1_read_state: past the end of the state");
+             py::array_t<float> a((py::ssize_t)n);
+             float* p = a.mutable_data();
+             {
+               py::gil_scoped_release nogil;
+               r.zero1_read_state(which, p, first, n);
+             }
+             return a;
+           },
+           py::arg("which"), py::arg("first"), py::arg("n"))
+      .def("reduce_adamw_push", &PeerRank::reduce_adamw_push, py::arg("v0"), py::arg("v1"), py::arg("scale"), py::arg("hyper"), nogil())
+      .def("reduce_q8_adamw_push", &PeerRank::reduce_q8_adamw_push, py::arg("b0"), py::arg("b1"), py::arg("scale"), py::arg("hyper"),
+           nogil())
       .def("repack_q8", &PeerRank::repack_q8, py::arg("b0"), py::arg("b1"), py::arg("scale") = 1.0f, nogil())
       .def("unpack_q8", &PeerRank::unpack_q8, py::arg("slices"), py::arg("out_dtype"), nogil())
       .def("gather", &PeerRank::gather, py::arg("slices"), nogil())
@@ -508,6 +622,7 @@ void bind_peer_rank(py::module_& m) {
       .def_property_readonly("capacity_bytes", &PeerRank::capacity_bytes)
       .def_property_readonly("packed_bytes", &PeerRank::packed_bytes)
       .def_property_readonly("residual_bytes", &PeerRank::residual_bytes)
+      .def_property_readonly("zero1_bytes", &PeerRank::zero1_bytes)
       .def_property_readonly("released", &PeerRank::released);
 }
 

@@ -42,6 +42,7 @@
 #include "peer_driver.h"     // K7 launch plan, PeerAllreduce and its entry points
 #include "peer_q8.h"         // K7 fp8 wire: block-scaled e4m3 quantize, sum, repack and unpack kernels
 #include "peer_rank.h"       // one rank of the peer communicator's device backend
+#include "peer_zero1.h"      // K7 ZeRO-1 step: the push reduce with the AdamW update as its epilogue
 #include "probe_common.h"    // geometry, SrcSet, pattern fill and verifier, guards, grids, timers
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));

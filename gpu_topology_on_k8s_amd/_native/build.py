@@ -120,6 +120,7 @@ class Target:
 def targets() -> List[Target]:
     rocm_lib = str(ROCM / "lib")
     stream_copy = CSRC / "common" / "stream_copy.h"  # the copy body the probe and the one-rank all-reduce share
+    adamw_update = CSRC / "common" / "adamw_update.h"  # the AdamW update body the optimizer and the probe's ZeRO-1 step share
     return [
         Target("_topo", [CSRC / "topo" / "topo_reader.cpp"], "gxx", HERE / f"_topo{EXT}", ["-ldl"]),
         # host-only sanitizer build of the sysfs reader; run by tests/test_topo_reader_asan.py
@@ -135,8 +136,8 @@ def targets() -> List[Target]:
                HERE / "bin" / "engine_selftest", ["-g", "-O1", "-fsanitize=address,undefined", "-fno-omit-frame-pointer"],
                deps=[CSRC / "placement" / "engine.h"], pybind=False, shared=False),
         Target("_probe", [CSRC / "probe" / "probe.hip"], "hipcc", HERE / f"_probe{EXT}",
-               deps=[stream_copy] + [CSRC / "probe" / h for h in ("probe_common.h", "peer_allreduce.h", "peer_q8.h", "peer_driver.h",
-                                                                  "peer_rank.h", "chase_latency.h")]),
+               deps=[stream_copy, adamw_update] + [CSRC / "probe" / h for h in ("probe_common.h", "peer_allreduce.h", "peer_q8.h", "peer_driver.h",
+                                                                                "peer_rank.h", "peer_zero1.h", "chase_latency.h")]),
         Target("_rccl", [CSRC / "rccl" / "rccl_module.hip"], "hipcc", HERE / f"_rccl{EXT}",
                [f"-L{rocm_lib}", "-lrccl", f"-Wl,-rpath,{rocm_lib}"],
                deps=[CSRC / "rccl" / "rccl_core.h", CSRC / "rccl" / "self_copy.h", stream_copy]),
@@ -172,7 +173,7 @@ def targets() -> List[Target]:
         # accumulators are pinned to AGPRs by their asm constraints).  The other kernels of the file fit
         # 256 VGPRs and select that form anyway.
         Target("_fused", sorted((CSRC / "ops").glob("*.hip")), "hipcc", HERE / f"_fused{EXT}",
-               deps=sorted((CSRC / "ops").glob("*.h")), pybind=True, torch=True,
+               deps=sorted((CSRC / "ops").glob("*.h")) + [adamw_update], pybind=True, torch=True,
                src_flags={"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}),
     ]
 

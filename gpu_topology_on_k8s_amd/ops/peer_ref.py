@@ -21,6 +21,10 @@ Error feedback (:func:`q8_quantize_ef_ref`, :func:`allreduce_q8_ef_ref`, :func:`
 sender adds what its last packing dropped, a float32 *residual* per element, to what it packs next, so over
 any number of calls the sum of what it sent differs from the sum of what it was given by the last residual
 alone.
+
+The ZeRO-1 step (``csrc/probe/peer_zero1.h``): :func:`adamw_ref` is the AdamW update body of
+``csrc/common/adamw_update.h`` in numpy, and :func:`zero1_step_ref` is a whole step, the reduce-scatter's fp32
+mean of every rank's slice fed to that update and the new bf16 weights of all slices side by side.
 """
 from __future__ import annotations
 
@@ -31,7 +35,7 @@ import numpy as np
 __all__ = ["ELEM", "peer_slices", "bf16_round", "bf16_to_f32", "bits", "out_dtype_of", "allreduce_ref", "reduce_scatter_ref",
            "is_nan_bits", "mismatches", "Q8_BLOCK", "Q8_EXP_MIN", "Q8_EXP_MAX", "q8_blocks", "q8_slices", "q8_quantize_ref", "q8_dequantize_ref",
            "allreduce_q8_ref", "reduce_scatter_q8_ref", "allreduce_q8x2_ref", "q8_quantize_ef_ref", "allreduce_q8_ef_ref",
-           "reduce_scatter_q8_ef_ref"]
+           "reduce_scatter_q8_ef_ref", "adamw_ref", "zero1_slices", "zero1_step_ref"]
 
 ELEM = {"bf16": 2, "fp32": 4}  # bytes per element
 
@@ -330,3 +334,80 @@ def reduce_scatter_q8_ef_ref(inputs: Sequence[np.ndarray], residuals: Sequence[n
     full, new = allreduce_q8_ef_ref(inputs, residuals, dtype, out_dtype, scale)
     count = int(full.shape[0])
     return [full[min(count, a * Q8_BLOCK):min(count, b * Q8_BLOCK)] for a, b in q8_slices(q8_blocks(count), len(inputs))], new
+
+
+# -- the ZeRO-1 step ------------------------------------------------------------------------------
+def adamw_ref(p: np.ndarray, m: np.ndarray, v: np.ndarray, g: np.ndarray, hyper: Sequence[float]):
+    """One AdamW update (decoupled weight decay) of float32 master ``p``, ``m`` and ``v`` with the float32
+    gradient ``g``: ``(p, m, v, w)``, new arrays, ``w`` the bf16 bit patterns of the new master.
+
+    ``hyper`` is the kernels' host form, eight values taken as float32: ``lr, beta1, beta2, eps, weight_decay,
+    grad_scale, bias_c1, bias_c2`` with ``bias_c = 1 - beta^t``.  Every operation is one float32 operation, in
+    the order of ``adam8_update`` (``csrc/common/adamw_update.h``)::
+
+        gr = g * grad_scale
+        m  = beta1 * m + (1 - beta1) * gr
+        v  = beta2 * v + ((1 - beta2) * gr) * gr
+        p  = p - lr * ((m / bias_c1) / (sqrt(v / bias_c2) + eps) + weight_decay * p)
+
+    The kernel may fuse a multiply into the add that follows it, so it matches this to a few units in the last
+    place, not bit for bit; with ``beta1 = beta2 = 0`` the new ``m`` is ``gr`` and the new ``v`` is ``gr * gr``
+    rounded once, fused or not.  A NaN or an Inf in ``g`` reaches its own element alone."""
+    lr, b1, b2, eps, wd, gs, bc1, bc2 = (np.float32(x) for x in hyper)
+    one = np.float32(1)
+    p, m, v, g = (np.ascontiguousarray(a, dtype=np.float32) for a in (p, m, v, g))
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore", under="ignore"):  # Inf and NaN are results here
+        gr = g * gs
+        m = b1 * m + (one - b1) * gr
+        v = b2 * v + (one - b2) * gr * gr
+        upd = (m / bc1) / (np.sqrt(v / bc2) + eps)
+        p = p - lr * (upd + wd * p)
+    assert p.dtype == m.dtype == v.dtype == np.float32
+    return p, m, v, bf16_round(p)
+
+
+def zero1_slices(count: int, k: int, wire: Optional[str] = None) -> List[Tuple[int, int]]:
+    """``[first, end)`` in elements of each of ``k`` ranks' slice of ``count`` parameters, in whole units of the
+    wire, not clipped to the count: vectors of 8 bf16 cut by :func:`peer_slices` on the native wire, blocks of 32
+    cut by :func:`q8_slices` on ``"fp8"``.  A rank's optimizer state has ``end - first`` elements."""
+    if wire == "fp8":
+        return [(a * Q8_BLOCK, b * Q8_BLOCK) for a, b in q8_slices(q8_blocks(count), k)]
+    if wire not in (None, "native"):
+        raise ValueError(f'wire must be None, "native" or "fp8", got {wire!r}')
+    return [(8 * a, 8 * b) for a, b in peer_slices(-(-int(count) // 8), k)]
+
+
+def zero1_step_ref(inputs: Sequence[np.ndarray], states: Sequence[Tuple[np.ndarray, np.ndarray, np.ndarray]], dtype: str, scale: float,
+                   hyper: Sequence[float], wire: Optional[str] = None, residuals: Optional[List[np.ndarray]] = None):
+    """One ZeRO-1 step: ``(new_states, weights)``.
+
+    ``inputs`` are the ranks' gradients (``dtype`` must be ``"bf16"``: bit patterns, ``count`` each), ``states[r]``
+    rank r's float32 ``(master, m, v)`` of its slice of :func:`zero1_slices`, padding included.  Rank r's gradient is
+    its piece of :func:`reduce_scatter_ref` with an fp32 output (``wire="fp8"``: of :func:`reduce_scatter_q8_ref`;
+    with ``residuals``, every rank's error-feedback residual, of :func:`reduce_scatter_q8_ef_ref`, and the list is
+    given the residuals after the step), zero in the padding; :func:`adamw_ref` with ``hyper`` updates the
+    slice.  ``weights`` are the ``count`` new bf16 weights every rank's out then holds."""
+    if dtype != "bf16":
+        raise ValueError("the ZeRO-1 step takes bf16 gradients: fp32 windows are refused")
+    k = len(inputs)
+    if len(states) != k:
+        raise ValueError("one state per rank")
+    count = int(np.asarray(inputs[0]).shape[0])
+    plan = zero1_slices(count, k, wire)
+    if residuals is not None:
+        if wire != "fp8":
+            raise ValueError('residuals belong to wire="fp8"')
+        pieces, after = reduce_scatter_q8_ef_ref(inputs, residuals, dtype, "fp32", scale)
+        residuals[:] = after
+    elif wire == "fp8":
+        pieces = reduce_scatter_q8_ref(inputs, dtype, "fp32", scale)
+    else:
+        pieces = reduce_scatter_ref(inputs, dtype, "fp32", scale)
+    new, w = [], []
+    for (a, b), piece, (p, m, v) in zip(plan, pieces, states):
+        g = np.zeros(b - a, np.float32)
+        g[:piece.shape[0]] = piece
+        p, m, v, bits16 = adamw_ref(p, m, v, g, hyper)
+        new.append((p, m, v))
+        w.append(bits16)
+    return new, np.concatenate(w)[:count]

@@ -82,6 +82,24 @@ Because the quantize runs before the descriptors are compared, a mismatched feed
 the residual with data that no one summed: when barrier A of a feedback call raises (``PeerCommMismatch``, or a
 timeout), the rank's residual is therefore reset to zero before the exception leaves.
 
+``zero1_step`` is a ZeRO-1 optimizer step as one push (``csrc/probe/peer_zero1.h``).  The optimizer state is split
+over the ranks: rank r keeps the fp32 master weights, m and v of slice r of the parameters (:meth:`PeerComm.zero1_init`).
+Every rank's window holds the bf16 gradient of all parameters; rank r sums slice r of every window as a push does,
+applies AdamW to its state with that sum as the gradient (``ops/peer_ref.zero1_step_ref``) and stores the new bf16
+weights into slice r of **every** rank's out:
+
+    (quantize -> synchronize ->) barrier A -> fused launch -> synchronize -> barrier B
+
+one launch and two barriers, where ``reduce_scatter``, an AdamW launch and ``all_gather`` take three launches and four,
+write and re-read the fp32 gradient shard and read the new weights once more to gather them.  The hazards are the
+push's: out is written by peers between barrier A and barrier B, exactly as in a push, every reader of it having
+synchronised before it entered barrier A and the slices of one step never overlapping.  The optimizer state is
+touched by its owner alone, in that launch: like the residual it is never published and no peer ever opens it, so it
+adds no hazard.  A rank whose slice is empty launches nothing and still takes both barriers.  On ``wire="fp8"`` the
+quantize stays before barrier A, with or without error feedback, and the residual is reset when barrier A raises, as
+for every feedback call.  All eight hyper-parameters travel in the call's descriptor, so ranks that disagree on one
+of them get ``PeerCommMismatch`` before any rank has touched a peer.
+
 Two backends exist, both with the ranks as threads of one process:
 
 ``backend="host"``: numpy buffers, the phases computed by ``ops/peer_ref.py``, every access logged; two
@@ -113,10 +131,10 @@ import numpy as np
 
 from ..ops.peer_ref import (ELEM as _ELEM, Q8_BLOCK, allreduce_q8_ef_ref, allreduce_q8_ref, allreduce_q8x2_ref, allreduce_ref, bf16_round,
                             bits as _bits, out_dtype_of as _out_dtype, peer_slices, q8_blocks, q8_dequantize_ref, q8_quantize_ef_ref,
-                            q8_quantize_ref, q8_slices, reduce_scatter_q8_ef_ref)
+                            q8_quantize_ref, q8_slices, reduce_scatter_q8_ef_ref, adamw_ref, bf16_to_f32, zero1_slices)
 
 __all__ = ["PeerComm", "PeerCommError", "PeerCommTimeout", "PeerCommMismatch", "HostFabric", "MemoryStore",
-           "selftest_cases", "selftest_cases_q8", "selftest_cases_q8x2", "selftest_cases_ef", "selftest_cases_push", "case_input", "run_case", "run_thread_ranks", "selftest", "thread_sweep", "timed_all_reduce", "parked_bytes",
+           "selftest_cases", "selftest_cases_q8", "selftest_cases_q8x2", "selftest_cases_ef", "selftest_cases_push", "case_input", "run_case", "run_thread_ranks", "selftest", "thread_sweep", "timed_all_reduce", "parked_bytes", "zero1_hyper",
            "MAX_WORLD"]
 
 MAX_WORLD = 16  # kMaxSrc of csrc/probe/probe_common.h
@@ -214,6 +232,7 @@ class HostFabric:
         self.packed = [np.zeros(_packed_bytes(capacity_bytes), np.uint8) for _ in range(world)]
         self.packed_out = [np.zeros(_packed_bytes(capacity_bytes), np.uint8) for _ in range(world)]
         self.residual: List[Optional[np.ndarray]] = [None] * world  # capacity_bytes // 2 floats each, once made
+        self.zero1: List[Optional[np.ndarray]] = [None] * world  # a rank's ZeRO-1 state, float32 [3, n]: master, m, v
         self.lock = threading.Lock()
         #: (accessor, owner, buffer, v0, v1, "r" | "w", the accessor's barrier count)
         self.log: List[Tuple[int, int, str, int, int, str, int]] = []
@@ -241,7 +260,8 @@ class HostFabric:
 
 
 class _HostBackend:
-    """One rank's phase calls (reduce, reduce_push, quantize, reduce_q8, reduce_q8_push, repack_q8, unpack_q8, gather, gather_windows, host copies) on a
+    """One rank's phase calls (reduce, reduce_push, quantize, reduce_q8, reduce_q8_push, repack_q8, unpack_q8, gather, gather_windows,
+    reduce_adamw_push, reduce_q8_adamw_push, host copies) on a
     :class:`HostFabric`, computed by ``ops/peer_ref.py``."""
 
     def __init__(self, rank: int, world: int, fabric: HostFabric):
@@ -376,6 +396,61 @@ class _HostBackend:
             xs.append(q8_dequantize_ref(c.copy(), x8.astype(np.int32) - _Q8_BIAS))
         return allreduce_ref(xs, "fp32", "fp32", scale)
 
+    # -- the ZeRO-1 step: the state is this rank's own, logged under "zero1" like the residual ------------
+    def zero1_alloc(self, n_elems: int) -> None:
+        if n_elems % 8 or n_elems > self.f.capacity_bytes // 2:
+            raise ValueError("zero1_alloc: whole vectors of 8 elements, at most a window full of bf16")
+        self.f.zero1[self.rank] = np.zeros((3, n_elems), np.float32) if n_elems else None
+
+    def _zero1(self, which: int, first: int, end: int, mode: str) -> np.ndarray:
+        st = self.f.zero1[self.rank]
+        n = 0 if st is None else st.shape[1]
+        if which not in (0, 1, 2) or first < 0 or end < first or end > n:
+            raise ValueError("zero1 state: which is 0 (master), 1 (m) or 2 (v), and the range lies inside the state")
+        if st is None:
+            return np.zeros(0, np.float32)
+        self.f.access(self.rank, self.rank, "zero1", (which * n + first) * 4 // 16, -(-(which * n + end) * 4 // 16), mode, self.epoch)
+        return st[which, first:end]
+
+    @property
+    def zero1_bytes(self) -> int:
+        return 0 if self.f.zero1[self.rank] is None else int(self.f.zero1[self.rank].nbytes)
+
+    def zero1_write_state(self, which: int, floats: np.ndarray, first: int = 0) -> None:
+        a = np.ascontiguousarray(floats, dtype=np.float32).reshape(-1)
+        self._zero1(which, first, first + a.size, "w")[:] = a
+
+    def zero1_read_state(self, which: int, first: int, n: int) -> np.ndarray:
+        return self._zero1(which, first, first + n, "r").copy()
+
+    def _adamw_push(self, g: np.ndarray, hyper: Sequence[float], v0: int, v1: int) -> None:
+        """AdamW on state floats ``[0, g.size)`` with the gradient ``g``; the new weights to vectors ``[v0, v1)`` of
+        every owner's out, this rank's first."""
+        new = adamw_ref(*(self._zero1(a, 0, g.size, "r") for a in range(3)), g, hyper)
+        for a in range(3):
+            self._zero1(a, 0, g.size, "w")[:] = new[a]
+        for j in range(self.world):
+            self._out((self.rank + j) % self.world, v0, v1, "w")[:] = new[3].view(np.uint8)
+
+    def reduce_adamw_push(self, v0: int, v1: int, scale: float, hyper: Sequence[float]) -> None:
+        if v0 > v1 or v1 * 16 > self.f.capacity_bytes or 8 * (v1 - v0) > self.zero1_bytes // 12:
+            raise ValueError("reduce_adamw_push: vectors past the end of the window or of the state")
+        if v0 == v1:
+            return
+        with self.f.lock:
+            self.f.launches += 1
+        xs = [self._win(p, v0, v1, "r").view(np.uint16).copy() for p in range(self.world)]
+        self._adamw_push(allreduce_ref(xs, "bf16", "fp32", scale), hyper, v0, v1)
+
+    def reduce_q8_adamw_push(self, b0: int, b1: int, scale: float, hyper: Sequence[float]) -> None:
+        if b0 > b1 or b1 > _max_blocks(self.f.capacity_bytes) or Q8_BLOCK * (b1 - b0) > self.zero1_bytes // 12:
+            raise ValueError("reduce_q8_adamw_push: blocks past the end of the packed buffer or of the state")
+        if b0 == b1:
+            return
+        with self.f.lock:
+            self.f.launches += 1
+        self._adamw_push(self._sum_q8(b0, b1, scale), hyper, b0 * Q8_BLOCK * 2 // 16, b1 * Q8_BLOCK * 2 // 16)
+
     def repack_q8(self, b0: int, b1: int, scale: float) -> None:
         if b0 > b1 or b1 > _max_blocks(self.f.capacity_bytes):
             raise ValueError("repack_q8: blocks past the end of the packed buffers")
@@ -435,9 +510,10 @@ _PARKED_LOCK = threading.Lock()
 def parked_bytes() -> int:
     """Device memory held by ranks of broken ``backend="device"`` communicators that were closed but
     not freed, in bytes (a window, an out of twice its size, two packed buffers and, where the rank had asked
-    for error feedback, its residual per rank)."""
+    for error feedback, its residual, and where it had a ZeRO-1 state, that, per rank)."""
     with _PARKED_LOCK:
-        return sum(3 * int(r.capacity_bytes) + 2 * int(r.packed_bytes) + int(getattr(r, "residual_bytes", 0)) for r in _PARKED)
+        return sum(3 * int(r.capacity_bytes) + 2 * int(r.packed_bytes) + int(getattr(r, "residual_bytes", 0))
+                   + int(getattr(r, "zero1_bytes", 0)) for r in _PARKED)
 
 
 class _DeviceBackend:
@@ -513,6 +589,25 @@ class _DeviceBackend:
     def repack_q8(self, b0: int, b1: int, scale: float) -> None:
         self.r.repack_q8(b0, b1, scale)
 
+    def zero1_alloc(self, n_elems: int) -> None:
+        self.r.zero1_alloc(n_elems)
+
+    @property
+    def zero1_bytes(self) -> int:
+        return int(self.r.zero1_bytes)
+
+    def zero1_write_state(self, which: int, floats: np.ndarray, first: int = 0) -> None:
+        self.r.zero1_write_state(which, np.ascontiguousarray(floats, dtype=np.float32).reshape(-1), first)
+
+    def zero1_read_state(self, which: int, first: int, n: int) -> np.ndarray:
+        return self.r.zero1_read_state(which, first, n)
+
+    def reduce_adamw_push(self, v0: int, v1: int, scale: float, hyper: Sequence[float]) -> None:
+        self.r.reduce_adamw_push(v0, v1, scale, [float(x) for x in hyper])
+
+    def reduce_q8_adamw_push(self, b0: int, b1: int, scale: float, hyper: Sequence[float]) -> None:
+        self.r.reduce_q8_adamw_push(b0, b1, scale, [float(x) for x in hyper])
+
     def unpack_q8(self, slices: Sequence[Tuple[int, int]], out_dtype: str) -> None:
         self.r.unpack_q8([(int(a), int(b)) for a, b in slices], out_dtype)
 
@@ -528,6 +623,14 @@ class _DeviceBackend:
     def read_host(self, first: int, n: int, dtype: str) -> np.ndarray:
         e = _ELEM[dtype]
         return self.r.read_host(first * e, n * e).view(_NP[dtype])
+
+
+def zero1_hyper(lr: float, beta1: float, beta2: float, eps: float, weight_decay: float, step: int, grad_scale: float = 1.0) -> List[float]:
+    """The AdamW kernels' host form of the hyper-parameters of step ``step`` (from 1), as ``models.optim.FlatAdamW`` makes it:
+    ``[lr, beta1, beta2, eps, weight_decay, grad_scale, 1 - beta1^step, 1 - beta2^step]``, each rounded to float32."""
+    if step < 1:
+        raise ValueError("step >= 1")
+    return [float(x) for x in np.array([lr, beta1, beta2, eps, weight_decay, grad_scale, 1 - beta1 ** step, 1 - beta2 ** step], np.float32)]
 
 
 class PeerComm:
@@ -563,6 +666,7 @@ class PeerComm:
         self.broken = False
         self._closed = False
         self._stale: List[List[str]] = [[], []]  # store keys to delete after the next barrier / the one after
+        self._zero1: Optional[Tuple[int, Optional[str]]] = None  # (count, wire) of zero1_init
         if backend not in BACKENDS:
             raise ValueError(f'backend must be "host" or "device", got {backend!r}')
         self.backend = backend
@@ -679,8 +783,8 @@ class PeerComm:
     def _leave(self) -> None:
         """Barrier B.  One-shot, reduce-scatter and all-gather: nobody is still reading any window, so
         the caller may refill its own.  Two-shot: every slice of out that phase 2 is about to read is
-        final (and, again, no window is still being read).  Push: every rank's stores into every out are
-        complete, so each rank may read its own."""
+        final (and, again, no window is still being read).  Push and ZeRO-1 step: every rank's stores into
+        every out are complete, so each rank may read its own."""
         self._b.synchronize()
         self._barrier()
 
@@ -812,6 +916,81 @@ class PeerComm:
         self._b.gather_windows(n)
         self._leave()
         return n
+
+    # -- the ZeRO-1 step -----------------------------------------------------------------------
+    def zero1_init(self, count: int, weights: np.ndarray, wire: Optional[str] = None,
+                   state: Optional[Sequence[np.ndarray]] = None) -> Tuple[int, int]:
+        """Makes this rank's optimizer state for ``count`` parameters: slice ``self.rank`` of ``zero1_slices`` (whole
+        vectors of ``peer_slices`` on the native wire, whole blocks of ``q8_slices`` on ``wire="fp8"``).  ``weights``
+        are the bf16 bit patterns (uint16) of all ``count`` parameters: the rank widens its own slice into its fp32
+        master and zeroes m and v.  ``state``, what :meth:`zero1_state` returned, restores master, m and v instead.
+        Local: no barrier, no peer.  Returns the ``(first, n)`` parameters this rank owns (``n`` may be 0).
+        ``ValueError``: ``wire="fp8x2"`` (a push has no gather phase to pack), a count past the window."""
+        self._check()
+        if wire not in (None, "native", "fp8"):
+            raise ValueError(f'zero1: wire must be None, "native" or "fp8", got {wire!r}: a push has no gather phase for "fp8x2" to pack')
+        if count < 1:
+            raise ValueError("count >= 1")
+        units = q8_blocks(count) * Q8_BLOCK if wire == "fp8" else _n_vec(count, "bf16") * 8
+        if units * 2 > self.capacity_bytes:
+            raise ValueError(f"{count} bf16 elements, in whole units of the wire, exceed the window of {self.capacity_bytes} bytes")
+        w = np.ascontiguousarray(weights)
+        if w.dtype != np.uint16 or w.shape != (count,):
+            raise ValueError("weights: the uint16 bit patterns of all count bf16 parameters")
+        a, b = zero1_slices(count, self.world, wire)[self.rank]
+        n = b - a
+        if state is None:
+            master = np.zeros(n, np.float32)
+            mine = bf16_to_f32(w[a:min(b, count)])
+            master[:mine.size] = mine
+            new = (master, None, None)  # zero1_alloc zeroes m and v
+        else:
+            new = tuple(np.ascontiguousarray(x, dtype=np.float32) for x in state)
+            if len(new) != 3 or any(x.shape != (n,) for x in new):
+                raise ValueError(f"state: master, m and v, {n} float32 each, as zero1_state returns them")
+        self._zero1 = None
+        self._b.zero1_alloc(n)
+        for which, x in enumerate(new):
+            if x is not None and n:
+                self._b.zero1_write_state(which, x, 0)
+        self._zero1 = (int(count), wire)
+        first, end = min(count, a), min(count, b)
+        return first, end - first
+
+    def zero1_state(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """This rank's master, m and v as float32 host arrays, the slice's padding included."""
+        self._check()
+        if self._zero1 is None:
+            raise ValueError("zero1_state: zero1_init first")
+        a, b = zero1_slices(self._zero1[0], self.world, self._zero1[1])[self.rank]
+        return tuple(self._b.zero1_read_state(which, 0, b - a) for which in range(3))
+
+    def zero1_step(self, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float, step: int, grad_scale: float = 1.0,
+                   scale: Optional[float] = None, error_feedback: bool = False) -> None:
+        """One AdamW step of the parameters of :meth:`zero1_init`.  Every rank's window holds its bf16 gradient in
+        ``[0, count)``; the gradient of the update is ``scale`` (default ``1 / world``: the mean) x the sum over ranks,
+        times ``grad_scale`` (a clipping factor the caller computed).  ``step`` is the number of this step, from 1; the
+        bias corrections ``1 - beta^step`` are computed here, on the host.  Afterwards out[0, count) of **every** rank
+        holds the same new bf16 weights and this rank's state is advanced.  One launch, two barriers.
+        ``ValueError``, before any barrier or launch: no :meth:`zero1_init`; ``error_feedback`` on the native wire."""
+        self._check()
+        if self._zero1 is None:
+            raise ValueError("zero1_step: zero1_init first")
+        count, wire = self._zero1
+        if error_feedback and wire != "fp8":
+            raise ValueError('error_feedback=True belongs to wire="fp8": the native wire drops nothing')
+        scale = float(np.float32(1.0 / self.world if scale is None else scale))
+        hyper = zero1_hyper(lr, beta1, beta2, eps, weight_decay, step, grad_scale)
+        desc = {"op": "zero1_step", "count": count, "wire": wire or "native", "scale": scale, "ef": bool(error_feedback), "hyper": hyper}
+        if wire == "fp8":
+            n = q8_blocks(count)
+            self._b.quantize(0, n, count, "bf16", error_feedback)
+            self._enter(desc)
+            self._b.reduce_q8_adamw_push(*q8_slices(n, self.world)[self.rank], scale, hyper)
+        else:
+            self._enter(desc)
+            self._b.reduce_adamw_push(*peer_slices(_n_vec(count, "bf16"), self.world)[self.rank], scale, hyper)
+        self._leave()  # every rank's stores into every out are complete
 
     # -- data movement ------------------------------------------------------------------------
     def write(self, array: np.ndarray, first_byte: int = 0) -> None:
