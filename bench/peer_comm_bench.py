@@ -35,6 +35,8 @@ launches and four barriers.  The two are alternated ``--reps`` times in one proc
 the fp8 wire, the quicker repetition of each reported; the number of interest is how far the fused step exceeds the bare
 communication, if at all.  After the timed steps every rank's weights must be rank 0's and its own master rounded once,
 and up to ``--check-max-mib`` the first step is compared with the host reference at the GPU tests' tolerances.
+``--clip-norm C`` alternates the clipped step (``zero1_step(clip_norm=C)``: two launches and three barriers) with those
+two, checks its first step and its norm against the reference, and reports the host time each step spends in barriers.
 """
 import argparse
 import json
@@ -167,8 +169,10 @@ def markdown_push(res) -> str:
 ZERO1_HP = dict(lr=1e-3, beta1=0.9, beta2=0.95, eps=1e-8, weight_decay=0.1)
 
 
-def measure_zero1(devs, sizes, iters, warmup, reps, check_max_bytes):
-    """Host seconds per call of the fused ZeRO-1 step and of reduce_scatter (fp32 out) + all_gather (count / k bf16), alternated."""
+def measure_zero1(devs, sizes, iters, warmup, reps, check_max_bytes, clip_norm=None):
+    """Host seconds per call of the fused ZeRO-1 step and of reduce_scatter (fp32 out) + all_gather (count / k bf16), alternated;
+    with ``clip_norm`` the clipped step (two launches, three barriers) is alternated with them, and the host seconds each
+    step spends inside its barriers are reported next to its time."""
     import time
 
     from gpu_topology_on_k8s_amd.ops.peer_ref import bf16_round, bf16_to_f32, zero1_slices, zero1_step_ref
@@ -190,12 +194,12 @@ def measure_zero1(devs, sizes, iters, warmup, reps, check_max_bytes):
         for i in range(warmup):
             call(i)
         comm.barrier()
-        t0 = time.perf_counter()
+        in_barriers, t0 = comm.barrier_s, time.perf_counter()
         for i in range(iters):
             call(warmup + i)
-        secs = (time.perf_counter() - t0) / iters
+        secs, waited = (time.perf_counter() - t0) / iters, (comm.barrier_s - in_barriers) / iters
         comm.barrier()  # no rank goes on to check its result, holding the interpreter, while another still reads its clock
-        return secs
+        return secs, waited
 
     def body(comm):
         rows = []
@@ -217,8 +221,21 @@ def measure_zero1(devs, sizes, iters, warmup, reps, check_max_bytes):
                     wrong = sum(int(np.count_nonzero(~np.isclose(g, r, rtol=1e-5, atol=tol)))
                                 for g, r, tol in zip(comm.zero1_state(), ref[0][comm.rank], (1e-6, 1e-6, 1e-7)))
                     comm.zero1_init(count, w0, wire)
+                clip_wrong, norm_rel = 0, 0.0
+                if checked and clip_norm is not None:  # the first clipped step against the host reference, its norm too
+                    ref = once.get(("clip", count, wire), lambda: zero1_step_ref(xs, start(w0, plan), "bf16", scale, pc.zero1_hyper(step=1, **ZERO1_HP),
+                                                                                  wire, clip_norm=clip_norm), lambda o: o[1] == count)
+                    norm = comm.zero1_step(step=1, clip_norm=clip_norm, **ZERO1_HP)
+                    clip_wrong = sum(int(np.count_nonzero(~np.isclose(g, r, rtol=1e-5, atol=tol)))
+                                     for g, r, tol in zip(comm.zero1_state(), ref[0][comm.rank], (1e-6, 1e-6, 1e-7)))
+                    norm_rel = abs(norm - ref[2]) / ref[2]
+                    comm.zero1_init(count, w0, wire)
                 for r in range(reps):
-                    fused = timed(comm, lambda i: comm.zero1_step(step=i + 1, **ZERO1_HP))
+                    clipped = (0.0, 0.0)
+                    if clip_norm is not None:
+                        clipped = timed(comm, lambda i: comm.zero1_step(step=i + 1, clip_norm=clip_norm, **ZERO1_HP))
+                        comm.zero1_init(count, w0, wire)  # the fused step starts where the clipped one did, and without a stash
+                    fused, fused_waited = timed(comm, lambda i: comm.zero1_step(step=i + 1, **ZERO1_HP))
                     out = comm.read(0, count, "bf16")
                     unrounded = int(np.count_nonzero(out[min(count, a):min(count, b)] != bf16_round(comm.zero1_state()[0])[:max(0, min(count, b) - a)]))
                     comm.barrier()
@@ -228,8 +245,9 @@ def measure_zero1(devs, sizes, iters, warmup, reps, check_max_bytes):
                         comm.all_gather(per, "bf16")
 
                     comm.write(xs[comm.rank])
-                    two = timed(comm, bare)
-                    rows.append((count, wire, r, fused, two, wrong if r == 0 else 0, unrounded, out if r == 0 else None, checked))
+                    two, _ = timed(comm, bare)
+                    rows.append((count, wire, r, fused, two, wrong if r == 0 else 0, unrounded, out if r == 0 else None, checked,
+                                 clipped[0], clipped[1], fused_waited, clip_wrong if r == 0 else 0, norm_rel))
                     comm.zero1_init(count, w0, wire)  # the same trajectory for every repetition
         return rows
 
@@ -248,10 +266,19 @@ def measure_zero1(devs, sizes, iters, warmup, reps, check_max_bytes):
                          "state_outside_tolerance": sum(r[5] for rows in mine for r in rows),
                          "weights_not_the_rounded_master": sum(r[6] for rows in mine for r in rows),
                          "weights_differ_between_ranks": sum(int(np.count_nonzero(rows[0][7] != mine[0][0][7])) for rows in mine)}
+            if clip_norm is not None:
+                clipped = [max(rows[r][9] for rows in mine) * 1e6 for r in range(reps)]
+                best = clipped.index(min(clipped))
+                row[wire].update({"clipped_step_time_us": min(clipped), "clipped_step_time_us_reps": clipped,
+                                  "clipped_over_fused": min(clipped) / min(fused), "clipped_over_bare_communication": min(clipped) / min(two),
+                                  "clipped_step_barrier_us": float(np.mean([rows[best][10] for rows in mine])) * 1e6,  # three barriers, mean over ranks
+                                  "fused_step_barrier_us": float(np.mean([rows[fused.index(min(fused))][11] for rows in mine])) * 1e6,  # two
+                                  "clipped_state_outside_tolerance": sum(r[12] for rows in mine for r in rows),
+                                  "clipped_norm_relative_error": max(r[13] for rows in mine for r in rows)})
         out.append(row)
         print(json.dumps(row), file=sys.stderr, flush=True)
     return {"members": list(devs), "k": k, "distinct_devices": len(set(devs)) == k, "dtype": "bf16", "iters": iters, "warmup": warmup,
-            "reps": reps, "zero1": True, "hyper": ZERO1_HP, "sizes": out}
+            "reps": reps, "zero1": True, "hyper": ZERO1_HP, **({} if clip_norm is None else {"clip_norm": clip_norm}), "sizes": out}
 
 
 ZERO1_CHECKS = ("state_outside_tolerance", "weights_not_the_rounded_master", "weights_differ_between_ranks")
@@ -268,6 +295,18 @@ def markdown_zero1(res) -> str:
             out.append(f"| {r['bytes'] / 2**20:.1f} MiB | {wire} | {a['fused_step_time_us']:.1f} | {a['reduce_scatter_all_gather_time_us']:.1f} "
                        f"| {a['fused_over_bare_communication']:.2f} | {sum(a[c] for c in ZERO1_CHECKS)} |")
     out.append("")
+    if "clip_norm" in res:
+        out += [f"### Clipped ZeRO-1 step (clip_norm = {res['clip_norm']}: two launches, three barriers) against the unclipped fused step and "
+                f"reduce_scatter (fp32 out) + all_gather, members {res['members']} (k = {res['k']})", "",
+                "| gradient per member | wire | clipped us / call | fused us / call | reduce_scatter + all_gather us / call | clipped / fused "
+                "| in barriers, clipped us | in barriers, fused us | failed checks |", "|---|---|---|---|---|---|---|---|---|"]
+        for r in res["sizes"]:
+            for wire in ("native", "fp8"):
+                a = r[wire]
+                out.append(f"| {r['bytes'] / 2**20:.1f} MiB | {wire} | {a['clipped_step_time_us']:.1f} | {a['fused_step_time_us']:.1f} "
+                           f"| {a['reduce_scatter_all_gather_time_us']:.1f} | {a['clipped_over_fused']:.2f} | {a['clipped_step_barrier_us']:.1f} "
+                           f"| {a['fused_step_barrier_us']:.1f} | {a['clipped_state_outside_tolerance']} |")
+        out.append("")
     return "\n".join(out)
 
 
@@ -378,6 +417,8 @@ def main():
     ap.add_argument("--push", action="store_true", help="thread ranks alone: the push all_reduce against the two-shot on the native and the fp8 wire, alternated")
     ap.add_argument("--zero1", action="store_true",
                     help="thread ranks alone: the fused ZeRO-1 step against reduce_scatter (fp32 out) + all_gather, on the native and the fp8 wire, alternated")
+    ap.add_argument("--clip-norm", type=float, default=None,
+                    help="--zero1: also time zero1_step(clip_norm=C), alternated with the unclipped step and the bare communication")
     ap.add_argument("--check-max-mib", type=float, default=64.0, help="--push, --zero1: the largest size whose result is compared with the host reference")
     ap.add_argument("--reps", type=int, default=2, help="alternated repetitions of each measurement")
     ap.add_argument("--out", default="", help="also write the JSON document here")
@@ -388,7 +429,7 @@ def main():
     probe.warmup(groups[0][0], 100.0)
     if a.zero1:
         doc = {"device": probe.device_props(groups[0][0])["name"],
-               "runs": [measure_zero1(g, sizes, a.iters, a.warmup, max(1, a.reps), int(a.check_max_mib * (1 << 20))) for g in groups]}
+               "runs": [measure_zero1(g, sizes, a.iters, a.warmup, max(1, a.reps), int(a.check_max_mib * (1 << 20)), a.clip_norm) for g in groups]}
         text = json.dumps(doc)
         print(text)
         for path, body in ((a.out, text + "\n"), (a.md, "\n".join(markdown_zero1(r) for r in doc["runs"]))):

@@ -11,7 +11,9 @@
 // error feedback also owns a residual (fp32, one value per element of a window full of bf16: twice the capacity),
 // allocated on its first feedback call; it is the rank's alone, never published and no part of open_peers.
 // The same holds for the ZeRO-1 optimizer state (zero1_alloc): master, m and v, fp32, of the rank's slice of the
-// parameters alone, read and written by the rank's own fused step (reduce_adamw_push, reduce_q8_adamw_push).
+// parameters alone, read and written by the rank's own fused step (reduce_adamw_push, reduce_q8_adamw_push), and
+// for the stash of the clipped step (zero1_stash_alloc): the scaled gradient sum that reduce_sqnorm_stash or
+// reduce_q8_sqnorm_stash leaves for adamw_push, with the sum-of-squares partials the host adds up in between.
 // Ranks are threads of one
 // process, so a peer's buffer is reached through its plain device address and, across devices,
 // hipDeviceEnablePeerAccess: no IPC call.  A PeerRank is used by one thread.  Nothing here waits on
@@ -84,7 +86,8 @@ class PeerRank {
   size_t packed_bytes() const { return std::max<size_t>(16, q8_packed_vecs(max_blocks()) * 16); }
   size_t residual_bytes() const { return residual_ ? 2 * cap_ : 0; }  // 0 until the first feedback call
   size_t zero1_elems() const { return zero1_n_; }  // floats of each of master, m and v; 0 until zero1_alloc
-  size_t zero1_bytes() const { return 3 * zero1_n_ * sizeof(float); }
+  size_t stash_elems() const { return stash_ ? zero1_n_ : 0; }  // floats of the clipped step's stash; 0 until zero1_stash_alloc
+  size_t zero1_bytes() const { return (3 * zero1_n_ + stash_elems()) * sizeof(float); }  // the partials, a few KiB, are not counted
   size_t launches() const { return launches_; }
   bool released() const { return released_; }
 
@@ -235,6 +238,7 @@ class PeerRank {
     {
       std::lock_guard<std::mutex> lock(peer_rank_mutex());
       zero1_.reset();
+      stash_.reset();  // the stash has the state's size: the next clipped step makes a new one
       zero1_n_ = 0;
       if (n_elems) zero1_.reset(new DevBuf(dev_, 3 * n_elems * sizeof(float)));
     }
@@ -252,9 +256,10 @@ class PeerRank {
     HIP_CHECK(hipStreamSynchronize(stream_));
   }
 
-  // Floats [first, first + n) of master, m or v to `dst`, after everything on the stream.
+  // Floats [first, first + n) of master, m or v (which = 3: of the stash, once it exists) to `dst`, after
+  // everything on the stream.
   void zero1_read_state(int which, float* dst, size_t first, size_t n) {
-    const float* src = zero1_ptr(which, first, n, "zero1_read_state");
+    const float* src = which == 3 ? stash_ptr(first, n) : zero1_ptr(which, first, n, "zero1_read_state");
     DeviceGuard g(dev_);
     if (n) HIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToHost, stream_));
     HIP_CHECK(hipStreamSynchronize(stream_));
@@ -287,6 +292,67 @@ class PeerRank {
     DeviceGuard g(dev_);
     launch_peer_q8_sum_adamw_push(packeds_, peer_push_dsts(outs_, rank_), world_, q8_exp_vec(max_blocks()), b0, b1, scale, zero1_state(0),
                                   zero1_state(1), zero1_state(2), zero1_hyper(hyper), grid, stream_);
+    ++launches_;
+  }
+
+  // The clipped ZeRO-1 step's stash: one float per float of master, the scaled gradient sum between the step's two
+  // launches, with one sum-of-squares partial per block of the first.  Allocated on first call, zeroed on the
+  // stream; nothing for an empty state.  zero1_alloc frees it.  The caller makes this call outside a barrier epoch.
+  void zero1_stash_alloc() {
+    live();
+    if (stash_ || !zero1_n_) return;
+    DeviceGuard g(dev_);
+    {
+      std::lock_guard<std::mutex> lock(peer_rank_mutex());
+      stash_.reset(new DevBuf(dev_, zero1_n_ * sizeof(float)));
+      if (!parts_) parts_.reset(new DevBuf(dev_, max_grid() * sizeof(float)));
+    }
+    HIP_CHECK(hipMemsetAsync(stash_->p, 0, zero1_n_ * sizeof(float), stream_));
+  }
+
+  // Launch 1 of the clipped step on the native wire: stash floats [0, 8 (v1 - v0)) = scale x the sum over ranks of
+  // vectors [v0, v1) of their bf16 windows.  Returns the sum of their squares: the blocks' fp32 partials, copied to
+  // the host after the launch and added in float64 in index order, so the call synchronises the stream.  An empty
+  // range launches nothing and returns 0.
+  double reduce_sqnorm_stash(size_t v0, size_t v1, float scale) {
+    need_peers();
+    if (v0 > v1 || v1 > cap_ / 16) throw std::invalid_argument("reduce_sqnorm_stash: vectors past the end of the window");
+    if (8 * (v1 - v0) > stash_elems()) throw std::invalid_argument("reduce_sqnorm_stash: more vectors than the stash holds");
+    if (v0 == v1) return 0.0;
+    const int grid = peer_reduce_grid(cus_, blocks_per_cu_, share_, v1 - v0);
+    DeviceGuard g(dev_);
+    launch_peer_reduce_sqnorm_stash(windows_, world_, v0, v1, scale, static_cast<float*>(stash_->p), static_cast<float*>(parts_->p), grid,
+                                    stream_);
+    ++launches_;
+    return sum_parts(grid);
+  }
+
+  // The same on the fp8 wire: blocks [b0, b1) of every rank's packed buffer, stash floats [0, 32 (b1 - b0)).
+  double reduce_q8_sqnorm_stash(size_t b0, size_t b1, float scale) {
+    need_q8();
+    if (b0 > b1 || b1 > max_blocks()) throw std::invalid_argument("reduce_q8_sqnorm_stash: blocks past the end of the packed buffer");
+    if (kQ8Block * (b1 - b0) > stash_elems()) throw std::invalid_argument("reduce_q8_sqnorm_stash: more blocks than the stash holds");
+    if (b0 == b1) return 0.0;
+    const int grid = peer_reduce_grid(cus_, blocks_per_cu_, share_, 2 * (b1 - b0));
+    DeviceGuard g(dev_);
+    launch_peer_q8_sum_sqnorm_stash(packeds_, world_, q8_exp_vec(max_blocks()), b0, b1, scale, static_cast<float*>(stash_->p),
+                                    static_cast<float*>(parts_->p), grid, stream_);
+    ++launches_;
+    return sum_parts(grid);
+  }
+
+  // Launch 2 of the clipped step, either wire: AdamW with `hyper` on state floats [0, 8 (v1 - v0)), the stash as the
+  // gradient, the new bf16 weights to vectors [v0, v1) of every rank's out, in reduce_push's order.  It reads
+  // rank-local memory only.  One launch; ranges of one epoch must not overlap.
+  void adamw_push(size_t v0, size_t v1, const std::array<float, 8>& hyper) {
+    need_peers();
+    if (v0 > v1 || v1 > cap_ / 16) throw std::invalid_argument("adamw_push: vectors past the end of a window's worth of out");
+    if (8 * (v1 - v0) > stash_elems()) throw std::invalid_argument("adamw_push: more vectors than the stash holds");
+    if (v0 == v1) return;
+    const int grid = peer_reduce_grid(cus_, blocks_per_cu_, share_, v1 - v0);
+    DeviceGuard g(dev_);
+    launch_peer_adamw_push(peer_push_dsts(outs_, rank_), world_, v0, v1, static_cast<const float*>(stash_->p), zero1_state(0),
+                           zero1_state(1), zero1_state(2), zero1_hyper(hyper), grid, stream_);
     ++launches_;
   }
 
@@ -453,6 +519,21 @@ class PeerRank {
     if (first > zero1_n_ || n > zero1_n_ - first) throw std::invalid_argument(std::string(what) + ": past the end of the state");
     return zero1_ ? zero1_state(which) + first : nullptr;
   }
+  const float* stash_ptr(size_t first, size_t n) const {
+    live();
+    if (first > stash_elems() || n > stash_elems() - first) throw std::invalid_argument("zero1_read_state: past the end of the stash");
+    return stash_ ? static_cast<const float*>(stash_->p) + first : nullptr;
+  }
+  size_t max_grid() const { return (size_t)std::max(1, cus_ * blocks_per_cu_); }  // no peer_reduce_grid exceeds it
+  // parts[0, grid) of the launch just made, added in float64 in index order; synchronises the stream.
+  double sum_parts(int grid) {
+    std::vector<float> host((size_t)grid);
+    HIP_CHECK(hipMemcpyAsync(host.data(), parts_->p, host.size() * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    double total = 0.0;
+    for (float x : host) total += (double)x;
+    return total;
+  }
   static gtk_adamw::Hyper zero1_hyper(const std::array<float, 8>& a) {
     return gtk_adamw::Hyper{a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7]};
   }
@@ -499,6 +580,8 @@ class PeerRank {
     packed_out_.reset();
     residual_.reset();
     zero1_.reset();
+    stash_.reset();
+    parts_.reset();
     zero1_n_ = 0;
   }
 
@@ -507,6 +590,8 @@ class PeerRank {
   int blocks_per_cu_, cus_ = 1, share_ = 1;
   std::unique_ptr<DevBuf> window_, out_, packed_, packed_out_, residual_;
   std::unique_ptr<DevBuf> zero1_;  // master, m and v, zero1_n_ floats each, in that order
+  std::unique_ptr<DevBuf> stash_;  // the clipped step's scaled gradient sum, zero1_n_ floats: scratch, no part of a checkpoint
+  std::unique_ptr<DevBuf> parts_;  // max_grid() floats: one sum-of-squares partial per block of launch 1
   size_t zero1_n_ = 0;
   hipStream_t stream_ = nullptr;
   SrcSet windows_{}, packeds_{};
@@ -574,8 +659,8 @@ void bind_peer_rank(py::module_& m) {
       .def("zero1_read_state",
            [](PeerRank& r, int which, size_t first, size_t n) {
              if (r.released()) throw std::runtime_error("the PeerRank is released");
-             if (first > r.zero1_elems() || n > r.zero1_elems() - first)
-               throw std::invalid_argument("zero1_read_state: past the end of the state");
+             const size_t have = which == 3 ? r.stash_elems() : r.zero1_elems();
+             if (first > have || n > have - first) throw std::invalid_argument("zero1_read_state: past the end of the state");
              py::array_t<float> a((py::ssize_t)n);
              float* p = a.mutable_data();
              {
@@ -588,6 +673,10 @@ void bind_peer_rank(py::module_& m) {
       .def("reduce_adamw_push", &PeerRank::reduce_adamw_push, py::arg("v0"), py::arg("v1"), py::arg("scale"), py::arg("hyper"), nogil())
       .def("reduce_q8_adamw_push", &PeerRank::reduce_q8_adamw_push, py::arg("b0"), py::arg("b1"), py::arg("scale"), py::arg("hyper"),
            nogil())
+      .def("zero1_stash_alloc", &PeerRank::zero1_stash_alloc, nogil())
+      .def("reduce_sqnorm_stash", &PeerRank::reduce_sqnorm_stash, py::arg("v0"), py::arg("v1"), py::arg("scale"), nogil())
+      .def("reduce_q8_sqnorm_stash", &PeerRank::reduce_q8_sqnorm_stash, py::arg("b0"), py::arg("b1"), py::arg("scale"), nogil())
+      .def("adamw_push", &PeerRank::adamw_push, py::arg("v0"), py::arg("v1"), py::arg("hyper"), nogil())
       .def("repack_q8", &PeerRank::repack_q8, py::arg("b0"), py::arg("b1"), py::arg("scale") = 1.0f, nogil())
       .def("unpack_q8", &PeerRank::unpack_q8, py::arg("slices"), py::arg("out_dtype"), nogil())
       .def("gather", &PeerRank::gather, py::arg("slices"), nogil())

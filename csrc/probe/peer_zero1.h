@@ -21,7 +21,8 @@
 // zero master/m/v stay zero under the update, so the padding of out is written as zero.
 //
 // fp32 windows have no kernel here: four lanes would give half a weight vector, and the wide bf16-to-fp32
-// mean is what the fusion makes unnecessary.  No kernel waits for another kernel; vector stores only; no LDS.
+// mean is what the fusion makes unnecessary.  No kernel waits for another kernel; vector stores only; no LDS in the fused
+// kernels (the clipped step's first launch, further down, keeps four floats there for its block sum).
 #pragma once
 #include "../common/adamw_update.h"
 #include "peer_allreduce.h"
@@ -143,6 +144,176 @@ void launch_peer_q8_sum_adamw_push(const SrcSet& packed, const DstSet& dsts, int
     peer_q8_sum_adamw_push_kernel<8, 1><<<g, b, 0, s>>>(packed, dsts, k, exp_vec, b0, b1, scale, master, m, v, h);
   else
     peer_q8_sum_adamw_push_kernel<16, 1><<<g, b, 0, s>>>(packed, dsts, k, exp_vec, b0, b1, scale, master, m, v, h);
+  HIP_CHECK(hipGetLastError());
+}
+
+// -- the clipped step: two launches, the global norm between them ---------------------------------------------
+// Clipping by the global norm needs the norm of the summed gradient before any element is updated, and the fused
+// kernels above never write that sum.  The clipped step keeps every gradient byte to one trip over a link:
+//   launch 1 (peer_reduce_sqnorm_stash_kernel, peer_q8_sum_sqnorm_stash_kernel) is the reduce's loads, sum and walk
+//     with PeerSqnormStashEpi: the scaled fp32 sum goes to a rank-local fp32 *stash* (a fourth array next to master,
+//     m and v, its owner's alone) and its squares into a per-lane accumulator, one partial per block at the end;
+//   the host adds the partials in float64, the ranks exchange their totals at a barrier and derive one factor;
+//   launch 2 (peer_adamw_push_kernel) walks the stash, rank-local memory only, and runs PeerAdamwEpi on it with
+//     scale = 1 and that factor as grad_scale: the update and the push of the fused step, unchanged.
+// The stash is stored plainly, not non-temporally: launch 2 reads it back at once, and the cache is where it should
+// be found.  No kernel waits for another kernel; vector stores only.
+
+// The sum of s over the block's 256 lanes, in lane 0: six exchanges inside a wave, two adds across the four waves.
+__device__ __forceinline__ float peer_block_sum(float s) {
+  __shared__ float red[kBlock / 64];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// The epilogue of launch 1 for a position of E summed elements: unit o of a range that starts at unit `first`
+// becomes floats [E (o - first), E (o - first) + E) of the stash, which is the range's `dst`, after the one
+// multiply by `scale` that peer_store and PeerAdamwEpi make, so these are the bits the update would have seen.
+// `sq` is the lane's sum of their squares so far.  The epilogue is handed down as const, hence `mutable`: the
+// kernel owns the one object, a local that ends up in a register, and reads the sum back after the walk.
+template <int E>
+struct PeerSqnormStashEpi {
+  float scale;
+  size_t first;
+  mutable float sq;
+
+  template <int U>
+  struct Pre {};
+  template <int U>
+  __device__ __forceinline__ void load(Pre<U>&, int, size_t) const {}
+  template <int U>
+  __device__ __forceinline__ void operator()(const Pre<U>&, int, float (&acc)[E], u32x4* __restrict__ dst, size_t o) const {
+    u32x4* out = dst + (size_t)(E / 4) * (o - first);
+#pragma unroll
+    for (int j = 0; j < E; ++j) acc[j] = acc[j] * scale;
+#pragma unroll
+    for (int q = 0; q < E / 4; ++q) {
+      u32x4 t;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) t[j] = __float_as_uint(acc[4 * q + j]);
+      out[q] = t;
+    }
+    float s = 0.f;  // the position's own sum first: one add per position on the chain that runs through the walk
+#pragma unroll
+    for (int j = 0; j < E; ++j) s = s + acc[j] * acc[j];
+    sq = sq + s;
+  }
+};
+
+// Vectors [v0, v1) of every member's bf16 window: stash floats [0, 8 (v1 - v0)) = scale * their sum, and
+// parts[blockIdx.x] = the sum of the squares of what this block stored (0 for a block with no work: every slot of
+// parts[0, gridDim.x) is written, so nothing needs a memset).
+template <int KB, int U>
+__global__ __launch_bounds__(gtk::kStreamBlock) void peer_reduce_sqnorm_stash_kernel(SrcSet srcs, int k, size_t v0, size_t v1, float scale,
+                                                                                     u32x4* __restrict__ stash, float* __restrict__ parts) {
+  const PeerSqnormStashEpi<8> epi{scale, v0, 0.f};
+  peer_reduce_range<uint16_t, KB, U>(srcs, k, v0, v1, epi, stash);
+  const float total = peer_block_sum(epi.sq);
+  if (threadIdx.x == 0) parts[blockIdx.x] = total;
+}
+
+// Blocks [b0, b1) of every member's packed buffer: stash floats [0, 32 (b1 - b0)) = scale * the sum of the
+// dequantised blocks, parts as above.
+template <int KB, int U>
+__global__ __launch_bounds__(gtk::kStreamBlock) void peer_q8_sum_sqnorm_stash_kernel(SrcSet srcs, int k, size_t exp_vec, size_t b0,
+                                                                                     size_t b1, float scale, u32x4* __restrict__ stash,
+                                                                                     float* __restrict__ parts) {
+  const PeerSqnormStashEpi<16> epi{scale, 2 * b0, 0.f};
+  peer_q8_sum_range<KB, U>(srcs, k, exp_vec, b0, b1, epi, stash);
+  const float total = peer_block_sum(epi.sq);
+  if (threadIdx.x == 0) parts[blockIdx.x] = total;
+}
+
+// U positions of launch 2 per lane, `stride` apart from `i`: a position is one weight vector, eight stash floats
+// and eight floats each of master, m and v.  The 2 U gradient loads and the 6 U state loads are issued before the
+// first state store, for the reason given at the top of this file.
+template <int KB, int U>
+__device__ __forceinline__ void peer_adamw_push_vecs(const f32x4* __restrict__ stash, const PeerAdamwEpi<KB, 8>& epi,
+                                                     u32x4* __restrict__ dst, size_t i, size_t stride) {
+  f32x4 g[U][2];
+  typename PeerAdamwEpi<KB, 8>::template Pre<U> pre;
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+#pragma unroll
+    for (int q = 0; q < 2; ++q) g[u][q] = stash[2 * (i + (size_t)u * stride - epi.first) + q];
+#pragma unroll
+  for (int u = 0; u < U; ++u) epi.load(pre, u, i + (size_t)u * stride);
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    float acc[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = g[u][j / 4][j % 4];
+    epi(pre, u, acc, dst, i + (size_t)u * stride);
+  }
+}
+
+// Weight vectors [v0, v1) of every dsts.p[d], d < k, from stash and state floats [0, 8 (v1 - v0)): AdamW with the
+// stash as the gradient, which launch 1 has scaled already, so the epilogue's own scale is 1 and changes no bit.
+// The walk is the reduce's: whole tiles in one contiguous run per block, the rest one position per lane.
+template <int KB, int U>
+__global__ __launch_bounds__(gtk::kStreamBlock) void peer_adamw_push_kernel(DstSet dsts, int k, size_t v0, size_t v1,
+                                                                            const f32x4* __restrict__ stash, float* __restrict__ master,
+                                                                            float* __restrict__ m, float* __restrict__ v,
+                                                                            gtk_adamw::Hyper h) {
+  const PeerAdamwEpi<KB, 8> epi{PeerPushDst<KB>{dsts, k}, 1.0f, master, m, v, v0, h};
+  const size_t tile = (size_t)gtk::kStreamBlock * U;
+  const size_t n_tiles = (v1 - v0) / tile;
+  const size_t per = (n_tiles + gridDim.x - 1) / gridDim.x;
+  const size_t t0 = (size_t)blockIdx.x * per;
+  const size_t t1 = std::min(n_tiles, t0 + per);
+  for (size_t t = t0; t < t1; ++t) peer_adamw_push_vecs<KB, U>(stash, epi, dsts.p[0], v0 + t * tile + threadIdx.x, gtk::kStreamBlock);
+  for (size_t i = v0 + n_tiles * tile + (size_t)blockIdx.x * gtk::kStreamBlock + threadIdx.x; i < v1;
+       i += (size_t)gridDim.x * gtk::kStreamBlock)
+    peer_adamw_push_vecs<KB, 1>(stash, epi, dsts.p[0], i, 0);
+}
+
+// Launch 1 has no state loads, so it starts from the reduce's own buckets (peer_driver.h).
+void launch_peer_reduce_sqnorm_stash(const SrcSet& set, int k, size_t v0, size_t v1, float scale, float* stash, float* parts, int grid,
+                                     hipStream_t s) {
+  const dim3 g(grid), b(kBlock);
+  u32x4* st = reinterpret_cast<u32x4*>(stash);
+  if (k <= 2)
+    peer_reduce_sqnorm_stash_kernel<2, 4><<<g, b, 0, s>>>(set, k, v0, v1, scale, st, parts);
+  else if (k <= 4)
+    peer_reduce_sqnorm_stash_kernel<4, 4><<<g, b, 0, s>>>(set, k, v0, v1, scale, st, parts);
+  else if (k <= 8)
+    peer_reduce_sqnorm_stash_kernel<8, 2><<<g, b, 0, s>>>(set, k, v0, v1, scale, st, parts);
+  else
+    peer_reduce_sqnorm_stash_kernel<16, 1><<<g, b, 0, s>>>(set, k, v0, v1, scale, st, parts);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_peer_q8_sum_sqnorm_stash(const SrcSet& packed, int k, size_t exp_vec, size_t b0, size_t b1, float scale, float* stash,
+                                     float* parts, int grid, hipStream_t s) {
+  const dim3 g(grid), b(kBlock);
+  u32x4* st = reinterpret_cast<u32x4*>(stash);
+  if (k <= 2)
+    peer_q8_sum_sqnorm_stash_kernel<2, 4><<<g, b, 0, s>>>(packed, k, exp_vec, b0, b1, scale, st, parts);
+  else if (k <= 4)
+    peer_q8_sum_sqnorm_stash_kernel<4, 4><<<g, b, 0, s>>>(packed, k, exp_vec, b0, b1, scale, st, parts);
+  else if (k <= 8)
+    peer_q8_sum_sqnorm_stash_kernel<8, 2><<<g, b, 0, s>>>(packed, k, exp_vec, b0, b1, scale, st, parts);
+  else
+    peer_q8_sum_sqnorm_stash_kernel<16, 1><<<g, b, 0, s>>>(packed, k, exp_vec, b0, b1, scale, st, parts);
+  HIP_CHECK(hipGetLastError());
+}
+
+// Launch 2 holds no member loads: a position is eight vectors whatever k is, and KB sizes the push alone.
+void launch_peer_adamw_push(const DstSet& dsts, int k, size_t v0, size_t v1, const float* stash, float* master, float* m, float* v,
+                            const gtk_adamw::Hyper& h, int grid, hipStream_t s) {
+  const dim3 g(grid), b(kBlock);
+  const f32x4* st = reinterpret_cast<const f32x4*>(stash);
+  if (k <= 2)
+    peer_adamw_push_kernel<2, 2><<<g, b, 0, s>>>(dsts, k, v0, v1, st, master, m, v, h);
+  else if (k <= 4)
+    peer_adamw_push_kernel<4, 2><<<g, b, 0, s>>>(dsts, k, v0, v1, st, master, m, v, h);
+  else if (k <= 8)
+    peer_adamw_push_kernel<8, 2><<<g, b, 0, s>>>(dsts, k, v0, v1, st, master, m, v, h);
+  else
+    peer_adamw_push_kernel<16, 2><<<g, b, 0, s>>>(dsts, k, v0, v1, st, master, m, v, h);
   HIP_CHECK(hipGetLastError());
 }
 

@@ -98,5 +98,5 @@ def dev_hyper_ref(hp_dev: Union[T, Sequence[float]], t: float, sumsq: Optional[f
     if sumsq is not None and clip > 0.0:
         norm = math.sqrt(sumsq) * gs
         f = clip / (norm + float(torch.tensor(1e-6, dtype=torch.float32)))
-        gs = gs * min(1.0, f)
+        gs = gs * (1.0 if f > 1.0 else f)  # not min(): a NaN norm passes, as in hyper<true>
     return [lr, b1, b2, eps, wd, gs, 1.0 - b1 ** float(t), 1.0 - b2 ** float(t)]

@@ -24,10 +24,14 @@ alone.
 
 The ZeRO-1 step (``csrc/probe/peer_zero1.h``): :func:`adamw_ref` is the AdamW update body of
 ``csrc/common/adamw_update.h`` in numpy, and :func:`zero1_step_ref` is a whole step, the reduce-scatter's fp32
-mean of every rank's slice fed to that update and the new bf16 weights of all slices side by side.
+mean of every rank's slice fed to that update and the new bf16 weights of all slices side by side.  With
+``clip_norm`` the step clips by the global norm of that mean: :func:`zero1_sqnorm_ref` is its sum of squares in
+float64 and :func:`clip_grad_scale` the one formula that turns it into the norm and the update's ``grad_scale``,
+for the reference and for both backends of the communicator.
 """
 from __future__ import annotations
 
+import math
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -35,7 +39,7 @@ import numpy as np
 __all__ = ["ELEM", "peer_slices", "bf16_round", "bf16_to_f32", "bits", "out_dtype_of", "allreduce_ref", "reduce_scatter_ref",
            "is_nan_bits", "mismatches", "Q8_BLOCK", "Q8_EXP_MIN", "Q8_EXP_MAX", "q8_blocks", "q8_slices", "q8_quantize_ref", "q8_dequantize_ref",
            "allreduce_q8_ref", "reduce_scatter_q8_ref", "allreduce_q8x2_ref", "q8_quantize_ef_ref", "allreduce_q8_ef_ref",
-           "reduce_scatter_q8_ef_ref", "adamw_ref", "zero1_slices", "zero1_step_ref"]
+           "reduce_scatter_q8_ef_ref", "adamw_ref", "zero1_slices", "zero1_step_ref", "clip_grad_scale", "zero1_sqnorm_ref"]
 
 ELEM = {"bf16": 2, "fp32": 4}  # bytes per element
 
@@ -377,16 +381,50 @@ def zero1_slices(count: int, k: int, wire: Optional[str] = None) -> List[Tuple[i
     return [(8 * a, 8 * b) for a, b in peer_slices(-(-int(count) // 8), k)]
 
 
+def clip_grad_scale(total: float, grad_scale: float, clip_norm: float) -> Tuple[float, float]:
+    """``(norm, grad_scale')`` of global-norm clipping, in float64::
+
+        norm        = sqrt(total) * grad_scale
+        grad_scale' = grad_scale * min(1, clip_norm / (norm + float32(1e-6)))
+
+    ``total`` is the sum of squares of the gradient before ``grad_scale``.  It is the formula of
+    ``models/optim_ref.dev_hyper_ref`` and of ``hyper<true>`` (``csrc/ops/adamw.hip``).  The minimum is a comparison,
+    not an ``fmin``: a NaN norm gives a NaN factor, and with it a NaN in every element, where an ``fmin`` would
+    switch the clipping off quietly.  An infinite norm gives the factor 0; ``clip_norm = inf`` never clips a finite
+    norm.  Every rank evaluates this on the same values in the same order and so holds the same bits."""
+    with np.errstate(all="ignore"):  # Inf and NaN are results here, not faults
+        gs = np.float64(grad_scale)
+        norm = np.sqrt(np.float64(total)) * gs
+        f = np.float64(clip_norm) / (norm + np.float64(np.float32(1e-6)))
+        return float(norm), float(gs * (np.float64(1.0) if f > 1.0 else f))
+
+
+def zero1_sqnorm_ref(pieces: Sequence[np.ndarray]) -> float:
+    """The sum of squares, in float64, of the ranks' float32 gradient pieces (what :func:`reduce_scatter_ref` with an
+    fp32 output returns).  Every element is widened first, so each square is exact; a piece's squares are added by
+    ``math.fsum``, which rounds their exact sum once, so neither the order inside a piece nor zeros appended to it change
+    a bit; the pieces' sums are then added one by one in rank order, as the ranks' published values are."""
+    total = 0.0
+    for p in pieces:
+        total += math.fsum(np.square(np.asarray(p, dtype=np.float32).astype(np.float64)).tolist())
+    return total
+
+
 def zero1_step_ref(inputs: Sequence[np.ndarray], states: Sequence[Tuple[np.ndarray, np.ndarray, np.ndarray]], dtype: str, scale: float,
-                   hyper: Sequence[float], wire: Optional[str] = None, residuals: Optional[List[np.ndarray]] = None):
-    """One ZeRO-1 step: ``(new_states, weights)``.
+                   hyper: Sequence[float], wire: Optional[str] = None, residuals: Optional[List[np.ndarray]] = None,
+                   clip_norm: Optional[float] = None):
+    """One ZeRO-1 step: ``(new_states, weights)``; with ``clip_norm``, ``(new_states, weights, norm)``.
 
     ``inputs`` are the ranks' gradients (``dtype`` must be ``"bf16"``: bit patterns, ``count`` each), ``states[r]``
     rank r's float32 ``(master, m, v)`` of its slice of :func:`zero1_slices`, padding included.  Rank r's gradient is
     its piece of :func:`reduce_scatter_ref` with an fp32 output (``wire="fp8"``: of :func:`reduce_scatter_q8_ref`;
     with ``residuals``, every rank's error-feedback residual, of :func:`reduce_scatter_q8_ef_ref`, and the list is
     given the residuals after the step), zero in the padding; :func:`adamw_ref` with ``hyper`` updates the
-    slice.  ``weights`` are the ``count`` new bf16 weights every rank's out then holds."""
+    slice.  ``weights`` are the ``count`` new bf16 weights every rank's out then holds.
+
+    ``clip_norm`` clips by the global norm: :func:`clip_grad_scale` of :func:`zero1_sqnorm_ref` of the pieces, which
+    are scaled already, with ``hyper``'s ``grad_scale`` gives ``norm`` and the ``grad_scale`` of the update, rounded to
+    float32 as every hyper-parameter is.  Clipping comes after the sum, so the residuals are those of an unclipped step."""
     if dtype != "bf16":
         raise ValueError("the ZeRO-1 step takes bf16 gradients: fp32 windows are refused")
     k = len(inputs)
@@ -403,6 +441,10 @@ def zero1_step_ref(inputs: Sequence[np.ndarray], states: Sequence[Tuple[np.ndarr
         pieces = reduce_scatter_q8_ref(inputs, dtype, "fp32", scale)
     else:
         pieces = reduce_scatter_ref(inputs, dtype, "fp32", scale)
+    norm = None
+    if clip_norm is not None:
+        norm, gs = clip_grad_scale(zero1_sqnorm_ref(pieces), float(hyper[5]), clip_norm)
+        hyper = list(hyper[:5]) + [float(np.float32(gs))] + list(hyper[6:])
     new, w = [], []
     for (a, b), piece, (p, m, v) in zip(plan, pieces, states):
         g = np.zeros(b - a, np.float32)
@@ -410,4 +452,6 @@ def zero1_step_ref(inputs: Sequence[np.ndarray], states: Sequence[Tuple[np.ndarr
         p, m, v, bits16 = adamw_ref(p, m, v, g, hyper)
         new.append((p, m, v))
         w.append(bits16)
+    if clip_norm is not None:
+        return new, np.concatenate(w)[:count], norm
     return new, np.concatenate(w)[:count]

@@ -100,6 +100,24 @@ quantize stays before barrier A, with or without error feedback, and the residua
 for every feedback call.  All eight hyper-parameters travel in the call's descriptor, so ranks that disagree on one
 of them get ``PeerCommMismatch`` before any rank has touched a peer.
 
+``zero1_step(clip_norm=c)`` clips by the global norm, which is the norm of the summed gradient: a sum the fused launch
+holds in registers and never writes.  The clipped step splits the launch in two and keeps every gradient byte to one
+trip over a link:
+
+    (quantize -> synchronize ->) barrier A -> sum, stash, square -> synchronize -> barrier N -> AdamW from the stash,
+    pushed -> synchronize -> barrier B
+
+Launch 1 sums the rank's slice exactly as the fused step does, stores the scaled fp32 sum into a rank-local *stash*
+(a fourth array next to master, m and v) and returns the sum of its squares, which the host adds up in float64.
+Barrier N carries every rank's value through the store, as barrier A carries the descriptors; every rank adds the k
+values in rank order and derives the one factor (``ops/peer_ref.clip_grad_scale``), so all ranks hold the same bits.
+Launch 2 reads the stash and the state, rank-local memory only, and pushes the new weights.  Two launches and three
+barriers; per element of n on the native wire ``4 + 32 / k`` bytes against the fused step's ``4 + 24 / k``, where a
+first pass that read every window again only to square it would move ``6 + 24 / k``.  The stash is its owner's alone,
+written between barriers A and N and read between N and B, so it adds no hazard; the windows and packed buffers are
+read before barrier N only, every out is written after it only.  It is allocated by the first clipped step after
+:meth:`PeerComm.zero1_init`, before barrier A, is scratch and no part of :meth:`PeerComm.zero1_state`.
+
 Two backends exist, both with the ranks as threads of one process:
 
 ``backend="host"``: numpy buffers, the phases computed by ``ops/peer_ref.py``, every access logged; two
@@ -131,7 +149,8 @@ import numpy as np
 
 from ..ops.peer_ref import (ELEM as _ELEM, Q8_BLOCK, allreduce_q8_ef_ref, allreduce_q8_ref, allreduce_q8x2_ref, allreduce_ref, bf16_round,
                             bits as _bits, out_dtype_of as _out_dtype, peer_slices, q8_blocks, q8_dequantize_ref, q8_quantize_ef_ref,
-                            q8_quantize_ref, q8_slices, reduce_scatter_q8_ef_ref, adamw_ref, bf16_to_f32, zero1_slices)
+                            q8_quantize_ref, q8_slices, reduce_scatter_q8_ef_ref, adamw_ref, bf16_to_f32, zero1_slices, clip_grad_scale,
+                            zero1_sqnorm_ref)
 
 __all__ = ["PeerComm", "PeerCommError", "PeerCommTimeout", "PeerCommMismatch", "HostFabric", "MemoryStore",
            "selftest_cases", "selftest_cases_q8", "selftest_cases_q8x2", "selftest_cases_ef", "selftest_cases_push", "case_input", "run_case", "run_thread_ranks", "selftest", "thread_sweep", "timed_all_reduce", "parked_bytes", "zero1_hyper",
@@ -233,6 +252,7 @@ class HostFabric:
         self.packed_out = [np.zeros(_packed_bytes(capacity_bytes), np.uint8) for _ in range(world)]
         self.residual: List[Optional[np.ndarray]] = [None] * world  # capacity_bytes // 2 floats each, once made
         self.zero1: List[Optional[np.ndarray]] = [None] * world  # a rank's ZeRO-1 state, float32 [3, n]: master, m, v
+        self.stash: List[Optional[np.ndarray]] = [None] * world  # a rank's clipped-step stash, float32 [n], once made; logged as row 3
         self.lock = threading.Lock()
         #: (accessor, owner, buffer, v0, v1, "r" | "w", the accessor's barrier count)
         self.log: List[Tuple[int, int, str, int, int, str, int]] = []
@@ -261,7 +281,7 @@ class HostFabric:
 
 class _HostBackend:
     """One rank's phase calls (reduce, reduce_push, quantize, reduce_q8, reduce_q8_push, repack_q8, unpack_q8, gather, gather_windows,
-    reduce_adamw_push, reduce_q8_adamw_push, host copies) on a
+    reduce_adamw_push, reduce_q8_adamw_push, reduce_sqnorm_stash, reduce_q8_sqnorm_stash, adamw_push, host copies) on a
     :class:`HostFabric`, computed by ``ops/peer_ref.py``."""
 
     def __init__(self, rank: int, world: int, fabric: HostFabric):
@@ -401,20 +421,66 @@ class _HostBackend:
         if n_elems % 8 or n_elems > self.f.capacity_bytes // 2:
             raise ValueError("zero1_alloc: whole vectors of 8 elements, at most a window full of bf16")
         self.f.zero1[self.rank] = np.zeros((3, n_elems), np.float32) if n_elems else None
+        self.f.stash[self.rank] = None  # it has the state's size: the next clipped step makes a new one
 
     def _zero1(self, which: int, first: int, end: int, mode: str) -> np.ndarray:
         st = self.f.zero1[self.rank]
         n = 0 if st is None else st.shape[1]
-        if which not in (0, 1, 2) or first < 0 or end < first or end > n:
-            raise ValueError("zero1 state: which is 0 (master), 1 (m) or 2 (v), and the range lies inside the state")
+        have = n if which != 3 or self.f.stash[self.rank] is not None else 0
+        if which not in (0, 1, 2, 3) or first < 0 or end < first or end > have:
+            raise ValueError("zero1 state: which is 0 (master), 1 (m), 2 (v) or 3 (the stash, once a clipped step has made it), "
+                             "and the range lies inside it")
         if st is None:
             return np.zeros(0, np.float32)
         self.f.access(self.rank, self.rank, "zero1", (which * n + first) * 4 // 16, -(-(which * n + end) * 4 // 16), mode, self.epoch)
-        return st[which, first:end]
+        return self.f.stash[self.rank][first:end] if which == 3 else st[which, first:end]
 
     @property
     def zero1_bytes(self) -> int:
-        return 0 if self.f.zero1[self.rank] is None else int(self.f.zero1[self.rank].nbytes)
+        st, stash = self.f.zero1[self.rank], self.f.stash[self.rank]
+        return (0 if st is None else int(st.nbytes)) + (0 if stash is None else int(stash.nbytes))
+
+    # -- the clipped step: launch 1 fills the rank's own stash, launch 2 reads it and writes every out ------
+    def zero1_stash_alloc(self) -> None:
+        st = self.f.zero1[self.rank]
+        if st is not None and self.f.stash[self.rank] is None:
+            self.f.stash[self.rank] = np.zeros(st.shape[1], np.float32)
+
+    def _sqnorm_stash(self, g: np.ndarray) -> float:
+        """The scaled gradient sum ``g`` into stash floats ``[0, g.size)``; its sum of squares in float64."""
+        self._zero1(3, 0, g.size, "w")[:] = g
+        return zero1_sqnorm_ref([g])
+
+    def reduce_sqnorm_stash(self, v0: int, v1: int, scale: float) -> float:
+        if v0 > v1 or v1 * 16 > self.f.capacity_bytes or 8 * (v1 - v0) > self._stash_elems():
+            raise ValueError("reduce_sqnorm_stash: vectors past the end of the window or of the stash")
+        if v0 == v1:
+            return 0.0
+        with self.f.lock:
+            self.f.launches += 1
+        xs = [self._win(p, v0, v1, "r").view(np.uint16).copy() for p in range(self.world)]
+        return self._sqnorm_stash(allreduce_ref(xs, "bf16", "fp32", scale))
+
+    def reduce_q8_sqnorm_stash(self, b0: int, b1: int, scale: float) -> float:
+        if b0 > b1 or b1 > _max_blocks(self.f.capacity_bytes) or Q8_BLOCK * (b1 - b0) > self._stash_elems():
+            raise ValueError("reduce_q8_sqnorm_stash: blocks past the end of the packed buffer or of the stash")
+        if b0 == b1:
+            return 0.0
+        with self.f.lock:
+            self.f.launches += 1
+        return self._sqnorm_stash(self._sum_q8(b0, b1, scale))
+
+    def adamw_push(self, v0: int, v1: int, hyper: Sequence[float]) -> None:
+        if v0 > v1 or v1 * 16 > self.f.capacity_bytes or 8 * (v1 - v0) > self._stash_elems():
+            raise ValueError("adamw_push: vectors past the end of a window's worth of out or of the stash")
+        if v0 == v1:
+            return
+        with self.f.lock:
+            self.f.launches += 1
+        self._adamw_push(self._zero1(3, 0, 8 * (v1 - v0), "r").copy(), hyper, v0, v1)
+
+    def _stash_elems(self) -> int:
+        return 0 if self.f.stash[self.rank] is None else int(self.f.stash[self.rank].size)
 
     def zero1_write_state(self, which: int, floats: np.ndarray, first: int = 0) -> None:
         a = np.ascontiguousarray(floats, dtype=np.float32).reshape(-1)
@@ -607,6 +673,18 @@ class _DeviceBackend:
 
     def reduce_q8_adamw_push(self, b0: int, b1: int, scale: float, hyper: Sequence[float]) -> None:
         self.r.reduce_q8_adamw_push(b0, b1, scale, [float(x) for x in hyper])
+
+    def zero1_stash_alloc(self) -> None:
+        self.r.zero1_stash_alloc()
+
+    def reduce_sqnorm_stash(self, v0: int, v1: int, scale: float) -> float:
+        return float(self.r.reduce_sqnorm_stash(v0, v1, scale))
+
+    def reduce_q8_sqnorm_stash(self, b0: int, b1: int, scale: float) -> float:
+        return float(self.r.reduce_q8_sqnorm_stash(b0, b1, scale))
+
+    def adamw_push(self, v0: int, v1: int, hyper: Sequence[float]) -> None:
+        self.r.adamw_push(v0, v1, [float(x) for x in hyper])
 
     def unpack_q8(self, slices: Sequence[Tuple[int, int]], out_dtype: str) -> None:
         self.r.unpack_q8([(int(a), int(b)) for a, b in slices], out_dtype)
@@ -966,22 +1044,37 @@ class PeerComm:
         return tuple(self._b.zero1_read_state(which, 0, b - a) for which in range(3))
 
     def zero1_step(self, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float, step: int, grad_scale: float = 1.0,
-                   scale: Optional[float] = None, error_feedback: bool = False) -> None:
+                   scale: Optional[float] = None, error_feedback: bool = False, clip_norm: Optional[float] = None) -> Optional[float]:
         """One AdamW step of the parameters of :meth:`zero1_init`.  Every rank's window holds its bf16 gradient in
         ``[0, count)``; the gradient of the update is ``scale`` (default ``1 / world``: the mean) x the sum over ranks,
-        times ``grad_scale`` (a clipping factor the caller computed).  ``step`` is the number of this step, from 1; the
-        bias corrections ``1 - beta^step`` are computed here, on the host.  Afterwards out[0, count) of **every** rank
-        holds the same new bf16 weights and this rank's state is advanced.  One launch, two barriers.
-        ``ValueError``, before any barrier or launch: no :meth:`zero1_init`; ``error_feedback`` on the native wire."""
+        times ``grad_scale``.  ``step`` is the number of this step, from 1; the bias corrections ``1 - beta^step`` are
+        computed here, on the host.  Afterwards out[0, count) of **every** rank holds the same new bf16 weights and this
+        rank's state is advanced.  One launch, two barriers; returns ``None``.
+
+        ``clip_norm=c`` clips by the global norm (``ops/peer_ref.clip_grad_scale``): the update's ``grad_scale`` becomes
+        ``grad_scale * min(1, c / (norm + 1e-6))`` with ``norm = grad_scale * |scale x the sum|`` over all parameters,
+        and ``norm`` is returned, the same float on every rank.  ``float("inf")`` measures the norm and never clips.  A
+        NaN anywhere in the summed gradient makes every weight NaN; an Inf makes the factor 0.  Two launches, three
+        barriers (see the module docstring); the first clipped step after :meth:`zero1_init` allocates the rank's stash.
+        ``ValueError``, before any barrier or launch: no :meth:`zero1_init`; ``error_feedback`` on the native wire;
+        ``clip_norm`` that is not above 0 (a NaN is not)."""
         self._check()
         if self._zero1 is None:
             raise ValueError("zero1_step: zero1_init first")
         count, wire = self._zero1
         if error_feedback and wire != "fp8":
             raise ValueError('error_feedback=True belongs to wire="fp8": the native wire drops nothing')
+        if clip_norm is not None:
+            clip_norm = float(clip_norm)
+            if not clip_norm > 0.0:
+                raise ValueError(f"clip_norm must be above 0 (inf: measure the norm, never clip), got {clip_norm!r}")
         scale = float(np.float32(1.0 / self.world if scale is None else scale))
         hyper = zero1_hyper(lr, beta1, beta2, eps, weight_decay, step, grad_scale)
-        desc = {"op": "zero1_step", "count": count, "wire": wire or "native", "scale": scale, "ef": bool(error_feedback), "hyper": hyper}
+        # the hyper of the descriptor keeps the caller's grad_scale: the clipped one is not known at barrier A
+        desc = {"op": "zero1_step", "count": count, "wire": wire or "native", "scale": scale, "ef": bool(error_feedback), "hyper": hyper,
+                "clip": clip_norm}
+        if clip_norm is not None:
+            return self._zero1_step_clipped(desc, count, wire, scale, hyper, error_feedback, clip_norm)
         if wire == "fp8":
             n = q8_blocks(count)
             self._b.quantize(0, n, count, "bf16", error_feedback)
@@ -991,6 +1084,43 @@ class PeerComm:
             self._enter(desc)
             self._b.reduce_adamw_push(*peer_slices(_n_vec(count, "bf16"), self.world)[self.rank], scale, hyper)
         self._leave()  # every rank's stores into every out are complete
+        return None
+
+    def _zero1_step_clipped(self, desc: Dict[str, object], count: int, wire: Optional[str], scale: float, hyper: List[float],
+                            error_feedback: bool, clip_norm: float) -> float:
+        """barrier A -> sum, stash, square -> barrier N, carrying every rank's sum of squares -> AdamW from the stash,
+        pushed -> barrier B.  Only the first launch reads a peer, so every gradient byte crosses a link once."""
+        self._b.zero1_stash_alloc()  # before barrier A: no allocation inside a barrier epoch
+        if wire == "fp8":
+            n = q8_blocks(count)
+            b0, b1 = q8_slices(n, self.world)[self.rank]
+            v0, v1 = b0 * Q8_BLOCK // 8, b1 * Q8_BLOCK // 8  # the slice in weight vectors of 8
+            self._b.quantize(0, n, count, "bf16", error_feedback)
+            self._enter(desc)
+            mine = self._b.reduce_q8_sqnorm_stash(b0, b1, scale)
+        else:
+            v0, v1 = peer_slices(_n_vec(count, "bf16"), self.world)[self.rank]
+            self._enter(desc)
+            mine = self._b.reduce_sqnorm_stash(v0, v1, scale)
+        total = 0.0
+        for x in self._exchange_sqnorm(self._seq - 1, mine):  # this call's number; float64, in rank order, on every rank alike
+            total += x
+        norm, gs = clip_grad_scale(total, hyper[5], clip_norm)
+        self._b.adamw_push(v0, v1, hyper[:5] + [float(np.float32(gs))] + hyper[6:])
+        self._leave()  # every rank's stores into every out are complete
+        return norm
+
+    def _exchange_sqnorm(self, seq: int, mine: float) -> List[float]:
+        """Barrier N of a clipped step: publishes this rank's sum of squares and returns every rank's, in rank order.  It
+        is the pattern by which :meth:`_enter` carries the descriptor, with its timeout and its key cleanup.  The value
+        travels as ``float.hex()``, which is exact and keeps NaN and Inf.  Hazards the barrier covers: no window or packed
+        buffer is read after it, and nothing has yet been written to any out."""
+        self._b.synchronize()
+        keys = [f"{self._prefix}/sqnorm/{seq}/{p}" for p in range(self.world)]
+        self._stale[1].append(keys[self.rank])
+        self._store_call(lambda: self._store.set(keys[self.rank], float(mine).hex()), "publishing the sum of squares failed")
+        self._barrier()
+        return self._store_call(lambda: [float.fromhex(bytes(self._store.get(k)).decode()) for k in keys], "reading the sums of squares failed")
 
     # -- data movement ------------------------------------------------------------------------
     def write(self, array: np.ndarray, first_byte: int = 0) -> None:
