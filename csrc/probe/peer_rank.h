@@ -37,8 +37,15 @@ std::mutex& peer_rank_mutex() {
 
 class PeerRank {
  public:
-  PeerRank(int dev, int rank, int world, size_t capacity_bytes, int blocks_per_cu)
-      : dev_(dev), rank_(rank), world_(world), cap_(capacity_bytes), blocks_per_cu_(std::max(1, blocks_per_cu)) {
+  // `max_ctas` (0: no cap) bounds the grid of every launch that peer_reduce_grid sizes: the reduce, the push, the fp8
+  // sum and its push, the repack, the quantize with and without feedback, the two fused ZeRO-1 kernels and both
+  // launches of the clipped step.  Those kernels walk their range with any grid, and every element is computed by one
+  // lane from the same operands whichever block holds it, so the cap changes no result bit (the clipped step's norm
+  // excepted: its summation order follows the grid).  The gather and unpack launches keep their grids, which must stay
+  // a multiple of the source count.
+  PeerRank(int dev, int rank, int world, size_t capacity_bytes, int blocks_per_cu, int max_ctas = 0)
+      : dev_(dev), rank_(rank), world_(world), cap_(capacity_bytes), blocks_per_cu_(std::max(1, blocks_per_cu)), max_ctas_(max_ctas) {
+    if (max_ctas < 0) throw std::invalid_argument("max_ctas >= 0 (0: no cap)");
     if (world < 2 || world > kMaxSrc) throw std::invalid_argument("2..16 ranks");
     if (rank < 0 || rank >= world) throw std::invalid_argument("rank out of range");
     if (capacity_bytes < 16 || capacity_bytes % 16) throw std::invalid_argument("capacity_bytes must be a positive multiple of 16");
@@ -89,6 +96,7 @@ class PeerRank {
   size_t stash_elems() const { return stash_ ? zero1_n_ : 0; }  // floats of the clipped step's stash; 0 until zero1_stash_alloc
   size_t zero1_bytes() const { return (3 * zero1_n_ + stash_elems()) * sizeof(float); }  // the partials, a few KiB, are not counted
   size_t launches() const { return launches_; }
+  int last_grid() const { return last_grid_; }  // blocks of the most recent launch; 0 before any
   bool released() const { return released_; }
 
   // Every rank's device and buffer addresses, this rank's own included (and checked to be its own).
@@ -149,7 +157,7 @@ class PeerRank {
     if (v0 > v1 || v1 > cap_ / 16) throw std::invalid_argument("reduce: vectors past the end of the window");
     if (v1 * t.ratio() > 2 * cap_ / 16) throw std::invalid_argument("reduce: vectors past the end of out");
     if (v0 == v1) return;
-    const int grid = peer_reduce_grid(cus_, blocks_per_cu_, share_, v1 - v0);
+    const int grid = reduce_grid(v1 - v0);
     DeviceGuard g(dev_);
     launch_peer_reduce(t, windows_, world_, v0, v1, reinterpret_cast<u32x4*>(out_->p), scale, grid, stream_);
     ++launches_;
@@ -164,7 +172,7 @@ class PeerRank {
     if (v0 > v1 || v1 > cap_ / 16) throw std::invalid_argument("reduce_push: vectors past the end of the window");
     if (v1 * t.ratio() > 2 * cap_ / 16) throw std::invalid_argument("reduce_push: vectors past the end of out");
     if (v0 == v1) return;
-    const int grid = peer_reduce_grid(cus_, blocks_per_cu_, share_, v1 - v0);
+    const int grid = reduce_grid(v1 - v0);
     DeviceGuard g(dev_);
     launch_peer_reduce_push(t, windows_, peer_push_dsts(outs_, rank_), world_, v0, v1, scale, grid, stream_);
     ++launches_;
@@ -181,7 +189,7 @@ class PeerRank {
     if (b0 > b1 || b1 * kQ8Block * t.in_elem() > cap_) throw std::invalid_argument("quantize: blocks past the end of the window");
     if (b1 > max_blocks()) throw std::invalid_argument("quantize: blocks past the end of the packed buffer");  // and of the residual
     if (b0 == b1) return;
-    const int grid = peer_reduce_grid(cus_, blocks_per_cu_, share_, (b1 - b0) * kQ8Block * t.in_elem() / 16);
+    const int grid = reduce_grid((b1 - b0) * kQ8Block * t.in_elem() / 16);
     DeviceGuard g(dev_);
     if (error_feedback) {
       need_residual();
@@ -274,7 +282,7 @@ class PeerRank {
     if (v0 > v1 || v1 > cap_ / 16) throw std::invalid_argument("reduce_adamw_push: vectors past the end of the window");
     if (8 * (v1 - v0) > zero1_n_) throw std::invalid_argument("reduce_adamw_push: more vectors than zero1_alloc made state for");
     if (v0 == v1) return;
-    const int grid = peer_reduce_grid(cus_, blocks_per_cu_, share_, v1 - v0);
+    const int grid = reduce_grid(v1 - v0);
     DeviceGuard g(dev_);
     launch_peer_reduce_adamw_push(windows_, peer_push_dsts(outs_, rank_), world_, v0, v1, scale, zero1_state(0), zero1_state(1),
                                   zero1_state(2), zero1_hyper(hyper), grid, stream_);
@@ -288,7 +296,7 @@ class PeerRank {
     if (b0 > b1 || b1 > max_blocks()) throw std::invalid_argument("reduce_q8_adamw_push: blocks past the end of the packed buffer");
     if (kQ8Block * (b1 - b0) > zero1_n_) throw std::invalid_argument("reduce_q8_adamw_push: more blocks than zero1_alloc made state for");
     if (b0 == b1) return;
-    const int grid = peer_reduce_grid(cus_, blocks_per_cu_, share_, 2 * (b1 - b0));
+    const int grid = reduce_grid(2 * (b1 - b0));
     DeviceGuard g(dev_);
     launch_peer_q8_sum_adamw_push(packeds_, peer_push_dsts(outs_, rank_), world_, q8_exp_vec(max_blocks()), b0, b1, scale, zero1_state(0),
                                   zero1_state(1), zero1_state(2), zero1_hyper(hyper), grid, stream_);
@@ -319,7 +327,7 @@ class PeerRank {
     if (v0 > v1 || v1 > cap_ / 16) throw std::invalid_argument("reduce_sqnorm_stash: vectors past the end of the window");
     if (8 * (v1 - v0) > stash_elems()) throw std::invalid_argument("reduce_sqnorm_stash: more vectors than the stash holds");
     if (v0 == v1) return 0.0;
-    const int grid = peer_reduce_grid(cus_, blocks_per_cu_, share_, v1 - v0);
+    const int grid = reduce_grid(v1 - v0);
     DeviceGuard g(dev_);
     launch_peer_reduce_sqnorm_stash(windows_, world_, v0, v1, scale, static_cast<float*>(stash_->p), static_cast<float*>(parts_->p), grid,
                                     stream_);
@@ -333,7 +341,7 @@ class PeerRank {
     if (b0 > b1 || b1 > max_blocks()) throw std::invalid_argument("reduce_q8_sqnorm_stash: blocks past the end of the packed buffer");
     if (kQ8Block * (b1 - b0) > stash_elems()) throw std::invalid_argument("reduce_q8_sqnorm_stash: more blocks than the stash holds");
     if (b0 == b1) return 0.0;
-    const int grid = peer_reduce_grid(cus_, blocks_per_cu_, share_, 2 * (b1 - b0));
+    const int grid = reduce_grid(2 * (b1 - b0));
     DeviceGuard g(dev_);
     launch_peer_q8_sum_sqnorm_stash(packeds_, world_, q8_exp_vec(max_blocks()), b0, b1, scale, static_cast<float*>(stash_->p),
                                     static_cast<float*>(parts_->p), grid, stream_);
@@ -349,7 +357,7 @@ class PeerRank {
     if (v0 > v1 || v1 > cap_ / 16) throw std::invalid_argument("adamw_push: vectors past the end of a window's worth of out");
     if (8 * (v1 - v0) > stash_elems()) throw std::invalid_argument("adamw_push: more vectors than the stash holds");
     if (v0 == v1) return;
-    const int grid = peer_reduce_grid(cus_, blocks_per_cu_, share_, v1 - v0);
+    const int grid = reduce_grid(v1 - v0);
     DeviceGuard g(dev_);
     launch_peer_adamw_push(peer_push_dsts(outs_, rank_), world_, v0, v1, static_cast<const float*>(stash_->p), zero1_state(0),
                            zero1_state(1), zero1_state(2), zero1_hyper(hyper), grid, stream_);
@@ -364,7 +372,7 @@ class PeerRank {
     if (b0 > b1 || b1 > max_blocks()) throw std::invalid_argument("reduce_q8: blocks past the end of the packed buffer");
     if (b1 * kQ8Block * t.out_elem() > 2 * cap_) throw std::invalid_argument("reduce_q8: blocks past the end of out");
     if (b0 == b1) return;
-    const int grid = peer_reduce_grid(cus_, blocks_per_cu_, share_, 2 * (b1 - b0));
+    const int grid = reduce_grid(2 * (b1 - b0));
     DeviceGuard g(dev_);
     launch_peer_q8_sum(t.out_bf16, packeds_, world_, q8_exp_vec(max_blocks()), b0, b1, reinterpret_cast<u32x4*>(out_->p), scale, grid,
                        stream_);
@@ -378,7 +386,7 @@ class PeerRank {
     if (b0 > b1 || b1 > max_blocks()) throw std::invalid_argument("reduce_q8_push: blocks past the end of the packed buffer");
     if (b1 * kQ8Block * t.out_elem() > 2 * cap_) throw std::invalid_argument("reduce_q8_push: blocks past the end of out");
     if (b0 == b1) return;
-    const int grid = peer_reduce_grid(cus_, blocks_per_cu_, share_, 2 * (b1 - b0));
+    const int grid = reduce_grid(2 * (b1 - b0));
     DeviceGuard g(dev_);
     launch_peer_q8_sum_push(t.out_bf16, packeds_, peer_push_dsts(outs_, rank_), world_, q8_exp_vec(max_blocks()), b0, b1, scale, grid,
                             stream_);
@@ -391,7 +399,7 @@ class PeerRank {
     need_q8x2();
     if (b0 > b1 || b1 > max_blocks()) throw std::invalid_argument("repack_q8: blocks past the end of the packed buffers");
     if (b0 == b1) return;
-    const int grid = peer_reduce_grid(cus_, blocks_per_cu_, share_, 2 * (b1 - b0));
+    const int grid = reduce_grid(2 * (b1 - b0));
     DeviceGuard g(dev_);
     launch_peer_q8_repack(packeds_, world_, q8_exp_vec(max_blocks()), b0, b1, reinterpret_cast<u32x4*>(packed_out_->p), scale, grid,
                           stream_);
@@ -415,8 +423,8 @@ class PeerRank {
       sl.count[p] = b - a;
     }
     DeviceGuard g(dev_);
-    launch_peer_q8_unpack(t.out_bf16, sl, world_, q8_exp_vec(max_blocks()), reinterpret_cast<u32x4*>(out_->p),
-                          gather_grid_cus(cus_, blocks_per_cu_, world_, share_), stream_);
+    last_grid_ = gather_grid_cus(cus_, blocks_per_cu_, world_, share_);
+    launch_peer_q8_unpack(t.out_bf16, sl, world_, q8_exp_vec(max_blocks()), reinterpret_cast<u32x4*>(out_->p), last_grid_, stream_);
     ++launches_;
   }
 
@@ -524,6 +532,11 @@ class PeerRank {
     if (first > stash_elems() || n > stash_elems() - first) throw std::invalid_argument("zero1_read_state: past the end of the stash");
     return stash_ ? static_cast<const float*>(stash_->p) + first : nullptr;
   }
+  // The grid of a launch over `n_vec` units that is about to be made: peer_reduce_grid, under the cap where one is set.
+  int reduce_grid(size_t n_vec) {
+    const int grid = peer_reduce_grid(cus_, blocks_per_cu_, share_, n_vec);
+    return last_grid_ = max_ctas_ > 0 ? std::min(grid, max_ctas_) : grid;
+  }
   size_t max_grid() const { return (size_t)std::max(1, cus_ * blocks_per_cu_); }  // no peer_reduce_grid exceeds it
   // parts[0, grid) of the launch just made, added in float64 in index order; synchronises the stream.
   double sum_parts(int grid) {
@@ -556,7 +569,8 @@ class PeerRank {
 
   void launch_gather(const SliceSet& sl, int nsrc) {
     DeviceGuard g(dev_);
-    launch_peer_gather(sl, nsrc, reinterpret_cast<u32x4*>(out_->p), gather_grid_cus(cus_, blocks_per_cu_, nsrc, share_), stream_);
+    last_grid_ = gather_grid_cus(cus_, blocks_per_cu_, nsrc, share_);
+    launch_peer_gather(sl, nsrc, reinterpret_cast<u32x4*>(out_->p), last_grid_, stream_);
     ++launches_;
   }
 
@@ -587,7 +601,8 @@ class PeerRank {
 
   int dev_, rank_, world_;
   size_t cap_;
-  int blocks_per_cu_, cus_ = 1, share_ = 1;
+  int blocks_per_cu_, max_ctas_, cus_ = 1, share_ = 1;
+  int last_grid_ = 0;
   std::unique_ptr<DevBuf> window_, out_, packed_, packed_out_, residual_;
   std::unique_ptr<DevBuf> zero1_;  // master, m and v, zero1_n_ floats each, in that order
   std::unique_ptr<DevBuf> stash_;  // the clipped step's scaled gradient sum, zero1_n_ floats: scratch, no part of a checkpoint
@@ -606,8 +621,8 @@ void bind_peer_rank(py::module_& m) {
   py::class_<PeerRank>(m, "PeerRank",
                        "one rank of the peer communicator's device backend: a window, an out and a stream on one device, "
                        "the K7 kernels launched over the peers' addresses; used by one thread")
-      .def(py::init<int, int, int, size_t, int>(), py::arg("dev"), py::arg("rank"), py::arg("world"), py::arg("capacity_bytes"),
-           py::arg("blocks_per_cu") = kBlocksPerCU)
+      .def(py::init<int, int, int, size_t, int, int>(), py::arg("dev"), py::arg("rank"), py::arg("world"), py::arg("capacity_bytes"),
+           py::arg("blocks_per_cu") = kBlocksPerCU, py::arg("max_ctas") = 0)
       .def("window_ptr", &PeerRank::window_ptr)
       .def("out_ptr", &PeerRank::out_ptr)
       .def("packed_ptr", &PeerRank::packed_ptr)
@@ -708,6 +723,7 @@ void bind_peer_rank(py::module_& m) {
       .def("synchronize", &PeerRank::synchronize, nogil())
       .def("release", &PeerRank::release, nogil())
       .def_property_readonly("launches", &PeerRank::launches)
+      .def_property_readonly("last_grid", &PeerRank::last_grid)
       .def_property_readonly("capacity_bytes", &PeerRank::capacity_bytes)
       .def_property_readonly("packed_bytes", &PeerRank::packed_bytes)
       .def_property_readonly("residual_bytes", &PeerRank::residual_bytes)

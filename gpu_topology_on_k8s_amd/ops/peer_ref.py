@@ -28,6 +28,10 @@ mean of every rank's slice fed to that update and the new bf16 weights of all sl
 ``clip_norm`` the step clips by the global norm of that mean: :func:`zero1_sqnorm_ref` is its sum of squares in
 float64 and :func:`clip_grad_scale` the one formula that turns it into the norm and the update's ``grad_scale``,
 for the reference and for both backends of the communicator.
+
+How a launch walks its range: :func:`launch_walk` mirrors ``peer_reduce_range`` (the walk of every K7 kernel that takes
+member buckets) and :data:`LAUNCH_U` lists the positions per lane of each of those kernels per bucket, so a test can
+say on the CPU which loops a count and a grid reach.
 """
 from __future__ import annotations
 
@@ -39,7 +43,8 @@ import numpy as np
 __all__ = ["ELEM", "peer_slices", "bf16_round", "bf16_to_f32", "bits", "out_dtype_of", "allreduce_ref", "reduce_scatter_ref",
            "is_nan_bits", "mismatches", "Q8_BLOCK", "Q8_EXP_MIN", "Q8_EXP_MAX", "q8_blocks", "q8_slices", "q8_quantize_ref", "q8_dequantize_ref",
            "allreduce_q8_ref", "reduce_scatter_q8_ref", "allreduce_q8x2_ref", "q8_quantize_ef_ref", "allreduce_q8_ef_ref",
-           "reduce_scatter_q8_ef_ref", "adamw_ref", "zero1_slices", "zero1_step_ref", "clip_grad_scale", "zero1_sqnorm_ref"]
+           "reduce_scatter_q8_ef_ref", "adamw_ref", "zero1_slices", "zero1_step_ref", "clip_grad_scale", "zero1_sqnorm_ref",
+           "LAUNCH_BLOCK", "LAUNCH_BUCKETS", "LAUNCH_U", "launch_u", "launch_walk"]
 
 ELEM = {"bf16": 2, "fp32": 4}  # bytes per element
 
@@ -455,3 +460,56 @@ def zero1_step_ref(inputs: Sequence[np.ndarray], states: Sequence[Tuple[np.ndarr
     if clip_norm is not None:
         return new, np.concatenate(w)[:count], norm
     return new, np.concatenate(w)[:count]
+
+
+# -- how a launch walks its range -----------------------------------------------------------------
+LAUNCH_BLOCK = 256               # gtk::kStreamBlock: lanes of a block, one unit (a 16-byte vector) per lane and position
+LAUNCH_BUCKETS = (2, 4, 8, 16)   # the member buckets KB: a launch of k members takes the first bucket with k <= KB
+
+#: Positions per lane, U, of each bucketed kernel (``name_kernel<.., KB, U>`` on the launch lines of
+#: ``csrc/probe/peer_driver.h`` and ``csrc/probe/peer_zero1.h``), in the order of :data:`LAUNCH_BUCKETS`.
+LAUNCH_U = {
+    "peer_reduce": (4, 4, 2, 1),
+    "peer_reduce_push": (4, 4, 2, 1),
+    "peer_q8_sum": (4, 4, 2, 1),
+    "peer_q8_sum_push": (4, 4, 2, 1),
+    "peer_q8_repack": (4, 4, 2, 1),
+    "peer_reduce_adamw_push": (4, 2, 2, 1),
+    "peer_q8_sum_adamw_push": (2, 2, 1, 1),
+    "peer_reduce_sqnorm_stash": (4, 4, 2, 1),
+    "peer_q8_sum_sqnorm_stash": (4, 4, 2, 1),
+    "peer_adamw_push": (2, 2, 2, 2),
+}
+
+
+def launch_u(kernel: str, k: int) -> int:
+    """U of ``kernel`` (a key of :data:`LAUNCH_U`) in a launch of ``k`` members."""
+    if not 1 <= k <= LAUNCH_BUCKETS[-1]:
+        raise ValueError(f"1..{LAUNCH_BUCKETS[-1]} members")
+    return LAUNCH_U[kernel][next(i for i, kb in enumerate(LAUNCH_BUCKETS) if k <= kb)]
+
+
+def launch_walk(n_units: int, grid: int, U: int) -> Tuple[List[int], List[List[int]]]:
+    """``peer_reduce_range`` (``csrc/probe/peer_allreduce.h``; ``peer_q8_sum_range``, the repack and
+    ``peer_adamw_push_kernel`` walk alike) over ``n_units`` units on ``grid`` blocks, transcribed: ``(tiles, trips)``.
+
+    ``tiles[b]`` is the number of whole tiles of ``256 * U`` units that block b takes: ``per = ceil(n_tiles / grid)``
+    consecutive ones from tile ``b * per``, as far as there are tiles.  ``trips[t][b]`` is the number of live lanes of
+    block b in trip t of the remainder loop, which walks what is left, under one tile, one unit per lane and ``grid *
+    256`` units per trip; a trip with no live lane is not listed, so an empty remainder gives ``[]``."""
+    if n_units < 0 or grid < 1 or U < 1:
+        raise ValueError("n_units >= 0, grid >= 1, U >= 1")
+    tile = LAUNCH_BLOCK * U
+    n_tiles = n_units // tile
+    per = -(-n_tiles // grid)
+    tiles = []
+    for b in range(grid):
+        t0 = b * per
+        t1 = min(n_tiles, t0 + per)
+        tiles.append(max(0, t1 - t0))
+    trips = []
+    first = n_tiles * tile
+    while first < n_units:
+        trips.append([max(0, min(LAUNCH_BLOCK, n_units - (first + b * LAUNCH_BLOCK))) for b in range(grid)])
+        first += grid * LAUNCH_BLOCK
+    return tiles, trips

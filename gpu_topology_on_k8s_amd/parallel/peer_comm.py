@@ -586,12 +586,12 @@ class _DeviceBackend:
     """One rank's phase calls on its own device: ``_probe.PeerRank`` holds the window, the out, the two packed
     buffers and the stream, and launches the K7 kernels over the peers' addresses."""
 
-    def __init__(self, rank: int, world: int, device: int, capacity_bytes: int):
+    def __init__(self, rank: int, world: int, device: int, capacity_bytes: int, max_ctas: int = 0):
         from .._native import load
 
         self.rank, self.world, self.device = rank, world, int(device)
         self.epoch = 0  # kept for PeerComm._barrier; nothing here reads it
-        self.r = load("_probe").PeerRank(self.device, rank, world, capacity_bytes)
+        self.r = load("_probe").PeerRank(self.device, rank, world, capacity_bytes, max_ctas=int(max_ctas))
 
     def record(self) -> Dict[str, int]:
         """What this rank publishes to its peers.  ``pid`` says whose address space the addresses are in."""
@@ -725,17 +725,26 @@ class PeerComm:
     ``backend="host"`` takes the :class:`HostFabric` the ranks share.  ``backend="device"`` takes none: the
     rank allocates on ``device`` and the constructor exchanges addresses through the store, waiting up to
     ``timeout_s`` for every rank; all ranks must be threads of this process (``PeerCommError`` otherwise).
+
+    ``max_ctas`` (keyword, 0: no cap) bounds the blocks of every reduce, push, quantize, repack and ZeRO-1 launch of
+    ``backend="device"``, and with them the CUs the communicator takes from the compute it runs beside.  It changes no
+    result bit; only the norm a clipped ``zero1_step`` returns follows the grid's summation order.  The gather and
+    unpack launches keep their grids, which must stay a multiple of the source count.  ``backend="host"`` has no grid
+    and ignores the value.  Negative: ``ValueError``.
     """
 
     def __init__(self, rank: int, world: int, device: int, store, capacity_bytes: int, timeout_s: float = 60.0,
-                 backend: str = "host", fabric: Optional[HostFabric] = None, prefix: str = "peer_comm"):
+                 backend: str = "host", fabric: Optional[HostFabric] = None, prefix: str = "peer_comm", *, max_ctas: int = 0):
         if not 2 <= world <= MAX_WORLD:
             raise ValueError(f"2..{MAX_WORLD} ranks, got {world}")
         if not 0 <= rank < world:
             raise ValueError("rank out of range")
         if capacity_bytes < 16 or capacity_bytes % 16:
             raise ValueError("capacity_bytes must be a positive multiple of 16")
+        if int(max_ctas) != max_ctas or max_ctas < 0:
+            raise ValueError(f"max_ctas must be an integer >= 0 (0: no cap), got {max_ctas!r}")
         self.rank, self.world, self.device = rank, world, device
+        self.max_ctas = int(max_ctas)
         self.capacity_bytes, self.timeout_s = capacity_bytes, float(timeout_s)
         self._store, self._prefix = store, prefix
         self.barriers = 0       # barriers passed
@@ -751,7 +760,7 @@ class PeerComm:
         if backend == "device":
             if fabric is not None:
                 raise ValueError('a HostFabric belongs to backend="host": backend="device" allocates on the device')
-            self._b = _DeviceBackend(rank, world, device, capacity_bytes)
+            self._b = _DeviceBackend(rank, world, device, capacity_bytes, self.max_ctas)
             try:
                 self._b.open_peers(self._exchange_pointers())
             except BaseException:

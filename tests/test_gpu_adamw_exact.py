@@ -30,6 +30,12 @@ reference runs on the CPU; every kernel is called once per case.
 3. The ZeRO-1 fused step (peer_reduce_adamw_push_kernel, peer_q8_sum_adamw_push_kernel), one step under the rule:
    k = 3 and 16 thread ranks of device 0, both wires, count = 8 * 1024 * k + 11 (tiles, a tail, padding), against
    adamw_step_ref of the reduced gradient that ops/peer_ref reproduces bit for bit.
+4. Launch 2 of the clipped ZeRO-1 step (peer_adamw_push_kernel, after peer_reduce_sqnorm_stash_kernel or
+   peer_q8_sum_sqnorm_stash_kernel has left the gradient in the stash), one clipped step under the rule at the same
+   count and ranks with the default grid, where every block takes one tile at most: the reference's grad_scale is the
+   factor the step derives from the norm it returned, so the norm's own error (held to its bound in
+   tests/test_gpu_peer_zero1_clip.py) plays no part.  tests/test_gpu_peer_zero1_loops.py runs the same body, and
+   section 3's, with a block walking many tiles.
 """
 import numpy as np
 import pytest
@@ -268,3 +274,22 @@ def test_zero1_fused_step_against_float64(k, wire):
         valid = {key: x[:n] for key, x in got.items()}
         O.assert_adamw(name, valid, type(ref)(*(x[:n] for x in ref)), exempt=exempt[:n])
         np.testing.assert_array_equal(out, res[0][1], err_msg=name + " vs rank 0's out")
+
+
+# -- 4. launch 2 of the clipped ZeRO-1 step under the rule ------------------------------------------------
+@pytest.mark.parametrize("wire", ["native", "fp8"])
+@pytest.mark.parametrize("k", [3, 16])
+def test_zero1_clipped_step_against_float64(k, wire):
+    """One clipped step from a random planted state with grad_scale 0.5 at step 3 and clip_norm at half the reference
+    norm, no cap on the grid: tests/test_peer_zero1_loops_cpu.step_under_the_rule."""
+    import test_peer_zero1_loops_cpu as L
+    from gpu_topology_on_k8s_amd.ops.peer_ref import launch_u, launch_walk, zero1_slices
+
+    count = 8 * 1024 * k + 11
+    figures, grids, _ = L.step_under_the_rule(k, wire, count, 0, clipped=True)
+    first = "peer_q8_sum_sqnorm_stash" if wire == "fp8" else "peer_reduce_sqnorm_stash"
+    for (a, b), (g1, g2) in zip(zero1_slices(count, k, wire), grids):  # about 1025 vectors on five blocks: no second tile
+        one = launch_walk((b - a) // (16 if wire == "fp8" else 8), g1, launch_u(first, k))[0]
+        two = launch_walk((b - a) // 8, g2, launch_u("peer_adamw_push", k))[0]
+        assert g1 >= 1 and g2 >= 1 and max(one) <= 1 and max(two) <= 1, (grids, one, two)
+    print(f"figures 4 k={k} {wire}: worst err/tol over ranks " + ", ".join(f"{key} {max(f[key] for f in figures):.3f}" for key in figures[0]))

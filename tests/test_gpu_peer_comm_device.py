@@ -15,7 +15,8 @@ import time
 import numpy as np
 import pytest
 
-from gpu_topology_on_k8s_amd.ops.peer_ref import allreduce_ref, bf16_round, reduce_scatter_ref
+from gpu_topology_on_k8s_amd.ops.peer_ref import (Q8_BLOCK, allreduce_ref, bf16_round, launch_u, launch_walk, peer_slices, q8_blocks,
+                                                   q8_dequantize_ref, q8_quantize_ef_ref, q8_quantize_ref, q8_slices, reduce_scatter_ref)
 from gpu_topology_on_k8s_amd.parallel import peer_comm as pc
 
 pytestmark = pytest.mark.gpu
@@ -40,8 +41,42 @@ def _inputs(k, count, dtype, issue):
 
 
 @functools.lru_cache(maxsize=None)
-def _reference(k, count, op, dtype, out, scale, issue):
-    """What every rank must hold: one array (all_reduce, all_gather) or rank r's piece (reduce_scatter)."""
+def _packed_inputs(k, count, dtype, issue, ef):
+    """What every member contributes on a packed wire: its input through q8_quantize_ref and q8_dequantize_ref, cut to
+    the count; ``ef``: through q8_quantize_ef_ref from a zero residual, with the residual that leaves.  Made once per
+    input set, since the packing is what a packed reference costs."""
+    wide, residuals = [], []
+    for x in _inputs(k, count, dtype, issue):
+        if ef:
+            codes, exps, res = q8_quantize_ef_ref(x, dtype, np.zeros(q8_blocks(count) * Q8_BLOCK, np.float32))
+            residuals.append(res)
+        else:
+            codes, exps = q8_quantize_ref(x, dtype)
+        wide.append(q8_dequantize_ref(codes, exps)[:count])
+    for a in wide + residuals:
+        a.setflags(write=False)
+    return tuple(wide), tuple(residuals)
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(k, count, op, dtype, out, scale, issue, wire=None, ef=False):
+    """What every rank must hold: one array (all_reduce, all_gather) or rank r's piece (reduce_scatter).  On a packed
+    wire it is ops/peer_ref's allreduce_q8_ref, allreduce_q8x2_ref, reduce_scatter_q8_ref and their feedback forms from
+    a zero residual, composed as those compose them from the members' packed inputs (tests/test_peer_zero1_loops_cpu.py
+    holds the composition to them)."""
+    if wire in ("fp8", "fp8x2"):
+        wide, _ = _packed_inputs(k, count, dtype, issue, ef)
+        acc = allreduce_ref(list(wide), "fp32", "fp32", scale)
+        if wire == "fp8x2":
+            acc = q8_dequantize_ref(*q8_quantize_ref(acc, "fp32"))[:count]
+        full = bf16_round(acc) if out == "bf16" else acc
+        if op == "all_reduce":
+            ref = [full] * k
+        else:
+            ref = [full[min(count, a * Q8_BLOCK):min(count, b * Q8_BLOCK)] for a, b in q8_slices(q8_blocks(count), k)]
+        for a in ref:
+            a.setflags(write=False)
+        return tuple(ref)
     xs = list(_inputs(k, count, dtype, issue))
     if op == "all_gather":
         ref = [np.concatenate(xs)] * k
@@ -54,45 +89,71 @@ def _reference(k, count, op, dtype, out, scale, issue):
     return tuple(ref)
 
 
-def _plan(k, counts):
-    """(case, issue, inputs, per-rank reference) of every case of ``selftest_cases``, each issued twice in a row."""
+def _plan(k, counts, cases=None, issues=2):
+    """(case, issue, inputs, per-rank reference) of every case of ``selftest_cases`` (or of ``cases``), each issued
+    ``issues`` times in a row."""
     plan = []
-    for case in pc.selftest_cases(k, counts):
-        for issue in range(2):
-            key = (k, case["count"], case["op"], case["dtype"], case["out_dtype"], case["scale"], issue)
+    for case in (pc.selftest_cases(k, counts) if cases is None else cases):
+        for issue in range(issues):
+            key = (k, case["count"], case["op"], case["dtype"], case["out_dtype"], case["scale"], issue, case.get("wire"), bool(case.get("ef")))
             plan.append((case, issue, list(_inputs(k, case["count"], case["dtype"], issue)), _reference(*key)))
     return plan
 
 
-def _capacity(k, counts):
-    return pc._case_capacity(k, pc.selftest_cases(k, counts))
+def _capacity(k, counts, cases=None):
+    return pc._case_capacity(k, pc.selftest_cases(k, counts) if cases is None else cases)
 
 
-def _issue_all(plan):
-    """A rank's body: issues the plan through ``run_case``; returns what differed."""
+def _issue(comm, case, x):
+    """A case as ``run_case`` issues it, without the reference that ``run_case`` computes in every rank's thread: the
+    packed wires' references cost too much for that.  A feedback case starts from a reset residual, which is what its
+    reference assumes."""
+    count, dtype, out, ef = int(case["count"]), case["dtype"], case["out_dtype"], bool(case.get("ef"))
+    if case["op"] == "all_gather":
+        comm.write(x, comm.gather_slot(count, dtype))
+        n = comm.all_gather(count, dtype)
+        return np.concatenate([comm.read(p * n * (16 // pc._ELEM[dtype]), count, dtype) for p in range(comm.world)])
+    if ef:
+        comm.reset_error_feedback()
+    comm.write(x)
+    if case["op"] == "all_reduce":
+        comm.all_reduce(count, dtype, case["algo"], out, case["scale"], wire=case.get("wire"), error_feedback=ef)
+        return comm.read(0, count, out)
+    first, n = comm.reduce_scatter(count, dtype, out, case["scale"], wire=case.get("wire"), error_feedback=ef)
+    return comm.read(first, n, out)
+
+
+def _issue_all(plan, run_case=True):
+    """A rank's body: issues the plan through ``run_case`` (or, for a plan with packed wires or large counts, through
+    ``_issue``, which makes the same calls); returns what differed."""
 
     def body(comm):
         bad = []
         for case, issue, xs, refs in plan:
             before = comm.barriers
-            got, _ = pc.run_case(comm, case, xs)
+            got = pc.run_case(comm, case, xs)[0] if run_case else _issue(comm, case, xs[comm.rank])
             ref = refs[comm.rank]
-            what = (case["op"], case["count"], case["dtype"], case["out_dtype"], case["algo"], issue)
+            what = (case["op"], case["count"], case["dtype"], case["out_dtype"], case["algo"], issue, case.get("wire"), bool(case.get("ef")))
             if comm.barriers - before != 2:
                 bad.append(("barriers", comm.barriers - before) + what)
             if got.dtype != ref.dtype or got.shape != ref.shape:
                 bad.append(("type", str(got.dtype), got.shape) + what)
             elif not np.array_equal(pc._bits(got), pc._bits(ref)):
                 bad.append(("bits", int(np.count_nonzero(pc._bits(got) != pc._bits(ref)))) + what)
+            if case.get("ef"):  # what the packing dropped, of the rank's whole window
+                want = _packed_inputs(comm.world, case["count"], case["dtype"], issue, True)[1][comm.rank]
+                res = comm.residual(0, want.size)
+                if not np.array_equal(pc._bits(res), pc._bits(want)):
+                    bad.append(("residual", int(np.count_nonzero(pc._bits(res) != pc._bits(want)))) + what)
         return bad, comm.launches
 
     return body
 
 
-def _assert_exact(devices, counts):
+def _assert_exact(devices, counts, cases=None, issues=2, comm_cls=pc.PeerComm, run_case=True):
     k = len(devices)
-    plan = _plan(k, counts)
-    res = pc.run_thread_ranks(devices, _issue_all(plan), _capacity(k, counts), timeout_s=30.0)
+    plan = _plan(k, counts, cases, issues)
+    res = pc.run_thread_ranks(devices, _issue_all(plan, run_case), _capacity(k, counts, cases), timeout_s=30.0, comm_cls=comm_cls)
     assert len(res) == k
     for r, (bad, launches) in enumerate(res):
         assert not bad, (r, bad[:4])
@@ -112,16 +173,39 @@ def test_every_op_is_exact_on_thread_ranks(k):
 
 
 # -- 2. more than one tile per block ----------------------------------------------------------
+class _Phase1Grids(pc.PeerComm):
+    """Records the grid of every phase 1: ``_leave`` is the first thing a rank does after that launch."""
+
+    def _leave(self):
+        self.grids = getattr(self, "grids", []) + [self._b.r.last_grid]
+        super()._leave()
+
+
+WIDE_CTAS = 16  # the cap of the test below
+
+
 def test_wide_mean_with_more_than_one_tile_per_block():
+    """131587 vectors are 128 tiles of 256 x 4: on the default grid (CUs x 8 / 4 members, 512 blocks on 256 CUs) every
+    block takes one tile at most, in the one-shot as in the two-shot's slice of 32 tiles.  The communicator is therefore
+    capped at WIDE_CTAS blocks, and the test asserts what its name says from the grids the launches had."""
     k, count = 4, (1 << 20) + 4113
     plan = []
     for algo in pc.ALGOS:
         case = {"op": "all_reduce", "count": count, "dtype": "bf16", "out_dtype": "fp32", "algo": algo, "scale": 1.0 / k}
         plan.append((case, 0, list(_inputs(k, count, "bf16", 0)), _reference(k, count, "all_reduce", "bf16", "fp32", 1.0 / k, 0)))
-    res = pc.run_thread_ranks([0] * k, _issue_all(plan), -(-count * 2 // 16) * 16, timeout_s=30.0)
-    for r, (bad, launches) in enumerate(res):
+    issue = _issue_all(plan)
+    res = pc.run_thread_ranks([0] * k, lambda comm: issue(comm) + (comm.grids,), -(-count * 2 // 16) * 16, timeout_s=30.0,
+                              comm_cls=functools.partial(_Phase1Grids, max_ctas=WIDE_CTAS))
+    n_vec = -(-count // 8)
+    units = {"oneshot": [n_vec] * k, "twoshot": [b - a for a, b in peer_slices(n_vec, k)]}
+    for r, (bad, launches, grids) in enumerate(res):
         assert not bad, (r, bad)
         assert launches == 3  # one-shot: a reduce; two-shot: a reduce and a gather
+        assert len(grids) == len(pc.ALGOS)
+        for algo, grid in zip(pc.ALGOS, grids):
+            tiles, _ = launch_walk(units[algo][r], grid, launch_u("peer_reduce", k))
+            print(f"wide mean rank {r} {algo}: grid {grid}, tiles per block {tiles}")
+            assert 1 <= grid <= WIDE_CTAS and min(tiles) >= 2, (r, algo, grid, tiles)
 
 
 # -- 3. mismatch ------------------------------------------------------------------------------

@@ -246,6 +246,8 @@ MUTANTS: List[Mutant] = [
            "        for j in range(self.world - 1):"),
     Mutant("peer_ref", PEER_COMM, "            self._b.reduce_push(a, b, dtype, out, scale)\n            self._leave()",
            "            self._b.reduce_push(a, b, dtype, out, scale)\n            self._b.synchronize()"),
+    # the CPU mirror of the kernels' walk: every block given `per` tiles, the last one past the end of the range
+    Mutant("peer_ref", PEER_REF, "        t1 = min(n_tiles, t0 + per)", "        t1 = t0 + per"),
 ]
 
 TESTS = {
@@ -270,7 +272,7 @@ TESTS = {
     "extender": ["tests/test_shares.py", "tests/test_extender.py", "tests/test_cluster_features.py"],
     "contract": ["tests/test_k8s.py", "tests/test_extender.py", "tests/test_extender_fuzz.py", "tests/test_extender_ledger.py",
                  "tests/test_deviceplugin.py", "tests/test_cluster_features.py"],
-    "peer_ref": ["tests/test_peer_nonfinite_cpu.py", "tests/test_peer_push_cpu.py"],
+    "peer_ref": ["tests/test_peer_nonfinite_cpu.py", "tests/test_peer_push_cpu.py", "tests/test_peer_zero1_loops_cpu.py"],
 }
 
 GUARD_TARGETS = "vgpu_guard,vgpu_selftest_asan,vgpu_selftest_tsan"
