@@ -13,17 +13,22 @@ kernel's fp32 arithmetic adds.  A kernel's fp32 error is a small multiple of 2^-
 with a slack (2^-18 or 2^-16) far below the 2^-9 of the rounding term: a wrong rounding mode or a
 single wrong element cannot pass.  Backward references take ``rstd`` / ``lse`` as arguments (the fp32
 tensor the kernel is given), so they are exact for whatever forward values a test passes.
+
+:func:`model_ref64` composes the forward definitions into the whole training step (nothing rounded,
+gradients from autograd): what ``tests/test_gpu_llama_model.py`` holds every parameter's gradient to,
+under the rule of ``tests/test_llama_model_ref.py``.
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import Dict, Optional, Tuple
 
 import torch
 
+from .attention_ref import attn_fwd_ref64
 from .mnist_ref import bf16_round
 
 __all__ = ["bf16_round", "rmsnorm_ref", "add_rmsnorm_ref", "rmsnorm_bwd_ref", "rope_split_ref64", "rope_split_bwd_ref64",
-           "swiglu_ref64", "swiglu_bwd_ref64", "xent_ref64", "xent_bwd_ref64", "embed_bwd_ref64"]
+           "swiglu_ref64", "swiglu_bwd_ref64", "xent_ref64", "xent_bwd_ref64", "embed_bwd_ref64", "model_ref64"]
 
 T = torch.Tensor
 
@@ -198,3 +203,45 @@ def embed_bwd_ref64(tok: T, dx: T, V: int) -> Tuple[T, T, T]:
     owned = torch.zeros(V, dtype=torch.bool)
     owned[tok[ok]] = True
     return rows, cond, owned
+
+
+# ------------------------------------------------------------------------------------ the whole model
+def _embed64(w: T, tokens: T) -> T:
+    """[B*S, D]: row tokens[i] of w.  Autograd sums the gradient of a repeated id over its positions."""
+    return w[tokens.reshape(-1)]
+
+
+def _add_norm64(x: T, r: Optional[T], w: T, eps: float) -> Tuple[T, T]:
+    """(h, y): h = x + r (h = x for r None) is the residual stream and y = rmsnorm(h) * w the branch input.
+    Nothing is rounded here (:func:`add_rmsnorm_ref` rounds h, as the kernel does)."""
+    h = x if r is None else x + r
+    return h, rmsnorm_ref(h, w, eps)[0]
+
+
+def model_ref64(cfg, weights: Dict[str, T], tokens: T, labels: T, cos: T, sin: T,
+                ignore_index: int = -100) -> Tuple[float, Dict[str, T]]:
+    """(loss, {name: gradient}) of the Llama training step (``models/llama.py``) in float64.
+
+    ``weights``: name -> tensor for every name of ``cfg.param_shapes()`` (the model's bf16 weights; their
+    float64 copies are the leaves), ``tokens`` / ``labels`` [B, S], ``cos`` / ``sin`` the fp32 RoPE tables.
+    Embedding, RMSNorm, the QKV projection, RoPE and split, causal GQA softmax attention, the residuals,
+    SwiGLU, the final norm and head, and the mean cross-entropy over the labels that are not
+    ``ignore_index``, composed of the float64 definitions of this file and of ``attention_ref.py``.
+    No intermediate is rounded and the gradients are autograd's: no GPU, no project kernel."""
+    w = {n: _f64(weights[n].detach()).clone().requires_grad_(True) for n, _ in cfg.param_shapes()}
+    tokens, labels = tokens.detach().cpu().long(), labels.detach().cpu().long()
+    B, S = tokens.shape
+    H, Hkv, Dh = cfg.n_heads, cfg.n_kv_heads, cfg.head_dim
+    x, r = _embed64(w["tok_emb"], tokens), None
+    for i in range(cfg.n_layers):
+        x, h = _add_norm64(x, r, w[f"l{i}.attn_norm"], cfg.norm_eps)
+        q, k, v, _, _ = rope_split_ref64(h @ w[f"l{i}.wqkv"].t(), cos, sin, B, S, H, Hkv, Dh)
+        o = attn_fwd_ref64(q, k, v, Dh ** -0.5)[0].reshape(B * S, H * Dh)
+        x, h = _add_norm64(x, o @ w[f"l{i}.wo"].t(), w[f"l{i}.ffn_norm"], cfg.norm_eps)
+        r = swiglu_ref64(h @ w[f"l{i}.w13"].t())[0] @ w[f"l{i}.w2"].t()
+    _, h = _add_norm64(x, r, w["norm"], cfg.norm_eps)
+    rows, _ = xent_ref64(h @ w["lm_head"].t(), labels, ignore_index)
+    loss = rows.sum() / (labels != ignore_index).sum().clamp_min(1)
+    names = list(w)
+    grads = torch.autograd.grad(loss, [w[n] for n in names])
+    return float(loss.detach()), dict(zip(names, grads))
