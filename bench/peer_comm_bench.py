@@ -3,6 +3,7 @@
 
     python bench/peer_comm_bench.py [--members 0,0,0,0] [--sizes-mib 1,4,16,64,256] [--dtype bf16]
                                     [--iters 20] [--warmup 2] [--wire native|fp8|fp8x2] [--error-feedback] [--push] [--zero1]
+                                    [--clip-norm C] [--accumulate M]
                                     [--out FILE] [--md FILE]
 
 Both run the same K7 kernels on the same members at the same count, in one process:
@@ -37,6 +38,13 @@ communication, if at all.  After the timed steps every rank's weights must be ra
 and up to ``--check-max-mib`` the first step is compared with the host reference at the GPU tests' tolerances.
 ``--clip-norm C`` alternates the clipped step (``zero1_step(clip_norm=C)``: two launches and three barriers) with those
 two, checks its first step and its norm against the reference, and reports the host time each step spends in barriers.
+
+``--zero1 --accumulate M`` measures gradient accumulation over M micro-batches: ``M - 1`` ``zero1_accumulate`` calls followed
+by ``zero1_step(accumulated=True)``, against ``M - 1`` ``reduce_scatter(out_dtype="fp32")`` calls followed by the plain step,
+which move the same link bytes and accumulate nothing.  The two are alternated ``--reps`` times in one process, without and
+(``--clip-norm C``) with clipping, the quicker repetition of each reported per optimizer step.  Up to ``--check-max-mib``
+the first accumulated step is compared with the host reference: the accumulator bit for bit, the state at the GPU tests'
+tolerances.
 """
 import argparse
 import json
@@ -281,6 +289,130 @@ def measure_zero1(devs, sizes, iters, warmup, reps, check_max_bytes, clip_norm=N
             "reps": reps, "zero1": True, "hyper": ZERO1_HP, **({} if clip_norm is None else {"clip_norm": clip_norm}), "sizes": out}
 
 
+def measure_zero1_accum(devs, sizes, iters, warmup, reps, check_max_bytes, micro, clip_norm=None):
+    """Host seconds per optimizer step of ``micro`` micro-batches: ``micro - 1`` accumulates and the accumulated step, against
+    ``micro - 1`` reduce_scatter calls (fp32 out) and the plain step; with ``clip_norm`` both pairs once more, clipped."""
+    import time
+
+    from gpu_topology_on_k8s_amd.ops.peer_ref import bf16_to_f32, zero1_accumulate_ref, zero1_slices, zero1_step_ref
+
+    k = len(devs)
+    counts = [max(1, n // 2) for n in sizes]
+    once = pc._Once()
+    scale = float(np.float32(1.0 / k))
+    clips = (None,) if clip_norm is None else (None, clip_norm)
+
+    def start(w0, plan):
+        out = []
+        for p, q in plan:
+            master = np.zeros(q - p, np.float32)
+            master[:max(0, min(q, w0.size) - p)] = bf16_to_f32(w0[p:q])
+            out.append((master, np.zeros(q - p, np.float32), np.zeros(q - p, np.float32)))
+        return out
+
+    def reference(xs, w0, plan, wire, clip):
+        acc = None
+        for j in range(micro - 1):
+            acc = zero1_accumulate_ref(acc, xs[j], "bf16", scale, wire)
+        return acc, zero1_step_ref(xs[micro - 1], start(w0, plan), "bf16", scale, pc.zero1_hyper(step=1, **ZERO1_HP), wire, clip_norm=clip,
+                                   accumulated=acc)
+
+    def timed(comm, call):
+        for i in range(warmup):
+            call(i)
+        comm.barrier()
+        t0 = time.perf_counter()
+        for i in range(iters):
+            call(warmup + i)
+        secs = (time.perf_counter() - t0) / iters
+        comm.barrier()  # no rank goes on to check its result, holding the interpreter, while another still reads its clock
+        return secs
+
+    def body(comm):
+        rows = []
+        for count in counts:
+            xs = once.get(("in", count), lambda: [[pc.case_input(0, j, p, count, "bf16") for p in range(k)] for j in range(micro)],
+                          lambda o: o[1] == count)
+            w0 = once.get(("w", count), lambda: pc.case_input(1, 0, 0, count, "bf16"), lambda o: o[1] == count)
+            for wire in ("native", "fp8"):
+                checked = count * 2 <= check_max_bytes
+                plan = zero1_slices(count, k, wire)
+                a, b = plan[comm.rank]
+                wrong = {}
+                for clip in clips if checked else ():  # the first accumulated step against the host reference
+                    acc, ref = once.get(("ref", count, wire, clip), lambda: reference(xs, w0, plan, wire, clip), lambda o: o[1] == count)
+                    comm.zero1_init(count, w0, wire)
+                    for j in range(micro - 1):
+                        comm.write(xs[j][comm.rank])
+                        comm.zero1_accumulate()
+                    acc_wrong = int(np.count_nonzero(pc._bits(comm._b.zero1_read_state(3, 0, b - a)) != pc._bits(acc[comm.rank])))
+                    comm.write(xs[micro - 1][comm.rank])
+                    norm = comm.zero1_step(step=1, clip_norm=clip, accumulated=True, **ZERO1_HP)
+                    state_wrong = sum(int(np.count_nonzero(~np.isclose(g, r, rtol=1e-5, atol=tol)))
+                                      for g, r, tol in zip(comm.zero1_state(), ref[0][comm.rank], (1e-6, 1e-6, 1e-7)))
+                    wrong[clip] = (acc_wrong, state_wrong, 0.0 if clip is None else abs(norm - ref[2]) / ref[2])
+                comm.write(xs[0][comm.rank])
+                for r in range(reps):
+                    for clip in clips:
+                        def accumulated(i):
+                            for _ in range(micro - 1):
+                                comm.zero1_accumulate()
+                            comm.zero1_step(step=i + 1, clip_norm=clip, accumulated=True, **ZERO1_HP)
+
+                        def plain(i):
+                            for _ in range(micro - 1):
+                                comm.reduce_scatter(count, "bf16", "fp32", scale, wire=None if wire == "native" else wire)
+                            comm.zero1_step(step=i + 1, clip_norm=clip, **ZERO1_HP)
+
+                        comm.zero1_init(count, w0, wire)
+                        acc_s = timed(comm, accumulated)
+                        comm.zero1_init(count, w0, wire)
+                        plain_s = timed(comm, plain)
+                        rows.append((count, wire, r, clip, acc_s, plain_s, wrong.get(clip, (0, 0, 0.0)) if r == 0 else (0, 0, 0.0), checked))
+        return rows
+
+    cap = q8_blocks(max(counts)) * Q8_BLOCK * 2
+    res = pc.run_thread_ranks(devs, body, cap, timeout_s=300.0, join_s=3000.0)
+    out = []
+    for count in counts:
+        row = {"bytes": count * 2, "count": count}
+        for wire in ("native", "fp8"):
+            row[wire] = {}
+            for clip in clips:
+                mine = [[r for r in rank_rows if r[:2] == (count, wire) and r[3] == clip] for rank_rows in res]
+                acc = [max(rows[r][4] for rows in mine) * 1e6 for r in range(reps)]  # the slowest rank of each repetition
+                plain = [max(rows[r][5] for rows in mine) * 1e6 for r in range(reps)]
+                row[wire]["unclipped" if clip is None else "clipped"] = {
+                    "accumulated_step_time_us": min(acc), "reduce_scatters_and_plain_step_time_us": min(plain),
+                    "accumulated_over_plain": min(acc) / min(plain), "accumulated_step_time_us_reps": acc,
+                    "reduce_scatters_and_plain_step_time_us_reps": plain, "checked_against_reference": bool(mine[0][0][7]),
+                    "accumulator_bits_wrong": sum(r[6][0] for rows in mine for r in rows),
+                    "state_outside_tolerance": sum(r[6][1] for rows in mine for r in rows),
+                    "norm_relative_error": max(r[6][2] for rows in mine for r in rows)}
+        out.append(row)
+        print(json.dumps(row), file=sys.stderr, flush=True)
+    return {"members": list(devs), "k": k, "distinct_devices": len(set(devs)) == k, "dtype": "bf16", "iters": iters, "warmup": warmup,
+            "reps": reps, "zero1": True, "accumulate": micro, "hyper": ZERO1_HP, **({} if clip_norm is None else {"clip_norm": clip_norm}),
+            "sizes": out}
+
+
+def markdown_zero1_accum(res) -> str:
+    m = res["accumulate"]
+    out = [f"### {m} micro-batches per optimizer step: {m - 1} zero1_accumulate + zero1_step(accumulated=True) against {m - 1} reduce_scatter "
+           f"(fp32 out) + the plain step, thread ranks, members {res['members']} (k = {res['k']}), {res['iters']} timed optimizer steps, best of "
+           f"{res['reps']} alternated repetitions", "",
+           "| gradient per member | wire | step | accumulated us / optimizer step | reduce_scatters + plain step us | accumulated / plain | failed checks |",
+           "|---|---|---|---|---|---|---|"]
+    for r in res["sizes"]:
+        for wire in ("native", "fp8"):
+            for name, a in r[wire].items():
+                out.append(f"| {r['bytes'] / 2**20:.1f} MiB | {wire} | {name} | {a['accumulated_step_time_us']:.1f} "
+                           f"| {a['reduce_scatters_and_plain_step_time_us']:.1f} | {a['accumulated_over_plain']:.2f} "
+                           f"| {a['accumulator_bits_wrong'] + a['state_outside_tolerance']} |")
+    out.append("")
+    return "\n".join(out)
+
+
 ZERO1_CHECKS = ("state_outside_tolerance", "weights_not_the_rounded_master", "weights_differ_between_ranks")
 
 
@@ -419,6 +551,9 @@ def main():
                     help="thread ranks alone: the fused ZeRO-1 step against reduce_scatter (fp32 out) + all_gather, on the native and the fp8 wire, alternated")
     ap.add_argument("--clip-norm", type=float, default=None,
                     help="--zero1: also time zero1_step(clip_norm=C), alternated with the unclipped step and the bare communication")
+    ap.add_argument("--accumulate", type=int, default=0, metavar="M",
+                    help="--zero1: M micro-batches per optimizer step, M - 1 zero1_accumulate and the accumulated step against M - 1 "
+                         "reduce_scatter (fp32 out) and the plain step, alternated; with --clip-norm both pairs clipped as well")
     ap.add_argument("--check-max-mib", type=float, default=64.0, help="--push, --zero1: the largest size whose result is compared with the host reference")
     ap.add_argument("--reps", type=int, default=2, help="alternated repetitions of each measurement")
     ap.add_argument("--out", default="", help="also write the JSON document here")
@@ -426,7 +561,22 @@ def main():
     a = ap.parse_args()
     groups = [[int(x) for x in m.split(",")] for m in (a.members or ["0,0,0,0"])]
     sizes = [int(float(x) * (1 << 20)) for x in a.sizes_mib.split(",")]
+    if a.accumulate and (not a.zero1 or a.accumulate < 2):
+        ap.error("--accumulate M belongs to --zero1 and needs M >= 2")
     probe.warmup(groups[0][0], 100.0)
+    if a.zero1 and a.accumulate:
+        doc = {"device": probe.device_props(groups[0][0])["name"],
+               "runs": [measure_zero1_accum(g, sizes, a.iters, a.warmup, max(1, a.reps), int(a.check_max_mib * (1 << 20)), a.accumulate,
+                                            a.clip_norm) for g in groups]}
+        text = json.dumps(doc)
+        print(text)
+        for path, body in ((a.out, text + "\n"), (a.md, "\n".join(markdown_zero1_accum(r) for r in doc["runs"]))):
+            if path:
+                os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+                with open(path, "w") as f:
+                    f.write(body)
+        return 1 if any(c[key] for run in doc["runs"] for r in run["sizes"] for w in ("native", "fp8") for c in r[w].values()
+                        for key in ("accumulator_bits_wrong", "state_outside_tolerance")) else 0
     if a.zero1:
         doc = {"device": probe.device_props(groups[0][0])["name"],
                "runs": [measure_zero1(g, sizes, a.iters, a.warmup, max(1, a.reps), int(a.check_max_mib * (1 << 20)), a.clip_norm) for g in groups]}

@@ -14,6 +14,8 @@
 // parameters alone, read and written by the rank's own fused step (reduce_adamw_push, reduce_q8_adamw_push), and
 // for the stash of the clipped step (zero1_stash_alloc): the scaled gradient sum that reduce_sqnorm_stash or
 // reduce_q8_sqnorm_stash leaves for adamw_push, with the sum-of-squares partials the host adds up in between.
+// reduce_sqnorm_accum and reduce_q8_sqnorm_accum add to that stash instead of overwriting it: between the first
+// micro-batch of an accumulation and the step that ends it the stash is the rank's fp32 gradient accumulator.
 // Ranks are threads of one
 // process, so a peer's buffer is reached through its plain device address and, across devices,
 // hipDeviceEnablePeerAccess: no IPC call.  A PeerRank is used by one thread.  Nothing here waits on
@@ -39,7 +41,7 @@ class PeerRank {
  public:
   // `max_ctas` (0: no cap) bounds the grid of every launch that peer_reduce_grid sizes: the reduce, the push, the fp8
   // sum and its push, the repack, the quantize with and without feedback, the two fused ZeRO-1 kernels and both
-  // launches of the clipped step.  Those kernels walk their range with any grid, and every element is computed by one
+  // launches of the clipped step, the adding launch of an accumulation among them.  Those kernels walk their range with any grid, and every element is computed by one
   // lane from the same operands whichever block holds it, so the cap changes no result bit (the clipped step's norm
   // excepted: its summation order follows the grid).  The gather and unpack launches keep their grids, which must stay
   // a multiple of the source count.
@@ -344,6 +346,36 @@ class PeerRank {
     const int grid = reduce_grid(2 * (b1 - b0));
     DeviceGuard g(dev_);
     launch_peer_q8_sum_sqnorm_stash(packeds_, world_, q8_exp_vec(max_blocks()), b0, b1, scale, static_cast<float*>(stash_->p),
+                                    static_cast<float*>(parts_->p), grid, stream_);
+    ++launches_;
+    return sum_parts(grid);
+  }
+
+  // The adding form of launch 1, for a gradient accumulated over micro-batches: stash floats [0, 8 (v1 - v0)) +=
+  // scale x the sum over ranks of vectors [v0, v1) of their bf16 windows, one fp32 multiply and one fp32 add per
+  // element.  Returns the sum of the squares of the totals it stored, as reduce_sqnorm_stash does.
+  double reduce_sqnorm_accum(size_t v0, size_t v1, float scale) {
+    need_peers();
+    if (v0 > v1 || v1 > cap_ / 16) throw std::invalid_argument("reduce_sqnorm_accum: vectors past the end of the window");
+    if (8 * (v1 - v0) > stash_elems()) throw std::invalid_argument("reduce_sqnorm_accum: more vectors than the stash holds");
+    if (v0 == v1) return 0.0;
+    const int grid = reduce_grid(v1 - v0);
+    DeviceGuard g(dev_);
+    launch_peer_reduce_sqnorm_accum(windows_, world_, v0, v1, scale, static_cast<float*>(stash_->p), static_cast<float*>(parts_->p), grid,
+                                    stream_);
+    ++launches_;
+    return sum_parts(grid);
+  }
+
+  // The same on the fp8 wire: blocks [b0, b1) of every rank's packed buffer, stash floats [0, 32 (b1 - b0)).
+  double reduce_q8_sqnorm_accum(size_t b0, size_t b1, float scale) {
+    need_q8();
+    if (b0 > b1 || b1 > max_blocks()) throw std::invalid_argument("reduce_q8_sqnorm_accum: blocks past the end of the packed buffer");
+    if (kQ8Block * (b1 - b0) > stash_elems()) throw std::invalid_argument("reduce_q8_sqnorm_accum: more blocks than the stash holds");
+    if (b0 == b1) return 0.0;
+    const int grid = reduce_grid(2 * (b1 - b0));
+    DeviceGuard g(dev_);
+    launch_peer_q8_sum_sqnorm_accum(packeds_, world_, q8_exp_vec(max_blocks()), b0, b1, scale, static_cast<float*>(stash_->p),
                                     static_cast<float*>(parts_->p), grid, stream_);
     ++launches_;
     return sum_parts(grid);
@@ -691,6 +723,8 @@ void bind_peer_rank(py::module_& m) {
       .def("zero1_stash_alloc", &PeerRank::zero1_stash_alloc, nogil())
       .def("reduce_sqnorm_stash", &PeerRank::reduce_sqnorm_stash, py::arg("v0"), py::arg("v1"), py::arg("scale"), nogil())
       .def("reduce_q8_sqnorm_stash", &PeerRank::reduce_q8_sqnorm_stash, py::arg("b0"), py::arg("b1"), py::arg("scale"), nogil())
+      .def("reduce_sqnorm_accum", &PeerRank::reduce_sqnorm_accum, py::arg("v0"), py::arg("v1"), py::arg("scale"), nogil())
+      .def("reduce_q8_sqnorm_accum", &PeerRank::reduce_q8_sqnorm_accum, py::arg("b0"), py::arg("b1"), py::arg("scale"), nogil())
       .def("adamw_push", &PeerRank::adamw_push, py::arg("v0"), py::arg("v1"), py::arg("hyper"), nogil())
       .def("repack_q8", &PeerRank::repack_q8, py::arg("b0"), py::arg("b1"), py::arg("scale") = 1.0f, nogil())
       .def("unpack_q8", &PeerRank::unpack_q8, py::arg("slices"), py::arg("out_dtype"), nogil())

@@ -227,6 +227,85 @@ __global__ __launch_bounds__(gtk::kStreamBlock) void peer_q8_sum_sqnorm_stash_ke
   if (threadIdx.x == 0) parts[blockIdx.x] = total;
 }
 
+// -- gradient accumulation: launch 1 adds to the stash ------------------------------------------------------------
+// A batch split into micro-batches keeps its gradient in the stash between calls: the first micro-batch's launch 1
+// (above) stores its scaled sum there, and every later one runs the same loads, sum and walk with PeerSqnormAccumEpi,
+// which adds the scaled sum to what the stash holds and stores the total back: an fp32 accumulator split over the
+// ranks, never rounded to bf16.  The total's squares go into the lane's `sq` as above, so the last micro-batch's launch
+// is launch 1 of a step on the accumulated gradient, and launch 2 (peer_adamw_push_kernel) follows unchanged.
+//
+// The epilogue of the adding launch for a position of E summed elements: unit o of a range that starts at unit `first`
+// is floats [E (o - first), E (o - first) + E) of the accumulator.  They are read and written through the one pointer
+// `acc` the epilogue holds, as PeerAdamwEpi reads and writes master, m and v, and the loads of all U positions are
+// issued with the members' loads, ahead of the first store, for the reason given at the top of this file.  The range's
+// `dst` is not used: it is a __restrict__ parameter, and what is stored through it must not be read through a member.
+// Per element: the sum, one multiply by `scale`, one add to the accumulator, each rounded to fp32.  The multiply is
+// not contracted into the add: the reference rounds twice, and the accumulator has its bits.
+template <int E>
+struct PeerSqnormAccumEpi {
+  float scale;
+  float* __restrict__ acc;
+  size_t first;
+  mutable float sq;
+
+  template <int U>
+  struct Pre {
+    f32x4 a[U][E / 4];
+  };
+  template <int U>
+  __device__ __forceinline__ void load(Pre<U>& pre, int u, size_t o) const {
+    const f32x4* src = reinterpret_cast<const f32x4*>(acc + (size_t)E * (o - first));
+#pragma unroll
+    for (int q = 0; q < E / 4; ++q) pre.a[u][q] = src[q];
+  }
+  template <int U>
+  __device__ __forceinline__ void operator()(const Pre<U>& pre, int u, float (&sum)[E], u32x4* __restrict__, size_t o) const {
+    f32x4* out = reinterpret_cast<f32x4*>(acc + (size_t)E * (o - first));
+    {
+#pragma clang fp contract(off)
+#pragma unroll
+      for (int j = 0; j < E; ++j) {
+        const float piece = sum[j] * scale;
+        sum[j] = pre.a[u][j / 4][j % 4] + piece;
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < E / 4; ++q) {
+      f32x4 t;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) t[j] = sum[4 * q + j];
+      out[q] = t;
+    }
+    float s = 0.f;  // as PeerSqnormStashEpi: the position's own sum first
+#pragma unroll
+    for (int j = 0; j < E; ++j) s = s + sum[j] * sum[j];
+    sq = sq + s;
+  }
+};
+
+// Vectors [v0, v1) of every member's bf16 window: accumulator floats [0, 8 (v1 - v0)) += scale * their sum, and
+// parts[blockIdx.x] = the sum of the squares of the totals this block stored (0 for a block with no work).
+template <int KB, int U>
+__global__ __launch_bounds__(gtk::kStreamBlock) void peer_reduce_sqnorm_accum_kernel(SrcSet srcs, int k, size_t v0, size_t v1, float scale,
+                                                                                     float* __restrict__ acc, float* __restrict__ parts) {
+  const PeerSqnormAccumEpi<8> epi{scale, acc, v0, 0.f};
+  peer_reduce_range<uint16_t, KB, U>(srcs, k, v0, v1, epi, nullptr);
+  const float total = peer_block_sum(epi.sq);
+  if (threadIdx.x == 0) parts[blockIdx.x] = total;
+}
+
+// Blocks [b0, b1) of every member's packed buffer: accumulator floats [0, 32 (b1 - b0)) += scale * the sum of the
+// dequantised blocks, parts as above.
+template <int KB, int U>
+__global__ __launch_bounds__(gtk::kStreamBlock) void peer_q8_sum_sqnorm_accum_kernel(SrcSet srcs, int k, size_t exp_vec, size_t b0,
+                                                                                     size_t b1, float scale, float* __restrict__ acc,
+                                                                                     float* __restrict__ parts) {
+  const PeerSqnormAccumEpi<16> epi{scale, acc, 2 * b0, 0.f};
+  peer_q8_sum_range<KB, U>(srcs, k, exp_vec, b0, b1, epi, nullptr);
+  const float total = peer_block_sum(epi.sq);
+  if (threadIdx.x == 0) parts[blockIdx.x] = total;
+}
+
 // U positions of launch 2 per lane, `stride` apart from `i`: a position is one weight vector, eight stash floats
 // and eight floats each of master, m and v.  The 2 U gradient loads and the 6 U state loads are issued before the
 // first state store, for the reason given at the top of this file.
@@ -298,6 +377,36 @@ void launch_peer_q8_sum_sqnorm_stash(const SrcSet& packed, int k, size_t exp_vec
     peer_q8_sum_sqnorm_stash_kernel<8, 2><<<g, b, 0, s>>>(packed, k, exp_vec, b0, b1, scale, st, parts);
   else
     peer_q8_sum_sqnorm_stash_kernel<16, 1><<<g, b, 0, s>>>(packed, k, exp_vec, b0, b1, scale, st, parts);
+  HIP_CHECK(hipGetLastError());
+}
+
+// The adding launch holds a position's two (fp8: four) accumulator vectors next to the members' loads; the reduce's
+// own buckets still leave no instantiation with scratch.
+void launch_peer_reduce_sqnorm_accum(const SrcSet& set, int k, size_t v0, size_t v1, float scale, float* acc, float* parts, int grid,
+                                     hipStream_t s) {
+  const dim3 g(grid), b(kBlock);
+  if (k <= 2)
+    peer_reduce_sqnorm_accum_kernel<2, 4><<<g, b, 0, s>>>(set, k, v0, v1, scale, acc, parts);
+  else if (k <= 4)
+    peer_reduce_sqnorm_accum_kernel<4, 4><<<g, b, 0, s>>>(set, k, v0, v1, scale, acc, parts);
+  else if (k <= 8)
+    peer_reduce_sqnorm_accum_kernel<8, 2><<<g, b, 0, s>>>(set, k, v0, v1, scale, acc, parts);
+  else
+    peer_reduce_sqnorm_accum_kernel<16, 1><<<g, b, 0, s>>>(set, k, v0, v1, scale, acc, parts);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_peer_q8_sum_sqnorm_accum(const SrcSet& packed, int k, size_t exp_vec, size_t b0, size_t b1, float scale, float* acc,
+                                     float* parts, int grid, hipStream_t s) {
+  const dim3 g(grid), b(kBlock);
+  if (k <= 2)
+    peer_q8_sum_sqnorm_accum_kernel<2, 4><<<g, b, 0, s>>>(packed, k, exp_vec, b0, b1, scale, acc, parts);
+  else if (k <= 4)
+    peer_q8_sum_sqnorm_accum_kernel<4, 4><<<g, b, 0, s>>>(packed, k, exp_vec, b0, b1, scale, acc, parts);
+  else if (k <= 8)
+    peer_q8_sum_sqnorm_accum_kernel<8, 2><<<g, b, 0, s>>>(packed, k, exp_vec, b0, b1, scale, acc, parts);
+  else
+    peer_q8_sum_sqnorm_accum_kernel<16, 1><<<g, b, 0, s>>>(packed, k, exp_vec, b0, b1, scale, acc, parts);
   HIP_CHECK(hipGetLastError());
 }
 

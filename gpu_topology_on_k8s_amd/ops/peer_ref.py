@@ -27,7 +27,8 @@ The ZeRO-1 step (``csrc/probe/peer_zero1.h``): :func:`adamw_ref` is the AdamW up
 mean of every rank's slice fed to that update and the new bf16 weights of all slices side by side.  With
 ``clip_norm`` the step clips by the global norm of that mean: :func:`zero1_sqnorm_ref` is its sum of squares in
 float64 and :func:`clip_grad_scale` the one formula that turns it into the norm and the update's ``grad_scale``,
-for the reference and for both backends of the communicator.
+for the reference and for both backends of the communicator.  :func:`zero1_accumulate_ref` is the fp32 gradient
+accumulator of a batch split into micro-batches, and ``accumulated=`` of :func:`zero1_step_ref` the step that ends it.
 
 How a launch walks its range: :func:`launch_walk` mirrors ``peer_reduce_range`` (the walk of every K7 kernel that takes
 member buckets) and :data:`LAUNCH_U` lists the positions per lane of each of those kernels per bucket, so a test can
@@ -43,7 +44,7 @@ import numpy as np
 __all__ = ["ELEM", "peer_slices", "bf16_round", "bf16_to_f32", "bits", "out_dtype_of", "allreduce_ref", "reduce_scatter_ref",
            "is_nan_bits", "mismatches", "Q8_BLOCK", "Q8_EXP_MIN", "Q8_EXP_MAX", "q8_blocks", "q8_slices", "q8_quantize_ref", "q8_dequantize_ref",
            "allreduce_q8_ref", "reduce_scatter_q8_ref", "allreduce_q8x2_ref", "q8_quantize_ef_ref", "allreduce_q8_ef_ref",
-           "reduce_scatter_q8_ef_ref", "adamw_ref", "zero1_slices", "zero1_step_ref", "clip_grad_scale", "zero1_sqnorm_ref",
+           "reduce_scatter_q8_ef_ref", "adamw_ref", "zero1_slices", "zero1_step_ref", "zero1_accumulate_ref", "clip_grad_scale", "zero1_sqnorm_ref",
            "LAUNCH_BLOCK", "LAUNCH_BUCKETS", "LAUNCH_U", "launch_u", "launch_walk"]
 
 ELEM = {"bf16": 2, "fp32": 4}  # bytes per element
@@ -415,9 +416,54 @@ def zero1_sqnorm_ref(pieces: Sequence[np.ndarray]) -> float:
     return total
 
 
+def _zero1_pieces(inputs: Sequence[np.ndarray], dtype: str, scale: float, wire: Optional[str],
+                  residuals: Optional[List[np.ndarray]]) -> List[np.ndarray]:
+    """Every rank's fp32 piece of the reduce-scatter of ``inputs`` on ``wire``, clipped to the count; with ``residuals``
+    (``wire="fp8"``) the packing feeds back, and the list is given the residuals after it."""
+    if residuals is not None:
+        if wire != "fp8":
+            raise ValueError('residuals belong to wire="fp8"')
+        pieces, after = reduce_scatter_q8_ef_ref(inputs, residuals, dtype, "fp32", scale)
+        residuals[:] = after
+        return pieces
+    if wire == "fp8":
+        return reduce_scatter_q8_ref(inputs, dtype, "fp32", scale)
+    return reduce_scatter_ref(inputs, dtype, "fp32", scale)
+
+
+def zero1_accumulate_ref(acc: Optional[Sequence[np.ndarray]], inputs: Sequence[np.ndarray], dtype: str, scale: float,
+                         wire: Optional[str] = None, residuals: Optional[List[np.ndarray]] = None) -> List[np.ndarray]:
+    """The ranks' float32 gradient accumulators after one more micro-batch: new arrays, rank r's of the size of its slice
+    of :func:`zero1_slices`, zero in the padding.
+
+    ``inputs`` are the ranks' bf16 gradients of the micro-batch.  Rank r's piece is the step's: its piece of
+    :func:`reduce_scatter_ref` with an fp32 output (``wire="fp8"``: of :func:`reduce_scatter_q8_ref`; with
+    ``residuals``: of :func:`reduce_scatter_q8_ef_ref`, and the list is given the residuals after the call), the sum in
+    member order multiplied once by ``scale``.  ``acc`` is ``None`` for the first micro-batch, which stores the piece;
+    otherwise the accumulators so far, and the new one is ``float32(acc + piece)``: one fp32 add per element, the
+    product rounded before it (no fused multiply-add)."""
+    if dtype != "bf16":
+        raise ValueError("the ZeRO-1 step takes bf16 gradients: fp32 windows are refused")
+    k = len(inputs)
+    count = int(np.asarray(inputs[0]).shape[0])
+    plan = zero1_slices(count, k, wire)
+    if acc is not None and (len(acc) != k or any(np.asarray(x).dtype != np.float32 or np.asarray(x).shape != (b - a,)
+                                                 for x, (a, b) in zip(acc, plan))):
+        raise ValueError("one float32 accumulator per rank, of the size of its slice")
+    out = []
+    for r, ((a, b), piece) in enumerate(zip(plan, _zero1_pieces(inputs, dtype, scale, wire, residuals))):
+        g = np.zeros(b - a, np.float32)
+        g[:piece.shape[0]] = piece
+        if acc is not None:
+            with np.errstate(over="ignore", invalid="ignore"):  # Inf and NaN are results here, not faults
+                g = (np.asarray(acc[r]) + g).astype(np.float32)
+        out.append(g)
+    return out
+
+
 def zero1_step_ref(inputs: Sequence[np.ndarray], states: Sequence[Tuple[np.ndarray, np.ndarray, np.ndarray]], dtype: str, scale: float,
                    hyper: Sequence[float], wire: Optional[str] = None, residuals: Optional[List[np.ndarray]] = None,
-                   clip_norm: Optional[float] = None):
+                   clip_norm: Optional[float] = None, accumulated: Optional[Sequence[np.ndarray]] = None):
     """One ZeRO-1 step: ``(new_states, weights)``; with ``clip_norm``, ``(new_states, weights, norm)``.
 
     ``inputs`` are the ranks' gradients (``dtype`` must be ``"bf16"``: bit patterns, ``count`` each), ``states[r]``
@@ -429,7 +475,12 @@ def zero1_step_ref(inputs: Sequence[np.ndarray], states: Sequence[Tuple[np.ndarr
 
     ``clip_norm`` clips by the global norm: :func:`clip_grad_scale` of :func:`zero1_sqnorm_ref` of the pieces, which
     are scaled already, with ``hyper``'s ``grad_scale`` gives ``norm`` and the ``grad_scale`` of the update, rounded to
-    float32 as every hyper-parameter is.  Clipping comes after the sum, so the residuals are those of an unclipped step."""
+    float32 as every hyper-parameter is.  Clipping comes after the sum, so the residuals are those of an unclipped step.
+
+    ``accumulated`` are the ranks' float32 accumulators of the micro-batches before this one, as
+    :func:`zero1_accumulate_ref` returned them; ``inputs`` is then the last micro-batch, and every rank's gradient piece
+    becomes ``float32(accumulator + piece)``, one add, before the norm and the update.  The residuals are those of an
+    unaccumulated step."""
     if dtype != "bf16":
         raise ValueError("the ZeRO-1 step takes bf16 gradients: fp32 windows are refused")
     k = len(inputs)
@@ -437,15 +488,10 @@ def zero1_step_ref(inputs: Sequence[np.ndarray], states: Sequence[Tuple[np.ndarr
         raise ValueError("one state per rank")
     count = int(np.asarray(inputs[0]).shape[0])
     plan = zero1_slices(count, k, wire)
-    if residuals is not None:
-        if wire != "fp8":
-            raise ValueError('residuals belong to wire="fp8"')
-        pieces, after = reduce_scatter_q8_ef_ref(inputs, residuals, dtype, "fp32", scale)
-        residuals[:] = after
-    elif wire == "fp8":
-        pieces = reduce_scatter_q8_ref(inputs, dtype, "fp32", scale)
+    if accumulated is not None:
+        pieces = zero1_accumulate_ref(accumulated, inputs, dtype, scale, wire, residuals)
     else:
-        pieces = reduce_scatter_ref(inputs, dtype, "fp32", scale)
+        pieces = _zero1_pieces(inputs, dtype, scale, wire, residuals)
     norm = None
     if clip_norm is not None:
         norm, gs = clip_grad_scale(zero1_sqnorm_ref(pieces), float(hyper[5]), clip_norm)
@@ -478,6 +524,8 @@ LAUNCH_U = {
     "peer_q8_sum_adamw_push": (2, 2, 1, 1),
     "peer_reduce_sqnorm_stash": (4, 4, 2, 1),
     "peer_q8_sum_sqnorm_stash": (4, 4, 2, 1),
+    "peer_reduce_sqnorm_accum": (4, 4, 2, 1),
+    "peer_q8_sum_sqnorm_accum": (4, 4, 2, 1),
     "peer_adamw_push": (2, 2, 2, 2),
 }
 

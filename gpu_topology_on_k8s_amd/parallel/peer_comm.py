@@ -118,6 +118,34 @@ written between barriers A and N and read between N and B, so it adds no hazard;
 read before barrier N only, every out is written after it only.  It is allocated by the first clipped step after
 :meth:`PeerComm.zero1_init`, before barrier A, is scratch and no part of :meth:`PeerComm.zero1_state`.
 
+``zero1_accumulate`` and ``zero1_step(accumulated=True)`` accumulate the gradient of a batch that is split into
+micro-batches, in fp32: summing the micro-batches in the bf16 window would round the partial sum after every one.  The
+accumulator is the stash, so it is split over the ranks, ``4 n / k`` bytes each, which is ZeRO-2's gradient partition.
+Every micro-batch but the last is one call
+
+    (quantize -> synchronize ->) barrier A -> sum, store or add to the stash -> synchronize -> barrier B
+
+after which the windows may be rewritten: one launch, two barriers.  The first call after :meth:`PeerComm.zero1_init`, a
+step or :meth:`PeerComm.zero1_reset_accumulated` is launch 1 of the clipped step with its partials ignored, ``acc = piece``;
+every later one is the adding launch (``peer_reduce_sqnorm_accum_kernel``, ``peer_q8_sum_sqnorm_accum_kernel``), ``acc =
+float32(acc + piece)`` with the piece rounded before the add (``ops/peer_ref.zero1_accumulate_ref``).  The last micro-batch
+goes to ``zero1_step(accumulated=True)``: its launch 1 is the adding launch, which stores the total back and squares it, and
+its launch 2 the clipped step's.  With ``clip_norm`` that is the clipped step as it stands, three barriers, the norm being
+that of the total.  Without it the two launches follow each other on the rank's stream,
+
+    (quantize -> synchronize ->) barrier A -> add to the stash -> AdamW from the stash, pushed -> synchronize -> barrier B
+
+two launches and two barriers: launch 2 reads the rank's own stash and state alone, so only the stream orders it after
+launch 1, and every out is written between barriers A and B, as in a push.  Every micro-batch's gradient byte crosses a link
+once.  Per element of n and rank on the native wire the first accumulate moves ``2 + 4 / k`` bytes, a later one ``2 + 8 /
+k`` and the accumulated step ``4 + 36 / k``, against the clipped step's ``4 + 32 / k``.  The hazards are those above: the
+stash is read and written by its owner alone.  What is new is that the stash is **state between calls**: from the first
+accumulate to the step that ends the accumulation it holds gradient that exists nowhere else.  So the number of micro-batches
+accumulated (:attr:`PeerComm.zero1_accumulated`) travels in the descriptor of every accumulate and every step, and ranks that
+disagree get ``PeerCommMismatch`` before any launch; a plain step while something is accumulated is refused, since it would
+overwrite the stash (clipped) or leave it behind (fused) and drop gradient silently; :meth:`PeerComm.zero1_init` frees the
+stash and with it the accumulation.  The accumulator is no part of :meth:`PeerComm.zero1_state`: checkpoint after a step.
+
 Two backends exist, both with the ranks as threads of one process:
 
 ``backend="host"``: numpy buffers, the phases computed by ``ops/peer_ref.py``, every access logged; two
@@ -281,7 +309,8 @@ class HostFabric:
 
 class _HostBackend:
     """One rank's phase calls (reduce, reduce_push, quantize, reduce_q8, reduce_q8_push, repack_q8, unpack_q8, gather, gather_windows,
-    reduce_adamw_push, reduce_q8_adamw_push, reduce_sqnorm_stash, reduce_q8_sqnorm_stash, adamw_push, host copies) on a
+    reduce_adamw_push, reduce_q8_adamw_push, reduce_sqnorm_stash, reduce_q8_sqnorm_stash, reduce_sqnorm_accum,
+    reduce_q8_sqnorm_accum, adamw_push, host copies) on a
     :class:`HostFabric`, computed by ``ops/peer_ref.py``."""
 
     def __init__(self, rank: int, world: int, fabric: HostFabric):
@@ -469,6 +498,34 @@ class _HostBackend:
         with self.f.lock:
             self.f.launches += 1
         return self._sqnorm_stash(self._sum_q8(b0, b1, scale))
+
+    # -- gradient accumulation: the adding form of launch 1 reads the rank's own stash and writes it back ------
+    def _sqnorm_accum(self, g: np.ndarray) -> float:
+        """The scaled gradient sum ``g`` added, one fp32 add per element, to stash floats ``[0, g.size)``; the sum of
+        squares of the totals in float64."""
+        with np.errstate(over="ignore", invalid="ignore"):  # Inf and NaN are results here, not faults
+            total = (self._zero1(3, 0, g.size, "r") + g).astype(np.float32)
+        self._zero1(3, 0, g.size, "w")[:] = total
+        return zero1_sqnorm_ref([total])
+
+    def reduce_sqnorm_accum(self, v0: int, v1: int, scale: float) -> float:
+        if v0 > v1 or v1 * 16 > self.f.capacity_bytes or 8 * (v1 - v0) > self._stash_elems():
+            raise ValueError("reduce_sqnorm_accum: vectors past the end of the window or of the stash")
+        if v0 == v1:
+            return 0.0
+        with self.f.lock:
+            self.f.launches += 1
+        xs = [self._win(p, v0, v1, "r").view(np.uint16).copy() for p in range(self.world)]
+        return self._sqnorm_accum(allreduce_ref(xs, "bf16", "fp32", scale))
+
+    def reduce_q8_sqnorm_accum(self, b0: int, b1: int, scale: float) -> float:
+        if b0 > b1 or b1 > _max_blocks(self.f.capacity_bytes) or Q8_BLOCK * (b1 - b0) > self._stash_elems():
+            raise ValueError("reduce_q8_sqnorm_accum: blocks past the end of the packed buffer or of the stash")
+        if b0 == b1:
+            return 0.0
+        with self.f.lock:
+            self.f.launches += 1
+        return self._sqnorm_accum(self._sum_q8(b0, b1, scale))
 
     def adamw_push(self, v0: int, v1: int, hyper: Sequence[float]) -> None:
         if v0 > v1 or v1 * 16 > self.f.capacity_bytes or 8 * (v1 - v0) > self._stash_elems():
@@ -683,6 +740,12 @@ class _DeviceBackend:
     def reduce_q8_sqnorm_stash(self, b0: int, b1: int, scale: float) -> float:
         return float(self.r.reduce_q8_sqnorm_stash(b0, b1, scale))
 
+    def reduce_sqnorm_accum(self, v0: int, v1: int, scale: float) -> float:
+        return float(self.r.reduce_sqnorm_accum(v0, v1, scale))
+
+    def reduce_q8_sqnorm_accum(self, b0: int, b1: int, scale: float) -> float:
+        return float(self.r.reduce_q8_sqnorm_accum(b0, b1, scale))
+
     def adamw_push(self, v0: int, v1: int, hyper: Sequence[float]) -> None:
         self.r.adamw_push(v0, v1, [float(x) for x in hyper])
 
@@ -754,6 +817,7 @@ class PeerComm:
         self._closed = False
         self._stale: List[List[str]] = [[], []]  # store keys to delete after the next barrier / the one after
         self._zero1: Optional[Tuple[int, Optional[str]]] = None  # (count, wire) of zero1_init
+        self._zero1_acc = 0  # micro-batches accumulated in the stash since the last step, reset or init
         if backend not in BACKENDS:
             raise ValueError(f'backend must be "host" or "device", got {backend!r}')
         self.backend = backend
@@ -1036,6 +1100,7 @@ class PeerComm:
             if len(new) != 3 or any(x.shape != (n,) for x in new):
                 raise ValueError(f"state: master, m and v, {n} float32 each, as zero1_state returns them")
         self._zero1 = None
+        self._zero1_acc = 0  # zero1_alloc frees the stash, and what was accumulated with it
         self._b.zero1_alloc(n)
         for which, x in enumerate(new):
             if x is not None and n:
@@ -1045,7 +1110,9 @@ class PeerComm:
         return first, end - first
 
     def zero1_state(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-        """This rank's master, m and v as float32 host arrays, the slice's padding included."""
+        """This rank's master, m and v as float32 host arrays, the slice's padding included.  A gradient accumulated by
+        :meth:`zero1_accumulate` is no part of it: checkpointing in the middle of an accumulation is out of scope, so
+        take the state after a step, when nothing is accumulated."""
         self._check()
         if self._zero1 is None:
             raise ValueError("zero1_state: zero1_init first")
@@ -1053,7 +1120,8 @@ class PeerComm:
         return tuple(self._b.zero1_read_state(which, 0, b - a) for which in range(3))
 
     def zero1_step(self, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float, step: int, grad_scale: float = 1.0,
-                   scale: Optional[float] = None, error_feedback: bool = False, clip_norm: Optional[float] = None) -> Optional[float]:
+                   scale: Optional[float] = None, error_feedback: bool = False, clip_norm: Optional[float] = None,
+                   accumulated: bool = False) -> Optional[float]:
         """One AdamW step of the parameters of :meth:`zero1_init`.  Every rank's window holds its bf16 gradient in
         ``[0, count)``; the gradient of the update is ``scale`` (default ``1 / world``: the mean) x the sum over ranks,
         times ``grad_scale``.  ``step`` is the number of this step, from 1; the bias corrections ``1 - beta^step`` are
@@ -1065,14 +1133,30 @@ class PeerComm:
         and ``norm`` is returned, the same float on every rank.  ``float("inf")`` measures the norm and never clips.  A
         NaN anywhere in the summed gradient makes every weight NaN; an Inf makes the factor 0.  Two launches, three
         barriers (see the module docstring); the first clipped step after :meth:`zero1_init` allocates the rank's stash.
+
+        ``accumulated=True`` ends a gradient accumulation (:meth:`zero1_accumulate`): the window holds the **last**
+        micro-batch, and the gradient of the update is ``grad_scale x float32(acc + scale x the sum over ranks)``, ``acc``
+        being what the earlier micro-batches left in the rank's stash.  Launch 1 is the adding launch, which stores the
+        total back to the stash and squares it; launch 2 applies AdamW from the stash and pushes.  Without ``clip_norm``
+        the two follow each other on the rank's stream, two launches and two barriers; with it the step is the clipped
+        one, three barriers, and the norm is that of the accumulated total.  The step ends the accumulation.
+
         ``ValueError``, before any barrier or launch: no :meth:`zero1_init`; ``error_feedback`` on the native wire;
-        ``clip_norm`` that is not above 0 (a NaN is not)."""
+        ``clip_norm`` that is not above 0 (a NaN is not); ``accumulated=True`` with nothing accumulated;
+        ``accumulated=False`` while something is, which would silently drop gradient
+        (:meth:`zero1_reset_accumulated` drops it on purpose)."""
         self._check()
         if self._zero1 is None:
             raise ValueError("zero1_step: zero1_init first")
         count, wire = self._zero1
         if error_feedback and wire != "fp8":
             raise ValueError('error_feedback=True belongs to wire="fp8": the native wire drops nothing')
+        accumulated = bool(accumulated)
+        if accumulated and not self._zero1_acc:
+            raise ValueError("zero1_step(accumulated=True): nothing is accumulated, zero1_accumulate first")
+        if not accumulated and self._zero1_acc:
+            raise ValueError(f"zero1_step(accumulated=False) while {self._zero1_acc} micro-batches are accumulated would drop their "
+                             "gradient: pass accumulated=True, or zero1_reset_accumulated() to drop it on purpose")
         if clip_norm is not None:
             clip_norm = float(clip_norm)
             if not clip_norm > 0.0:
@@ -1081,9 +1165,17 @@ class PeerComm:
         hyper = zero1_hyper(lr, beta1, beta2, eps, weight_decay, step, grad_scale)
         # the hyper of the descriptor keeps the caller's grad_scale: the clipped one is not known at barrier A
         desc = {"op": "zero1_step", "count": count, "wire": wire or "native", "scale": scale, "ef": bool(error_feedback), "hyper": hyper,
-                "clip": clip_norm}
+                "clip": clip_norm, "accumulated": accumulated, "micro": self._zero1_acc}
         if clip_norm is not None:
-            return self._zero1_step_clipped(desc, count, wire, scale, hyper, error_feedback, clip_norm)
+            norm = self._zero1_step_clipped(desc, count, wire, scale, hyper, error_feedback, clip_norm, accumulated)
+            self._zero1_acc = 0
+            return norm
+        if accumulated:
+            v0, v1 = self._zero1_sum_to_stash(desc, count, wire, scale, error_feedback, add=True)[:2]
+            self._b.adamw_push(v0, v1, hyper)  # the stash is this rank's own: no barrier between the two launches
+            self._leave()  # every rank's stores into every out are complete
+            self._zero1_acc = 0
+            return None
         if wire == "fp8":
             n = q8_blocks(count)
             self._b.quantize(0, n, count, "bf16", error_feedback)
@@ -1095,22 +1187,61 @@ class PeerComm:
         self._leave()  # every rank's stores into every out are complete
         return None
 
-    def _zero1_step_clipped(self, desc: Dict[str, object], count: int, wire: Optional[str], scale: float, hyper: List[float],
-                            error_feedback: bool, clip_norm: float) -> float:
-        """barrier A -> sum, stash, square -> barrier N, carrying every rank's sum of squares -> AdamW from the stash,
-        pushed -> barrier B.  Only the first launch reads a peer, so every gradient byte crosses a link once."""
+    def _zero1_sum_to_stash(self, desc: Dict[str, object], count: int, wire: Optional[str], scale: float, error_feedback: bool,
+                            add: bool) -> Tuple[int, int, float]:
+        """(quantize -> synchronize ->) barrier A -> launch 1: ``scale`` x the sum over ranks of this rank's slice, stored
+        to its stash or, with ``add``, added to what the stash holds.  Returns the slice in weight vectors of 8 and the sum
+        of squares of what the launch stored (0.0, and no launch, for an empty slice)."""
         self._b.zero1_stash_alloc()  # before barrier A: no allocation inside a barrier epoch
         if wire == "fp8":
             n = q8_blocks(count)
             b0, b1 = q8_slices(n, self.world)[self.rank]
-            v0, v1 = b0 * Q8_BLOCK // 8, b1 * Q8_BLOCK // 8  # the slice in weight vectors of 8
             self._b.quantize(0, n, count, "bf16", error_feedback)
             self._enter(desc)
-            mine = self._b.reduce_q8_sqnorm_stash(b0, b1, scale)
-        else:
-            v0, v1 = peer_slices(_n_vec(count, "bf16"), self.world)[self.rank]
-            self._enter(desc)
-            mine = self._b.reduce_sqnorm_stash(v0, v1, scale)
+            mine = (self._b.reduce_q8_sqnorm_accum if add else self._b.reduce_q8_sqnorm_stash)(b0, b1, scale)
+            return b0 * Q8_BLOCK // 8, b1 * Q8_BLOCK // 8, mine
+        v0, v1 = peer_slices(_n_vec(count, "bf16"), self.world)[self.rank]
+        self._enter(desc)
+        return v0, v1, (self._b.reduce_sqnorm_accum if add else self._b.reduce_sqnorm_stash)(v0, v1, scale)
+
+    def zero1_accumulate(self, scale: Optional[float] = None, error_feedback: bool = False) -> None:
+        """Adds one micro-batch to this rank's gradient accumulator.  Every rank's window holds the micro-batch's bf16
+        gradient in ``[0, count)``; rank r adds ``scale`` (default ``1 / world``) x the sum over ranks of slice r to its
+        accumulator, fp32, the rank's stash (``ops/peer_ref.zero1_accumulate_ref``).  The first call after
+        :meth:`zero1_init`, after a step or after :meth:`zero1_reset_accumulated` stores the piece, every later one adds
+        to it with one fp32 add per element.  One launch, two barriers; after the call the window may be rewritten.  The
+        last micro-batch is not accumulated but given to ``zero1_step(accumulated=True)``.  A rank whose slice is empty
+        launches nothing and takes both barriers.  ``ValueError``, before any barrier or launch: no :meth:`zero1_init`;
+        ``error_feedback`` on the native wire."""
+        self._check()
+        if self._zero1 is None:
+            raise ValueError("zero1_accumulate: zero1_init first")
+        count, wire = self._zero1
+        if error_feedback and wire != "fp8":
+            raise ValueError('error_feedback=True belongs to wire="fp8": the native wire drops nothing')
+        scale = float(np.float32(1.0 / self.world if scale is None else scale))
+        desc = {"op": "zero1_accumulate", "count": count, "wire": wire or "native", "scale": scale, "ef": bool(error_feedback),
+                "accumulated": self._zero1_acc}
+        self._zero1_sum_to_stash(desc, count, wire, scale, error_feedback, add=self._zero1_acc > 0)
+        self._leave()  # nobody is still reading any window
+        self._zero1_acc += 1
+
+    @property
+    def zero1_accumulated(self) -> int:
+        """Micro-batches accumulated since the last step, :meth:`zero1_reset_accumulated` or :meth:`zero1_init`."""
+        return self._zero1_acc
+
+    def zero1_reset_accumulated(self) -> None:
+        """Drops what is accumulated: the next :meth:`zero1_accumulate` stores again.  Local, no barrier and no launch;
+        it serves a skipped step, and every rank must skip alike, the count being part of the next call's descriptor."""
+        self._zero1_acc = 0
+
+    def _zero1_step_clipped(self, desc: Dict[str, object], count: int, wire: Optional[str], scale: float, hyper: List[float],
+                            error_feedback: bool, clip_norm: float, accumulated: bool = False) -> float:
+        """barrier A -> sum, stash, square -> barrier N, carrying every rank's sum of squares -> AdamW from the stash,
+        pushed -> barrier B.  Only the first launch reads a peer, so every gradient byte crosses a link once.  With
+        ``accumulated`` launch 1 adds to the stash, and the squares are those of the total."""
+        v0, v1, mine = self._zero1_sum_to_stash(desc, count, wire, scale, error_feedback, add=accumulated)
         total = 0.0
         for x in self._exchange_sqnorm(self._seq - 1, mine):  # this call's number; float64, in rank order, on every rank alike
             total += x
