@@ -966,6 +966,13 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k, const
 std::vector<at::Tensor> attn_fwd_t(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, double scale);
 std::vector<at::Tensor> attn_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                                  const at::Tensor& out, const at::Tensor& lse, double scale);
+std::vector<at::Tensor> attn_fwd_doc(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, double scale,
+                                     const at::Tensor& doc_start, const at::Tensor& doc_end);
+std::vector<at::Tensor> attn_fwd_t_doc(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, double scale,
+                                       const at::Tensor& doc_start, const at::Tensor& doc_end);
+std::vector<at::Tensor> attn_bwd_doc(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                                     const at::Tensor& out, const at::Tensor& lse, double scale, const at::Tensor& doc_start,
+                                     const at::Tensor& doc_end);
 }  // namespace gtk_attn
 
 namespace gtk_xpose {  // csrc/ops/transpose.hip
@@ -992,6 +999,10 @@ PYBIND11_MODULE(_fused, m) {
   m.def("attn_fwd", &gtk_attn::attn_fwd, "causal GQA flash attention forward (bf16, D=128): -> (o [B,S,H,D], lse2 [B,H,S])");
   m.def("attn_fwd_t", &gtk_attn::attn_fwd_t, "attn_fwd that also writes O^T [H*D, B*S]: -> (o, lse2, ot)");
   m.def("attn_bwd", &gtk_attn::attn_bwd, "flash attention backward: -> (dq, dk, dv)");
+  m.def("attn_fwd_doc", &gtk_attn::attn_fwd_doc,
+        "attn_fwd under the document mask of a packed batch (int32 [B,S] doc_start, doc_end): -> (o, lse2)");
+  m.def("attn_fwd_t_doc", &gtk_attn::attn_fwd_t_doc, "attn_fwd_doc that also writes O^T [H*D, B*S]: -> (o, lse2, ot)");
+  m.def("attn_bwd_doc", &gtk_attn::attn_bwd_doc, "document-masked flash attention backward: -> (dq, dk, dv)");
   m.doc() = "gfx950 fused kernels for the Llama-3 DP validation workload";
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
   m.def("rmsnorm_bwd", &rmsnorm_bwd);

@@ -171,10 +171,13 @@ def targets() -> List[Target]:
         # attention.hip: MFMAs whose accumulators the code does not pin to AGPRs take the VGPR form even in
         # the one-wave-per-SIMD dK/dV kernel (its S / dP chains feed the softmax VALU directly; the dV/dK
         # accumulators are pinned to AGPRs by their asm constraints).  The other kernels of the file fit
-        # 256 VGPRs and select that form anyway.
+        # 256 VGPRs and select that form anyway.  attention_doc.hip compiles the same kernels
+        # (attention_kernels.h) under the document mask with the same flag and packed fp32 VALU off.
         Target("_fused", sorted((CSRC / "ops").glob("*.hip")), "hipcc", HERE / f"_fused{EXT}",
                deps=sorted((CSRC / "ops").glob("*.h")) + [adamw_update], pybind=True, torch=True,
-               src_flags={"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}),
+               src_flags={"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+                          "attention_doc.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-Xclang", "-target-feature", "-Xclang",
+                                                "-packed-fp32-ops"]}),
     ]
 
 

@@ -76,11 +76,21 @@ def _grouped(q: T, k: T, v: T):
     return q.view(B, Hkv, H // Hkv, S, D), k.view(B, Hkv, 1, S, D), v.view(B, Hkv, 1, S, D)
 
 
-def _scores2(q: T, k: T, c: float) -> T:
-    """c QK^T in log2 units, [B, Hkv, G, S, S], -inf above the diagonal."""
+def _scores2(q: T, k: T, c: float, doc_start=None) -> T:
+    """c QK^T in log2 units, [B, Hkv, G, S, S], -inf above the diagonal and, with ``doc_start`` [B, S],
+    at the keys j < doc_start[b, i] of query i (per batch row)."""
     S = q.shape[-2]
     s2 = c * (q @ k.transpose(-1, -2))
-    return s2.masked_fill(torch.ones(S, S, dtype=torch.bool).triu(1), float("-inf"))
+    s2 = s2.masked_fill(torch.ones(S, S, dtype=torch.bool).triu(1), float("-inf"))
+    if doc_start is not None:
+        before = torch.arange(S).view(1, 1, 1, 1, S) < doc_start.cpu().long().view(-1, 1, 1, S, 1)
+        s2 = s2.masked_fill(before, float("-inf"))
+    return s2
+
+
+def _doc(doc_start) -> tuple:
+    """The optional last argument of :func:`_scores2`: the causal call stays ``_scores2(q, k, c)``."""
+    return () if doc_start is None else (doc_start,)
 
 
 def _token_major(t: T) -> T:
@@ -95,15 +105,16 @@ def _head_major(t: T, Hkv: int) -> T:
     return t.transpose(1, 2).reshape(B, Hkv, H // Hkv, S, D)
 
 
-def attn_fwd_ref64(q: T, k: T, v: T, scale: float) -> Tuple[T, T, T]:
+def attn_fwd_ref64(q: T, k: T, v: T, scale: float, doc_start=None) -> Tuple[T, T, T]:
     """(o [B, S, H, D], lse2 [B, H, S], cond_o [B, S, H, D]).
 
     P = softmax over the visible keys of c QK^T (base 2), o = P V, lse2 = log2 sum_k 2^(c q.k),
-    cond_o[q, d] = sum_k P_qk |V_kd|."""
+    cond_o[q, d] = sum_k P_qk |V_kd|.  The visible keys of query i are j <= i, and with ``doc_start``
+    (integer [B, S], the document mask of a packed batch) doc_start[b, i] <= j <= i."""
     c, _ = kernel_constants(scale)
     qg, kg, vg = _grouped(q, k, v)
     B, Hkv, G, S, D = qg.shape
-    s2 = _scores2(qg, kg, c)
+    s2 = _scores2(qg, kg, c, *_doc(doc_start))
     m = s2.amax(-1, keepdim=True)
     p = torch.exp2(s2 - m)
     l = p.sum(-1, keepdim=True)
@@ -112,7 +123,7 @@ def attn_fwd_ref64(q: T, k: T, v: T, scale: float) -> Tuple[T, T, T]:
     return _token_major(p @ vg), lse2, _token_major(p @ vg.abs())
 
 
-def attn_bwd_ref64(dout: T, q: T, k: T, v: T, out: T, lse2: T, scale: float):
+def attn_bwd_ref64(dout: T, q: T, k: T, v: T, out: T, lse2: T, scale: float, doc_start=None):
     """(dq, dk, dv, cond_dq, cond_dk, cond_dv, cond2_dq, cond2_dk), dq [B, H, S, D], dk / dv [B, Hkv, S, D].
 
     A function of the ``out`` and ``lse2`` it is given.  With P = 2^(c QK^T - lse2) on the visible keys,
@@ -122,13 +133,14 @@ def attn_bwd_ref64(dout: T, q: T, k: T, v: T, out: T, lse2: T, scale: float):
         dk = scale sum_g dS^T Q         cond_dk = scale sum_g |dS|^T |Q|     cond2_dk = scale sum_g condS^T |Q|
         dq = scale dS K                 cond_dq = scale |dS| |K|             cond2_dq = scale condS |K|
 
-    condS = P (|dout| |V|^T + rowsum|dout * out|): the cancellation in dP - delta."""
+    condS = P (|dout| |V|^T + rowsum|dout * out|): the cancellation in dP - delta.  With ``doc_start``
+    (integer [B, S]) the visible keys of query i are doc_start[b, i] <= j <= i, as in the forward."""
     c, sc = kernel_constants(scale)
     qg, kg, vg = _grouped(q, k, v)
     B, Hkv, G, S, D = qg.shape
     do, o = _head_major(_f64(dout), Hkv), _head_major(_f64(out), Hkv)
     l2 = _f64(lse2).view(B, Hkv, G, S, 1)
-    p = torch.exp2(_scores2(qg, kg, c) - l2)  # exactly 0 above the diagonal
+    p = torch.exp2(_scores2(qg, kg, c, *_doc(doc_start)) - l2)  # exactly 0 above the diagonal
     delta = (do * o).sum(-1, keepdim=True)
     ds = p * (do @ vg.transpose(-1, -2) - delta)
     conds = p * (do.abs() @ vg.abs().transpose(-1, -2) + (do * o).abs().sum(-1, keepdim=True))

@@ -573,21 +573,28 @@ class Llama(torch.nn.Module):
         return _FlatLinear.apply(x, self.P(name).detach(), self.flat, name, self.gemm_layout == "nt", x_t)
 
     # ---------------------------------------------------------------- blocks
-    def _attention(self, q, k, v, want_t: bool = False):
+    def _attention(self, q, k, v, want_t: bool = False, doc=None):
         """q [B,H,S,Dh], k/v [B,Hkv,S,Dh] -> [B,S,H,Dh] (token-major, what the o-projection reads);
-        ``want_t``: ``(o, o^T [H*Dh, B*S])`` with the transposed copy written by the forward kernel."""
+        ``want_t``: ``(o, o^T [H*Dh, B*S])`` with the transposed copy written by the forward kernel;
+        ``doc``: the pair of ``fused.doc_bounds`` of a packed batch (the document mask)."""
         if self.attn == "hip" and (not q.is_cuda or fused.flash_attention_supported(q, k)):
             if want_t:
-                return fused.attention_t(q, k, v)
-            return fused.attention(q, k, v)  # HIP MFMA flash attention (PyTorch reference on CPU)
+                return fused.attention_t(q, k, v, doc=doc)
+            return fused.attention(q, k, v, doc=doc)  # HIP MFMA flash attention (PyTorch reference on CPU)
+        causal, mask = True, None
+        if doc is not None:  # the same mask, dense, for the library paths: doc_start[b, i] <= j <= i
+            S = q.size(2)
+            j = torch.arange(S, device=q.device)
+            mask = ((j.view(1, 1, 1, S) >= doc[0].view(-1, 1, S, 1)) & (j.view(1, 1, 1, S) <= j.view(1, 1, S, 1)))
+            causal = False
         if self.attn in ("hip", "sdpa"):  # library SDPA: A/B baseline, or shapes the HIP kernel does not cover
-            o = F.scaled_dot_product_attention(q, k, v, is_causal=True, enable_gqa=q.size(1) != k.size(1))
+            o = F.scaled_dot_product_attention(q, k, v, attn_mask=mask, is_causal=causal, enable_gqa=q.size(1) != k.size(1))
         else:  # "sdpa-expand": explicit GQA expansion for SDPA backends without native GQA
             rep = q.size(1) // k.size(1)
             if rep > 1:
                 k = k.repeat_interleave(rep, dim=1)
                 v = v.repeat_interleave(rep, dim=1)
-            o = F.scaled_dot_product_attention(q, k, v, is_causal=True)
+            o = F.scaled_dot_product_attention(q, k, v, attn_mask=mask, is_causal=causal)
         o = o.transpose(1, 2)
         return (o, None) if want_t else o
 
@@ -603,7 +610,7 @@ class Llama(torch.nn.Module):
             return x, fused.rmsnorm(x, self.P(name), self.cfg.norm_eps)
         return fused.add_rmsnorm(x, r, self.P(name), self.cfg.norm_eps)
 
-    def _layer(self, i: int, x: torch.Tensor, B: int, S: int, r: Optional[torch.Tensor] = None):
+    def _layer(self, i: int, x: torch.Tensor, B: int, S: int, r: Optional[torch.Tensor] = None, doc=None):
         """One block; returns ``(x, r)``: the residual stream and the block's last branch output, which
         the next block's (or the final) norm adds in its own kernel."""
         cfg = self.cfg
@@ -615,16 +622,21 @@ class Llama(torch.nn.Module):
             # o^T from the attention kernel's epilogue: +47 us per layer in the kernel against the 43 us
             # transpose it replaces, step time unchanged in an interleaved A/B, +4.3 GB kept from the
             # forward (profiles/r04_otab)
-            o, o_t = self._attention(q, k, v, want_t=True)
+            o, o_t = self._attention(q, k, v, want_t=True, doc=doc)
         else:
-            o, o_t = self._attention(q, k, v), None
+            o, o_t = self._attention(q, k, v, doc=doc), None
         o = o.reshape(B * S, H * Dh)  # [B, S, H, Dh] -> [B*S, H*Dh]
         x, h = self._norm(x, self._linear(o, f"l{i}.wo", x_t=o_t), f"l{i}.ffn_norm")
         a, a_t = _FlatLinearSwiGLU.apply(h, self.P(f"l{i}.w13").detach(), self.flat, f"l{i}.w13", self.gemm_layout == "nt")
         return x, self._linear(a, f"l{i}.w2", x_t=a_t)
 
-    def forward(self, tokens: torch.Tensor, labels: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def forward(self, tokens: torch.Tensor, labels: Optional[torch.Tensor] = None,
+                doc_start: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``doc_start`` (integer [B, S], the first position of each token's document): the document mask of
+        a packed batch, built once here and handed to every layer.  RoPE positions are not reset at
+        document starts (Llama 3 does not reset them)."""
         B, S = tokens.shape
+        doc = None if doc_start is None else fused.doc_bounds(doc_start)
         fused.clear_t()  # transposed gradients a previous backward offered and nobody took
         if self.flat_grads:
             x = _FlatEmbedding.apply(tokens.reshape(-1), self.P("tok_emb"), self.flat, "tok_emb")  # [B*S, D]
@@ -633,9 +645,9 @@ class Llama(torch.nn.Module):
         r = None
         for i in range(self.cfg.n_layers):
             if self.checkpoint and self.training:
-                x, r = torch.utils.checkpoint.checkpoint(self._layer, i, x, B, S, r, use_reentrant=False)
+                x, r = torch.utils.checkpoint.checkpoint(self._layer, i, x, B, S, r, doc, use_reentrant=False)
             else:
-                x, r = self._layer(i, x, B, S, r)
+                x, r = self._layer(i, x, B, S, r, doc)
         _, x = self._norm(x, r, "norm")
         logits = self._linear(x, "lm_head")  # [B*S, V]
         if labels is None:

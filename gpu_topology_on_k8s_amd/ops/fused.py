@@ -15,7 +15,7 @@ from .._native import load
 __all__ = [
     "rmsnorm", "rmsnorm_ref", "rope_tables", "rope_split", "rope_split_ref", "swiglu", "swiglu_ref", "cross_entropy",
     "cross_entropy_ref", "hip", "attention", "attention_ref", "flash_attention_supported", "transpose", "swiglu_bwd_ref",
-    "swiglu_bwd_t", "swiglu_fwd_t", "attention_t", "offer_t", "take_t", "clear_t",
+    "swiglu_bwd_t", "swiglu_fwd_t", "attention_t", "offer_t", "take_t", "clear_t", "doc_bounds", "doc_start_from_eos",
 ]
 
 
@@ -280,8 +280,45 @@ def cross_entropy(logits: torch.Tensor, labels: torch.Tensor, ignore_index: int 
 
 
 # ------------------------------------------------------------------------------------ attention
-def attention_ref(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float | None = None) -> torch.Tensor:
-    """fp32 causal GQA attention: q [B,H,S,D], k/v [B,Hkv,S,D] -> o [B,S,H,D] (same dtype as q)."""
+def doc_start_from_eos(tokens: torch.Tensor, eos_id: int) -> torch.Tensor:
+    """int32 ``doc_start`` [B, S] of a packed batch whose documents end with their EOS token: the token
+    after an EOS starts a new document, token 0 starts the first."""
+    S = tokens.size(-1)
+    pos = torch.arange(S, device=tokens.device, dtype=torch.int32).expand_as(tokens)
+    first = torch.ones_like(tokens, dtype=torch.bool)
+    first[..., 1:] = tokens[..., :-1] == eos_id
+    return torch.where(first, pos, torch.zeros_like(pos)).cummax(-1).values.to(torch.int32)
+
+
+def doc_bounds(doc_start: torch.Tensor, check: bool = True):
+    """``(doc_start, doc_end)`` as contiguous int32 [B, S] on ``doc_start``'s device: the document mask
+    of a packed batch as the attention kernels read it.  ``doc_start[b, i]`` is the position of the first
+    token of token i's document; query i sees key j iff ``doc_start[b, i] <= j <= i``, which from the
+    key's side is ``j <= i < doc_end[b, j]``, one past the last token of j's document.  Computed once
+    per batch; ``check`` (one sync) raises ``ValueError`` unless ``doc_start[b, i] <= i``, non-decreasing
+    along i and constant inside a document (``doc_start[b, doc_start[b, i]] == doc_start[b, i]``)."""
+    if doc_start.dim() != 2 or doc_start.dtype.is_floating_point or doc_start.dtype == torch.bool:
+        raise ValueError("doc_bounds: doc_start must be an integer [B, S] tensor")
+    ds = doc_start.to(torch.int64)
+    B, S = ds.shape
+    pos = torch.arange(S, device=ds.device).expand(B, S)
+    if check:
+        ok = (ds >= 0) & (ds <= pos)
+        ok[:, 1:] &= ds[:, 1:] >= ds[:, :-1]
+        ok &= ds.gather(1, ds.clamp(0, S - 1)) == ds  # a document's first token starts it: constant inside it
+        if not bool(ok.all()):
+            raise ValueError("doc_bounds: doc_start must satisfy doc_start[b, i] <= i, be non-decreasing and constant "
+                             "inside a document")
+    # the next document's start, per token: the smallest first-token position after i (S after the last)
+    first = ds == pos
+    nxt = torch.where(first, pos, torch.full_like(pos, S)).flip(1).cummin(1).values.flip(1)  # first start at or after i
+    end = torch.cat([nxt[:, 1:], torch.full_like(pos[:, :1], S)], 1)
+    return ds.to(torch.int32).contiguous(), end.to(torch.int32).contiguous()
+
+
+def attention_ref(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float | None = None, doc=None) -> torch.Tensor:
+    """fp32 causal GQA attention: q [B,H,S,D], k/v [B,Hkv,S,D] -> o [B,S,H,D] (same dtype as q).
+    ``doc``: the pair of :func:`doc_bounds`; keys before ``doc_start[b, i]`` are masked too."""
     B, H, S, Dh = q.shape
     rep = H // k.size(1)
     kf = k.float().repeat_interleave(rep, dim=1)
@@ -289,54 +326,65 @@ def attention_ref(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: floa
     sc = (scale if scale is not None else Dh ** -0.5)
     s = torch.matmul(q.float(), kf.transpose(-1, -2)) * sc
     mask = torch.ones(S, S, dtype=torch.bool, device=q.device).triu(1)
+    if doc is not None:
+        mask = mask | (torch.arange(S, device=q.device).view(1, 1, 1, S) < doc[0].view(B, 1, S, 1))
     p = torch.softmax(s.masked_fill(mask, float("-inf")), dim=-1)
     return torch.matmul(p, vf).transpose(1, 2).to(q.dtype).contiguous()
 
 
 class _FlashAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, scale, with_t=False):
+    def forward(ctx, q, k, v, scale, with_t=False, doc=None):
         ctx.set_materialize_grads(False)  # no zero-filled gradient for O^T (non-differentiable) in backward
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        if with_t:  # the kernel also writes O^T [H*D, B*S] (the o-projection's NT-layout x^T)
+        if doc is not None:  # the document-masked kernels
+            res = (hip().attn_fwd_t_doc if with_t else hip().attn_fwd_doc)(q, k, v, float(scale), doc[0], doc[1])
+            o, lse, o_t = res if with_t else (*res, None)
+            if with_t:
+                ctx.mark_non_differentiable(o_t)
+        elif with_t:  # the kernel also writes O^T [H*D, B*S] (the o-projection's NT-layout x^T)
             o, lse, o_t = hip().attn_fwd_t(q, k, v, float(scale))
             ctx.mark_non_differentiable(o_t)
         else:
             o, lse = hip().attn_fwd(q, k, v, float(scale))
             o_t = None
-        ctx.save_for_backward(q, k, v, o, lse)
+        ctx.save_for_backward(q, k, v, o, lse, *(doc or ()))
         ctx.scale = float(scale)
         return o, o_t
 
     @staticmethod
     def backward(ctx, do, _do_t=None):
-        q, k, v, o, lse = ctx.saved_tensors
-        dq, dk, dv = hip().attn_bwd(do.contiguous(), q, k, v, o, lse, ctx.scale)
-        return dq, dk, dv, None, None
+        q, k, v, o, lse, *doc = ctx.saved_tensors
+        if doc:
+            dq, dk, dv = hip().attn_bwd_doc(do.contiguous(), q, k, v, o, lse, ctx.scale, doc[0], doc[1])
+        else:
+            dq, dk, dv = hip().attn_bwd(do.contiguous(), q, k, v, o, lse, ctx.scale)
+        return dq, dk, dv, None, None, None
 
 
 def flash_attention_supported(q: torch.Tensor, k: torch.Tensor) -> bool:
     return q.is_cuda and q.dtype == torch.bfloat16 and q.size(-1) == 128 and q.size(2) % 128 == 0 and q.size(1) % k.size(1) == 0
 
 
-def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float | None = None):
-    """Causal GQA attention -> [B, S, H, D]; the HIP flash kernel on GPU (head dim 128, S % 128 == 0)."""
+def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float | None = None, doc=None):
+    """Causal GQA attention -> [B, S, H, D]; the HIP flash kernel on GPU (head dim 128, S % 128 == 0).
+    ``doc``: the pair of :func:`doc_bounds` of a packed batch, no token attends across a document start."""
     sc = scale if scale is not None else q.size(-1) ** -0.5
     if q.is_cuda:
         if not flash_attention_supported(q, k):
             raise ValueError("HIP flash attention needs bf16, head dim 128 and S % 128 == 0")
-        return _FlashAttention.apply(q, k, v, sc, False)[0]
-    return attention_ref(q, k, v, sc)
+        return _FlashAttention.apply(q, k, v, sc, False, doc)[0]
+    return attention_ref(q, k, v, sc, doc)
 
 
-def attention_t(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float | None = None):
+def attention_t(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float | None = None, doc=None):
     """``(o [B, S, H, D], o^T [H*D, B*S])``: on GPU the forward kernel writes the transposed copy from
     its LDS tile (no gradient flows through it); elsewhere the reference plus a transpose."""
     sc = scale if scale is not None else q.size(-1) ** -0.5
     if q.is_cuda:
         if not flash_attention_supported(q, k):
             raise ValueError("HIP flash attention needs bf16, head dim 128 and S % 128 == 0")
-        return _FlashAttention.apply(q, k, v, sc, True)
-    o = attention_ref(q, k, v, sc)
+        return _FlashAttention.apply(q, k, v, sc, True, doc)
+    o = attention_ref(q, k, v, sc, doc)
     B, S, H, D = o.shape
     return o, o.detach().reshape(B * S, H * D).t().contiguous()
