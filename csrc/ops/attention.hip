@@ -1,8 +1,24 @@
 // Causal GQA flash attention for gfx950: the causal kernels and the pre-kernel (attention_kernels.h
 // compiled with kDoc = false) and the host code of both masks.  The document-masked kernels of packed
 // sequences are the same header compiled with kDoc = true in attention_doc.hip; the bindings here reach
-// them through gtk_docmask::launch_*.
+// them through gtk_docmask::launch_*.  Head dim 64 goes to the kernels of attention_d64.hip (both masks)
+// through gtk_attn64::launch_*; the host checks and the outputs are the same.
 #include "attention_kernels.h"
+
+namespace gtk_attn64 {  // csrc/ops/attention_d64.hip; a null document bound: the causal kernels
+
+using gtk::u16;
+
+void launch_fwd(hipStream_t st, const u16* q, const u16* k, const u16* v, u16* o, float* lse2, int B, int H, int Hkv, int S,
+                float c, u16* ot, const int* doc_start);
+void launch_bwd_pre(hipStream_t st, const u16* dout, const u16* out, const float* lse2, float* delta, float* nls, float* ndl,
+                    int B, int H, int S, float inv_c);
+void launch_dkdv(hipStream_t st, const u16* q, const u16* k, const u16* v, const u16* dout, const float* nls, const float* ndl,
+                 u16* dk, u16* dv, int B, int H, int Hkv, int S, float c, float scale, const int* doc_end);
+void launch_dq(hipStream_t st, const u16* q, const u16* k, const u16* v, const u16* dout, const float* lse2, const float* delta,
+               u16* dq, int B, int H, int Hkv, int S, float c, float scale, const int* doc_start);
+
+}  // namespace gtk_attn64
 
 namespace gtk_attn {
 
@@ -11,11 +27,12 @@ void check_qkv(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v) {
   for (const at::Tensor* x : {&q, &k, &v})
     TORCH_CHECK(x->is_cuda() && x->scalar_type() == at::kBFloat16 && x->is_contiguous() && x->dim() == 4,
                 "attention: q/k/v must be contiguous bf16 [B, heads, S, D] GPU tensors");
-  TORCH_CHECK(q.size(3) == D && k.size(3) == D && v.size(3) == D, "attention: head dim must be 128");
+  const int64_t Dh = q.size(3);
+  TORCH_CHECK((Dh == 64 || Dh == D) && k.size(3) == Dh && v.size(3) == Dh, "attention: head dim must be 64 or 128");
   TORCH_CHECK(k.sizes() == v.sizes() && q.size(0) == k.size(0) && q.size(2) == k.size(2), "attention: shape mismatch");
   TORCH_CHECK(q.size(1) % k.size(1) == 0, "attention: q heads must be a multiple of kv heads");
   TORCH_CHECK(q.size(2) % BQ == 0, "attention: sequence length must be a multiple of 128");
-  TORCH_CHECK(q.size(1) * q.size(2) * D * 2 < (int64_t(1) << 31), "attention: per-batch q/dO bytes must fit the 32-bit buffer offsets");
+  TORCH_CHECK(q.size(1) * q.size(2) * Dh * 2 < (int64_t(1) << 31), "attention: per-batch q/dO bytes must fit the 32-bit buffer offsets");
   TORCH_CHECK(k.device() == q.device() && v.device() == q.device(), "attention: q/k/v must be on one device");
 }
 
@@ -41,13 +58,16 @@ std::vector<at::Tensor> attn_fwd_impl(const at::Tensor& q, const at::Tensor& k, 
   check_qkv(q, k, v);
   check_scale(scale);
   if (doc_start) check_doc(q, *doc_start, *doc_end);
-  const int B = q.size(0), H = q.size(1), S = q.size(2), Hkv = k.size(1);
-  auto o = at::empty({B, S, H, D}, q.options());
+  const int B = q.size(0), H = q.size(1), S = q.size(2), Hkv = k.size(1), Dh = q.size(3);
+  auto o = at::empty({B, S, H, Dh}, q.options());
   auto lse = at::empty({B, H, S}, q.options().dtype(at::kFloat));
   const float c = (float)(scale * 1.4426950408889634);
   at::Tensor ot;
-  if (with_t) ot = at::empty({(int64_t)H * D, (int64_t)B * S}, q.options());
-  if (doc_start)
+  if (with_t) ot = at::empty({(int64_t)H * Dh, (int64_t)B * S}, q.options());
+  if (Dh == 64)
+    gtk_attn64::launch_fwd(cur_stream(), bp(q), bp(k), bp(v), bpm(o), lse.data_ptr<float>(), B, H, Hkv, S, c,
+                           with_t ? bpm(ot) : nullptr, doc_start ? doc_start->data_ptr<int>() : nullptr);
+  else if (doc_start)
     gtk_docmask::launch_fwd(dim3(B * H, S / BQ), cur_stream(), bp(q), bp(k), bp(v), bpm(o), lse.data_ptr<float>(), H, Hkv, S, c,
                             with_t ? bpm(ot) : nullptr, doc_start->data_ptr<int>());
   else
@@ -84,10 +104,10 @@ std::vector<at::Tensor> attn_bwd_impl(const at::Tensor& dout, const at::Tensor& 
   check_qkv(q, k, v);
   check_scale(scale);
   if (doc_start) check_doc(q, *doc_start, *doc_end);
-  const int B = q.size(0), H = q.size(1), S = q.size(2), Hkv = k.size(1);
+  const int B = q.size(0), H = q.size(1), S = q.size(2), Hkv = k.size(1), Dh = q.size(3);
   for (const at::Tensor* x : {&dout, &out})
     TORCH_CHECK(x->is_cuda() && x->device() == q.device() && x->scalar_type() == at::kBFloat16 && x->is_contiguous() &&
-                    x->dim() == 4 && x->size(0) == B && x->size(1) == S && x->size(2) == H && x->size(3) == D,
+                    x->dim() == 4 && x->size(0) == B && x->size(1) == S && x->size(2) == H && x->size(3) == Dh,
                 "attention bwd: dout/out must be contiguous bf16 [B, S, H, D] GPU tensors on q's device");
   TORCH_CHECK(lse.is_cuda() && lse.device() == q.device() && lse.is_contiguous() && lse.scalar_type() == at::kFloat &&
                   lse.dim() == 3 && lse.size(0) == B && lse.size(1) == H && lse.size(2) == S,
@@ -97,6 +117,15 @@ std::vector<at::Tensor> attn_bwd_impl(const at::Tensor& dout, const at::Tensor& 
   auto dq = at::empty_like(q), dk = at::empty_like(k), dv = at::empty_like(v);
   const int rows = B * S * H;
   const float c = (float)(scale * 1.4426950408889634);
+  if (Dh == 64) {
+    gtk_attn64::launch_bwd_pre(cur_stream(), bp(dout), bp(out), lse.data_ptr<float>(), delta.data_ptr<float>(),
+                               nls.data_ptr<float>(), ndl.data_ptr<float>(), B, H, S, 1.f / c);
+    gtk_attn64::launch_dkdv(cur_stream(), bp(q), bp(k), bp(v), bp(dout), nls.data_ptr<float>(), ndl.data_ptr<float>(), bpm(dk),
+                            bpm(dv), B, H, Hkv, S, c, (float)scale, doc_end ? doc_end->data_ptr<int>() : nullptr);
+    gtk_attn64::launch_dq(cur_stream(), bp(q), bp(k), bp(v), bp(dout), lse.data_ptr<float>(), delta.data_ptr<float>(), bpm(dq), B,
+                          H, Hkv, S, c, (float)scale, doc_start ? doc_start->data_ptr<int>() : nullptr);
+    return {dq, dk, dv};
+  }
   hipLaunchKernelGGL(attn_bwd_pre_kernel, dim3((rows + 15) / 16), dim3(256), 0, cur_stream(), bp(dout), bp(out),
                      lse.data_ptr<float>(), delta.data_ptr<float>(), nls.data_ptr<float>(), ndl.data_ptr<float>(), B, H, S,
                      1.f / c);

@@ -996,9 +996,9 @@ void adamw_step_t(at::Tensor& master, at::Tensor& m, at::Tensor& v, const at::Te
 }  // namespace gtk_adamw
 
 PYBIND11_MODULE(_fused, m) {
-  m.def("attn_fwd", &gtk_attn::attn_fwd, "causal GQA flash attention forward (bf16, D=128): -> (o [B,S,H,D], lse2 [B,H,S])");
+  m.def("attn_fwd", &gtk_attn::attn_fwd, "causal GQA flash attention forward (bf16, D=64 or 128): -> (o [B,S,H,D], lse2 [B,H,S])");
   m.def("attn_fwd_t", &gtk_attn::attn_fwd_t, "attn_fwd that also writes O^T [H*D, B*S]: -> (o, lse2, ot)");
-  m.def("attn_bwd", &gtk_attn::attn_bwd, "flash attention backward: -> (dq, dk, dv)");
+  m.def("attn_bwd", &gtk_attn::attn_bwd, "flash attention backward (D=64 or 128): -> (dq, dk, dv)");
   m.def("attn_fwd_doc", &gtk_attn::attn_fwd_doc,
         "attn_fwd under the document mask of a packed batch (int32 [B,S] doc_start, doc_end): -> (o, lse2)");
   m.def("attn_fwd_t_doc", &gtk_attn::attn_fwd_t_doc, "attn_fwd_doc that also writes O^T [H*D, B*S]: -> (o, lse2, ot)");

@@ -509,16 +509,19 @@ class _FlatEmbedding(torch.autograd.Function):
 
 class Llama(torch.nn.Module):
     def __init__(self, cfg: LlamaConfig, device="cuda", seed: int = 0, checkpoint: bool = False, attn: str = "hip",
-                 gemm_layout: str = "nt", persistent_wt: bool = True):
+                 gemm_layout: str = "nt", persistent_wt: bool = True, attn_d64: bool = False):
         """``gemm_layout``: "nt" (the GPU default, see the module docstring) or "native" (autograd's
         layouts: the reference the NT path is checked against).  ``persistent_wt=False`` re-makes every
-        W^T by a transpose in every backward (the round-3 path; A/B reference for the AdamW-written W^T)."""
+        W^T by a transpose in every backward (the round-3 path; A/B reference for the AdamW-written W^T).
+        ``attn_d64``: with ``attn="hip"``, head dim 64 runs the HIP flash kernels too (opt-in; without it
+        head dim 64 takes the library SDPA path on the GPU)."""
         super().__init__()
         if gemm_layout not in ("nt", "native"):
             raise ValueError("gemm_layout must be 'nt' or 'native'")
         self.cfg = cfg
         self.checkpoint = checkpoint
         self.attn = attn
+        self.attn_d64 = bool(attn_d64)
         self.gemm_layout = gemm_layout
         # called with a parameter name before its first use in forward (ZeRO-1: wait for that
         # bucket's weight all-gather, parallel/dp.py BucketedAllReduce.wait_param)
@@ -577,7 +580,7 @@ class Llama(torch.nn.Module):
         """q [B,H,S,Dh], k/v [B,Hkv,S,Dh] -> [B,S,H,Dh] (token-major, what the o-projection reads);
         ``want_t``: ``(o, o^T [H*Dh, B*S])`` with the transposed copy written by the forward kernel;
         ``doc``: the pair of ``fused.doc_bounds`` of a packed batch (the document mask)."""
-        if self.attn == "hip" and (not q.is_cuda or fused.flash_attention_supported(q, k)):
+        if self.attn == "hip" and (not q.is_cuda or fused.flash_attention_supported(q, k, d64=self.attn_d64)):
             if want_t:
                 return fused.attention_t(q, k, v, doc=doc)
             return fused.attention(q, k, v, doc=doc)  # HIP MFMA flash attention (PyTorch reference on CPU)

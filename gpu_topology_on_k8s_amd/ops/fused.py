@@ -362,17 +362,20 @@ class _FlashAttention(torch.autograd.Function):
         return dq, dk, dv, None, None, None
 
 
-def flash_attention_supported(q: torch.Tensor, k: torch.Tensor) -> bool:
-    return q.is_cuda and q.dtype == torch.bfloat16 and q.size(-1) == 128 and q.size(2) % 128 == 0 and q.size(1) % k.size(1) == 0
+def flash_attention_supported(q: torch.Tensor, k: torch.Tensor, d64: bool = False) -> bool:
+    """Whether the HIP flash kernels serve q, k: head dim 128, and with ``d64`` head dim 64 as well (the
+    kernels of csrc/ops/attention_d64.hip, which the model routes to only when asked: ``Llama(attn_d64=True)``)."""
+    dims = (64, 128) if d64 else (128,)
+    return q.is_cuda and q.dtype == torch.bfloat16 and q.size(-1) in dims and q.size(2) % 128 == 0 and q.size(1) % k.size(1) == 0
 
 
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float | None = None, doc=None):
-    """Causal GQA attention -> [B, S, H, D]; the HIP flash kernel on GPU (head dim 128, S % 128 == 0).
+    """Causal GQA attention -> [B, S, H, D]; the HIP flash kernel on GPU (head dim 64 or 128, S % 128 == 0).
     ``doc``: the pair of :func:`doc_bounds` of a packed batch, no token attends across a document start."""
     sc = scale if scale is not None else q.size(-1) ** -0.5
     if q.is_cuda:
-        if not flash_attention_supported(q, k):
-            raise ValueError("HIP flash attention needs bf16, head dim 128 and S % 128 == 0")
+        if not flash_attention_supported(q, k, d64=True):
+            raise ValueError("HIP flash attention needs bf16, head dim 64 or 128 and S % 128 == 0")
         return _FlashAttention.apply(q, k, v, sc, False, doc)[0]
     return attention_ref(q, k, v, sc, doc)
 
@@ -382,8 +385,8 @@ def attention_t(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float 
     its LDS tile (no gradient flows through it); elsewhere the reference plus a transpose."""
     sc = scale if scale is not None else q.size(-1) ** -0.5
     if q.is_cuda:
-        if not flash_attention_supported(q, k):
-            raise ValueError("HIP flash attention needs bf16, head dim 128 and S % 128 == 0")
+        if not flash_attention_supported(q, k, d64=True):
+            raise ValueError("HIP flash attention needs bf16, head dim 64 or 128 and S % 128 == 0")
         return _FlashAttention.apply(q, k, v, sc, True, doc)
     o = attention_ref(q, k, v, sc, doc)
     B, S, H, D = o.shape
