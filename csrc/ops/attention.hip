@@ -2,7 +2,8 @@
 // compiled with kDoc = false) and the host code of both masks.  The document-masked kernels of packed
 // sequences are the same header compiled with kDoc = true in attention_doc.hip; the bindings here reach
 // them through gtk_docmask::launch_*.  Head dim 64 goes to the kernels of attention_d64.hip (both masks)
-// through gtk_attn64::launch_*; the host checks and the outputs are the same.
+// through gtk_attn64::launch_*; the host checks and the outputs are the same.  A query chunk at an offset
+// into longer K/V (attn_*_qoff) goes to the kernels of attention_qoff.hip through gtk_qoff::launch_*.
 #include "attention_kernels.h"
 
 namespace gtk_attn64 {  // csrc/ops/attention_d64.hip; a null document bound: the causal kernels
@@ -146,6 +147,83 @@ std::vector<at::Tensor> attn_bwd_impl(const at::Tensor& dout, const at::Tensor& 
 std::vector<at::Tensor> attn_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                                  const at::Tensor& out, const at::Tensor& lse, double scale) {
   return attn_bwd_impl(dout, q, k, v, out, lse, scale);
+}
+
+// ---------------------------------------------------------------- a query chunk at an offset into longer K/V
+// q [B, H, Sq, 128] stands at positions q_offset .. q_offset + Sq - 1 of the Sk keys of k, v [B, Hkv, Sk, 128];
+// query i sees key j iff j <= q_offset + i.  check_qkv's checks with the equal sequence lengths replaced by
+// the window's requirements; every refusal names what was wrong.
+void check_qkv_qoff(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, int64_t q_offset) {
+  for (const at::Tensor* x : {&q, &k, &v})
+    TORCH_CHECK(x->is_cuda() && x->scalar_type() == at::kBFloat16 && x->is_contiguous() && x->dim() == 4,
+                "attention: q/k/v must be contiguous bf16 [B, heads, S, D] GPU tensors");
+  TORCH_CHECK(q.size(3) == D && k.size(3) == D && v.size(3) == D, "attention: q_offset needs head dim 128, got ", q.size(3));
+  TORCH_CHECK(k.sizes() == v.sizes() && q.size(0) == k.size(0), "attention: shape mismatch (k and v alike, one batch size)");
+  TORCH_CHECK(q.size(1) % k.size(1) == 0, "attention: q heads must be a multiple of kv heads");
+  const int64_t Sq = q.size(2), Sk = k.size(2);
+  TORCH_CHECK(Sq > 0 && Sq % BQ == 0, "attention: query length must be a positive multiple of 128, got ", Sq);
+  TORCH_CHECK(Sk % KB == 0, "attention: key length must be a multiple of 128, got ", Sk);
+  TORCH_CHECK(q_offset >= 0 && q_offset % BQ == 0, "attention: q_offset must be a non-negative multiple of 128, got ", q_offset);
+  TORCH_CHECK(q_offset + Sq <= Sk, "attention: q_offset + query length (", q_offset, " + ", Sq, ") exceeds the key length ", Sk);
+  TORCH_CHECK(q.size(1) * Sq * D * 2 < (int64_t(1) << 31), "attention: per-batch q/dO bytes must fit the 32-bit buffer offsets");
+  TORCH_CHECK(k.size(1) * Sk * D * 2 < (int64_t(1) << 31), "attention: per-batch K/V bytes must fit the 32-bit buffer offsets");
+  TORCH_CHECK(k.device() == q.device() && v.device() == q.device(), "attention: q/k/v must be on one device");
+}
+
+std::vector<at::Tensor> attn_fwd_qoff_impl(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, double scale,
+                                           int64_t q_offset, bool with_t) {
+  check_qkv_qoff(q, k, v, q_offset);
+  check_scale(scale);
+  const int B = q.size(0), H = q.size(1), Sq = q.size(2), Hkv = k.size(1), Sk = k.size(2);
+  auto o = at::empty({B, Sq, H, D}, q.options());
+  auto lse = at::empty({B, H, Sq}, q.options().dtype(at::kFloat));
+  at::Tensor ot;
+  if (with_t) ot = at::empty({(int64_t)H * D, (int64_t)B * Sq}, q.options());
+  gtk_qoff::launch_fwd(dim3(B * H, Sq / BQ), cur_stream(), bp(q), bp(k), bp(v), bpm(o), lse.data_ptr<float>(), H, Hkv, Sq,
+                       (float)(scale * 1.4426950408889634), with_t ? bpm(ot) : nullptr, Sk, (int)q_offset);
+  if (with_t) return {o, lse, ot};
+  return {o, lse};
+}
+
+// -> (o [B, Sq, H, 128], lse2 [B, H, Sq])
+std::vector<at::Tensor> attn_fwd_qoff(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, double scale,
+                                      int64_t q_offset) {
+  return attn_fwd_qoff_impl(q, k, v, scale, q_offset, false);
+}
+
+// -> (o, lse2, O^T [H*128, B*Sq])
+std::vector<at::Tensor> attn_fwd_t_qoff(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, double scale,
+                                        int64_t q_offset) {
+  return attn_fwd_qoff_impl(q, k, v, scale, q_offset, true);
+}
+
+// -> (dq [B, H, Sq, 128], dk, dv [B, Hkv, Sk, 128]) from the out and lse it is given; keys no query sees
+// (at or after q_offset + Sq) get zeros, written by the dK/dV kernel
+std::vector<at::Tensor> attn_bwd_qoff(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                                      const at::Tensor& out, const at::Tensor& lse, double scale, int64_t q_offset) {
+  check_qkv_qoff(q, k, v, q_offset);
+  check_scale(scale);
+  const int B = q.size(0), H = q.size(1), Sq = q.size(2), Hkv = k.size(1), Sk = k.size(2);
+  for (const at::Tensor* x : {&dout, &out})
+    TORCH_CHECK(x->is_cuda() && x->device() == q.device() && x->scalar_type() == at::kBFloat16 && x->is_contiguous() &&
+                    x->dim() == 4 && x->size(0) == B && x->size(1) == Sq && x->size(2) == H && x->size(3) == D,
+                "attention bwd: dout/out must be contiguous bf16 [B, Sq, H, D] GPU tensors on q's device");
+  TORCH_CHECK(lse.is_cuda() && lse.device() == q.device() && lse.is_contiguous() && lse.scalar_type() == at::kFloat &&
+                  lse.dim() == 3 && lse.size(0) == B && lse.size(1) == H && lse.size(2) == Sq,
+              "attention bwd: lse must be a contiguous fp32 [B, H, Sq] GPU tensor on q's device");
+  auto fopt = q.options().dtype(at::kFloat);
+  auto delta = at::empty({B, H, Sq}, fopt), nls = at::empty({B, H, Sq}, fopt), ndl = at::empty({B, H, Sq}, fopt);
+  auto dq = at::empty_like(q), dk = at::empty_like(k), dv = at::empty_like(v);
+  const int rows = B * Sq * H;
+  const float c = (float)(scale * 1.4426950408889634);
+  hipLaunchKernelGGL(attn_bwd_pre_kernel, dim3((rows + 15) / 16), dim3(256), 0, cur_stream(), bp(dout), bp(out),
+                     lse.data_ptr<float>(), delta.data_ptr<float>(), nls.data_ptr<float>(), ndl.data_ptr<float>(), B, H, Sq,
+                     1.f / c);
+  gtk_qoff::launch_dkdv(dim3(B * Hkv, Sk / KB), cur_stream(), bp(q), bp(k), bp(v), bp(dout), nls.data_ptr<float>(),
+                        ndl.data_ptr<float>(), bpm(dk), bpm(dv), H, Hkv, Sq, c, (float)scale, Sk, (int)q_offset);
+  gtk_qoff::launch_dq(dim3(B * H, Sq / BQ), cur_stream(), bp(q), bp(k), bp(v), bp(dout), lse.data_ptr<float>(),
+                      delta.data_ptr<float>(), bpm(dq), H, Hkv, Sq, c, (float)scale, Sk, (int)q_offset);
+  return {dq, dk, dv};
 }
 
 // the document-masked backward, from the outputs of attn_fwd_doc

@@ -33,7 +33,7 @@
 
 #include "bf16.h"
 
-// This header is compiled twice.  Included by attention.hip it gives the causal kernels (kDoc = false:
+// This header is compiled three times.  Included by attention.hip it gives the causal kernels (kDoc = false:
 // every `if (kDoc)` below is dead code and the kernels are the ones measured in profiles/) and the
 // pre-kernel.  Included by attention_doc.hip with GTK_ATTN_DOC_TU defined it gives the document-masked
 // kernels of packed sequences (kDoc = true, one more parameter: the int32 [B, S] bound) in namespace
@@ -42,14 +42,44 @@
 // bodies inlined into wrapper kernels the compiler chose another form of v_pk_mul_f32 for the forward's
 // O rescale, and that build's outputs changed from launch to launch at the training shape.  The cause
 // of that is not known (profiles/attn_doc/SUMMARY.md); until it is, the causal code is not to move.
+//
+// Included by attention_qoff.hip with GTK_ATTN_QOFF_TU defined it gives, in namespace gtk_qoff and with
+// attention_doc.hip's flags, the causal kernels of a query chunk at an offset into longer K/V (kQoff =
+// true, kDoc = false): S is then the number of QUERIES, and two more parameters give the number of keys
+// Sk >= S and the position q_offset of query 0 in the key sequence (both multiples of 128, q_offset +
+// S <= Sk).  Query i sees key j iff j <= q_offset + i.  The mode enters through four macros that expand
+// to the old text in the other two translation units (the gfx950 assembly of both is instruction for
+// instruction what it was, profiles/attn_qoff/SUMMARY.md), and through `if (kQoff)` blocks that are dead
+// code there:
+//   GTK_QOFF_PARAM(decl)  one more kernel parameter;
+//   GTK_QOFF_ARG(x, old)  x here, the old text elsewhere (where x may name such a parameter);
+//   GTK_KLEN(S)           the length of the key sequence: Sk here, S elsewhere;
+//   GTK_QPOS(x)           the key-sequence position of query index x: q_offset + x here, x elsewhere.
+// Everything addressed by a query (q, dO, o, O^T, lse, delta, dq) keeps S; the K/V staging, kvoff and the
+// dk / dv stores take GTK_KLEN(S); every comparison of a key with a query takes GTK_QPOS of the query.
 #ifdef GTK_ATTN_DOC_TU
 #define GTK_ATTN_NS gtk_docmask
 #define GTK_DOC_PARAM(decl) , decl
 #define GTK_DOC_ARG(x) x
 #else
+#ifdef GTK_ATTN_QOFF_TU
+#define GTK_ATTN_NS gtk_qoff
+#else
 #define GTK_ATTN_NS gtk_attn
+#endif
 #define GTK_DOC_PARAM(decl)
 #define GTK_DOC_ARG(x) static_cast<const int*>(nullptr)
+#endif
+#ifdef GTK_ATTN_QOFF_TU
+#define GTK_QOFF_PARAM(decl) , decl
+#define GTK_QOFF_ARG(x, dflt) x
+#define GTK_KLEN(S) Sk
+#define GTK_QPOS(x) (q_offset + (x))
+#else
+#define GTK_QOFF_PARAM(decl)
+#define GTK_QOFF_ARG(x, dflt) dflt
+#define GTK_KLEN(S) S
+#define GTK_QPOS(x) (x)
 #endif
 
 namespace GTK_ATTN_NS {
@@ -60,6 +90,11 @@ using namespace gtk;
 constexpr bool kDoc = true;
 #else
 constexpr bool kDoc = false;
+#endif
+#ifdef GTK_ATTN_QOFF_TU
+constexpr bool kQoff = true;
+#else
+constexpr bool kQoff = false;
 #endif
 
 typedef u16 u16x4 __attribute__((ext_vector_type(4)));
@@ -263,7 +298,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd2_kernel(const u16* __restrict
                                                            const u16* __restrict__ v, u16* __restrict__ o,
                                                            float* __restrict__ lse2, int H, int Hkv, int S, float c,
                                                            u16* __restrict__ ot = nullptr
-                                                           GTK_DOC_PARAM(const int* __restrict__ doc_start = nullptr)) {
+                                                           GTK_DOC_PARAM(const int* __restrict__ doc_start = nullptr)
+                                                           GTK_QOFF_PARAM(int Sk = 0) GTK_QOFF_PARAM(int q_offset = 0)) {
   __shared__ __attribute__((aligned(16))) char smem[2 * 2 * BK * D * 2];  // [buf][K image | V image]
   const int t = threadIdx.x, lane = t & 63, r = lane & 31, hh = lane >> 5;
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -271,7 +307,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd2_kernel(const u16* __restrict
   const int qb = nqb - 1 - blockIdx.y;  // heaviest first
   const int bh = xcd_head(blockIdx.x, gridDim.x), b = bh / H, hq = bh % H, hk = hq / (H / Hkv);
   const u16* qp = q + ((size_t)(b * H + hq) * S) * D;
-  const size_t kvoff = ((size_t)(b * Hkv + hk) * S) * D;
+  const size_t kvoff = ((size_t)(b * Hkv + hk) * GTK_KLEN(S)) * D;
   const int q0 = qb * BQ + w * 32;
   const int myq = q0 + r;
 
@@ -284,11 +320,11 @@ __global__ __launch_bounds__(256, 2) void attn_fwd2_kernel(const u16* __restrict
   for (int dt = 0; dt < 4; ++dt) oacc[dt] = f32x16{};
   float m = kDoc ? kMinM : -INFINITY, l = 0.f;  // m in units of log2 (score * c)
 
-  const int ntiles = (qb * BQ + BQ) / BK;
+  const int ntiles = (GTK_QPOS(qb * BQ) + BQ) / BK;  // kQoff: q_offset / BK more, all of them unmasked
   DocTiles dt_;
   if (kDoc) dt_ = DocTiles(GTK_DOC_ARG(doc_start) + (size_t)b * S, qb, q0, myq, ntiles);
   const int lo = dt_.lo, kt0 = kDoc ? dt_.kt0 : 0, ktm = dt_.ktm, wlo0 = dt_.wlo0, wlo1 = dt_.wlo1;
-  const KVStage stage(k + kvoff, v + kvoff, S, w, lane);
+  const KVStage stage(k + kvoff, v + kvoff, GTK_KLEN(S), w, lane);
   auto gload = [&](int kt, char* img) { stage.load(kt, img); };
 
   // one KV tile: QK^T, DMA of the next tile, online softmax, PV.  `masked` (compile-time at each
@@ -325,8 +361,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd2_kernel(const u16* __restrict
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         const int k0i = key0 + crow(i, hh);
-        if (k0i > myq) s0[i] = -INFINITY;
-        if (k0i + 32 > myq) s1[i] = -INFINITY;
+        if (k0i > GTK_QPOS(myq)) s0[i] = -INFINITY;
+        if (k0i + 32 > GTK_QPOS(myq)) s1[i] = -INFINITY;
       }
     }
     if (kDoc && low) {
@@ -395,10 +431,11 @@ __global__ __launch_bounds__(256, 2) void attn_fwd2_kernel(const u16* __restrict
     dma_sync();
   }
   // the block's diagonal: tile ntiles-2 covers keys [128 qb, 128 qb + 64), ntiles-1 the next 64
+  // (kQoff: both from q_offset on)
   for (; kt < ntiles; ++kt) {
     const int key0 = kt * BK;
-    if (key0 <= q0 + 31 && (!kDoc || key0 + BK > wlo0)) {
-      tile(kt, key0 + BK - 1 > q0, kDoc && key0 < wlo1);
+    if (key0 <= GTK_QPOS(q0) + 31 && (!kDoc || key0 + BK > wlo0)) {
+      tile(kt, key0 + BK - 1 > GTK_QPOS(q0), kDoc && key0 < wlo1);
     } else if (kt + 1 < ntiles) {
       gload(kt + 1, smem + ((kt + 1) & 1) * (2 * BK * D * 2));
     }
@@ -453,7 +490,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd2_kernel(const u16* __restrict
 // ==================================================================================== backward
 // delta[b, h, q] = sum_d dO[b, q, h, d] * O[b, q, h, d] (one 16-lane group per row; dQ reads it), plus
 // what dK/dV starts its S / dP chains from: nls = -lse2 / c, ndl = -delta
-#ifndef GTK_ATTN_DOC_TU
+#if !defined(GTK_ATTN_DOC_TU) && !defined(GTK_ATTN_QOFF_TU)
 __global__ __launch_bounds__(256) void attn_bwd_pre_kernel(const u16* __restrict__ dout, const u16* __restrict__ out,
                                                             const float* __restrict__ lse2, float* __restrict__ delta,
                                                             float* __restrict__ nls, float* __restrict__ ndl, int B, int H,
@@ -514,19 +551,37 @@ constexpr int SL_Q = 0, SL_DO = QT * D * 2, SL_LSE = 2 * QT * D * 2, SL_DEL = SL
 // last key, and needs the document mask (query >= doc_end of the lane's key -> p = 0, in gap 8 beside
 // the causal select) iff it ends after doc_end of the wave's first key.  doc_end is clamped to
 // [key + 1, S]: the block's four diagonal slices are always swept and no slice lies past S.
+//
+// kQoff: the grid is (B*Hkv, Sk/KB) and a key block is of one of three wave-uniform classes.  Below the
+// window (kb*KB < q_offset) it sweeps all G * S/QT slices, none dead and none masked (ndiag = 0): the
+// heaviest blocks, equally heavy, and first in launch order.  Inside the window it is the causal block
+// whose first slice is qt0 = (kb*KB - q_offset) / QT, the dead and diagonal tests on key-sequence
+// positions.  Past the window (kb*KB >= q_offset + S) no query sees it: it stores zeros to its 128 rows
+// of dk and dv and returns before anything else, since the ring below assumes at least one slice.
 __global__ __launch_bounds__(256, 1) void attn_bwd_dkdv_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
                                                                 const u16* __restrict__ v, const u16* __restrict__ dout,
                                                                 const float* __restrict__ nls, const float* __restrict__ ndl,
                                                                 u16* __restrict__ dk, u16* __restrict__ dv, int H, int Hkv,
                                                                 int S, float c, float scale
-                                                                GTK_DOC_PARAM(const int* __restrict__ doc_end)) {
+                                                                GTK_DOC_PARAM(const int* __restrict__ doc_end)
+                                                                GTK_QOFF_PARAM(int Sk) GTK_QOFF_PARAM(int q_offset)) {
   __shared__ __attribute__((aligned(16))) char smem[3 * SL_BYTES];  // slice ring
   const int t = threadIdx.x, lane = t & 63, r = lane & 31, hh = lane >> 5;
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);
   const int kb = blockIdx.y;
   const int bk = xcd_head(blockIdx.x, gridDim.x), b = bk / Hkv, hk = bk % Hkv, G = H / Hkv;
-  const size_t kvoff = ((size_t)(b * Hkv + hk) * S + (size_t)kb * KB) * D;
+  const size_t kvoff = ((size_t)(b * Hkv + hk) * GTK_KLEN(S) + (size_t)kb * KB) * D;
   const int krow = w * 32 + r, mykey = kb * KB + krow, kmin = kb * KB + w * 32;
+  if (kQoff) {
+    if (kb * KB >= GTK_QPOS(S)) {  // past the window: KB rows x 256 B of zeros to each of dk and dv
+#pragma unroll
+      for (int i = 0; i < KB * D * 2 / 16 / 256; ++i) {
+        reinterpret_cast<uint4*>(dk + kvoff)[t + 256 * i] = uint4{0u, 0u, 0u, 0u};
+        reinterpret_cast<uint4*>(dv + kvoff)[t + 256 * i] = uint4{0u, 0u, 0u, 0u};
+      }
+      return;
+    }
+  }
   bf16x8 kf[8], vf[8];
 #pragma unroll
   for (int s = 0; s < 8; ++s) {
@@ -547,7 +602,15 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkdv_kernel(const u16* __rest
     dmax = clampi(de[kmin + 31], kmin + 32, S);
     myend = clampi(de[mykey], mykey + 1, S);
   }
-  const int qt0 = (kb * KB) / QT, nqt = (kDoc ? (qend + QT - 1) / QT : S / QT) - qt0, nslice = G * nqt;
+  int qt0 = (kb * KB) / QT, nqt = (kDoc ? (qend + QT - 1) / QT : S / QT) - qt0;
+  [[maybe_unused]] int ndiag = KB / QT;  // kQoff: slices of each q-head that touch the block's diagonal
+  if (kQoff) {
+    const int krel = kb * KB - GTK_QOFF_ARG(q_offset, 0);  // the block's first key from the window's first query
+    qt0 = krel < 0 ? 0 : krel / QT;
+    nqt = S / QT - qt0;
+    ndiag = krel < 0 ? 0 : KB / QT;
+  }
+  const int nslice = G * nqt;
 
   const uint32_t qbytes = (uint32_t)((size_t)H * S * D * 2), dbytes = (uint32_t)((size_t)S * H * D * 2);
   const auto qrs = __builtin_amdgcn_make_buffer_rsrc((void*)(q + (size_t)b * H * S * D), 0, qbytes, 0x00020000);
@@ -648,10 +711,10 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkdv_kernel(const u16* __rest
     // (3) softmax / dS of this slice under the deferred dV/dK MFMAs of the previous one
     // diagonal slices (the block's first KB/QT query tiles) mask from qbase; slices wholly above this
     // wave's keys are dead (every score masked)
-    const int qbase = (qt0 + cur_j) * QT;
-    const bool dead = (cur_j < KB / QT && qbase + QT - 1 < kmin) || (kDoc && qbase >= dmax);
+    const int qbase = GTK_QPOS((qt0 + cur_j) * QT);
+    const bool dead = (cur_j < GTK_QOFF_ARG(ndiag, KB / QT) && qbase + QT - 1 < kmin) || (kDoc && qbase >= dmax);
     const bool docm = kDoc && qbase + QT > dmin;  // wave-uniform: some query of the slice is past some key's document
-    const int kill_from = dead ? -(1 << 30) : (cur_j < KB / QT ? qbase : 1 << 30);
+    const int kill_from = dead ? -(1 << 30) : (cur_j < GTK_QOFF_ARG(ndiag, KB / QT) ? qbase : 1 << 30);
     Packs cur;
     // The dV/dK MFMAs are asm statements, which the scheduling-group barriers do not see; each gap's
     // VALU is pinned between its two MFMAs instead: an empty asm right after MFMA i "writes" the gap's
@@ -737,8 +800,8 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkdv_kernel(const u16* __rest
   // asm MFMAs are invisible to the hazard recognizer: their results settle before the reads
   asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" : "+a"(dvt[0]), "+a"(dvt[1]), "+a"(dvt[2]), "+a"(dvt[3]), "+a"(dkt[0]),
                  "+a"(dkt[1]), "+a"(dkt[2]), "+a"(dkt[3]));
-  u16* dkrow = dk + ((size_t)(b * Hkv + hk) * S + mykey) * D;
-  u16* dvrow = dv + ((size_t)(b * Hkv + hk) * S + mykey) * D;
+  u16* dkrow = dk + ((size_t)(b * Hkv + hk) * GTK_KLEN(S) + mykey) * D;
+  u16* dvrow = dv + ((size_t)(b * Hkv + hk) * GTK_KLEN(S) + mykey) * D;
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
@@ -816,13 +879,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq2n_kernel(const u16* __rest
                                                                const u16* __restrict__ v, const u16* __restrict__ dout,
                                                                const float* __restrict__ lse2, const float* __restrict__ delta,
                                                                u16* __restrict__ dq, int H, int Hkv, int S, float c, float scale
-                                                               GTK_DOC_PARAM(const int* __restrict__ doc_start)) {
+                                                               GTK_DOC_PARAM(const int* __restrict__ doc_start)
+                                                               GTK_QOFF_PARAM(int Sk) GTK_QOFF_PARAM(int q_offset)) {
   __shared__ __attribute__((aligned(16))) char smem[2 * 2 * BK * D * 2];  // [buf][K image | V image]
   const int t = threadIdx.x, lane = t & 63, r = lane & 31, hh = lane >> 5;
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);
   const int nqb = gridDim.y, qb = nqb - 1 - blockIdx.y;
   const int bh = xcd_head(blockIdx.x, gridDim.x), b = bh / H, hq = bh % H, hk = hq / (H / Hkv);
-  const size_t kvoff = ((size_t)(b * Hkv + hk) * S) * D;
+  const size_t kvoff = ((size_t)(b * Hkv + hk) * GTK_KLEN(S)) * D;
   const int q0 = qb * BQ + w * 32, myq = q0 + r;
   const u16* qrow = q + ((size_t)(b * H + hq) * S + myq) * D;
   const u16* dorow = dout + (((size_t)b * S + myq) * H + hq) * D;
@@ -836,10 +900,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq2n_kernel(const u16* __rest
   f32x16 dqt[4];
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) dqt[dt] = f32x16{};
-  const int ntiles = (qb * BQ + BQ) / BK;
+  const int ntiles = (GTK_QPOS(qb * BQ) + BQ) / BK;
   DocTiles dt_;
   if (kDoc) dt_ = DocTiles(GTK_DOC_ARG(doc_start) + (size_t)b * S, qb, q0, myq, ntiles);
-  const KVStage stage(k + kvoff, v + kvoff, S, w, lane);
+  const KVStage stage(k + kvoff, v + kvoff, GTK_KLEN(S), w, lane);
   auto tile = [&](int kt, bool masked) {
     const char* kimg = smem + (kt & 1) * (2 * BK * D * 2);
     char* nimg = smem + ((kt + 1) & 1) * (2 * BK * D * 2);
@@ -847,9 +911,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq2n_kernel(const u16* __rest
       dq_tile_na<true, true>(kimg, kimg + BK * D * 2, nimg, kt + 1 < ntiles, stage, kt, qf, df, dqt, lse_q, del_q, lane, r, hh,
                              myq, c, dt_.lo);
     else if (masked)
-      dq_tile_na<true>(kimg, kimg + BK * D * 2, nimg, kt + 1 < ntiles, stage, kt, qf, df, dqt, lse_q, del_q, lane, r, hh, myq, c);
+      dq_tile_na<true>(kimg, kimg + BK * D * 2, nimg, kt + 1 < ntiles, stage, kt, qf, df, dqt, lse_q, del_q, lane, r, hh,
+                       GTK_QPOS(myq), c);
     else
-      dq_tile_na<false>(kimg, kimg + BK * D * 2, nimg, kt + 1 < ntiles, stage, kt, qf, df, dqt, lse_q, del_q, lane, r, hh, myq, c);
+      dq_tile_na<false>(kimg, kimg + BK * D * 2, nimg, kt + 1 < ntiles, stage, kt, qf, df, dqt, lse_q, del_q, lane, r, hh,
+                        GTK_QPOS(myq), c);
   };
   const int kt0 = kDoc ? dt_.kt0 : 0;
   stage.load(kt0, smem + (kt0 & 1) * (2 * BK * D * 2));
@@ -886,8 +952,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq2n_kernel(const u16* __rest
     }
     for (; kt < ntiles; ++kt) {
       const int key0 = kt * BK;
-      if (key0 <= q0 + 31) {
-        tile(kt, key0 + BK - 1 > q0);
+      if (key0 <= GTK_QPOS(q0) + 31) {
+        tile(kt, key0 + BK - 1 > GTK_QPOS(q0));
       } else if (kt + 1 < ntiles) {
         stage.load(kt + 1, smem + ((kt + 1) & 1) * (2 * BK * D * 2));
       }
@@ -931,3 +997,18 @@ void launch_dq(dim3 grid, hipStream_t st, const u16* q, const u16* k, const u16*
                const float* delta, u16* dq, int H, int Hkv, int S, float c, float scale, const int* doc_start);
 
 }  // namespace gtk_docmask
+
+// ============================================================================ offset-window launches
+// The same for the kernels of attention_qoff.hip: S queries at q_offset into Sk keys.
+namespace gtk_qoff {
+
+using gtk::u16;
+
+void launch_fwd(dim3 grid, hipStream_t st, const u16* q, const u16* k, const u16* v, u16* o, float* lse2, int H, int Hkv, int S,
+                float c, u16* ot, int Sk, int q_offset);
+void launch_dkdv(dim3 grid, hipStream_t st, const u16* q, const u16* k, const u16* v, const u16* dout, const float* nls,
+                 const float* ndl, u16* dk, u16* dv, int H, int Hkv, int S, float c, float scale, int Sk, int q_offset);
+void launch_dq(dim3 grid, hipStream_t st, const u16* q, const u16* k, const u16* v, const u16* dout, const float* lse2,
+               const float* delta, u16* dq, int H, int Hkv, int S, float c, float scale, int Sk, int q_offset);
+
+}  // namespace gtk_qoff

@@ -973,6 +973,12 @@ std::vector<at::Tensor> attn_fwd_t_doc(const at::Tensor& q, const at::Tensor& k,
 std::vector<at::Tensor> attn_bwd_doc(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                                      const at::Tensor& out, const at::Tensor& lse, double scale, const at::Tensor& doc_start,
                                      const at::Tensor& doc_end);
+std::vector<at::Tensor> attn_fwd_qoff(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, double scale,
+                                      int64_t q_offset);
+std::vector<at::Tensor> attn_fwd_t_qoff(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, double scale,
+                                        int64_t q_offset);
+std::vector<at::Tensor> attn_bwd_qoff(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                                      const at::Tensor& out, const at::Tensor& lse, double scale, int64_t q_offset);
 }  // namespace gtk_attn
 
 namespace gtk_xpose {  // csrc/ops/transpose.hip
@@ -1003,6 +1009,11 @@ PYBIND11_MODULE(_fused, m) {
         "attn_fwd under the document mask of a packed batch (int32 [B,S] doc_start, doc_end): -> (o, lse2)");
   m.def("attn_fwd_t_doc", &gtk_attn::attn_fwd_t_doc, "attn_fwd_doc that also writes O^T [H*D, B*S]: -> (o, lse2, ot)");
   m.def("attn_bwd_doc", &gtk_attn::attn_bwd_doc, "document-masked flash attention backward: -> (dq, dk, dv)");
+  m.def("attn_fwd_qoff", &gtk_attn::attn_fwd_qoff,
+        "attn_fwd (D=128) for Sq queries at q_offset into Sk >= Sq keys: -> (o [B,Sq,H,D], lse2 [B,H,Sq])");
+  m.def("attn_fwd_t_qoff", &gtk_attn::attn_fwd_t_qoff, "attn_fwd_qoff that also writes O^T [H*D, B*Sq]: -> (o, lse2, ot)");
+  m.def("attn_bwd_qoff", &gtk_attn::attn_bwd_qoff,
+        "backward of attn_fwd_qoff: -> (dq [B,H,Sq,D], dk, dv [B,Hkv,Sk,D]; zeros for keys past the window)");
   m.doc() = "gfx950 fused kernels for the Llama-3 DP validation workload";
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
   m.def("rmsnorm_bwd", &rmsnorm_bwd);

@@ -173,14 +173,17 @@ def targets() -> List[Target]:
         # accumulators are pinned to AGPRs by their asm constraints).  The other kernels of the file fit
         # 256 VGPRs and select that form anyway.  attention_doc.hip compiles the same kernels
         # (attention_kernels.h) under the document mask with the same flag and packed fp32 VALU off.
-        # attention_d64.hip (the head-dim-64 family, attention_d64_kernels.h) takes attention_doc.hip's flags.
+        # attention_d64.hip (the head-dim-64 family, attention_d64_kernels.h) takes attention_doc.hip's flags, and
+        # so does attention_qoff.hip (attention_kernels.h for a query chunk at an offset into longer K/V).
         Target("_fused", sorted((CSRC / "ops").glob("*.hip")), "hipcc", HERE / f"_fused{EXT}",
                deps=sorted((CSRC / "ops").glob("*.h")) + [adamw_update], pybind=True, torch=True,
                src_flags={"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                           "attention_doc.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-Xclang", "-target-feature", "-Xclang",
                                                 "-packed-fp32-ops"],
                           "attention_d64.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-Xclang", "-target-feature", "-Xclang",
-                                                "-packed-fp32-ops"]}),
+                                                "-packed-fp32-ops"],
+                          "attention_qoff.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-Xclang", "-target-feature", "-Xclang",
+                                                 "-packed-fp32-ops"]}),
     ]
 
 

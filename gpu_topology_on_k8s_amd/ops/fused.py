@@ -316,9 +316,37 @@ def doc_bounds(doc_start: torch.Tensor, check: bool = True):
     return ds.to(torch.int32).contiguous(), end.to(torch.int32).contiguous()
 
 
-def attention_ref(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float | None = None, doc=None) -> torch.Tensor:
+def _check_q_offset(q: torch.Tensor, k: torch.Tensor, q_offset, doc) -> None:
+    """The requirements of a query chunk at ``q_offset`` into longer K/V, refused before any launch."""
+    if doc is not None:
+        raise ValueError("attention: q_offset cannot be combined with doc")
+    if q.size(-1) != 128:
+        raise ValueError(f"attention: q_offset needs head dim 128, got {q.size(-1)}")
+    Sq, Sk = q.size(2), k.size(2)
+    if isinstance(q_offset, bool) or not isinstance(q_offset, int) or q_offset < 0 or q_offset % 128:
+        raise ValueError(f"attention: q_offset must be a non-negative multiple of 128, got {q_offset!r}")
+    if Sq == 0 or Sq % 128:
+        raise ValueError(f"attention: query length must be a positive multiple of 128, got {Sq}")
+    if Sk % 128:
+        raise ValueError(f"attention: key length must be a multiple of 128, got {Sk}")
+    if q_offset + Sq > Sk:
+        raise ValueError(f"attention: q_offset + query length ({q_offset} + {Sq}) exceeds the key length {Sk}")
+
+
+def attention_ref(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float | None = None, doc=None,
+                  q_offset: int | None = None) -> torch.Tensor:
     """fp32 causal GQA attention: q [B,H,S,D], k/v [B,Hkv,S,D] -> o [B,S,H,D] (same dtype as q).
-    ``doc``: the pair of :func:`doc_bounds`; keys before ``doc_start[b, i]`` are masked too."""
+    ``doc``: the pair of :func:`doc_bounds`; keys before ``doc_start[b, i]`` are masked too.
+    ``q_offset``: q is a chunk of Sq queries at that position of the Sk >= Sq keys, k/v [B,Hkv,Sk,D]:
+    query i sees key j iff ``j <= q_offset + i``."""
+    if q_offset is not None:
+        _check_q_offset(q, k, q_offset, doc)
+        rep = q.size(1) // k.size(1)
+        s = torch.matmul(q.float(), k.float().repeat_interleave(rep, dim=1).transpose(-1, -2))
+        s = s * (scale if scale is not None else q.size(-1) ** -0.5)
+        mask = torch.ones(q.size(2), k.size(2), dtype=torch.bool, device=q.device).triu(1 + q_offset)  # j > q_offset + i
+        p = torch.softmax(s.masked_fill(mask, float("-inf")), dim=-1)
+        return torch.matmul(p, v.float().repeat_interleave(rep, dim=1)).transpose(1, 2).to(q.dtype).contiguous()
     B, H, S, Dh = q.shape
     rep = H // k.size(1)
     kf = k.float().repeat_interleave(rep, dim=1)
@@ -334,10 +362,16 @@ def attention_ref(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: floa
 
 class _FlashAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, scale, with_t=False, doc=None):
+    def forward(ctx, q, k, v, scale, with_t=False, doc=None, q_offset=None):
         ctx.set_materialize_grads(False)  # no zero-filled gradient for O^T (non-differentiable) in backward
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        if doc is not None:  # the document-masked kernels
+        ctx.q_offset = q_offset
+        if q_offset is not None:  # a query chunk at an offset into longer K/V
+            res = (hip().attn_fwd_t_qoff if with_t else hip().attn_fwd_qoff)(q, k, v, float(scale), q_offset)
+            o, lse, o_t = res if with_t else (*res, None)
+            if with_t:
+                ctx.mark_non_differentiable(o_t)
+        elif doc is not None:  # the document-masked kernels
             res = (hip().attn_fwd_t_doc if with_t else hip().attn_fwd_doc)(q, k, v, float(scale), doc[0], doc[1])
             o, lse, o_t = res if with_t else (*res, None)
             if with_t:
@@ -355,39 +389,55 @@ class _FlashAttention(torch.autograd.Function):
     @staticmethod
     def backward(ctx, do, _do_t=None):
         q, k, v, o, lse, *doc = ctx.saved_tensors
-        if doc:
+        if ctx.q_offset is not None:
+            dq, dk, dv = hip().attn_bwd_qoff(do.contiguous(), q, k, v, o, lse, ctx.scale, ctx.q_offset)
+        elif doc:
             dq, dk, dv = hip().attn_bwd_doc(do.contiguous(), q, k, v, o, lse, ctx.scale, doc[0], doc[1])
         else:
             dq, dk, dv = hip().attn_bwd(do.contiguous(), q, k, v, o, lse, ctx.scale)
-        return dq, dk, dv, None, None, None
+        return dq, dk, dv, None, None, None, None
 
 
 def flash_attention_supported(q: torch.Tensor, k: torch.Tensor, d64: bool = False) -> bool:
     """Whether the HIP flash kernels serve q, k: head dim 128, and with ``d64`` head dim 64 as well (the
-    kernels of csrc/ops/attention_d64.hip, which the model routes to only when asked: ``Llama(attn_d64=True)``)."""
+    kernels of csrc/ops/attention_d64.hip, which the model routes to only when asked: ``Llama(attn_d64=True)``).
+    The query length is what is tested: with ``q_offset`` (head dim 128 only) the key length and the offset
+    have requirements of their own, which :func:`attention` checks."""
     dims = (64, 128) if d64 else (128,)
     return q.is_cuda and q.dtype == torch.bfloat16 and q.size(-1) in dims and q.size(2) % 128 == 0 and q.size(1) % k.size(1) == 0
 
 
-def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float | None = None, doc=None):
+def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float | None = None, doc=None,
+              q_offset: int | None = None):
     """Causal GQA attention -> [B, S, H, D]; the HIP flash kernel on GPU (head dim 64 or 128, S % 128 == 0).
-    ``doc``: the pair of :func:`doc_bounds` of a packed batch, no token attends across a document start."""
+    ``doc``: the pair of :func:`doc_bounds` of a packed batch, no token attends across a document start.
+    ``q_offset``: q [B, H, Sq, 128] is a chunk of queries at that position of the keys k/v [B, Hkv, Sk, 128]
+    (a rank's chunk of a context-parallel sequence after the all-gather of K and V, or a prefill chunk against
+    a KV cache); query i sees key j iff ``j <= q_offset + i``.  Sq, Sk and q_offset are multiples of 128 with
+    ``0 <= q_offset`` and ``q_offset + Sq <= Sk``; not together with ``doc`` or head dim 64 (``ValueError``).
+    The gradients of k and v are [B, Hkv, Sk, 128], zero for the keys no query sees."""
     sc = scale if scale is not None else q.size(-1) ** -0.5
+    if q_offset is not None:
+        _check_q_offset(q, k, q_offset, doc)
     if q.is_cuda:
         if not flash_attention_supported(q, k, d64=True):
             raise ValueError("HIP flash attention needs bf16, head dim 64 or 128 and S % 128 == 0")
-        return _FlashAttention.apply(q, k, v, sc, False, doc)[0]
-    return attention_ref(q, k, v, sc, doc)
+        return _FlashAttention.apply(q, k, v, sc, False, doc, q_offset)[0]
+    return attention_ref(q, k, v, sc, doc, q_offset)
 
 
-def attention_t(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float | None = None, doc=None):
+def attention_t(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float | None = None, doc=None,
+                q_offset: int | None = None):
     """``(o [B, S, H, D], o^T [H*D, B*S])``: on GPU the forward kernel writes the transposed copy from
-    its LDS tile (no gradient flows through it); elsewhere the reference plus a transpose."""
+    its LDS tile (no gradient flows through it); elsewhere the reference plus a transpose.  ``q_offset`` as
+    in :func:`attention` (S is then the query length Sq)."""
     sc = scale if scale is not None else q.size(-1) ** -0.5
+    if q_offset is not None:
+        _check_q_offset(q, k, q_offset, doc)
     if q.is_cuda:
         if not flash_attention_supported(q, k, d64=True):
             raise ValueError("HIP flash attention needs bf16, head dim 64 or 128 and S % 128 == 0")
-        return _FlashAttention.apply(q, k, v, sc, True, doc)
-    o = attention_ref(q, k, v, sc, doc)
+        return _FlashAttention.apply(q, k, v, sc, True, doc, q_offset)
+    o = attention_ref(q, k, v, sc, doc, q_offset)
     B, S, H, D = o.shape
     return o, o.detach().reshape(B * S, H * D).t().contiguous()
