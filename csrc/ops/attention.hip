@@ -3,8 +3,10 @@
 // sequences are the same header compiled with kDoc = true in attention_doc.hip; the bindings here reach
 // them through gtk_docmask::launch_*.  Head dim 64 goes to the kernels of attention_d64.hip (both masks)
 // through gtk_attn64::launch_*; the host checks and the outputs are the same.  A query chunk at an offset
-// into longer K/V (attn_*_qoff) goes to the kernels of attention_qoff.hip through gtk_qoff::launch_*.
+// into longer K/V (attn_*_qoff) goes to the kernels of attention_qoff.hip through gtk_qoff::launch_*, and with
+// its keys split over several workgroups (attn_*_qoff_split) to those of attention_splitkv.hip.
 #include "attention_kernels.h"
+#include "attention_splitkv.h"
 
 namespace gtk_attn64 {  // csrc/ops/attention_d64.hip; a null document bound: the causal kernels
 
@@ -197,13 +199,9 @@ std::vector<at::Tensor> attn_fwd_t_qoff(const at::Tensor& q, const at::Tensor& k
   return attn_fwd_qoff_impl(q, k, v, scale, q_offset, true);
 }
 
-// -> (dq [B, H, Sq, 128], dk, dv [B, Hkv, Sk, 128]) from the out and lse it is given; keys no query sees
-// (at or after q_offset + Sq) get zeros, written by the dK/dV kernel
-std::vector<at::Tensor> attn_bwd_qoff(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
-                                      const at::Tensor& out, const at::Tensor& lse, double scale, int64_t q_offset) {
-  check_qkv_qoff(q, k, v, q_offset);
-  check_scale(scale);
-  const int B = q.size(0), H = q.size(1), Sq = q.size(2), Hkv = k.size(1), Sk = k.size(2);
+// what the window's backward is given beside q, k, v
+void check_bwd_qoff(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& out, const at::Tensor& lse) {
+  const int64_t B = q.size(0), H = q.size(1), Sq = q.size(2);
   for (const at::Tensor* x : {&dout, &out})
     TORCH_CHECK(x->is_cuda() && x->device() == q.device() && x->scalar_type() == at::kBFloat16 && x->is_contiguous() &&
                     x->dim() == 4 && x->size(0) == B && x->size(1) == Sq && x->size(2) == H && x->size(3) == D,
@@ -211,6 +209,16 @@ std::vector<at::Tensor> attn_bwd_qoff(const at::Tensor& dout, const at::Tensor& 
   TORCH_CHECK(lse.is_cuda() && lse.device() == q.device() && lse.is_contiguous() && lse.scalar_type() == at::kFloat &&
                   lse.dim() == 3 && lse.size(0) == B && lse.size(1) == H && lse.size(2) == Sq,
               "attention bwd: lse must be a contiguous fp32 [B, H, Sq] GPU tensor on q's device");
+}
+
+// -> (dq [B, H, Sq, 128], dk, dv [B, Hkv, Sk, 128]) from the out and lse it is given; keys no query sees
+// (at or after q_offset + Sq) get zeros, written by the dK/dV kernel
+std::vector<at::Tensor> attn_bwd_qoff(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                                      const at::Tensor& out, const at::Tensor& lse, double scale, int64_t q_offset) {
+  check_qkv_qoff(q, k, v, q_offset);
+  check_scale(scale);
+  const int B = q.size(0), H = q.size(1), Sq = q.size(2), Hkv = k.size(1), Sk = k.size(2);
+  check_bwd_qoff(dout, q, out, lse);
   auto fopt = q.options().dtype(at::kFloat);
   auto delta = at::empty({B, H, Sq}, fopt), nls = at::empty({B, H, Sq}, fopt), ndl = at::empty({B, H, Sq}, fopt);
   auto dq = at::empty_like(q), dk = at::empty_like(k), dv = at::empty_like(v);
@@ -223,6 +231,60 @@ std::vector<at::Tensor> attn_bwd_qoff(const at::Tensor& dout, const at::Tensor& 
                         ndl.data_ptr<float>(), bpm(dk), bpm(dv), H, Hkv, Sq, c, (float)scale, Sk, (int)q_offset);
   gtk_qoff::launch_dq(dim3(B * H, Sq / BQ), cur_stream(), bp(q), bp(k), bp(v), bp(dout), lse.data_ptr<float>(),
                       delta.data_ptr<float>(), bpm(dq), H, Hkv, Sq, c, (float)scale, Sk, (int)q_offset);
+  return {dq, dk, dv};
+}
+
+// ---------------------------------------------------------------- the same window, its keys split over n workgroups
+// The kernels of attention_splitkv.hip: every query block's key range dealt to n workgroups, whose fp32
+// partials a second kernel merges in split order.  The workspace is the caching allocator's, per call, and
+// is not cleared: the merges read no partial that was not written.
+void check_splits(const at::Tensor& q, int64_t n) {
+  TORCH_CHECK(n >= 1 && n <= gtk_splitkv::kMaxSplits, "attention: kv_splits must be between 1 and ", gtk_splitkv::kMaxSplits,
+              ", got ", n);
+  TORCH_CHECK(q.size(0) * q.size(1) * q.size(2) < (int64_t(1) << 31), "attention: kv_splits needs B * H * Sq below 2^31");
+}
+
+// -> (o [B, Sq, H, 128], lse2 [B, H, Sq]), as attn_fwd_qoff
+std::vector<at::Tensor> attn_fwd_qoff_split(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, double scale,
+                                            int64_t q_offset, int64_t n) {
+  check_qkv_qoff(q, k, v, q_offset);
+  check_scale(scale);
+  check_splits(q, n);
+  const int B = q.size(0), H = q.size(1), Sq = q.size(2), Hkv = k.size(1), Sk = k.size(2);
+  auto fopt = q.options().dtype(at::kFloat);
+  auto o = at::empty({B, Sq, H, D}, q.options());
+  auto lse = at::empty({B, H, Sq}, fopt);
+  auto o_part = at::empty({n, B, Sq, H, D}, fopt), lse_part = at::empty({n, B, H, Sq}, fopt);
+  gtk_splitkv::launch_fwd(dim3(B * H, Sq / BQ, (unsigned)n), cur_stream(), bp(q), bp(k), bp(v), o_part.data_ptr<float>(),
+                          lse_part.data_ptr<float>(), H, Hkv, Sq, (float)(scale * 1.4426950408889634), Sk, (int)q_offset);
+  gtk_splitkv::launch_combine(cur_stream(), o_part.data_ptr<float>(), lse_part.data_ptr<float>(), bpm(o), lse.data_ptr<float>(),
+                              B, H, Sq, (int)n);
+  return {o, lse};
+}
+
+// -> (dq, dk, dv) as attn_bwd_qoff: its pre-kernel and its dK/dV kernel, dQ from n splits and their sum
+std::vector<at::Tensor> attn_bwd_qoff_split(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k,
+                                            const at::Tensor& v, const at::Tensor& out, const at::Tensor& lse, double scale,
+                                            int64_t q_offset, int64_t n) {
+  check_qkv_qoff(q, k, v, q_offset);
+  check_scale(scale);
+  check_splits(q, n);
+  const int B = q.size(0), H = q.size(1), Sq = q.size(2), Hkv = k.size(1), Sk = k.size(2);
+  check_bwd_qoff(dout, q, out, lse);
+  auto fopt = q.options().dtype(at::kFloat);
+  auto delta = at::empty({B, H, Sq}, fopt), nls = at::empty({B, H, Sq}, fopt), ndl = at::empty({B, H, Sq}, fopt);
+  auto dq = at::empty_like(q), dk = at::empty_like(k), dv = at::empty_like(v);
+  auto dq_part = at::empty({n, B, H, Sq, D}, fopt);
+  const int rows = B * Sq * H;
+  const float c = (float)(scale * 1.4426950408889634);
+  hipLaunchKernelGGL(attn_bwd_pre_kernel, dim3((rows + 15) / 16), dim3(256), 0, cur_stream(), bp(dout), bp(out),
+                     lse.data_ptr<float>(), delta.data_ptr<float>(), nls.data_ptr<float>(), ndl.data_ptr<float>(), B, H, Sq,
+                     1.f / c);
+  gtk_qoff::launch_dkdv(dim3(B * Hkv, Sk / KB), cur_stream(), bp(q), bp(k), bp(v), bp(dout), nls.data_ptr<float>(),
+                        ndl.data_ptr<float>(), bpm(dk), bpm(dv), H, Hkv, Sq, c, (float)scale, Sk, (int)q_offset);
+  gtk_splitkv::launch_dq(dim3(B * H, Sq / BQ, (unsigned)n), cur_stream(), bp(q), bp(k), bp(v), bp(dout), lse.data_ptr<float>(),
+                         delta.data_ptr<float>(), dq_part.data_ptr<float>(), H, Hkv, Sq, c, Sk, (int)q_offset);
+  gtk_splitkv::launch_dq_reduce(cur_stream(), dq_part.data_ptr<float>(), bpm(dq), B, H, Sq, (float)scale, (int)q_offset, (int)n);
   return {dq, dk, dv};
 }
 

@@ -57,12 +57,18 @@
 //   GTK_QPOS(x)           the key-sequence position of query index x: q_offset + x here, x elsewhere.
 // Everything addressed by a query (q, dO, o, O^T, lse, delta, dq) keeps S; the K/V staging, kvoff and the
 // dk / dv stores take GTK_KLEN(S); every comparison of a key with a query takes GTK_QPOS of the query.
+//
+// Included by attention_splitkv.hip with GTK_ATTN_SPLITKV_TU defined it gives the device helpers alone, in
+// namespace gtk_splitkv (the swizzle, the fragment reads, KVStage, dma_sync, dq_tile_na): the split-KV
+// kernels are kernels of their own and the three families above are left out of that unit.
 #ifdef GTK_ATTN_DOC_TU
 #define GTK_ATTN_NS gtk_docmask
 #define GTK_DOC_PARAM(decl) , decl
 #define GTK_DOC_ARG(x) x
 #else
-#ifdef GTK_ATTN_QOFF_TU
+#if defined(GTK_ATTN_SPLITKV_TU)
+#define GTK_ATTN_NS gtk_splitkv
+#elif defined(GTK_ATTN_QOFF_TU)
 #define GTK_ATTN_NS gtk_qoff
 #else
 #define GTK_ATTN_NS gtk_attn
@@ -294,6 +300,7 @@ struct DocTiles {
 //     branch-free main loop.
 // Every bound is clamped to [0, its query], so a row always sees itself and every range stays inside
 // the causal one.
+#ifndef GTK_ATTN_SPLITKV_TU
 __global__ __launch_bounds__(256, 2) void attn_fwd2_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
                                                            const u16* __restrict__ v, u16* __restrict__ o,
                                                            float* __restrict__ lse2, int H, int Hkv, int S, float c,
@@ -816,7 +823,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkdv_kernel(const u16* __rest
       *reinterpret_cast<u16x4*>(dvrow + 32 * dt + 8 * g4 + 4 * hh) = b4;
     }
 }
-
+#endif  // !GTK_ATTN_SPLITKV_TU
 
 // dQ: forward-shaped (query on the lane), dQ^T += K^T.dS^T accumulated in registers; LDS-DMA
 // double-buffered K/V tiles with one barrier per tile, the block's diagonal tiles peeled out of a
@@ -875,6 +882,7 @@ __device__ __forceinline__ void dq_tile_na(const char* __restrict__ kimg, const 
 }
 
 // kDoc: the forward's tile ranges and per-wave tests (attn_fwd2_kernel), the lower mask as p = 0.
+#ifndef GTK_ATTN_SPLITKV_TU
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq2n_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
                                                                const u16* __restrict__ v, const u16* __restrict__ dout,
                                                                const float* __restrict__ lse2, const float* __restrict__ delta,
@@ -979,6 +987,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq2n_kernel(const u16* __rest
       *reinterpret_cast<uint4*>(out + 32 * dt + 8 * g4 + 8 * hh) = o4;
     }
 }
+#endif  // !GTK_ATTN_SPLITKV_TU
 
 }  // namespace GTK_ATTN_NS
 

@@ -979,6 +979,11 @@ std::vector<at::Tensor> attn_fwd_t_qoff(const at::Tensor& q, const at::Tensor& k
                                         int64_t q_offset);
 std::vector<at::Tensor> attn_bwd_qoff(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                                       const at::Tensor& out, const at::Tensor& lse, double scale, int64_t q_offset);
+std::vector<at::Tensor> attn_fwd_qoff_split(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, double scale,
+                                            int64_t q_offset, int64_t n);
+std::vector<at::Tensor> attn_bwd_qoff_split(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k,
+                                            const at::Tensor& v, const at::Tensor& out, const at::Tensor& lse, double scale,
+                                            int64_t q_offset, int64_t n);
 }  // namespace gtk_attn
 
 namespace gtk_xpose {  // csrc/ops/transpose.hip
@@ -1014,6 +1019,10 @@ PYBIND11_MODULE(_fused, m) {
   m.def("attn_fwd_t_qoff", &gtk_attn::attn_fwd_t_qoff, "attn_fwd_qoff that also writes O^T [H*D, B*Sq]: -> (o, lse2, ot)");
   m.def("attn_bwd_qoff", &gtk_attn::attn_bwd_qoff,
         "backward of attn_fwd_qoff: -> (dq [B,H,Sq,D], dk, dv [B,Hkv,Sk,D]; zeros for keys past the window)");
+  m.def("attn_fwd_qoff_split", &gtk_attn::attn_fwd_qoff_split,
+        "attn_fwd_qoff with every query block's keys split over n (1..16) workgroups and an fp32 merge: -> (o, lse2)");
+  m.def("attn_bwd_qoff_split", &gtk_attn::attn_bwd_qoff_split,
+        "attn_bwd_qoff with dQ from n (1..16) key splits summed in fp32; dK/dV as attn_bwd_qoff: -> (dq, dk, dv)");
   m.doc() = "gfx950 fused kernels for the Llama-3 DP validation workload";
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
   m.def("rmsnorm_bwd", &rmsnorm_bwd);

@@ -183,7 +183,10 @@ def targets() -> List[Target]:
                           "attention_d64.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-Xclang", "-target-feature", "-Xclang",
                                                 "-packed-fp32-ops"],
                           "attention_qoff.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-Xclang", "-target-feature", "-Xclang",
-                                                 "-packed-fp32-ops"]}),
+                                                 "-packed-fp32-ops"],
+                          # the split-KV kernels of the offset window, kernels of their own over the header's helpers
+                          "attention_splitkv.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-Xclang", "-target-feature", "-Xclang",
+                                                    "-packed-fp32-ops"]}),
     ]
 
 

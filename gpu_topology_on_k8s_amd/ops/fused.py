@@ -16,6 +16,7 @@ __all__ = [
     "rmsnorm", "rmsnorm_ref", "rope_tables", "rope_split", "rope_split_ref", "swiglu", "swiglu_ref", "cross_entropy",
     "cross_entropy_ref", "hip", "attention", "attention_ref", "flash_attention_supported", "transpose", "swiglu_bwd_ref",
     "swiglu_bwd_t", "swiglu_fwd_t", "attention_t", "offer_t", "take_t", "clear_t", "doc_bounds", "doc_start_from_eos",
+    "kv_splits_for",
 ]
 
 
@@ -333,6 +334,48 @@ def _check_q_offset(q: torch.Tensor, k: torch.Tensor, q_offset, doc) -> None:
         raise ValueError(f"attention: q_offset + query length ({q_offset} + {Sq}) exceeds the key length {Sk}")
 
 
+FWD_BLOCK_SLOTS = 512  # 256 CUs x the two workgroups per CU of the forward and dQ kernels
+# The fewest 128-key blocks "auto" leaves each split of the call's largest query block.  Measured on an MI355X
+# (bench/attn_splitkv_bench.py, B 1, 32 / 8 heads, Sk 8192, the 30 calls of 2, 4, 8 and 16 chunks, each against
+# the unsplit call in the same process, two runs; profiles/attn_splitkv/SUMMARY.md): 9 is the smallest value at
+# which no call gets an n > 1 that is slower than the unsplit call by more than the run-to-run spread (the
+# largest of the 30 calls: forward 4.6 %, backward 3.0 %).  At 8 and below, Sq 1024 at q_offset 1024 gets n = 2
+# with 8 key blocks a split and its forward takes 1.11 to 1.12 times the unsplit one; from 9 on every n > 1
+# chosen is a gain (forward 0.51 to 0.98, backward 0.75 to 0.98 of the unsplit call).
+MIN_KEY_BLOCKS_PER_SPLIT = 9
+
+
+def kv_splits_for(B: int, H: int, Sq: int, Sk: int, q_offset: int) -> int:
+    """The ``kv_splits`` that ``"auto"`` uses: the smallest n of 1, 2, 4, 8 with ``B * H * (Sq / 128) * n`` at
+    least the chip's 512 forward block slots, but no larger than leaves every split of the largest query block
+    (``(q_offset + Sq) / 128`` key blocks) ``MIN_KEY_BLOCKS_PER_SPLIT`` key blocks.  A function of the shapes
+    alone (``Sk`` does not enter: keys past the window are never visited)."""
+    blocks, kmax = B * H * (Sq // 128), (q_offset + Sq) // 128
+    n = 1
+    while n < 8 and blocks * n < FWD_BLOCK_SLOTS and kmax // (2 * n) >= MIN_KEY_BLOCKS_PER_SPLIT:
+        n *= 2
+    return n
+
+
+def _check_kv_splits(q: torch.Tensor, k: torch.Tensor, kv_splits, q_offset, doc):
+    """-> None (the unsplit kernels) or the int n of the split ones; refusals before any launch."""
+    if kv_splits is None:
+        return None
+    if doc is not None:
+        raise ValueError("attention: kv_splits cannot be combined with doc")
+    if q_offset is None:
+        raise ValueError("attention: kv_splits needs q_offset (the plain causal case is q_offset=0)")
+    if q.size(-1) != 128:
+        raise ValueError(f"attention: kv_splits needs head dim 128, got {q.size(-1)}")
+    if kv_splits == "auto":
+        _check_q_offset(q, k, q_offset, doc)
+        n = kv_splits_for(q.size(0), q.size(1), q.size(2), k.size(2), q_offset)
+        return n if n > 1 else None  # one split is the unsplit kernel, without the workspace round trip
+    if isinstance(kv_splits, bool) or not isinstance(kv_splits, int) or not 1 <= kv_splits <= 16:
+        raise ValueError(f"attention: kv_splits must be None, 'auto' or an int from 1 to 16, got {kv_splits!r}")
+    return kv_splits
+
+
 def attention_ref(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float | None = None, doc=None,
                   q_offset: int | None = None) -> torch.Tensor:
     """fp32 causal GQA attention: q [B,H,S,D], k/v [B,Hkv,S,D] -> o [B,S,H,D] (same dtype as q).
@@ -362,11 +405,14 @@ def attention_ref(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: floa
 
 class _FlashAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, scale, with_t=False, doc=None, q_offset=None):
+    def forward(ctx, q, k, v, scale, with_t=False, doc=None, q_offset=None, kv_splits=None):
         ctx.set_materialize_grads(False)  # no zero-filled gradient for O^T (non-differentiable) in backward
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        ctx.q_offset = q_offset
-        if q_offset is not None:  # a query chunk at an offset into longer K/V
+        ctx.q_offset, ctx.kv_splits = q_offset, kv_splits
+        if kv_splits is not None:  # the window with every query block's keys split over kv_splits workgroups
+            o, lse = hip().attn_fwd_qoff_split(q, k, v, float(scale), q_offset, kv_splits)
+            o_t = None
+        elif q_offset is not None:  # a query chunk at an offset into longer K/V
             res = (hip().attn_fwd_t_qoff if with_t else hip().attn_fwd_qoff)(q, k, v, float(scale), q_offset)
             o, lse, o_t = res if with_t else (*res, None)
             if with_t:
@@ -389,13 +435,15 @@ class _FlashAttention(torch.autograd.Function):
     @staticmethod
     def backward(ctx, do, _do_t=None):
         q, k, v, o, lse, *doc = ctx.saved_tensors
-        if ctx.q_offset is not None:
+        if ctx.kv_splits is not None:
+            dq, dk, dv = hip().attn_bwd_qoff_split(do.contiguous(), q, k, v, o, lse, ctx.scale, ctx.q_offset, ctx.kv_splits)
+        elif ctx.q_offset is not None:
             dq, dk, dv = hip().attn_bwd_qoff(do.contiguous(), q, k, v, o, lse, ctx.scale, ctx.q_offset)
         elif doc:
             dq, dk, dv = hip().attn_bwd_doc(do.contiguous(), q, k, v, o, lse, ctx.scale, doc[0], doc[1])
         else:
             dq, dk, dv = hip().attn_bwd(do.contiguous(), q, k, v, o, lse, ctx.scale)
-        return dq, dk, dv, None, None, None, None
+        return dq, dk, dv, None, None, None, None, None
 
 
 def flash_attention_supported(q: torch.Tensor, k: torch.Tensor, d64: bool = False) -> bool:
@@ -408,29 +456,38 @@ def flash_attention_supported(q: torch.Tensor, k: torch.Tensor, d64: bool = Fals
 
 
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float | None = None, doc=None,
-              q_offset: int | None = None):
+              q_offset: int | None = None, kv_splits=None):
     """Causal GQA attention -> [B, S, H, D]; the HIP flash kernel on GPU (head dim 64 or 128, S % 128 == 0).
     ``doc``: the pair of :func:`doc_bounds` of a packed batch, no token attends across a document start.
     ``q_offset``: q [B, H, Sq, 128] is a chunk of queries at that position of the keys k/v [B, Hkv, Sk, 128]
     (a rank's chunk of a context-parallel sequence after the all-gather of K and V, or a prefill chunk against
     a KV cache); query i sees key j iff ``j <= q_offset + i``.  Sq, Sk and q_offset are multiples of 128 with
     ``0 <= q_offset`` and ``q_offset + Sq <= Sk``; not together with ``doc`` or head dim 64 (``ValueError``).
-    The gradients of k and v are [B, Hkv, Sk, 128], zero for the keys no query sees."""
+    The gradients of k and v are [B, Hkv, Sk, 128], zero for the keys no query sees.
+    ``kv_splits`` (with ``q_offset`` only; on the CPU accepted and ignored): ``None`` is the kernels above, one
+    workgroup per 128 queries walking all of their keys.  An int n from 1 to 16 deals every query block's keys
+    to n workgroups and merges their fp32 partials in split order (csrc/ops/attention_splitkv.hip), forward and
+    dQ alike; for a short chunk against long K/V, which alone does not fill the GPU.  ``"auto"`` takes
+    :func:`kv_splits_for` of the shapes and, where that is 1, the unsplit kernels."""
     sc = scale if scale is not None else q.size(-1) ** -0.5
+    n = _check_kv_splits(q, k, kv_splits, q_offset, doc)
     if q_offset is not None:
         _check_q_offset(q, k, q_offset, doc)
     if q.is_cuda:
         if not flash_attention_supported(q, k, d64=True):
             raise ValueError("HIP flash attention needs bf16, head dim 64 or 128 and S % 128 == 0")
-        return _FlashAttention.apply(q, k, v, sc, False, doc, q_offset)[0]
+        return _FlashAttention.apply(q, k, v, sc, False, doc, q_offset, n)[0]
     return attention_ref(q, k, v, sc, doc, q_offset)
 
 
 def attention_t(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float | None = None, doc=None,
-                q_offset: int | None = None):
+                q_offset: int | None = None, kv_splits=None):
     """``(o [B, S, H, D], o^T [H*D, B*S])``: on GPU the forward kernel writes the transposed copy from
     its LDS tile (no gradient flows through it); elsewhere the reference plus a transpose.  ``q_offset`` as
-    in :func:`attention` (S is then the query length Sq)."""
+    in :func:`attention` (S is then the query length Sq).  The split kernels write no O^T: ``kv_splits`` is
+    refused."""
+    if kv_splits is not None:
+        raise ValueError("attention_t: kv_splits is not supported (the split kernels write no O^T)")
     sc = scale if scale is not None else q.size(-1) ** -0.5
     if q_offset is not None:
         _check_q_offset(q, k, q_offset, doc)
