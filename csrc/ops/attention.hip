@@ -4,7 +4,8 @@
 // them through gtk_docmask::launch_*.  Head dim 64 goes to the kernels of attention_d64.hip (both masks)
 // through gtk_attn64::launch_*; the host checks and the outputs are the same.  A query chunk at an offset
 // into longer K/V (attn_*_qoff) goes to the kernels of attention_qoff.hip through gtk_qoff::launch_*, and with
-// its keys split over several workgroups (attn_*_qoff_split) to those of attention_splitkv.hip.
+// its keys split over several workgroups (attn_*_qoff_split) to those of attention_splitkv.hip.  A decode step
+// over a ragged KV cache (attn_decode) goes to the kernel of attention_decode.hip through gtk_decode::launch.
 #include "attention_kernels.h"
 #include "attention_splitkv.h"
 
@@ -22,6 +23,20 @@ void launch_dq(hipStream_t st, const u16* q, const u16* k, const u16* v, const u
                u16* dq, int B, int H, int Hkv, int S, float c, float scale, const int* doc_start);
 
 }  // namespace gtk_attn64
+
+namespace gtk_decode {  // csrc/ops/attention_decode.hip
+
+using gtk::u16;
+
+constexpr int kMaxRows = 32;    // Sq * (H / Hkv): the query columns of one 32x32 MFMA tile
+constexpr int kMaxSplits = 64;
+
+// grid (B*Hkv, n).  n = 1: o bf16 [B, Sq, H, 128] and lse2 fp32 [B, H, Sq]; n > 1: the partials o_part fp32
+// [n, B, Sq, H, 128] and lse_part fp32 [n, B, H, Sq] that gtk_splitkv::launch_combine reads
+void launch(hipStream_t st, const u16* q, const u16* kc, const u16* vc, const int* kv_len, u16* o, float* lse2, float* o_part,
+            float* lse_part, int B, int H, int Hkv, int Sq, int Smax, float c, int n);
+
+}  // namespace gtk_decode
 
 namespace gtk_attn {
 
@@ -286,6 +301,49 @@ std::vector<at::Tensor> attn_bwd_qoff_split(const at::Tensor& dout, const at::Te
                          delta.data_ptr<float>(), dq_part.data_ptr<float>(), H, Hkv, Sq, c, Sk, (int)q_offset);
   gtk_splitkv::launch_dq_reduce(cur_stream(), dq_part.data_ptr<float>(), bpm(dq), B, H, Sq, (float)scale, (int)q_offset, (int)n);
   return {dq, dk, dv};
+}
+
+// ---------------------------------------------------------------- a decode step over a ragged KV cache
+// q [B, H, Sq, 128], Sq * (H / Hkv) <= 32 new tokens' queries; k_cache, v_cache [B, Hkv, Smax, 128]; kv_len int32 [B]
+// on the device, the valid keys of each sequence with the Sq new tokens appended.  Query i of sequence b sees
+// key j iff j <= kv_len[b] - Sq + i.  The kernel of attention_decode.hip clamps kv_len into [Sq, Smax]; nothing
+// here reads it.  n key splits per (sequence, KV head), merged by the split-KV combine when n > 1.
+// -> (o [B, Sq, H, 128], lse2 [B, H, Sq])
+std::vector<at::Tensor> attn_decode(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                                    const at::Tensor& kv_len, double scale, int64_t n) {
+  for (const at::Tensor* x : {&q, &k_cache, &v_cache})
+    TORCH_CHECK(x->is_cuda() && x->scalar_type() == at::kBFloat16 && x->is_contiguous() && x->dim() == 4,
+                "attention decode: q and the caches must be contiguous bf16 [B, heads, S, D] GPU tensors");
+  TORCH_CHECK(q.size(3) == D && k_cache.size(3) == D && v_cache.size(3) == D, "attention decode: head dim must be 128, got ",
+              q.size(3));
+  TORCH_CHECK(k_cache.sizes() == v_cache.sizes() && q.size(0) == k_cache.size(0),
+              "attention decode: shape mismatch (k_cache and v_cache alike, one batch size)");
+  TORCH_CHECK(k_cache.device() == q.device() && v_cache.device() == q.device(), "attention decode: q and the caches must be on one device");
+  const int64_t B = q.size(0), H = q.size(1), Sq = q.size(2), Hkv = k_cache.size(1), Smax = k_cache.size(2);
+  TORCH_CHECK(B > 0 && Hkv > 0 && H % Hkv == 0, "attention decode: q heads must be a multiple of kv heads");
+  TORCH_CHECK(Sq >= 1 && Sq * (H / Hkv) <= gtk_decode::kMaxRows, "attention decode: Sq * (H / Hkv) must be between 1 and ",
+              gtk_decode::kMaxRows, ", got ", Sq * (H / Hkv));
+  TORCH_CHECK(Smax >= Sq, "attention decode: the cache length ", Smax, " is below the query length ", Sq);
+  TORCH_CHECK(Smax * D * 2 < (int64_t(1) << 31), "attention decode: one head's cache bytes must fit the 32-bit buffer offsets");
+  TORCH_CHECK(B * H * Sq < (int64_t(1) << 31) && B * Hkv < (int64_t(1) << 31), "attention decode: B * H * Sq must be below 2^31");
+  TORCH_CHECK(kv_len.is_cuda() && kv_len.device() == q.device() && kv_len.scalar_type() == at::kInt && kv_len.is_contiguous() &&
+                  kv_len.dim() == 1 && kv_len.size(0) == B,
+              "attention decode: kv_len must be a contiguous int32 [B] GPU tensor on q's device");
+  check_scale(scale);
+  TORCH_CHECK(n >= 1 && n <= gtk_decode::kMaxSplits, "attention decode: kv_splits must be between 1 and ", gtk_decode::kMaxSplits,
+              ", got ", n);
+  auto fopt = q.options().dtype(at::kFloat);
+  auto o = at::empty({B, Sq, H, D}, q.options());
+  auto lse = at::empty({B, H, Sq}, fopt);
+  at::Tensor o_part, lse_part;
+  if (n > 1) o_part = at::empty({n, B, Sq, H, D}, fopt), lse_part = at::empty({n, B, H, Sq}, fopt);
+  gtk_decode::launch(cur_stream(), bp(q), bp(k_cache), bp(v_cache), kv_len.data_ptr<int>(), bpm(o), lse.data_ptr<float>(),
+                     n > 1 ? o_part.data_ptr<float>() : nullptr, n > 1 ? lse_part.data_ptr<float>() : nullptr, (int)B, (int)H,
+                     (int)Hkv, (int)Sq, (int)Smax, (float)(scale * 1.4426950408889634), (int)n);
+  if (n > 1)
+    gtk_splitkv::launch_combine(cur_stream(), o_part.data_ptr<float>(), lse_part.data_ptr<float>(), bpm(o), lse.data_ptr<float>(),
+                                (int)B, (int)H, (int)Sq, (int)n);
+  return {o, lse};
 }
 
 // the document-masked backward, from the outputs of attn_fwd_doc

@@ -302,8 +302,9 @@ void launch_fwd(dim3 grid, hipStream_t st, const u16* q, const u16* k, const u16
 void launch_combine(hipStream_t st, const float* o_part, const float* lse_part, u16* o, float* lse2, int B, int H, int Sq,
                     int n) {
   const int rows = B * Sq * H;
-  hipLaunchKernelGGL(splitkv_merge_kernel<true>, dim3(rows / 8), dim3(256), 0, st, o_part, lse_part, o, lse2, rows, H, Sq, 1.f, 0,
-                     n);
+  // rounded up: the decode kernel's rows need not be a multiple of 8 (the kernel guards row >= rows)
+  hipLaunchKernelGGL(splitkv_merge_kernel<true>, dim3((rows + 7) / 8), dim3(256), 0, st, o_part, lse_part, o, lse2, rows, H, Sq,
+                     1.f, 0, n);
 }
 void launch_dq(dim3 grid, hipStream_t st, const u16* q, const u16* k, const u16* v, const u16* dout, const float* lse2,
                const float* delta, float* dq_part, int H, int Hkv, int Sq, float c, int Sk, int q_offset) {

@@ -984,6 +984,8 @@ std::vector<at::Tensor> attn_fwd_qoff_split(const at::Tensor& q, const at::Tenso
 std::vector<at::Tensor> attn_bwd_qoff_split(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k,
                                             const at::Tensor& v, const at::Tensor& out, const at::Tensor& lse, double scale,
                                             int64_t q_offset, int64_t n);
+std::vector<at::Tensor> attn_decode(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                                    const at::Tensor& kv_len, double scale, int64_t n);
 }  // namespace gtk_attn
 
 namespace gtk_xpose {  // csrc/ops/transpose.hip
@@ -1023,6 +1025,9 @@ PYBIND11_MODULE(_fused, m) {
         "attn_fwd_qoff with every query block's keys split over n (1..16) workgroups and an fp32 merge: -> (o, lse2)");
   m.def("attn_bwd_qoff_split", &gtk_attn::attn_bwd_qoff_split,
         "attn_bwd_qoff with dQ from n (1..16) key splits summed in fp32; dK/dV as attn_bwd_qoff: -> (dq, dk, dv)");
+  m.def("attn_decode", &gtk_attn::attn_decode,
+        "decode attention (D=128), Sq * H / Hkv <= 32 queries per KV head against a ragged cache [B,Hkv,Smax,D] with int32 "
+        "kv_len [B] read on the device, n (1..64) key splits: -> (o [B,Sq,H,D], lse2 [B,H,Sq])");
   m.doc() = "gfx950 fused kernels for the Llama-3 DP validation workload";
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
   m.def("rmsnorm_bwd", &rmsnorm_bwd);

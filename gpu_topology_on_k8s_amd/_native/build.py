@@ -186,7 +186,10 @@ def targets() -> List[Target]:
                                                  "-packed-fp32-ops"],
                           # the split-KV kernels of the offset window, kernels of their own over the header's helpers
                           "attention_splitkv.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-Xclang", "-target-feature", "-Xclang",
-                                                    "-packed-fp32-ops"]}),
+                                                    "-packed-fp32-ops"],
+                          # the decode kernel over a ragged KV cache, a kernel of its own over the same helpers
+                          "attention_decode.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-Xclang", "-target-feature", "-Xclang",
+                                                   "-packed-fp32-ops"]}),
     ]
 
 

@@ -51,7 +51,7 @@ import torch
 
 from .mnist_ref import bf16_round
 
-__all__ = ["bf16_round", "kernel_constants", "attn_fwd_ref64", "attn_bwd_ref64"]
+__all__ = ["bf16_round", "kernel_constants", "attn_fwd_ref64", "attn_bwd_ref64", "attn_decode_ref64"]
 
 T = torch.Tensor
 LOG2E = 1.4426950408889634
@@ -121,6 +121,31 @@ def attn_fwd_ref64(q: T, k: T, v: T, scale: float, doc_start=None) -> Tuple[T, T
     lse2 = (m + torch.log2(l)).squeeze(-1).reshape(B, Hkv * G, S)
     p = p / l
     return _token_major(p @ vg), lse2, _token_major(p @ vg.abs())
+
+
+def attn_decode_ref64(q: T, k_cache: T, v_cache: T, kv_len: T, scale: float) -> Tuple[T, T, T]:
+    """(o [B, Sq, H, D], lse2 [B, H, Sq], cond_o [B, Sq, H, D]) of a decode step over a ragged cache
+    (``csrc/ops/attention_decode.hip``): q [B, H, Sq, D], k_cache / v_cache [B, Hkv, Smax, D], kv_len integer [B]
+    with Sq <= kv_len[b] <= Smax.  Query i of sequence b sees key j iff j <= kv_len[b] - Sq + i.  Cache rows at
+    or past kv_len[b] do not enter, whatever they hold (they are replaced by zeros before any product)."""
+    c, _ = kernel_constants(scale)
+    q, k, v = _f64(q), _f64(k_cache), _f64(v_cache)
+    B, H, Sq, D = q.shape
+    Hkv, Smax = k.shape[1], k.shape[2]
+    assert H % Hkv == 0 and k.shape == v.shape == (B, Hkv, Smax, D)
+    n = kv_len.cpu().long().view(B, 1, 1, 1, 1)
+    assert bool((n >= Sq).all()) and bool((n <= Smax).all())
+    j = torch.arange(Smax).view(1, 1, 1, 1, Smax)
+    valid = (j < n).view(B, 1, Smax, 1)
+    k, v = torch.where(valid, k, 0.0).view(B, Hkv, 1, Smax, D), torch.where(valid, v, 0.0).view(B, Hkv, 1, Smax, D)
+    s2 = c * (q.view(B, Hkv, H // Hkv, Sq, D) @ k.transpose(-1, -2))
+    s2 = s2.masked_fill(j > n - Sq + torch.arange(Sq).view(1, 1, 1, Sq, 1), float("-inf"))
+    m = s2.amax(-1, keepdim=True)
+    p = torch.exp2(s2 - m)
+    l = p.sum(-1, keepdim=True)
+    lse2 = (m + torch.log2(l)).squeeze(-1).reshape(B, H, Sq)
+    p = p / l
+    return _token_major(p @ v), lse2, _token_major(p @ v.abs())
 
 
 def attn_bwd_ref64(dout: T, q: T, k: T, v: T, out: T, lse2: T, scale: float, doc_start=None):

@@ -16,7 +16,7 @@ __all__ = [
     "rmsnorm", "rmsnorm_ref", "rope_tables", "rope_split", "rope_split_ref", "swiglu", "swiglu_ref", "cross_entropy",
     "cross_entropy_ref", "hip", "attention", "attention_ref", "flash_attention_supported", "transpose", "swiglu_bwd_ref",
     "swiglu_bwd_t", "swiglu_fwd_t", "attention_t", "offer_t", "take_t", "clear_t", "doc_bounds", "doc_start_from_eos",
-    "kv_splits_for",
+    "kv_splits_for", "attention_decode", "attention_decode_ref", "decode_splits_for",
 ]
 
 
@@ -498,3 +498,107 @@ def attention_t(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float 
     o = attention_ref(q, k, v, sc, doc, q_offset)
     B, S, H, D = o.shape
     return o, o.detach().reshape(B * S, H * D).t().contiguous()
+
+
+# ------------------------------------------------------------------------------------ decode attention
+DECODE_BLOCK_SLOTS = 256  # 256 CUs x the one workgroup per CU of the decode kernel (128 KiB of LDS)
+DECODE_MAX_ROWS = 32  # Sq * (H / Hkv): the query columns of one 32x32 MFMA tile
+# The fewest 64-key tiles "auto" leaves each split of a full cache: two tiles for each of a workgroup's four
+# waves.  Measured on one MI355X (bench/attn_decode_bench.py, 32 / 8 heads, Sq 1, B 1, 8, 64 at kv_len 2048, 8192,
+# 32768 and B 8 mixed, every n interleaved in one process, two runs; profiles/attn_decode/SUMMARY.md): the rule
+# that set MIN_KEY_BLOCKS_PER_SPLIT does not tell the candidates 1, 2, 4, .. 64 apart here, since with none of
+# them does a shape get an n > 1 slower than n = 1 by more than the spread (0.7 %).  Among them 8 has the
+# smallest time summed over the shapes (0.595 of n = 1; 0.603 at 1, 0.612 at 32): at 1, B 1 at kv_len 2048 gets
+# n = 32 and 34.9 us where n = 4 takes 16.8 (n = 1: 42.0); at 32, B 1 at 32768 falls from n = 32 to 16.
+MIN_TILES_PER_DECODE_SPLIT = 8
+
+
+def decode_splits_for(B: int, Hkv: int, Smax: int) -> int:
+    """The ``kv_splits`` that ``attention_decode(..., kv_splits="auto")`` uses: the smallest power of two n with
+    ``B * Hkv * n`` at least the chip's 256 decode workgroup slots, at most 64, and no larger than leaves every
+    split of a full cache (``ceil(Smax / 64)`` tiles) ``MIN_TILES_PER_DECODE_SPLIT`` tiles.  A function of the
+    shapes alone: ``kv_len`` lives on the device."""
+    tiles, n = -(-Smax // 64), 1
+    while n < 64 and B * Hkv * n < DECODE_BLOCK_SLOTS and tiles // (2 * n) >= MIN_TILES_PER_DECODE_SPLIT:
+        n *= 2
+    return n
+
+
+def _check_decode(q, k_cache, v_cache, kv_len, kv_splits) -> int:
+    """The requirements of :func:`attention_decode`, refused before any launch; -> the number of splits."""
+    for name, x in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
+        if x.dim() != 4 or x.dtype != torch.bfloat16:
+            raise ValueError(f"attention_decode: {name} must be a bf16 [B, heads, S, 128] tensor, got {x.dtype} {tuple(x.shape)}")
+        if x.size(-1) != 128:
+            raise ValueError(f"attention_decode: head dim must be 128, got {x.size(-1)}")
+    if k_cache.shape != v_cache.shape or k_cache.size(0) != q.size(0):
+        raise ValueError("attention_decode: k_cache and v_cache must have one shape and q's batch size")
+    if k_cache.device != q.device or v_cache.device != q.device:
+        raise ValueError("attention_decode: q and the caches must be on one device")
+    if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
+        raise ValueError("attention_decode: the caches must be contiguous")
+    B, H, Sq, _ = q.shape
+    Hkv, Smax = k_cache.size(1), k_cache.size(2)
+    if Hkv == 0 or H % Hkv:
+        raise ValueError(f"attention_decode: q heads ({H}) must be a multiple of kv heads ({Hkv})")
+    if not 1 <= Sq * (H // Hkv) <= DECODE_MAX_ROWS:
+        raise ValueError(f"attention_decode: Sq * (H / Hkv) must be between 1 and {DECODE_MAX_ROWS}, got {Sq * (H // Hkv)}")
+    if Smax < Sq:
+        raise ValueError(f"attention_decode: the cache length {Smax} is below the query length {Sq}")
+    if not isinstance(kv_len, torch.Tensor) or kv_len.dtype != torch.int32 or kv_len.shape != (B,) or kv_len.device != q.device:
+        raise ValueError("attention_decode: kv_len must be an int32 [B] tensor on the caches' device")
+    if torch.is_grad_enabled() and any(x.requires_grad for x in (q, k_cache, v_cache)):
+        raise ValueError("attention_decode: forward only, an input requires grad")
+    if kv_splits == "auto":
+        return decode_splits_for(B, Hkv, Smax)
+    if isinstance(kv_splits, bool) or not isinstance(kv_splits, int) or not 1 <= kv_splits <= 64:
+        raise ValueError(f"attention_decode: kv_splits must be 'auto' or an int from 1 to 64, got {kv_splits!r}")
+    return kv_splits
+
+
+def attention_decode_ref(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, kv_len: torch.Tensor,
+                         scale: float | None = None):
+    """fp32 decode attention -> (o [B, Sq, H, D] in q's dtype, lse2 [B, H, Sq] fp32, log2 units): query i of
+    sequence b sees the keys ``j <= kv_len[b] - Sq + i`` of its cache; rows at or past ``kv_len[b]`` do not
+    enter, whatever they hold."""
+    B, H, Sq, D = q.shape
+    Hkv, Smax = k_cache.size(1), k_cache.size(2)
+    n = kv_len.long().clamp(Sq, Smax).view(B, 1, 1, 1, 1)  # the kernel's clamp
+    j = torch.arange(Smax, device=q.device).view(1, 1, 1, 1, Smax)
+    valid = (j < n).view(B, 1, 1, Smax, 1)
+    k = torch.where(valid, k_cache.float().view(B, Hkv, 1, Smax, D), 0.0)
+    v = torch.where(valid, v_cache.float().view(B, Hkv, 1, Smax, D), 0.0)
+    sc = scale if scale is not None else D ** -0.5
+    s = torch.matmul(q.float().view(B, Hkv, H // Hkv, Sq, D), k.transpose(-1, -2)) * sc
+    s = s.masked_fill(j > n - Sq + torch.arange(Sq, device=q.device).view(1, 1, 1, Sq, 1), float("-inf"))
+    o = torch.matmul(torch.softmax(s, dim=-1), v).reshape(B, H, Sq, D).transpose(1, 2).to(q.dtype).contiguous()
+    return o, (torch.logsumexp(s, dim=-1) * 1.4426950408889634).reshape(B, H, Sq)
+
+
+def attention_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, kv_len: torch.Tensor,
+                     scale: float | None = None, kv_splits="auto", return_lse: bool = False, check: bool = False):
+    """One decode step of GQA attention over a ragged KV cache -> o [B, Sq, H, 128] bf16 (with ``return_lse``
+    also lse2 [B, H, Sq] fp32, log2 units).  Forward only.
+
+    ``q`` [B, H, Sq, 128] bf16 holds the Sq new tokens' queries, ``1 <= Sq`` and ``Sq * (H / Hkv) <= 32``.
+    ``k_cache``, ``v_cache`` [B, Hkv, Smax, 128] bf16, contiguous, any Smax >= Sq.  ``kv_len`` int32 [B] on the
+    caches' device: the valid keys of each sequence with the new tokens already appended, ``Sq <= kv_len[b] <=
+    Smax``.  Query i of sequence b sits at position ``kv_len[b] - Sq + i`` and sees the keys up to it.  The
+    kernel (csrc/ops/attention_decode.hip) reads ``kv_len`` on the device and clamps it into [Sq, Smax]: no
+    host sync, and no value moves an access outside the cache.  ``check=True`` costs one sync and raises
+    ``ValueError`` for a value outside that range.  The result does not depend on cache rows at or past
+    ``kv_len[b]``, NaN and Inf included.
+
+    ``kv_splits``: an int n from 1 to 64 deals each sequence's 64-key tiles to n workgroups per KV head, whose
+    fp32 partials the split-KV merge combines in split order; ``"auto"`` is :func:`decode_splits_for`.  On CPU
+    tensors the call is :func:`attention_decode_ref`, and ``kv_splits`` is accepted and ignored."""
+    n = _check_decode(q, k_cache, v_cache, kv_len, kv_splits)
+    Sq, Smax = q.size(2), k_cache.size(2)
+    if check and not bool(((kv_len >= Sq) & (kv_len <= Smax)).all()):
+        raise ValueError(f"attention_decode: kv_len must lie in [{Sq}, {Smax}], got {kv_len.tolist()}")
+    sc = scale if scale is not None else q.size(-1) ** -0.5
+    if q.is_cuda:
+        o, lse2 = hip().attn_decode(q.contiguous(), k_cache, v_cache, kv_len.contiguous(), float(sc), n)
+    else:
+        o, lse2 = attention_decode_ref(q, k_cache, v_cache, kv_len, sc)
+    return (o, lse2) if return_lse else o
