@@ -14,7 +14,14 @@ Printed: one JSON line; per shape the median us per call and the K/V bytes read 
 kv_len * 256 bytes over the time; and for each candidate MIN_TILES_PER_DECODE_SPLIT the shapes where the n that
 ``decode_splits_for`` would pick is slower than n = 1 by more than the spread.
 
-    python bench/attn_decode_bench.py [--iters 10] [--rounds 5]
+With ``--page-size P`` (repeatable) every shape also times ``fused.attention_decode_paged`` over the same K/V laid
+out in pages of P rows, in the same rounds as the contiguous callers and at the same ``"auto"`` n: under a block
+table that is a seeded random permutation of the pool (the worst locality; two series, which give that caller's
+spread), under the identity table, and the only route without the kernel, a torch gather of the pages into a slab
+followed by the contiguous call.  Before timing, the paged result is compared bit for bit with the contiguous one.
+A second table reports paged / contiguous per shape and page size next to the spreads.
+
+    python bench/attn_decode_bench.py [--iters 10] [--rounds 5] [--page-size 64 --page-size 256]
 """
 import argparse
 import json
@@ -55,7 +62,32 @@ def auto_for(B, Smax, min_tiles):
         fused.MIN_TILES_PER_DECODE_SPLIT = saved
 
 
-def bench_shape(B, lens, Smax, iters, rounds):
+def paged_callers(fns, q, kv_len, caches, auto, P, Smax):
+    """Adds the callers of page size P to ``fns``; -> whether the paged result equals the contiguous one bit for bit."""
+    B, MP, copies = q.size(0), Smax // P, len(caches)
+    g = torch.Generator(device="cuda").manual_seed(P)
+    tables = {"perm": torch.randperm(B * MP, generator=g, device="cuda").int().view(B, MP),
+              "ident": torch.arange(B * MP, dtype=torch.int32, device="cuda").view(B, MP)}
+    pools = {}
+    for name, tab in tables.items():  # pool[tab[b, p]] = page p of sequence b
+        pools[name] = []
+        for k, v in caches:
+            kp, vp = (torch.empty(B * MP, HKV, P, D, dtype=torch.bfloat16, device="cuda") for _ in range(2))
+            kp[tab.long().flatten()] = k.view(B, HKV, MP, P, D).transpose(1, 2).flatten(0, 1)
+            vp[tab.long().flatten()] = v.view(B, HKV, MP, P, D).transpose(1, 2).flatten(0, 1)
+            pools[name].append((kp, vp))
+    call = lambda name, i: fused.attention_decode_paged(q, *pools[name][i % copies], tables[name], kv_len, kv_splits=auto)  # noqa: E731
+    fns[f"perm{P}"] = lambda i: call("perm", i)
+    fns[f"perm{P}_2"] = lambda i: call("perm", i)
+    fns[f"ident{P}"] = lambda i: call("ident", i)
+    fns[f"gather{P}"] = lambda i: fused.attention_decode(
+        q, fused._gather_pages(pools["perm"][i % copies][0], tables["perm"]), fused._gather_pages(pools["perm"][i % copies][1], tables["perm"]),
+        kv_len, kv_splits=auto)
+    want = fused.attention_decode(q, *caches[0], kv_len, kv_splits=auto)
+    return all(torch.equal(fns[f"{name}{P}"](0), want) for name in ("perm", "ident", "gather"))
+
+
+def bench_shape(B, lens, Smax, iters, rounds, page_sizes=()):
     g = torch.Generator(device="cuda").manual_seed(0)
     bf = lambda *s: torch.randn(*s, generator=g, device="cuda").to(torch.bfloat16)  # noqa: E731
     kv_bytes = 2 * HKV * sum(lens) * D * 2
@@ -70,6 +102,7 @@ def bench_shape(B, lens, Smax, iters, rounds):
     for n in [s for s in SPLITS if -(-Smax // 64) >= s]:
         fns[n] = lambda i, n=n: fused.attention_decode(q, *caches[i % copies], kv_len, kv_splits=n)
     fns["auto2"] = lambda i: fused.attention_decode(q, *caches[i % copies], kv_len, kv_splits=auto)
+    paged_equal = {P: paged_callers(fns, q, kv_len, caches, auto, P, Smax) for P in page_sizes}
     o = fused.attention_decode(q, *caches[0], kv_len, kv_splits=auto).transpose(1, 2).float()
     err = float((o - fns["torch"](0).float()).abs().max())
     keys = list(fns)
@@ -82,16 +115,20 @@ def bench_shape(B, lens, Smax, iters, rounds):
     med = {key: statistics.median(t) for key, t in times.items()}
     return {"B": B, "kv_len": lens[0] if uniform else "mixed", "Smax": Smax, "auto": auto, "copies": copies, "kv_bytes": kv_bytes,
             "max_abs_diff_vs_torch": err, "median_us": {str(k): round(t, 2) for k, t in med.items()},
-            "spread": abs(med[auto] - med["auto2"]) / med[auto]}
+            "spread": abs(med[auto] - med["auto2"]) / med[auto],
+            "paged": {str(P): {"bit_equal": paged_equal[P], "perm": med[f"perm{P}"] / med[auto], "ident": med[f"ident{P}"] / med[auto],
+                               "gather": med[f"gather{P}"] / med[auto], "perm_over_ident": med[f"perm{P}"] / med[f"ident{P}"],
+                               "spread": abs(med[f"perm{P}"] - med[f"perm{P}_2"]) / med[f"perm{P}"]} for P in page_sizes}}
 
 
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--page-size", type=int, action="append", default=[], help="also time the paged kernel at this page size (repeatable)")
     a = ap.parse_args()
     fused.hip()
-    res = [bench_shape(B, lens, Smax, a.iters, a.rounds) for B, lens, Smax in SHAPES]
+    res = [bench_shape(B, lens, Smax, a.iters, a.rounds, tuple(a.page_size)) for B, lens, Smax in SHAPES]
     spread = max(r["spread"] for r in res)
     print(json.dumps({"heads": [H, HKV], "iters": a.iters, "rounds": a.rounds, "spread_max": spread, "shapes": res}))
     print(f"run-to-run spread of the auto n (two interleaved series), max over shapes: {100 * spread:.2f} %")
@@ -111,6 +148,14 @@ def main() -> int:
                if n > 1 and r["median_us"][str(n)] > r["median_us"]["1"] * (1 + spread)]
         tot = sum(r["median_us"][str(n)] for r, n in picked) / sum(r["median_us"]["1"] for r, _ in picked)
         print(f"| {c} | {sum(n > 1 for _, n in picked)} | {'; '.join(bad) or 'none'} | {tot:.3f} |")
+    if a.page_size:
+        print("\nratios to the contiguous kernel at the auto n, same rounds; spread c / p: two interleaved series of the contiguous / the paged caller"
+              "\n| B | kv_len | page | bit-equal | paged perm / contig | paged ident / contig | gather + contig / contig | perm / ident | spread c | spread p |\n"
+              + "|---" * 10 + "|")
+        for r in res:
+            for P, x in r["paged"].items():
+                print(f"| {r['B']} | {r['kv_len']} | {P} | {x['bit_equal']} | {x['perm']:.3f} | {x['ident']:.3f} | {x['gather']:.2f} | "
+                      f"{x['perm_over_ident']:.3f} | {100 * r['spread']:.2f} % | {100 * x['spread']:.2f} % |")
     return 0
 
 

@@ -5,7 +5,8 @@
 // through gtk_attn64::launch_*; the host checks and the outputs are the same.  A query chunk at an offset
 // into longer K/V (attn_*_qoff) goes to the kernels of attention_qoff.hip through gtk_qoff::launch_*, and with
 // its keys split over several workgroups (attn_*_qoff_split) to those of attention_splitkv.hip.  A decode step
-// over a ragged KV cache (attn_decode) goes to the kernel of attention_decode.hip through gtk_decode::launch.
+// over a ragged KV cache (attn_decode) goes to the kernel of attention_decode.hip through gtk_decode::launch, and
+// over a paged cache (attn_decode_paged, kv_append_paged) to those of attention_decode_paged.hip.
 #include "attention_kernels.h"
 #include "attention_splitkv.h"
 
@@ -35,6 +36,15 @@ constexpr int kMaxSplits = 64;
 // [n, B, Sq, H, 128] and lse_part fp32 [n, B, H, Sq] that gtk_splitkv::launch_combine reads
 void launch(hipStream_t st, const u16* q, const u16* kc, const u16* vc, const int* kv_len, u16* o, float* lse2, float* o_part,
             float* lse_part, int B, int H, int Hkv, int Sq, int Smax, float c, int n);
+
+// csrc/ops/attention_decode_paged.hip: the same over pools [num_pages, Hkv, page_size, 128] and an int32 block table
+// [B, max_pages], and the append of k_new, v_new [B, Hkv, Sq, 128] at positions kv_len[b] - Sq .. kv_len[b] - 1
+constexpr int kMaxAppend = 32;
+void launch_paged(hipStream_t st, const u16* q, const u16* kp, const u16* vp, const int* block_table, const int* kv_len, u16* o,
+                  float* lse2, float* o_part, float* lse_part, int B, int H, int Hkv, int Sq, int page_size, int max_pages,
+                  int num_pages, float c, int n);
+void launch_append(hipStream_t st, const u16* k_new, const u16* v_new, u16* kp, u16* vp, const int* block_table, const int* kv_len,
+                   int B, int Hkv, int Sq, int page_size, int max_pages, int num_pages);
 
 }  // namespace gtk_decode
 
@@ -344,6 +354,77 @@ std::vector<at::Tensor> attn_decode(const at::Tensor& q, const at::Tensor& k_cac
     gtk_splitkv::launch_combine(cur_stream(), o_part.data_ptr<float>(), lse_part.data_ptr<float>(), bpm(o), lse.data_ptr<float>(),
                                 (int)B, (int)H, (int)Sq, (int)n);
   return {o, lse};
+}
+
+// ---------------------------------------------------------------- a decode step over a paged KV cache
+// what the two paged calls share: the pools [num_pages, Hkv, page_size, 128], the table [B, max_pages], kv_len [B]
+static void check_paged(const char* who, const at::Tensor& x, const at::Tensor& k_pool, const at::Tensor& v_pool,
+                        const at::Tensor& block_table, const at::Tensor& kv_len) {
+  for (const at::Tensor* y : {&x, &k_pool, &v_pool})
+    TORCH_CHECK(y->is_cuda() && y->scalar_type() == at::kBFloat16 && y->is_contiguous() && y->dim() == 4, who,
+                ": the new rows and the pools must be contiguous bf16 4-d GPU tensors");
+  TORCH_CHECK(x.size(3) == D && k_pool.size(3) == D && v_pool.size(3) == D, who, ": head dim must be 128, got ", x.size(3));
+  TORCH_CHECK(k_pool.sizes() == v_pool.sizes(), who, ": shape mismatch (k_pool and v_pool alike)");
+  TORCH_CHECK(k_pool.device() == x.device() && v_pool.device() == x.device(), who, ": all tensors must be on one device");
+  const int64_t B = x.size(0), P = k_pool.size(2);
+  TORCH_CHECK(k_pool.size(0) > 0 && k_pool.size(0) < (int64_t(1) << 31), who, ": the pool must hold between 1 and 2^31 - 1 pages");
+  TORCH_CHECK(P >= 64 && P <= 1024 && P % 64 == 0, who, ": page_size must be a multiple of 64 from 64 to 1024, got ", P);
+  TORCH_CHECK(block_table.is_cuda() && block_table.device() == x.device() && block_table.scalar_type() == at::kInt &&
+                  block_table.is_contiguous() && block_table.dim() == 2 && block_table.size(0) == B && block_table.size(1) > 0,
+              who, ": block_table must be a contiguous int32 [B, max_pages] GPU tensor on the pools' device");
+  TORCH_CHECK(block_table.size(1) * P < (int64_t(1) << 31), who, ": max_pages * page_size must be below 2^31");
+  TORCH_CHECK(kv_len.is_cuda() && kv_len.device() == x.device() && kv_len.scalar_type() == at::kInt && kv_len.is_contiguous() &&
+                  kv_len.dim() == 1 && kv_len.size(0) == B,
+              who, ": kv_len must be a contiguous int32 [B] GPU tensor on the pools' device");
+}
+
+// attn_decode over a cache of pages: q [B, H, Sq, 128]; k_pool, v_pool [num_pages, Hkv, page_size, 128]; block_table
+// int32 [B, max_pages], entry [b, p] the pool page of keys p * page_size .. of sequence b; kv_len int32 [B].  The
+// kernel clamps kv_len into [Sq, max_pages * page_size] and every page id into [0, num_pages); nothing here reads
+// either.  -> (o [B, Sq, H, 128], lse2 [B, H, Sq]), bit for bit attn_decode's on the gathered slab at the same n
+std::vector<at::Tensor> attn_decode_paged(const at::Tensor& q, const at::Tensor& k_pool, const at::Tensor& v_pool,
+                                          const at::Tensor& block_table, const at::Tensor& kv_len, double scale, int64_t n) {
+  check_paged("attention decode paged", q, k_pool, v_pool, block_table, kv_len);
+  const int64_t B = q.size(0), H = q.size(1), Sq = q.size(2), Hkv = k_pool.size(1), P = k_pool.size(2), MP = block_table.size(1);
+  TORCH_CHECK(B > 0 && Hkv > 0 && H % Hkv == 0, "attention decode paged: q heads must be a multiple of kv heads");
+  TORCH_CHECK(Sq >= 1 && Sq * (H / Hkv) <= gtk_decode::kMaxRows, "attention decode paged: Sq * (H / Hkv) must be between 1 and ",
+              gtk_decode::kMaxRows, ", got ", Sq * (H / Hkv));
+  TORCH_CHECK(B * H * Sq < (int64_t(1) << 31) && B * Hkv < (int64_t(1) << 31), "attention decode paged: B * H * Sq must be below 2^31");
+  check_scale(scale);
+  TORCH_CHECK(n >= 1 && n <= gtk_decode::kMaxSplits, "attention decode paged: kv_splits must be between 1 and ",
+              gtk_decode::kMaxSplits, ", got ", n);
+  auto fopt = q.options().dtype(at::kFloat);
+  auto o = at::empty({B, Sq, H, D}, q.options());
+  auto lse = at::empty({B, H, Sq}, fopt);
+  at::Tensor o_part, lse_part;
+  if (n > 1) o_part = at::empty({n, B, Sq, H, D}, fopt), lse_part = at::empty({n, B, H, Sq}, fopt);
+  gtk_decode::launch_paged(cur_stream(), bp(q), bp(k_pool), bp(v_pool), block_table.data_ptr<int>(), kv_len.data_ptr<int>(), bpm(o),
+                           lse.data_ptr<float>(), n > 1 ? o_part.data_ptr<float>() : nullptr,
+                           n > 1 ? lse_part.data_ptr<float>() : nullptr, (int)B, (int)H, (int)Hkv, (int)Sq, (int)P, (int)MP,
+                           (int)k_pool.size(0), (float)(scale * 1.4426950408889634), (int)n);
+  if (n > 1)
+    gtk_splitkv::launch_combine(cur_stream(), o_part.data_ptr<float>(), lse_part.data_ptr<float>(), bpm(o), lse.data_ptr<float>(),
+                                (int)B, (int)H, (int)Sq, (int)n);
+  return {o, lse};
+}
+
+// the Sq new tokens' rows k_new, v_new [B, Hkv, Sq, 128] into the pages, in place: row i of sequence b at position
+// kv_len[b] - Sq + i, kv_len counting the new tokens.  A sequence with kv_len outside [Sq, max_pages * page_size]
+// and a row whose page id is outside [0, num_pages) are skipped by the kernel
+void kv_append_paged(const at::Tensor& k_new, const at::Tensor& v_new, at::Tensor& k_pool, at::Tensor& v_pool,
+                     const at::Tensor& block_table, const at::Tensor& kv_len) {
+  check_paged("kv append paged", k_new, k_pool, v_pool, block_table, kv_len);
+  TORCH_CHECK(v_new.is_cuda() && v_new.scalar_type() == at::kBFloat16 && v_new.is_contiguous() && v_new.sizes() == k_new.sizes() &&
+                  v_new.device() == k_new.device(),
+              "kv append paged: k_new and v_new must be contiguous bf16 GPU tensors of one shape on one device");
+  const int64_t B = k_new.size(0), Hkv = k_new.size(1), Sq = k_new.size(2);
+  TORCH_CHECK(B > 0 && Hkv == k_pool.size(1), "kv append paged: the new rows and the pools must have the same KV heads");
+  TORCH_CHECK(Sq >= 1 && Sq <= gtk_decode::kMaxAppend, "kv append paged: Sq must be between 1 and ", gtk_decode::kMaxAppend,
+              ", got ", Sq);
+  TORCH_CHECK(B * Hkv * Sq < (int64_t(1) << 31), "kv append paged: B * Hkv * Sq must be below 2^31");
+  gtk_decode::launch_append(cur_stream(), bp(k_new), bp(v_new), bpm(k_pool), bpm(v_pool), block_table.data_ptr<int>(),
+                            kv_len.data_ptr<int>(), (int)B, (int)Hkv, (int)Sq, (int)k_pool.size(2), (int)block_table.size(1),
+                            (int)k_pool.size(0));
 }
 
 // the document-masked backward, from the outputs of attn_fwd_doc

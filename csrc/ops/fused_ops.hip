@@ -986,6 +986,10 @@ std::vector<at::Tensor> attn_bwd_qoff_split(const at::Tensor& dout, const at::Te
                                             int64_t q_offset, int64_t n);
 std::vector<at::Tensor> attn_decode(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
                                     const at::Tensor& kv_len, double scale, int64_t n);
+std::vector<at::Tensor> attn_decode_paged(const at::Tensor& q, const at::Tensor& k_pool, const at::Tensor& v_pool,
+                                          const at::Tensor& block_table, const at::Tensor& kv_len, double scale, int64_t n);
+void kv_append_paged(const at::Tensor& k_new, const at::Tensor& v_new, at::Tensor& k_pool, at::Tensor& v_pool,
+                     const at::Tensor& block_table, const at::Tensor& kv_len);
 }  // namespace gtk_attn
 
 namespace gtk_xpose {  // csrc/ops/transpose.hip
@@ -1028,6 +1032,11 @@ PYBIND11_MODULE(_fused, m) {
   m.def("attn_decode", &gtk_attn::attn_decode,
         "decode attention (D=128), Sq * H / Hkv <= 32 queries per KV head against a ragged cache [B,Hkv,Smax,D] with int32 "
         "kv_len [B] read on the device, n (1..64) key splits: -> (o [B,Sq,H,D], lse2 [B,H,Sq])");
+  m.def("attn_decode_paged", &gtk_attn::attn_decode_paged,
+        "attn_decode over a paged cache: pools [num_pages,Hkv,page_size,D] (page_size % 64 == 0), int32 block_table "
+        "[B,max_pages] and kv_len [B] read on the device, n (1..64) key splits: -> (o [B,Sq,H,D], lse2 [B,H,Sq])");
+  m.def("kv_append_paged", &gtk_attn::kv_append_paged,
+        "k_new, v_new [B,Hkv,Sq,D] (Sq 1..32) into the pages of a paged cache at positions kv_len[b] - Sq .., in place");
   m.doc() = "gfx950 fused kernels for the Llama-3 DP validation workload";
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
   m.def("rmsnorm_bwd", &rmsnorm_bwd);

@@ -189,7 +189,10 @@ def targets() -> List[Target]:
                                                     "-packed-fp32-ops"],
                           # the decode kernel over a ragged KV cache, a kernel of its own over the same helpers
                           "attention_decode.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-Xclang", "-target-feature", "-Xclang",
-                                                   "-packed-fp32-ops"]}),
+                                                   "-packed-fp32-ops"],
+                          # its paged-cache sibling (the same body, attention_decode_body.h) and the page append
+                          "attention_decode_paged.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-Xclang", "-target-feature",
+                                                         "-Xclang", "-packed-fp32-ops"]}),
     ]
 
 

@@ -17,6 +17,7 @@ __all__ = [
     "cross_entropy_ref", "hip", "attention", "attention_ref", "flash_attention_supported", "transpose", "swiglu_bwd_ref",
     "swiglu_bwd_t", "swiglu_fwd_t", "attention_t", "offer_t", "take_t", "clear_t", "doc_bounds", "doc_start_from_eos",
     "kv_splits_for", "attention_decode", "attention_decode_ref", "decode_splits_for",
+    "attention_decode_paged", "attention_decode_paged_ref", "kv_cache_append", "kv_cache_append_ref",
 ]
 
 
@@ -602,3 +603,143 @@ def attention_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
     else:
         o, lse2 = attention_decode_ref(q, k_cache, v_cache, kv_len, sc)
     return (o, lse2) if return_lse else o
+
+
+# ------------------------------------------------------------------------------------ decode over a paged KV cache
+KV_APPEND_MAX_ROWS = 32  # the new tokens one kv_cache_append call takes per sequence
+
+
+def _check_paged(who, x, k_pool, v_pool, block_table, kv_len):
+    """What :func:`attention_decode_paged` and :func:`kv_cache_append` ask of the pools, the table and the lengths;
+    ``x`` is q or k_new."""
+    for name, t in ((("q" if who == "attention_decode_paged" else "k_new"), x), ("k_pool", k_pool), ("v_pool", v_pool)):
+        if t.dim() != 4 or t.dtype != torch.bfloat16:
+            raise ValueError(f"{who}: {name} must be a bf16 4-d tensor with head dim 128, got {t.dtype} {tuple(t.shape)}")
+        if t.size(-1) != 128:
+            raise ValueError(f"{who}: head dim must be 128, got {t.size(-1)}")
+    if k_pool.shape != v_pool.shape:
+        raise ValueError(f"{who}: k_pool and v_pool must have one shape")
+    if k_pool.device != x.device or v_pool.device != x.device:
+        raise ValueError(f"{who}: all tensors must be on one device")
+    if not (k_pool.is_contiguous() and v_pool.is_contiguous()):
+        raise ValueError(f"{who}: the pools must be contiguous")
+    P = k_pool.size(2)
+    if k_pool.size(0) == 0 or P % 64 or not 64 <= P <= 1024:
+        raise ValueError(f"{who}: page_size must be a multiple of 64 from 64 to 1024 (and the pool not empty), got {P}")
+    B = x.size(0)
+    if (not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2
+            or block_table.size(0) != B or block_table.size(1) == 0 or block_table.device != x.device):
+        raise ValueError(f"{who}: block_table must be an int32 [B, max_pages] tensor on the pools' device")
+    if not isinstance(kv_len, torch.Tensor) or kv_len.dtype != torch.int32 or kv_len.shape != (B,) or kv_len.device != x.device:
+        raise ValueError(f"{who}: kv_len must be an int32 [B] tensor on the pools' device")
+
+
+def _check_paged_content(who, Sq, k_pool, block_table, kv_len):
+    """``check=True``: one sync.  The lengths lie in [Sq, max_pages * page_size] and every table entry a sequence
+    needs names a page of the pool."""
+    P, Smax = k_pool.size(2), block_table.size(1) * k_pool.size(2)
+    if not bool(((kv_len >= Sq) & (kv_len <= Smax)).all()):
+        raise ValueError(f"{who}: kv_len must lie in [{Sq}, {Smax}], got {kv_len.tolist()}")
+    needed = torch.arange(block_table.size(1), device=kv_len.device).view(1, -1) * P < kv_len.view(-1, 1)
+    if bool((needed & ((block_table < 0) | (block_table >= k_pool.size(0)))).any()):
+        raise ValueError(f"{who}: a needed block_table entry lies outside [0, {k_pool.size(0)})")
+
+
+def _gather_pages(pool: torch.Tensor, block_table: torch.Tensor) -> torch.Tensor:
+    """The slab [B, Hkv, max_pages * page_size, D] a block table names; ids clamped into the pool as the kernel does."""
+    B, MP = block_table.shape
+    pages = pool[block_table.long().clamp(0, pool.size(0) - 1)]  # [B, MP, Hkv, P, D]
+    return pages.transpose(1, 2).reshape(B, pool.size(1), MP * pool.size(2), pool.size(3))
+
+
+def attention_decode_paged_ref(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor,
+                               kv_len: torch.Tensor, scale: float | None = None):
+    """:func:`attention_decode_ref` on the slab gathered from the pages -> (o, lse2)."""
+    return attention_decode_ref(q, _gather_pages(k_pool, block_table), _gather_pages(v_pool, block_table), kv_len, scale)
+
+
+def attention_decode_paged(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor,
+                           kv_len: torch.Tensor, scale: float | None = None, kv_splits="auto", return_lse: bool = False,
+                           check: bool = False):
+    """:func:`attention_decode` over a paged KV cache -> o [B, Sq, H, 128] bf16 (with ``return_lse`` also lse2).
+    Forward only.
+
+    ``k_pool``, ``v_pool`` [num_pages, Hkv, page_size, 128] bf16, contiguous, ``page_size`` a multiple of 64 from
+    64 to 1024; the pool may exceed 4 GiB.  ``block_table`` int32 [B, max_pages] on the pools' device: entry
+    [b, p] is the pool page holding keys ``p * page_size ..`` of sequence b; only the entries below
+    ``ceil(kv_len[b] / page_size)`` are read, and sequences may share pages.  ``kv_len`` and ``q`` as in
+    :func:`attention_decode` with ``Smax = max_pages * page_size``.  The kernel
+    (csrc/ops/attention_decode_paged.hip) follows the table on the device and clamps the lengths and every page
+    id, so no content of either moves an access outside the pools; ``check=True`` costs one sync and raises
+    ``ValueError`` for a length out of range or a needed entry outside ``[0, num_pages)``.  The result is
+    :func:`attention_decode`'s on the gathered slab at the same ``kv_splits``, bit for bit; ``"auto"`` is
+    ``decode_splits_for(B, Hkv, max_pages * page_size)``.  On CPU tensors the call is
+    :func:`attention_decode_paged_ref`."""
+    who = "attention_decode_paged"
+    _check_paged(who, q, k_pool, v_pool, block_table, kv_len)
+    B, H, Sq, _ = q.shape
+    Hkv, Smax = k_pool.size(1), block_table.size(1) * k_pool.size(2)
+    if Hkv == 0 or H % Hkv:
+        raise ValueError(f"{who}: q heads ({H}) must be a multiple of kv heads ({Hkv})")
+    if not 1 <= Sq * (H // Hkv) <= DECODE_MAX_ROWS:
+        raise ValueError(f"{who}: Sq * (H / Hkv) must be between 1 and {DECODE_MAX_ROWS}, got {Sq * (H // Hkv)}")
+    if torch.is_grad_enabled() and any(x.requires_grad for x in (q, k_pool, v_pool)):
+        raise ValueError(f"{who}: forward only, an input requires grad")
+    if kv_splits == "auto":
+        n = decode_splits_for(B, Hkv, Smax)
+    elif isinstance(kv_splits, bool) or not isinstance(kv_splits, int) or not 1 <= kv_splits <= 64:
+        raise ValueError(f"{who}: kv_splits must be 'auto' or an int from 1 to 64, got {kv_splits!r}")
+    else:
+        n = kv_splits
+    if check:
+        _check_paged_content(who, Sq, k_pool, block_table, kv_len)
+    sc = scale if scale is not None else q.size(-1) ** -0.5
+    if q.is_cuda:
+        o, lse2 = hip().attn_decode_paged(q.contiguous(), k_pool, v_pool, block_table.contiguous(), kv_len.contiguous(), float(sc), n)
+    else:
+        o, lse2 = attention_decode_paged_ref(q, k_pool, v_pool, block_table, kv_len, sc)
+    return (o, lse2) if return_lse else o
+
+
+def kv_cache_append_ref(k_new: torch.Tensor, v_new: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor,
+                        block_table: torch.Tensor, kv_len: torch.Tensor) -> None:
+    """The append as an indexed assignment, in place: row i of sequence b to position ``kv_len[b] - Sq + i``.  A
+    sequence whose length is outside [Sq, max_pages * page_size] and a row whose page id is outside the pool
+    are skipped."""
+    B, _, Sq, _ = k_new.shape
+    P, MP = k_pool.size(2), block_table.size(1)
+    n = kv_len.long().view(B, 1)
+    pos = n - Sq + torch.arange(Sq, device=k_new.device).view(1, Sq)
+    page = block_table.long().gather(1, (pos // P).clamp(0, MP - 1))
+    ok = (n >= Sq) & (n <= MP * P) & (page >= 0) & (page < k_pool.size(0))
+    b, i = ok.nonzero(as_tuple=True)
+    k_pool[page[b, i], :, pos[b, i] % P] = k_new[b, :, i]
+    v_pool[page[b, i], :, pos[b, i] % P] = v_new[b, :, i]
+
+
+def kv_cache_append(k_new: torch.Tensor, v_new: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor,
+                    block_table: torch.Tensor, kv_len: torch.Tensor, check: bool = False) -> None:
+    """The other half of a decode step over a paged cache: write the Sq new tokens' rows ``k_new``, ``v_new``
+    [B, Hkv, Sq, 128] bf16 (``1 <= Sq <= 32``) into the pages, in place and on the current stream.  ``kv_len``
+    counts the new tokens, the same tensor :func:`attention_decode_paged` then takes: row i of sequence b goes to
+    position ``kv_len[b] - Sq + i``, page ``block_table[b, pos // page_size]``, row ``pos % page_size``.  The
+    kernel (csrc/ops/attention_decode_paged.hip) skips a sequence whose length is outside [Sq, max_pages *
+    page_size] and a row whose page id is outside the pool: a wrong table overwrites nobody's keys.
+    ``check=True`` costs one sync and raises ``ValueError`` for either.  On CPU tensors the call is
+    :func:`kv_cache_append_ref`."""
+    who = "kv_cache_append"
+    _check_paged(who, k_new, k_pool, v_pool, block_table, kv_len)
+    if v_new.shape != k_new.shape or v_new.dtype != torch.bfloat16 or v_new.device != k_new.device:
+        raise ValueError(f"{who}: k_new and v_new must be bf16 tensors of one shape on one device")
+    if k_new.size(1) != k_pool.size(1):
+        raise ValueError(f"{who}: the new rows have {k_new.size(1)} KV heads, the pools {k_pool.size(1)}")
+    if not 1 <= k_new.size(2) <= KV_APPEND_MAX_ROWS:
+        raise ValueError(f"{who}: Sq must be between 1 and {KV_APPEND_MAX_ROWS}, got {k_new.size(2)}")
+    if torch.is_grad_enabled() and any(x.requires_grad for x in (k_new, v_new, k_pool, v_pool)):
+        raise ValueError(f"{who}: forward only, an input requires grad")
+    if check:
+        _check_paged_content(who, k_new.size(2), k_pool, block_table, kv_len)
+    if k_new.is_cuda:
+        hip().kv_append_paged(k_new.contiguous(), v_new.contiguous(), k_pool, v_pool, block_table.contiguous(), kv_len.contiguous())
+    else:
+        kv_cache_append_ref(k_new, v_new, k_pool, v_pool, block_table, kv_len)
