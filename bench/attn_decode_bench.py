@@ -21,7 +21,13 @@ spread), under the identity table, and the only route without the kernel, a torc
 followed by the contiguous call.  Before timing, the paged result is compared bit for bit with the contiguous one.
 A second table reports paged / contiguous per shape and page size next to the spreads.
 
-    python bench/attn_decode_bench.py [--iters 10] [--rounds 5] [--page-size 64 --page-size 256]
+With ``--kv-fp8`` next to ``--page-size`` every shape also times ``fused.attention_decode_paged_fp8`` on the quantised
+copy (``kv_quantize_ref``) of the permuted pools, two series in the same rounds, and one-token appends into the bf16
+and the fp8 pools.  Before timing, the fp8 result is compared by ``torch.equal`` with the bf16 paged call on the
+dequantised pools.  A third table reports fp8 / bf16 paged per shape with both callers' spreads.  ``--shape I``
+(repeatable) keeps only ``SHAPES[I]``.
+
+    python bench/attn_decode_bench.py [--iters 10] [--rounds 5] [--page-size 64 --page-size 256] [--kv-fp8] [--shape 5]
 """
 import argparse
 import json
@@ -62,8 +68,33 @@ def auto_for(B, Smax, min_tiles):
         fused.MIN_TILES_PER_DECODE_SPLIT = saved
 
 
-def paged_callers(fns, q, kv_len, caches, auto, P, Smax):
-    """Adds the callers of page size P to ``fns``; -> whether the paged result equals the contiguous one bit for bit."""
+def quantize_pool(pool, pages=128):
+    """kv_quantize_ref over a pool, ``pages`` pages at a time (the rule works in float64) -> (codes, exp)."""
+    parts = [fused.kv_quantize_ref(pool[i:i + pages]) for i in range(0, pool.size(0), pages)]
+    return torch.cat([c for c, _ in parts]), torch.cat([e for _, e in parts])
+
+
+def fp8_callers(fns, q, kv_len, pools, table, auto, P):
+    """Adds the fp8 callers of page size P (two series) over the quantised copies of ``pools`` under ``table``, and the
+    append's; -> whether the fp8 result equals the bf16 paged call on the dequantised pools bit for bit."""
+    copies, q8 = len(pools), []
+    for kp, vp in pools:
+        (kc, ke), (vc, ve) = quantize_pool(kp), quantize_pool(vp)
+        q8.append((kc, vc, ke, ve))
+    call = lambda i: fused.attention_decode_paged_fp8(q, *q8[i % copies], table, kv_len, kv_splits=auto)  # noqa: E731
+    fns[f"fp8_{P}"] = call
+    fns[f"fp8_{P}_2"] = lambda i: call(i)
+    new = torch.randn(q.size(0), HKV, 1, D, device="cuda").to(torch.bfloat16)  # the step's token lands on row kv_len - 1
+    fns[f"append8_{P}"] = lambda i: fused.kv_cache_append_fp8(new, new, *q8[i % copies], table, kv_len)
+    fns[f"append{P}"] = lambda i: fused.kv_cache_append(new, new, *pools[i % copies], table, kv_len)
+    kc, vc, ke, ve = q8[0]
+    deq = [torch.cat([fused.kv_dequantize_ref(c[i:i + 128], e[i:i + 128]) for i in range(0, c.size(0), 128)]) for c, e in ((kc, ke), (vc, ve))]
+    return torch.equal(call(0), fused.attention_decode_paged(q, *deq, table, kv_len, kv_splits=auto))
+
+
+def paged_callers(fns, q, kv_len, caches, auto, P, Smax, kv_fp8=False):
+    """Adds the callers of page size P to ``fns``; -> whether the paged result equals the contiguous one bit for bit
+    (and, with ``kv_fp8``, whether the fp8 result equals the bf16 paged one on the dequantised pools)."""
     B, MP, copies = q.size(0), Smax // P, len(caches)
     g = torch.Generator(device="cuda").manual_seed(P)
     tables = {"perm": torch.randperm(B * MP, generator=g, device="cuda").int().view(B, MP),
@@ -84,10 +115,11 @@ def paged_callers(fns, q, kv_len, caches, auto, P, Smax):
         q, fused._gather_pages(pools["perm"][i % copies][0], tables["perm"]), fused._gather_pages(pools["perm"][i % copies][1], tables["perm"]),
         kv_len, kv_splits=auto)
     want = fused.attention_decode(q, *caches[0], kv_len, kv_splits=auto)
-    return all(torch.equal(fns[f"{name}{P}"](0), want) for name in ("perm", "ident", "gather"))
+    equal = all(torch.equal(fns[f"{name}{P}"](0), want) for name in ("perm", "ident", "gather"))
+    return (equal, fp8_callers(fns, q, kv_len, pools["perm"], tables["perm"], auto, P)) if kv_fp8 else equal
 
 
-def bench_shape(B, lens, Smax, iters, rounds, page_sizes=()):
+def bench_shape(B, lens, Smax, iters, rounds, page_sizes=(), kv_fp8=False):
     g = torch.Generator(device="cuda").manual_seed(0)
     bf = lambda *s: torch.randn(*s, generator=g, device="cuda").to(torch.bfloat16)  # noqa: E731
     kv_bytes = 2 * HKV * sum(lens) * D * 2
@@ -102,7 +134,10 @@ def bench_shape(B, lens, Smax, iters, rounds, page_sizes=()):
     for n in [s for s in SPLITS if -(-Smax // 64) >= s]:
         fns[n] = lambda i, n=n: fused.attention_decode(q, *caches[i % copies], kv_len, kv_splits=n)
     fns["auto2"] = lambda i: fused.attention_decode(q, *caches[i % copies], kv_len, kv_splits=auto)
-    paged_equal = {P: paged_callers(fns, q, kv_len, caches, auto, P, Smax) for P in page_sizes}
+    paged_equal = {P: paged_callers(fns, q, kv_len, caches, auto, P, Smax, kv_fp8) for P in page_sizes}
+    fp8_equal = {P: eq[1] for P, eq in paged_equal.items()} if kv_fp8 else {}
+    if kv_fp8:
+        paged_equal = {P: eq[0] for P, eq in paged_equal.items()}
     o = fused.attention_decode(q, *caches[0], kv_len, kv_splits=auto).transpose(1, 2).float()
     err = float((o - fns["torch"](0).float()).abs().max())
     keys = list(fns)
@@ -118,7 +153,12 @@ def bench_shape(B, lens, Smax, iters, rounds, page_sizes=()):
             "spread": abs(med[auto] - med["auto2"]) / med[auto],
             "paged": {str(P): {"bit_equal": paged_equal[P], "perm": med[f"perm{P}"] / med[auto], "ident": med[f"ident{P}"] / med[auto],
                                "gather": med[f"gather{P}"] / med[auto], "perm_over_ident": med[f"perm{P}"] / med[f"ident{P}"],
-                               "spread": abs(med[f"perm{P}"] - med[f"perm{P}_2"]) / med[f"perm{P}"]} for P in page_sizes}}
+                               "spread": abs(med[f"perm{P}"] - med[f"perm{P}_2"]) / med[f"perm{P}"]} for P in page_sizes},
+            # the fp8 cache against the bf16 paged caller on the same table; the spreads of the two callers' two series
+            "fp8": {str(P): {"bit_equal": fp8_equal[P], "fp8_over_paged": med[f"fp8_{P}"] / med[f"perm{P}"],
+                             "spread_fp8": abs(med[f"fp8_{P}"] - med[f"fp8_{P}_2"]) / med[f"fp8_{P}"],
+                             "spread_paged": abs(med[f"perm{P}"] - med[f"perm{P}_2"]) / med[f"perm{P}"],
+                             "append_fp8_us": med[f"append8_{P}"], "append_bf16_us": med[f"append{P}"]} for P in fp8_equal}}
 
 
 def main() -> int:
@@ -126,9 +166,14 @@ def main() -> int:
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--page-size", type=int, action="append", default=[], help="also time the paged kernel at this page size (repeatable)")
+    ap.add_argument("--kv-fp8", action="store_true", help="with --page-size: also time the fp8 cache against the bf16 paged caller")
+    ap.add_argument("--shape", type=int, action="append", default=[], help="only this shape, an index into SHAPES (repeatable)")
     a = ap.parse_args()
+    if a.kv_fp8 and not a.page_size:
+        ap.error("--kv-fp8 needs --page-size")
     fused.hip()
-    res = [bench_shape(B, lens, Smax, a.iters, a.rounds, tuple(a.page_size)) for B, lens, Smax in SHAPES]
+    res = [bench_shape(B, lens, Smax, a.iters, a.rounds, tuple(a.page_size), a.kv_fp8)
+           for i, (B, lens, Smax) in enumerate(SHAPES) if not a.shape or i in a.shape]
     spread = max(r["spread"] for r in res)
     print(json.dumps({"heads": [H, HKV], "iters": a.iters, "rounds": a.rounds, "spread_max": spread, "shapes": res}))
     print(f"run-to-run spread of the auto n (two interleaved series), max over shapes: {100 * spread:.2f} %")
@@ -156,6 +201,17 @@ def main() -> int:
             for P, x in r["paged"].items():
                 print(f"| {r['B']} | {r['kv_len']} | {P} | {x['bit_equal']} | {x['perm']:.3f} | {x['ident']:.3f} | {x['gather']:.2f} | "
                       f"{x['perm_over_ident']:.3f} | {100 * r['spread']:.2f} % | {100 * x['spread']:.2f} % |")
+    if a.kv_fp8:
+        print("\nthe fp8 cache against the bf16 paged kernel, both under the permuted table at the auto n, same rounds; bit-equal: to the bf16 paged "
+              "call on the dequantised pools; append: one token per sequence, us\n"
+              "| B | kv_len | page | bit-equal | paged us | fp8 us | fp8 / paged | spread paged | spread fp8 | faster by more than both | append bf16 | append fp8 |\n"
+              + "|---" * 12 + "|")
+        for r in res:
+            for P, x in r["fp8"].items():
+                m = r["median_us"]
+                print(f"| {r['B']} | {r['kv_len']} | {P} | {x['bit_equal']} | {m[f'perm{P}']:.1f} | {m[f'fp8_{P}']:.1f} | {x['fp8_over_paged']:.3f} | "
+                      f"{100 * x['spread_paged']:.2f} % | {100 * x['spread_fp8']:.2f} % | "
+                      f"{x['fp8_over_paged'] < 1 - max(x['spread_paged'], x['spread_fp8'])} | {x['append_bf16_us']:.1f} | {x['append_fp8_us']:.1f} |")
     return 0
 
 

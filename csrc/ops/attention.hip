@@ -6,7 +6,8 @@
 // into longer K/V (attn_*_qoff) goes to the kernels of attention_qoff.hip through gtk_qoff::launch_*, and with
 // its keys split over several workgroups (attn_*_qoff_split) to those of attention_splitkv.hip.  A decode step
 // over a ragged KV cache (attn_decode) goes to the kernel of attention_decode.hip through gtk_decode::launch, and
-// over a paged cache (attn_decode_paged, kv_append_paged) to those of attention_decode_paged.hip.
+// over a paged cache (attn_decode_paged, kv_append_paged) to those of attention_decode_paged.hip, over a paged
+// cache of e4m3 codes (attn_decode_paged_fp8, kv_append_paged_fp8) to those of attention_decode_paged_fp8.hip.
 #include "attention_kernels.h"
 #include "attention_splitkv.h"
 
@@ -45,6 +46,14 @@ void launch_paged(hipStream_t st, const u16* q, const u16* kp, const u16* vp, co
                   int num_pages, float c, int n);
 void launch_append(hipStream_t st, const u16* k_new, const u16* v_new, u16* kp, u16* vp, const int* block_table, const int* kv_len,
                    int B, int Hkv, int Sq, int page_size, int max_pages, int num_pages);
+
+// csrc/ops/attention_decode_paged_fp8.hip: the same two over a cache of e4m3 codes, kc, vc uint8 [num_pages, Hkv,
+// page_size, 128], and one exponent byte per row, kx, vx uint8 [num_pages, Hkv, page_size]; the append quantises
+void launch_paged_fp8(hipStream_t st, const u16* q, const uint8_t* kc, const uint8_t* vc, const uint8_t* kx, const uint8_t* vx,
+                      const int* block_table, const int* kv_len, u16* o, float* lse2, float* o_part, float* lse_part, int B, int H,
+                      int Hkv, int Sq, int page_size, int max_pages, int num_pages, float c, int n);
+void launch_append_fp8(hipStream_t st, const u16* k_new, const u16* v_new, uint8_t* kc, uint8_t* vc, uint8_t* kx, uint8_t* vx,
+                       const int* block_table, const int* kv_len, int B, int Hkv, int Sq, int page_size, int max_pages, int num_pages);
 
 }  // namespace gtk_decode
 
@@ -358,14 +367,9 @@ std::vector<at::Tensor> attn_decode(const at::Tensor& q, const at::Tensor& k_cac
 
 // ---------------------------------------------------------------- a decode step over a paged KV cache
 // what the two paged calls share: the pools [num_pages, Hkv, page_size, 128], the table [B, max_pages], kv_len [B]
-static void check_paged(const char* who, const at::Tensor& x, const at::Tensor& k_pool, const at::Tensor& v_pool,
-                        const at::Tensor& block_table, const at::Tensor& kv_len) {
-  for (const at::Tensor* y : {&x, &k_pool, &v_pool})
-    TORCH_CHECK(y->is_cuda() && y->scalar_type() == at::kBFloat16 && y->is_contiguous() && y->dim() == 4, who,
-                ": the new rows and the pools must be contiguous bf16 4-d GPU tensors");
-  TORCH_CHECK(x.size(3) == D && k_pool.size(3) == D && v_pool.size(3) == D, who, ": head dim must be 128, got ", x.size(3));
-  TORCH_CHECK(k_pool.sizes() == v_pool.sizes(), who, ": shape mismatch (k_pool and v_pool alike)");
-  TORCH_CHECK(k_pool.device() == x.device() && v_pool.device() == x.device(), who, ": all tensors must be on one device");
+// the pages' geometry, the table and the lengths: k_pool is the bf16 pool or the pool of codes
+static void check_pages(const char* who, const at::Tensor& x, const at::Tensor& k_pool, const at::Tensor& block_table,
+                        const at::Tensor& kv_len) {
   const int64_t B = x.size(0), P = k_pool.size(2);
   TORCH_CHECK(k_pool.size(0) > 0 && k_pool.size(0) < (int64_t(1) << 31), who, ": the pool must hold between 1 and 2^31 - 1 pages");
   TORCH_CHECK(P >= 64 && P <= 1024 && P % 64 == 0, who, ": page_size must be a multiple of 64 from 64 to 1024, got ", P);
@@ -376,6 +380,33 @@ static void check_paged(const char* who, const at::Tensor& x, const at::Tensor& 
   TORCH_CHECK(kv_len.is_cuda() && kv_len.device() == x.device() && kv_len.scalar_type() == at::kInt && kv_len.is_contiguous() &&
                   kv_len.dim() == 1 && kv_len.size(0) == B,
               who, ": kv_len must be a contiguous int32 [B] GPU tensor on the pools' device");
+}
+
+static void check_paged(const char* who, const at::Tensor& x, const at::Tensor& k_pool, const at::Tensor& v_pool,
+                        const at::Tensor& block_table, const at::Tensor& kv_len) {
+  for (const at::Tensor* y : {&x, &k_pool, &v_pool})
+    TORCH_CHECK(y->is_cuda() && y->scalar_type() == at::kBFloat16 && y->is_contiguous() && y->dim() == 4, who,
+                ": the new rows and the pools must be contiguous bf16 4-d GPU tensors");
+  TORCH_CHECK(x.size(3) == D && k_pool.size(3) == D && v_pool.size(3) == D, who, ": head dim must be 128, got ", x.size(3));
+  TORCH_CHECK(k_pool.sizes() == v_pool.sizes(), who, ": shape mismatch (k_pool and v_pool alike)");
+  TORCH_CHECK(k_pool.device() == x.device() && v_pool.device() == x.device(), who, ": all tensors must be on one device");
+  check_pages(who, x, k_pool, block_table, kv_len);
+}
+
+// the fp8 cache: codes uint8 [num_pages, Hkv, page_size, 128] and exponent bytes uint8 [num_pages, Hkv, page_size]
+static void check_paged_fp8(const char* who, const at::Tensor& x, const at::Tensor& k_codes, const at::Tensor& v_codes,
+                            const at::Tensor& k_exp, const at::Tensor& v_exp, const at::Tensor& block_table,
+                            const at::Tensor& kv_len) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.is_contiguous() && x.dim() == 4 && x.size(3) == D, who,
+              ": q and the new rows must be contiguous bf16 [.., .., .., 128] GPU tensors");
+  for (const at::Tensor* y : {&k_codes, &v_codes, &k_exp, &v_exp})
+    TORCH_CHECK(y->is_cuda() && y->scalar_type() == at::kByte && y->is_contiguous() && y->device() == x.device(), who,
+                ": the code and exponent pools must be contiguous uint8 GPU tensors on one device");
+  TORCH_CHECK(k_codes.dim() == 4 && k_codes.size(3) == D && v_codes.sizes() == k_codes.sizes(), who,
+              ": k_codes and v_codes must be [num_pages, Hkv, page_size, 128] alike");
+  TORCH_CHECK(k_exp.dim() == 3 && k_exp.sizes() == k_codes.sizes().slice(0, 3) && v_exp.sizes() == k_exp.sizes(), who,
+              ": k_exp and v_exp must be [num_pages, Hkv, page_size] of the code pools");
+  check_pages(who, x, k_codes, block_table, kv_len);
 }
 
 // attn_decode over a cache of pages: q [B, H, Sq, 128]; k_pool, v_pool [num_pages, Hkv, page_size, 128]; block_table
@@ -425,6 +456,53 @@ void kv_append_paged(const at::Tensor& k_new, const at::Tensor& v_new, at::Tenso
   gtk_decode::launch_append(cur_stream(), bp(k_new), bp(v_new), bpm(k_pool), bpm(v_pool), block_table.data_ptr<int>(),
                             kv_len.data_ptr<int>(), (int)B, (int)Hkv, (int)Sq, (int)k_pool.size(2), (int)block_table.size(1),
                             (int)k_pool.size(0));
+}
+
+// attn_decode_paged over the fp8 cache -> (o, lse2), bit for bit attn_decode_paged's on the dequantised pools at the same n
+std::vector<at::Tensor> attn_decode_paged_fp8(const at::Tensor& q, const at::Tensor& k_codes, const at::Tensor& v_codes,
+                                              const at::Tensor& k_exp, const at::Tensor& v_exp, const at::Tensor& block_table,
+                                              const at::Tensor& kv_len, double scale, int64_t n) {
+  check_paged_fp8("attention decode paged fp8", q, k_codes, v_codes, k_exp, v_exp, block_table, kv_len);
+  const int64_t B = q.size(0), H = q.size(1), Sq = q.size(2), Hkv = k_codes.size(1), P = k_codes.size(2), MP = block_table.size(1);
+  TORCH_CHECK(B > 0 && Hkv > 0 && H % Hkv == 0, "attention decode paged fp8: q heads must be a multiple of kv heads");
+  TORCH_CHECK(Sq >= 1 && Sq * (H / Hkv) <= gtk_decode::kMaxRows, "attention decode paged fp8: Sq * (H / Hkv) must be between 1 and ",
+              gtk_decode::kMaxRows, ", got ", Sq * (H / Hkv));
+  TORCH_CHECK(B * H * Sq < (int64_t(1) << 31) && B * Hkv < (int64_t(1) << 31), "attention decode paged fp8: B * H * Sq must be below 2^31");
+  check_scale(scale);
+  TORCH_CHECK(n >= 1 && n <= gtk_decode::kMaxSplits, "attention decode paged fp8: kv_splits must be between 1 and ",
+              gtk_decode::kMaxSplits, ", got ", n);
+  auto fopt = q.options().dtype(at::kFloat);
+  auto o = at::empty({B, Sq, H, D}, q.options());
+  auto lse = at::empty({B, H, Sq}, fopt);
+  at::Tensor o_part, lse_part;
+  if (n > 1) o_part = at::empty({n, B, Sq, H, D}, fopt), lse_part = at::empty({n, B, H, Sq}, fopt);
+  gtk_decode::launch_paged_fp8(cur_stream(), bp(q), k_codes.data_ptr<uint8_t>(), v_codes.data_ptr<uint8_t>(), k_exp.data_ptr<uint8_t>(),
+                               v_exp.data_ptr<uint8_t>(), block_table.data_ptr<int>(), kv_len.data_ptr<int>(), bpm(o),
+                               lse.data_ptr<float>(), n > 1 ? o_part.data_ptr<float>() : nullptr,
+                               n > 1 ? lse_part.data_ptr<float>() : nullptr, (int)B, (int)H, (int)Hkv, (int)Sq, (int)P, (int)MP,
+                               (int)k_codes.size(0), (float)(scale * 1.4426950408889634), (int)n);
+  if (n > 1)
+    gtk_splitkv::launch_combine(cur_stream(), o_part.data_ptr<float>(), lse_part.data_ptr<float>(), bpm(o), lse.data_ptr<float>(),
+                                (int)B, (int)H, (int)Sq, (int)n);
+  return {o, lse};
+}
+
+// kv_append_paged into the fp8 cache: every new row is quantised by the row rule on its way in
+void kv_append_paged_fp8(const at::Tensor& k_new, const at::Tensor& v_new, at::Tensor& k_codes, at::Tensor& v_codes, at::Tensor& k_exp,
+                         at::Tensor& v_exp, const at::Tensor& block_table, const at::Tensor& kv_len) {
+  check_paged_fp8("kv append paged fp8", k_new, k_codes, v_codes, k_exp, v_exp, block_table, kv_len);
+  TORCH_CHECK(v_new.is_cuda() && v_new.scalar_type() == at::kBFloat16 && v_new.is_contiguous() && v_new.sizes() == k_new.sizes() &&
+                  v_new.device() == k_new.device(),
+              "kv append paged fp8: k_new and v_new must be contiguous bf16 GPU tensors of one shape on one device");
+  const int64_t B = k_new.size(0), Hkv = k_new.size(1), Sq = k_new.size(2);
+  TORCH_CHECK(B > 0 && Hkv == k_codes.size(1), "kv append paged fp8: the new rows and the pools must have the same KV heads");
+  TORCH_CHECK(Sq >= 1 && Sq <= gtk_decode::kMaxAppend, "kv append paged fp8: Sq must be between 1 and ", gtk_decode::kMaxAppend,
+              ", got ", Sq);
+  TORCH_CHECK(B * Hkv * Sq < (int64_t(1) << 31), "kv append paged fp8: B * Hkv * Sq must be below 2^31");
+  gtk_decode::launch_append_fp8(cur_stream(), bp(k_new), bp(v_new), k_codes.data_ptr<uint8_t>(), v_codes.data_ptr<uint8_t>(),
+                                k_exp.data_ptr<uint8_t>(), v_exp.data_ptr<uint8_t>(), block_table.data_ptr<int>(),
+                                kv_len.data_ptr<int>(), (int)B, (int)Hkv, (int)Sq, (int)k_codes.size(2), (int)block_table.size(1),
+                                (int)k_codes.size(0));
 }
 
 // the document-masked backward, from the outputs of attn_fwd_doc

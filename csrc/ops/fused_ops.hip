@@ -990,6 +990,11 @@ std::vector<at::Tensor> attn_decode_paged(const at::Tensor& q, const at::Tensor&
                                           const at::Tensor& block_table, const at::Tensor& kv_len, double scale, int64_t n);
 void kv_append_paged(const at::Tensor& k_new, const at::Tensor& v_new, at::Tensor& k_pool, at::Tensor& v_pool,
                      const at::Tensor& block_table, const at::Tensor& kv_len);
+std::vector<at::Tensor> attn_decode_paged_fp8(const at::Tensor& q, const at::Tensor& k_codes, const at::Tensor& v_codes,
+                                              const at::Tensor& k_exp, const at::Tensor& v_exp, const at::Tensor& block_table,
+                                              const at::Tensor& kv_len, double scale, int64_t n);
+void kv_append_paged_fp8(const at::Tensor& k_new, const at::Tensor& v_new, at::Tensor& k_codes, at::Tensor& v_codes, at::Tensor& k_exp,
+                         at::Tensor& v_exp, const at::Tensor& block_table, const at::Tensor& kv_len);
 }  // namespace gtk_attn
 
 namespace gtk_xpose {  // csrc/ops/transpose.hip
@@ -1037,6 +1042,11 @@ PYBIND11_MODULE(_fused, m) {
         "[B,max_pages] and kv_len [B] read on the device, n (1..64) key splits: -> (o [B,Sq,H,D], lse2 [B,H,Sq])");
   m.def("kv_append_paged", &gtk_attn::kv_append_paged,
         "k_new, v_new [B,Hkv,Sq,D] (Sq 1..32) into the pages of a paged cache at positions kv_len[b] - Sq .., in place");
+  m.def("attn_decode_paged_fp8", &gtk_attn::attn_decode_paged_fp8,
+        "attn_decode_paged over an fp8 cache: e4m3 codes uint8 [num_pages,Hkv,page_size,D] and one exponent byte (e + 127) per "
+        "row uint8 [num_pages,Hkv,page_size] for K and for V: -> (o, lse2), attn_decode_paged's on the dequantised pools");
+  m.def("kv_append_paged_fp8", &gtk_attn::kv_append_paged_fp8,
+        "kv_append_paged into the fp8 cache: every new row quantised to e4m3 codes under its own power-of-two scale, in place");
   m.doc() = "gfx950 fused kernels for the Llama-3 DP validation workload";
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
   m.def("rmsnorm_bwd", &rmsnorm_bwd);

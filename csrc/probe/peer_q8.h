@@ -50,14 +50,15 @@
 // an exact fp32 multiply; the scaling forms (cvt_scalef32_*) are not used, so which way they apply their
 // scale operand plays no part here.  tests/test_gpu_peer_q8.py compares every code with the numpy rule.
 #pragma once
+#include "../common/q8_block.h"
 #include "peer_allreduce.h"
 #include "probe_common.h"
 
 namespace {
 
 constexpr int kQ8Block = 32;                    // elements that share one scale
-constexpr int kQ8ExpMin = -100, kQ8ExpMax = 120;
-constexpr int kQ8Bias = 127;                    // the stored byte is e + 127
+// the exponent's range and bias, q8_pow2, q8_block_exp and q8_codes2: the rule the fp8 KV cache shares
+using namespace gtk_q8;
 
 // Vectors of a packed buffer for `n_blocks` blocks, and where its exponent bytes start.
 constexpr size_t q8_exp_vec(size_t n_blocks) { return 2 * n_blocks; }
@@ -65,21 +66,6 @@ constexpr size_t q8_packed_vecs(size_t n_blocks) { return 2 * n_blocks + (n_bloc
 
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float q8_pow2(int n) { return __uint_as_float((unsigned int)(n + 127) << 23); }
-
-// amax = m * 2^E with m in [1, 2): e = E - 8 when m <= 1.75 (448 = 1.75 * 2^8), else E - 7.  A zero or
-// subnormal amax lands below the clamp, an infinite one above it.
-__device__ __forceinline__ int q8_block_exp(float amax) {
-  const unsigned int a = __float_as_uint(amax);
-  const int e = (int)(a >> 23) - 127 - 8 + (int)((a & 0x7fffffu) > 0x600000u);
-  return min(max(e, kQ8ExpMin), kQ8ExpMax);
-}
-
-// Two scaled values to two codes, the first in the low byte.
-__device__ __forceinline__ unsigned int q8_codes2(float a, float b) {
-  return (unsigned int)__builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false) & 0xffffu;
-}
 
 // One 16-byte vector `r` of the window, vector v of it (elements [v L, v L + L)), as one of the G
 // consecutive lanes that hold a block (bf16: 4 lanes of 8 elements; fp32: 8 lanes of 4): the block's amax

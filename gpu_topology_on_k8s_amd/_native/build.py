@@ -121,8 +121,9 @@ def targets() -> List[Target]:
     rocm_lib = str(ROCM / "lib")
     stream_copy = CSRC / "common" / "stream_copy.h"  # the copy body the probe and the one-rank all-reduce share
     adamw_update = CSRC / "common" / "adamw_update.h"  # the AdamW update body the optimizer and the probe's ZeRO-1 step share
+    q8_block = CSRC / "common" / "q8_block.h"  # the fp8 block rule the probe's fp8 wire and the fp8 KV cache share
     return [
-        Target("_topo", [CSRC / "topo" / "topo_reader.cpp"], "gxx", HERE / f"_topo{EXT}", ["-ldl"]),
+        Target("_topo",[CSRC / "topo" / "topo_reader.cpp"], "gxx", HERE / f"_topo{EXT}", ["-ldl"]),
         # host-only sanitizer build of the sysfs reader; run by tests/test_topo_reader_asan.py
         Target("topo_selftest", [CSRC / "topo" / "topo_selftest.cpp"], "gxx", HERE / "bin" / "topo_selftest",
                ["-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
@@ -136,7 +137,7 @@ def targets() -> List[Target]:
                HERE / "bin" / "engine_selftest", ["-g", "-O1", "-fsanitize=address,undefined", "-fno-omit-frame-pointer"],
                deps=[CSRC / "placement" / "engine.h"], pybind=False, shared=False),
         Target("_probe", [CSRC / "probe" / "probe.hip"], "hipcc", HERE / f"_probe{EXT}",
-               deps=[stream_copy, adamw_update] + [CSRC / "probe" / h for h in ("probe_common.h", "peer_allreduce.h", "peer_q8.h", "peer_driver.h",
+               deps=[stream_copy, adamw_update, q8_block] + [CSRC / "probe" / h for h in ("probe_common.h", "peer_allreduce.h", "peer_q8.h", "peer_driver.h",
                                                                                 "peer_rank.h", "peer_zero1.h", "chase_latency.h")]),
         Target("_rccl", [CSRC / "rccl" / "rccl_module.hip"], "hipcc", HERE / f"_rccl{EXT}",
                [f"-L{rocm_lib}", "-lrccl", f"-Wl,-rpath,{rocm_lib}"],
@@ -176,7 +177,7 @@ def targets() -> List[Target]:
         # attention_d64.hip (the head-dim-64 family, attention_d64_kernels.h) takes attention_doc.hip's flags, and
         # so does attention_qoff.hip (attention_kernels.h for a query chunk at an offset into longer K/V).
         Target("_fused", sorted((CSRC / "ops").glob("*.hip")), "hipcc", HERE / f"_fused{EXT}",
-               deps=sorted((CSRC / "ops").glob("*.h")) + [adamw_update], pybind=True, torch=True,
+               deps=sorted((CSRC / "ops").glob("*.h")) + [adamw_update, q8_block], pybind=True, torch=True,
                src_flags={"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                           "attention_doc.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-Xclang", "-target-feature", "-Xclang",
                                                 "-packed-fp32-ops"],
@@ -192,7 +193,10 @@ def targets() -> List[Target]:
                                                    "-packed-fp32-ops"],
                           # its paged-cache sibling (the same body, attention_decode_body.h) and the page append
                           "attention_decode_paged.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-Xclang", "-target-feature",
-                                                         "-Xclang", "-packed-fp32-ops"]}),
+                                                         "-Xclang", "-packed-fp32-ops"],
+                          # and the paged kernel and append over a cache of e4m3 codes
+                          "attention_decode_paged_fp8.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-Xclang", "-target-feature",
+                                                             "-Xclang", "-packed-fp32-ops"]}),
     ]
 
 

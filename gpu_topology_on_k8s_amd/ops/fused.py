@@ -18,6 +18,8 @@ __all__ = [
     "swiglu_bwd_t", "swiglu_fwd_t", "attention_t", "offer_t", "take_t", "clear_t", "doc_bounds", "doc_start_from_eos",
     "kv_splits_for", "attention_decode", "attention_decode_ref", "decode_splits_for",
     "attention_decode_paged", "attention_decode_paged_ref", "kv_cache_append", "kv_cache_append_ref",
+    "kv_quantize_ref", "kv_dequantize_ref", "attention_decode_paged_fp8", "attention_decode_paged_fp8_ref",
+    "kv_cache_append_fp8", "kv_cache_append_fp8_ref",
 ]
 
 
@@ -743,3 +745,182 @@ def kv_cache_append(k_new: torch.Tensor, v_new: torch.Tensor, k_pool: torch.Tens
         hip().kv_append_paged(k_new.contiguous(), v_new.contiguous(), k_pool, v_pool, block_table.contiguous(), kv_len.contiguous())
     else:
         kv_cache_append_ref(k_new, v_new, k_pool, v_pool, block_table, kv_len)
+
+
+# ------------------------------------------------------------------------------------ the paged KV cache in fp8
+# Cache format (csrc/ops/attention_decode_paged_fp8.hip): ``k_codes``, ``v_codes`` uint8 [num_pages, Hkv, page_size,
+# 128], one OCP e4m3fn code per element, and ``k_exp``, ``v_exp`` uint8 [num_pages, Hkv, page_size], one byte
+# ``e + 127`` per key row and KV head: 129 bytes a row against 256.  A block is one 128-element row and its rule is
+# the one of the K7 fp8 wire (csrc/probe/peer_q8.h, ops/peer_ref.q8_quantize_ref); V is row-major like K.
+KV_EXP_MIN, KV_EXP_MAX = -100, 120
+
+
+def _pow2(e: torch.Tensor) -> torch.Tensor:
+    """fp32 ``2^e`` from the exponent field: exact on every device; ``e`` an integer tensor in [-127, 128]."""
+    return ((e.to(torch.int32) + 127) << 23).view(torch.float32)
+
+
+def _e4m3_values() -> torch.Tensor:
+    """float32 value of every e4m3fn code; 0x7f and 0xff, the format's only non-finite codes, are NaN."""
+    c = torch.arange(256)
+    e, m = (c >> 3) & 15, (c & 7).float()
+    mag = torch.where(e == 0, m * 2.0 ** -9, (8 + m) * _pow2(e - 10))
+    mag[(c & 0x7F) == 0x7F] = float("nan")
+    return torch.where((c & 0x80) != 0, -mag, mag)
+
+
+_E4M3 = _e4m3_values()
+
+
+def kv_quantize_ref(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Rows ``x`` [..., 128] -> ``(codes uint8 [..., 128], exp uint8 [...])``, the cache format's rule, which decides:
+    per row ``e`` is the smallest integer with ``amax * 2^-e <= 448``, clamped to [-100, 120] (``amax == 0``: -100),
+    the amax taken over the row's elements that are not NaN (an Inf counts: ``e = 120``); a code is ``x * 2^-e``
+    rounded to nearest even into e4m3fn, subnormal codes (quantum ``2^-9``) included; a NaN or an Inf gets the code
+    0x7f under its sign bit.  The stored byte is ``e + 127``."""
+    v = x.float()
+    special = ~torch.isfinite(v)
+    amax = torch.where(torch.isnan(v), 0.0, v.abs()).amax(-1)
+    inf = torch.isinf(amax)
+    m, ex = torch.frexp(torch.where(inf, 0.0, amax))  # amax = m * 2^ex, m in [0.5, 1); 448 = 0.875 * 2^9
+    e = torch.where(amax == 0, KV_EXP_MIN, (ex - 9 + (m > 0.875)).clamp(KV_EXP_MIN, KV_EXP_MAX))
+    e = torch.where(inf, KV_EXP_MAX, e)
+    y = torch.where(special, 0.0, v) * _pow2(-e).unsqueeze(-1)  # exact, or too small for any code but 0
+    a = y.abs().double()
+    _, ea = torch.frexp(a)  # a in [2^(ea - 1), 2^ea): three mantissa bits below the leading one
+    quantum = _pow2((ea - 4).clamp(min=-9)).double()
+    r = torch.round(a / quantum) * quantum  # torch.round rounds halves to even
+    mr, er = torch.frexp(r)
+    code = torch.where(r >= 2.0 ** -6, (er + 6) * 8 + torch.round((mr * 2 - 1) * 8), torch.round(r * 512)).long()
+    code = torch.where(special, 0x7F, code.clamp(max=0x7E)) | (torch.signbit(v).long() << 7)
+    return code.to(torch.uint8), (e + 127).to(torch.uint8)
+
+
+def kv_dequantize_ref(codes: torch.Tensor, exp: torch.Tensor) -> torch.Tensor:
+    """``float(code) * 2^e`` as bf16 [..., 128], exact: a code has at most 4 significant bits.  The codes 0x7f and
+    0xff give NaN."""
+    return (_E4M3.to(codes.device)[codes.long()] * _pow2(exp.to(torch.int32) - 127).unsqueeze(-1)).to(torch.bfloat16)
+
+
+def _check_paged_fp8(who, x, k_codes, v_codes, k_exp, v_exp, block_table, kv_len):
+    """What :func:`attention_decode_paged_fp8` and :func:`kv_cache_append_fp8` ask of the four pools, the table and
+    the lengths; ``x`` is q or k_new."""
+    name = "q" if who == "attention_decode_paged_fp8" else "k_new"
+    if x.dim() != 4 or x.dtype != torch.bfloat16 or x.size(-1) != 128:
+        raise ValueError(f"{who}: {name} must be a bf16 4-d tensor with head dim 128, got {x.dtype} {tuple(x.shape)}")
+    pools = (("k_codes", k_codes), ("v_codes", v_codes), ("k_exp", k_exp), ("v_exp", v_exp))
+    for pname, t in pools:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+            raise ValueError(f"{who}: {pname} must be a uint8 tensor, got {getattr(t, 'dtype', type(t))}")
+    if k_codes.dim() != 4 or k_codes.size(-1) != 128 or v_codes.shape != k_codes.shape:
+        raise ValueError(f"{who}: k_codes and v_codes must be [num_pages, Hkv, page_size, 128] alike, got "
+                         f"{tuple(k_codes.shape)} and {tuple(v_codes.shape)}")
+    if k_exp.shape != k_codes.shape[:3] or v_exp.shape != k_codes.shape[:3]:
+        raise ValueError(f"{who}: k_exp and v_exp must be [num_pages, Hkv, page_size] of the code pools, got "
+                         f"{tuple(k_exp.shape)} and {tuple(v_exp.shape)}")
+    if any(t.device != x.device for _, t in pools):
+        raise ValueError(f"{who}: all tensors must be on one device")
+    if not all(t.is_contiguous() for _, t in pools):
+        raise ValueError(f"{who}: the pools must be contiguous")
+    P = k_codes.size(2)
+    if k_codes.size(0) == 0 or P % 64 or not 64 <= P <= 1024:
+        raise ValueError(f"{who}: page_size must be a multiple of 64 from 64 to 1024 (and the pool not empty), got {P}")
+    B = x.size(0)
+    if (not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2
+            or block_table.size(0) != B or block_table.size(1) == 0 or block_table.device != x.device):
+        raise ValueError(f"{who}: block_table must be an int32 [B, max_pages] tensor on the pools' device")
+    if not isinstance(kv_len, torch.Tensor) or kv_len.dtype != torch.int32 or kv_len.shape != (B,) or kv_len.device != x.device:
+        raise ValueError(f"{who}: kv_len must be an int32 [B] tensor on the pools' device")
+
+
+def attention_decode_paged_fp8_ref(q: torch.Tensor, k_codes: torch.Tensor, v_codes: torch.Tensor, k_exp: torch.Tensor,
+                                   v_exp: torch.Tensor, block_table: torch.Tensor, kv_len: torch.Tensor,
+                                   scale: float | None = None):
+    """:func:`attention_decode_paged_ref` on the dequantised pools -> (o, lse2)."""
+    return attention_decode_paged_ref(q, kv_dequantize_ref(k_codes, k_exp), kv_dequantize_ref(v_codes, v_exp), block_table, kv_len,
+                                      scale)
+
+
+def attention_decode_paged_fp8(q: torch.Tensor, k_codes: torch.Tensor, v_codes: torch.Tensor, k_exp: torch.Tensor,
+                               v_exp: torch.Tensor, block_table: torch.Tensor, kv_len: torch.Tensor,
+                               scale: float | None = None, kv_splits="auto", return_lse: bool = False, check: bool = False):
+    """:func:`attention_decode_paged` over a KV cache kept in 8 bits -> o [B, Sq, H, 128] bf16 (with ``return_lse``
+    also lse2).  Forward only.
+
+    ``k_codes``, ``v_codes`` uint8 [num_pages, Hkv, page_size, 128] and ``k_exp``, ``v_exp`` uint8 [num_pages, Hkv,
+    page_size], contiguous: the format :func:`kv_quantize_ref` defines and :func:`kv_cache_append_fp8` writes, half
+    the bytes of the bf16 pools and so twice the tokens a pool holds.  ``page_size``, ``block_table``, ``kv_len``,
+    ``q``, ``kv_splits`` and ``check`` are :func:`attention_decode_paged`'s.  The kernel
+    (csrc/ops/attention_decode_paged_fp8.hip) widens the codes exactly and carries the rows' power-of-two scales
+    on the fp32 scores and probabilities, so the result is :func:`attention_decode_paged`'s on the dequantised pools
+    (:func:`kv_dequantize_ref`) at the same ``kv_splits``, bit for bit.  It does not depend on the bytes of unused
+    pages or of rows at or past ``kv_len[b]``, and no content of the table, the lengths or the exponent bytes moves
+    an access outside the pools.  On CPU tensors the call is :func:`attention_decode_paged_fp8_ref`."""
+    who = "attention_decode_paged_fp8"
+    _check_paged_fp8(who, q, k_codes, v_codes, k_exp, v_exp, block_table, kv_len)
+    B, H, Sq, _ = q.shape
+    Hkv, Smax = k_codes.size(1), block_table.size(1) * k_codes.size(2)
+    if Hkv == 0 or H % Hkv:
+        raise ValueError(f"{who}: q heads ({H}) must be a multiple of kv heads ({Hkv})")
+    if not 1 <= Sq * (H // Hkv) <= DECODE_MAX_ROWS:
+        raise ValueError(f"{who}: Sq * (H / Hkv) must be between 1 and {DECODE_MAX_ROWS}, got {Sq * (H // Hkv)}")
+    if torch.is_grad_enabled() and q.requires_grad:
+        raise ValueError(f"{who}: forward only, an input requires grad")
+    if kv_splits == "auto":
+        n = decode_splits_for(B, Hkv, Smax)
+    elif isinstance(kv_splits, bool) or not isinstance(kv_splits, int) or not 1 <= kv_splits <= 64:
+        raise ValueError(f"{who}: kv_splits must be 'auto' or an int from 1 to 64, got {kv_splits!r}")
+    else:
+        n = kv_splits
+    if check:
+        _check_paged_content(who, Sq, k_codes, block_table, kv_len)
+    sc = scale if scale is not None else q.size(-1) ** -0.5
+    if q.is_cuda:
+        o, lse2 = hip().attn_decode_paged_fp8(q.contiguous(), k_codes, v_codes, k_exp, v_exp, block_table.contiguous(),
+                                              kv_len.contiguous(), float(sc), n)
+    else:
+        o, lse2 = attention_decode_paged_fp8_ref(q, k_codes, v_codes, k_exp, v_exp, block_table, kv_len, sc)
+    return (o, lse2) if return_lse else o
+
+
+def kv_cache_append_fp8_ref(k_new: torch.Tensor, v_new: torch.Tensor, k_codes: torch.Tensor, v_codes: torch.Tensor,
+                            k_exp: torch.Tensor, v_exp: torch.Tensor, block_table: torch.Tensor, kv_len: torch.Tensor) -> None:
+    """:func:`kv_cache_append_ref` of the new rows' quantised form (:func:`kv_quantize_ref`), in place: the same
+    positions, the same skips."""
+    B, _, Sq, _ = k_new.shape
+    P, MP = k_codes.size(2), block_table.size(1)
+    n = kv_len.long().view(B, 1)
+    pos = n - Sq + torch.arange(Sq, device=k_new.device).view(1, Sq)
+    page = block_table.long().gather(1, (pos // P).clamp(0, MP - 1))
+    ok = (n >= Sq) & (n <= MP * P) & (page >= 0) & (page < k_codes.size(0))
+    b, i = ok.nonzero(as_tuple=True)
+    for new, codes, exp in ((k_new, k_codes, k_exp), (v_new, v_codes, v_exp)):
+        c, e = kv_quantize_ref(new)
+        codes[page[b, i], :, pos[b, i] % P] = c[b, :, i]
+        exp[page[b, i], :, pos[b, i] % P] = e[b, :, i]
+
+
+def kv_cache_append_fp8(k_new: torch.Tensor, v_new: torch.Tensor, k_codes: torch.Tensor, v_codes: torch.Tensor,
+                        k_exp: torch.Tensor, v_exp: torch.Tensor, block_table: torch.Tensor, kv_len: torch.Tensor,
+                        check: bool = False) -> None:
+    """:func:`kv_cache_append` into the fp8 cache: the Sq new tokens' rows ``k_new``, ``v_new`` [B, Hkv, Sq, 128] bf16
+    are quantised by the row rule on their way into the pages, 128 code bytes and one exponent byte a row, in place
+    and on the current stream, in one launch that reads nothing of the cache.  Positions, skips and ``check`` are
+    :func:`kv_cache_append`'s.  On CPU tensors the call is :func:`kv_cache_append_fp8_ref`."""
+    who = "kv_cache_append_fp8"
+    _check_paged_fp8(who, k_new, k_codes, v_codes, k_exp, v_exp, block_table, kv_len)
+    if v_new.shape != k_new.shape or v_new.dtype != torch.bfloat16 or v_new.device != k_new.device:
+        raise ValueError(f"{who}: k_new and v_new must be bf16 tensors of one shape on one device")
+    if k_new.size(1) != k_codes.size(1):
+        raise ValueError(f"{who}: the new rows have {k_new.size(1)} KV heads, the pools {k_codes.size(1)}")
+    if not 1 <= k_new.size(2) <= KV_APPEND_MAX_ROWS:
+        raise ValueError(f"{who}: Sq must be between 1 and {KV_APPEND_MAX_ROWS}, got {k_new.size(2)}")
+    if torch.is_grad_enabled() and (k_new.requires_grad or v_new.requires_grad):
+        raise ValueError(f"{who}: forward only, an input requires grad")
+    if check:
+        _check_paged_content(who, k_new.size(2), k_codes, block_table, kv_len)
+    if k_new.is_cuda:
+        hip().kv_append_paged_fp8(k_new.contiguous(), v_new.contiguous(), k_codes, v_codes, k_exp, v_exp, block_table.contiguous(),
+                                  kv_len.contiguous())
+    else:
+        kv_cache_append_fp8_ref(k_new, v_new, k_codes, v_codes, k_exp, v_exp, block_table, kv_len)
