@@ -7,7 +7,8 @@
 // its keys split over several workgroups (attn_*_qoff_split) to those of attention_splitkv.hip.  A decode step
 // over a ragged KV cache (attn_decode) goes to the kernel of attention_decode.hip through gtk_decode::launch, and
 // over a paged cache (attn_decode_paged, kv_append_paged) to those of attention_decode_paged.hip, over a paged
-// cache of e4m3 codes (attn_decode_paged_fp8, kv_append_paged_fp8) to those of attention_decode_paged_fp8.hip.
+// cache of e4m3 codes (attn_decode_paged_fp8, kv_append_paged_fp8) to those of attention_decode_paged_fp8.hip.  Prefill
+// over the paged cache (attn_prefill_paged, kv_append_paged_chunk) goes to the kernels of attention_prefill_paged.hip.
 #include "attention_kernels.h"
 #include "attention_splitkv.h"
 
@@ -54,6 +55,14 @@ void launch_paged_fp8(hipStream_t st, const u16* q, const uint8_t* kc, const uin
                       int Hkv, int Sq, int page_size, int max_pages, int num_pages, float c, int n);
 void launch_append_fp8(hipStream_t st, const u16* k_new, const u16* v_new, uint8_t* kc, uint8_t* vc, uint8_t* kx, uint8_t* vx,
                        const int* block_table, const int* kv_len, int B, int Hkv, int Sq, int page_size, int max_pages, int num_pages);
+
+// csrc/ops/attention_prefill_paged.hip: ragged query chunks over the bf16 pools, grid (B*H, ceil(Sq / 128)), q_len int32
+// [B] the real rows of each sequence; and the append of a chunk's rows, any Sq, in one launch
+void launch_prefill_paged(hipStream_t st, const u16* q, const u16* kp, const u16* vp, const int* block_table, const int* kv_len,
+                          const int* q_len, u16* o, float* lse2, int B, int H, int Hkv, int Sq, int page_size, int max_pages,
+                          int num_pages, float c);
+void launch_append_chunk(hipStream_t st, const u16* k_new, const u16* v_new, u16* kp, u16* vp, const int* block_table,
+                         const int* kv_len, const int* q_len, int B, int Hkv, int Sq, int page_size, int max_pages, int num_pages);
 
 }  // namespace gtk_decode
 
@@ -456,6 +465,55 @@ void kv_append_paged(const at::Tensor& k_new, const at::Tensor& v_new, at::Tenso
   gtk_decode::launch_append(cur_stream(), bp(k_new), bp(v_new), bpm(k_pool), bpm(v_pool), block_table.data_ptr<int>(),
                             kv_len.data_ptr<int>(), (int)B, (int)Hkv, (int)Sq, (int)k_pool.size(2), (int)block_table.size(1),
                             (int)k_pool.size(0));
+}
+
+// ---------------------------------------------------------------- prefill over a paged KV cache
+// what the two chunk calls add to check_paged: q_len, and a padded chunk no longer than the table can hold
+static void check_chunk(const char* who, const at::Tensor& x, const at::Tensor& k_pool, const at::Tensor& block_table,
+                        const at::Tensor& q_len) {
+  TORCH_CHECK(q_len.is_cuda() && q_len.device() == x.device() && q_len.scalar_type() == at::kInt && q_len.is_contiguous() &&
+                  q_len.dim() == 1 && q_len.size(0) == x.size(0),
+              who, ": q_len must be a contiguous int32 [B] GPU tensor on the pools' device");
+  TORCH_CHECK(x.size(0) > 0 && x.size(2) >= 1 && x.size(2) <= block_table.size(1) * k_pool.size(2), who,
+              ": Sq must be between 1 and max_pages * page_size, got ", x.size(2));
+}
+
+// q [B, H, Sq, 128], any Sq, the batch padded to Sq rows of which q_len[b] are real; pools, table and kv_len as in
+// attn_decode_paged.  Row i < q_len[b] sits at kv_len[b] - q_len[b] + i; rows past q_len[b] give o = 0, lse2 = -inf.
+// The kernel clamps q_len, kv_len and every page id; nothing here reads them.  -> (o [B, Sq, H, 128], lse2 [B, H, Sq])
+std::vector<at::Tensor> attn_prefill_paged(const at::Tensor& q, const at::Tensor& k_pool, const at::Tensor& v_pool,
+                                           const at::Tensor& block_table, const at::Tensor& kv_len, const at::Tensor& q_len,
+                                           double scale) {
+  check_paged("attention prefill paged", q, k_pool, v_pool, block_table, kv_len);
+  check_chunk("attention prefill paged", q, k_pool, block_table, q_len);
+  const int64_t B = q.size(0), H = q.size(1), Sq = q.size(2), Hkv = k_pool.size(1), P = k_pool.size(2), MP = block_table.size(1);
+  TORCH_CHECK(Hkv > 0 && H > 0 && H % Hkv == 0, "attention prefill paged: q heads must be a multiple of kv heads");
+  TORCH_CHECK(B * H * Sq < (int64_t(1) << 31), "attention prefill paged: B * H * Sq must be below 2^31");
+  check_scale(scale);
+  auto o = at::empty({B, Sq, H, D}, q.options());
+  auto lse = at::empty({B, H, Sq}, q.options().dtype(at::kFloat));
+  gtk_decode::launch_prefill_paged(cur_stream(), bp(q), bp(k_pool), bp(v_pool), block_table.data_ptr<int>(), kv_len.data_ptr<int>(),
+                                   q_len.data_ptr<int>(), bpm(o), lse.data_ptr<float>(), (int)B, (int)H, (int)Hkv, (int)Sq, (int)P,
+                                   (int)MP, (int)k_pool.size(0), (float)(scale * 1.4426950408889634));
+  return {o, lse};
+}
+
+// the chunk's rows k_new, v_new [B, Hkv, Sq, 128] into the pages, in place: row i < q_len[b] of sequence b at position
+// kv_len[b] - q_len[b] + i.  The kernel skips a sequence with kv_len outside [q_len, max_pages * page_size] and a row
+// whose page id is outside [0, num_pages)
+void kv_append_paged_chunk(const at::Tensor& k_new, const at::Tensor& v_new, at::Tensor& k_pool, at::Tensor& v_pool,
+                           const at::Tensor& block_table, const at::Tensor& kv_len, const at::Tensor& q_len) {
+  check_paged("kv append paged chunk", k_new, k_pool, v_pool, block_table, kv_len);
+  check_chunk("kv append paged chunk", k_new, k_pool, block_table, q_len);
+  TORCH_CHECK(v_new.is_cuda() && v_new.scalar_type() == at::kBFloat16 && v_new.is_contiguous() && v_new.sizes() == k_new.sizes() &&
+                  v_new.device() == k_new.device(),
+              "kv append paged chunk: k_new and v_new must be contiguous bf16 GPU tensors of one shape on one device");
+  const int64_t B = k_new.size(0), Hkv = k_new.size(1), Sq = k_new.size(2);
+  TORCH_CHECK(Hkv == k_pool.size(1), "kv append paged chunk: the new rows and the pools must have the same KV heads");
+  TORCH_CHECK(B * Hkv * Sq < (int64_t(1) << 31), "kv append paged chunk: B * Hkv * Sq must be below 2^31");
+  gtk_decode::launch_append_chunk(cur_stream(), bp(k_new), bp(v_new), bpm(k_pool), bpm(v_pool), block_table.data_ptr<int>(),
+                                  kv_len.data_ptr<int>(), q_len.data_ptr<int>(), (int)B, (int)Hkv, (int)Sq, (int)k_pool.size(2),
+                                  (int)block_table.size(1), (int)k_pool.size(0));
 }
 
 // attn_decode_paged over the fp8 cache -> (o, lse2), bit for bit attn_decode_paged's on the dequantised pools at the same n

@@ -995,6 +995,11 @@ std::vector<at::Tensor> attn_decode_paged_fp8(const at::Tensor& q, const at::Ten
                                               const at::Tensor& kv_len, double scale, int64_t n);
 void kv_append_paged_fp8(const at::Tensor& k_new, const at::Tensor& v_new, at::Tensor& k_codes, at::Tensor& v_codes, at::Tensor& k_exp,
                          at::Tensor& v_exp, const at::Tensor& block_table, const at::Tensor& kv_len);
+std::vector<at::Tensor> attn_prefill_paged(const at::Tensor& q, const at::Tensor& k_pool, const at::Tensor& v_pool,
+                                           const at::Tensor& block_table, const at::Tensor& kv_len, const at::Tensor& q_len,
+                                           double scale);
+void kv_append_paged_chunk(const at::Tensor& k_new, const at::Tensor& v_new, at::Tensor& k_pool, at::Tensor& v_pool,
+                           const at::Tensor& block_table, const at::Tensor& kv_len, const at::Tensor& q_len);
 }  // namespace gtk_attn
 
 namespace gtk_xpose {  // csrc/ops/transpose.hip
@@ -1047,6 +1052,12 @@ PYBIND11_MODULE(_fused, m) {
         "row uint8 [num_pages,Hkv,page_size] for K and for V: -> (o, lse2), attn_decode_paged's on the dequantised pools");
   m.def("kv_append_paged_fp8", &gtk_attn::kv_append_paged_fp8,
         "kv_append_paged into the fp8 cache: every new row quantised to e4m3 codes under its own power-of-two scale, in place");
+  m.def("attn_prefill_paged", &gtk_attn::attn_prefill_paged,
+        "prefill attention (D=128) over a paged cache: q [B,H,Sq,D] (any Sq, q_len[b] real rows at positions kv_len[b] - "
+        "q_len[b] ..), pools [num_pages,Hkv,page_size,D], int32 block_table [B,max_pages], kv_len [B], q_len [B] -> "
+        "(o [B,Sq,H,D], lse2 [B,H,Sq]); padded rows give 0 and -inf");
+  m.def("kv_append_paged_chunk", &gtk_attn::kv_append_paged_chunk,
+        "k_new, v_new [B,Hkv,Sq,D] (any Sq, q_len[b] real rows) into the pages at positions kv_len[b] - q_len[b] .., in place");
   m.doc() = "gfx950 fused kernels for the Llama-3 DP validation workload";
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
   m.def("rmsnorm_bwd", &rmsnorm_bwd);

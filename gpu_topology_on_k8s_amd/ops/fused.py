@@ -20,6 +20,7 @@ __all__ = [
     "attention_decode_paged", "attention_decode_paged_ref", "kv_cache_append", "kv_cache_append_ref",
     "kv_quantize_ref", "kv_dequantize_ref", "attention_decode_paged_fp8", "attention_decode_paged_fp8_ref",
     "kv_cache_append_fp8", "kv_cache_append_fp8_ref",
+    "attention_prefill_paged", "attention_prefill_paged_ref", "kv_cache_append_prefill", "kv_cache_append_prefill_ref",
 ]
 
 
@@ -614,7 +615,7 @@ KV_APPEND_MAX_ROWS = 32  # the new tokens one kv_cache_append call takes per seq
 def _check_paged(who, x, k_pool, v_pool, block_table, kv_len):
     """What :func:`attention_decode_paged` and :func:`kv_cache_append` ask of the pools, the table and the lengths;
     ``x`` is q or k_new."""
-    for name, t in ((("q" if who == "attention_decode_paged" else "k_new"), x), ("k_pool", k_pool), ("v_pool", v_pool)):
+    for name, t in ((("q" if who.startswith("attention_") else "k_new"), x), ("k_pool", k_pool), ("v_pool", v_pool)):
         if t.dim() != 4 or t.dtype != torch.bfloat16:
             raise ValueError(f"{who}: {name} must be a bf16 4-d tensor with head dim 128, got {t.dtype} {tuple(t.shape)}")
         if t.size(-1) != 128:
@@ -745,6 +746,127 @@ def kv_cache_append(k_new: torch.Tensor, v_new: torch.Tensor, k_pool: torch.Tens
         hip().kv_append_paged(k_new.contiguous(), v_new.contiguous(), k_pool, v_pool, block_table.contiguous(), kv_len.contiguous())
     else:
         kv_cache_append_ref(k_new, v_new, k_pool, v_pool, block_table, kv_len)
+
+
+# ------------------------------------------------------------------------------------ prefill over the paged KV cache
+def _chunk_lengths(who, x, k_pool, block_table, kv_len, q_len, check):
+    """-> q_len as an int32 [B] tensor (``None``: every sequence has Sq rows); the refusals :func:`attention_prefill_paged`
+    and :func:`kv_cache_append_prefill` add to :func:`_check_paged`.  ``check=True``: one sync."""
+    B, Sq = x.size(0), x.size(2)
+    P, Smax = k_pool.size(2), block_table.size(1) * k_pool.size(2)
+    if B == 0 or not 1 <= Sq <= Smax:
+        raise ValueError(f"{who}: Sq must be between 1 and max_pages * page_size = {Smax}, got {Sq}")
+    if q_len is None:
+        q_len = torch.full((B,), Sq, dtype=torch.int32, device=x.device)
+    elif not isinstance(q_len, torch.Tensor) or q_len.dtype != torch.int32 or q_len.shape != (B,) or q_len.device != x.device:
+        raise ValueError(f"{who}: q_len must be an int32 [B] tensor on the pools' device")
+    if check:
+        if not bool(((q_len >= 0) & (q_len <= Sq)).all()):
+            raise ValueError(f"{who}: q_len must lie in [0, {Sq}], got {q_len.tolist()}")
+        if not bool(((kv_len >= q_len) & (kv_len <= Smax)).all()):
+            raise ValueError(f"{who}: kv_len must lie in [q_len, {Smax}], got {kv_len.tolist()} for q_len {q_len.tolist()}")
+        needed = (torch.arange(block_table.size(1), device=kv_len.device).view(1, -1) * P < kv_len.view(-1, 1)) & (q_len > 0).view(-1, 1)
+        if bool((needed & ((block_table < 0) | (block_table >= k_pool.size(0)))).any()):
+            raise ValueError(f"{who}: a needed block_table entry lies outside [0, {k_pool.size(0)})")
+    return q_len
+
+
+def attention_prefill_paged_ref(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor,
+                                kv_len: torch.Tensor, q_len: Optional[torch.Tensor] = None, scale: float | None = None):
+    """fp32 prefill attention over the pages -> (o [B, Sq, H, D] in q's dtype, lse2 [B, H, Sq] fp32, log2 units):
+    :func:`attention_decode_ref` of each sequence's ``ql = clamp(q_len[b], 0, Sq)`` real rows on the gathered slab.
+    Rows at or past ``ql`` are not read and give ``o = 0``, ``lse2 = -inf``."""
+    B, H, Sq, D = q.shape
+    k, v = _gather_pages(k_pool, block_table), _gather_pages(v_pool, block_table)
+    ql = [Sq] * B if q_len is None else q_len.clamp(0, Sq).tolist()
+    o = torch.zeros(B, Sq, H, D, dtype=q.dtype, device=q.device)
+    lse2 = torch.full((B, H, Sq), float("-inf"), dtype=torch.float32, device=q.device)
+    for b, n in enumerate(ql):
+        if n:
+            ob, lb = attention_decode_ref(q[b:b + 1, :, :n], k[b:b + 1], v[b:b + 1], kv_len[b:b + 1], scale)
+            o[b, :n], lse2[b, :, :n] = ob[0], lb[0]
+    return o, lse2
+
+
+def attention_prefill_paged(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor,
+                            kv_len: torch.Tensor, q_len: Optional[torch.Tensor] = None, scale: float | None = None,
+                            return_lse: bool = False, check: bool = False):
+    """Prefill and chunked prefill of GQA attention straight over a paged KV cache -> o [B, Sq, H, 128] bf16 (with
+    ``return_lse`` also lse2 [B, H, Sq] fp32, log2 units).  Forward only.
+
+    ``q`` [B, H, Sq, 128] bf16, any ``1 <= Sq <= max_pages * page_size``: the batch's chunks padded to Sq rows.
+    ``q_len`` int32 [B] on the pools' device says how many rows of each sequence are real (``None``: all Sq); 0 is
+    an idle batch slot.  The pools, ``block_table`` and ``kv_len`` are :func:`attention_decode_paged`'s, ``kv_len``
+    counting the chunk's tokens (append them first with :func:`kv_cache_append_prefill`).  With ``ql = clamp(q_len[b],
+    0, Sq)`` and ``len = clamp(kv_len[b], ql, max_pages * page_size)``, row ``i < ql`` sits at position ``len - ql +
+    i`` and sees the keys up to it; rows ``i >= ql`` are not read (they may hold NaN) and give ``o = 0``, ``lse2 =
+    -inf``.  The kernel (csrc/ops/attention_prefill_paged.hip) reads the lengths and the table on the device and
+    clamps them and every page id: no host sync, and no content moves an access outside the pools, the table or
+    ``q``.  The result does not depend on pool rows at or past ``kv_len[b]``, on unused pages or on table entries
+    past ``ceil(len / page_size)``, NaN and Inf included.  ``check=True`` costs one sync and raises ``ValueError``
+    for a ``q_len`` outside [0, Sq], a ``kv_len`` outside [q_len, max_pages * page_size] or a needed table entry
+    outside the pool.  On CPU tensors the call is :func:`attention_prefill_paged_ref`.
+
+    Not served: split-KV for a short chunk against a very long prefix (one workgroup walks a query block's whole
+    prefix), the fp8 pools, a backward, head dim 64."""
+    who = "attention_prefill_paged"
+    _check_paged(who, q, k_pool, v_pool, block_table, kv_len)
+    H, Hkv = q.size(1), k_pool.size(1)
+    if Hkv == 0 or H == 0 or H % Hkv:
+        raise ValueError(f"{who}: q heads ({H}) must be a multiple of kv heads ({Hkv})")
+    if torch.is_grad_enabled() and any(x.requires_grad for x in (q, k_pool, v_pool)):
+        raise ValueError(f"{who}: forward only, an input requires grad")
+    ql = _chunk_lengths(who, q, k_pool, block_table, kv_len, q_len, check)
+    sc = scale if scale is not None else q.size(-1) ** -0.5
+    if q.is_cuda:
+        o, lse2 = hip().attn_prefill_paged(q.contiguous(), k_pool, v_pool, block_table.contiguous(), kv_len.contiguous(),
+                                           ql.contiguous(), float(sc))
+    else:
+        o, lse2 = attention_prefill_paged_ref(q, k_pool, v_pool, block_table, kv_len, ql, sc)
+    return (o, lse2) if return_lse else o
+
+
+def kv_cache_append_prefill_ref(k_new: torch.Tensor, v_new: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor,
+                                block_table: torch.Tensor, kv_len: torch.Tensor, q_len: Optional[torch.Tensor] = None) -> None:
+    """:func:`kv_cache_append_ref`'s indexed assignment for a ragged chunk, in place: row ``i < ql`` of sequence b to
+    position ``kv_len[b] - ql + i``.  A sequence whose length is outside [ql, max_pages * page_size] and a row whose
+    page id is outside the pool are skipped; rows at or past ``ql`` are not read."""
+    B, _, Sq, _ = k_new.shape
+    P, MP = k_pool.size(2), block_table.size(1)
+    n = kv_len.long().view(B, 1)
+    ql = torch.full_like(n, Sq) if q_len is None else q_len.long().clamp(0, Sq).view(B, 1)
+    i = torch.arange(Sq, device=k_new.device).view(1, Sq)
+    pos = n - ql + i
+    page = block_table.long().gather(1, (pos // P).clamp(0, MP - 1))
+    ok = (i < ql) & (n >= ql) & (n <= MP * P) & (page >= 0) & (page < k_pool.size(0))
+    b, i = ok.nonzero(as_tuple=True)
+    k_pool[page[b, i], :, pos[b, i] % P] = k_new[b, :, i]
+    v_pool[page[b, i], :, pos[b, i] % P] = v_new[b, :, i]
+
+
+def kv_cache_append_prefill(k_new: torch.Tensor, v_new: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor,
+                            block_table: torch.Tensor, kv_len: torch.Tensor, q_len: Optional[torch.Tensor] = None,
+                            check: bool = False) -> None:
+    """The other half of a prefill step: write a ragged chunk's rows ``k_new``, ``v_new`` [B, Hkv, Sq, 128] bf16, any
+    Sq, into the pages in one launch, in place and on the current stream.  ``kv_len`` and ``q_len`` are the tensors
+    :func:`attention_prefill_paged` then takes: row ``i < q_len[b]`` goes to position ``kv_len[b] - q_len[b] + i``.
+    The kernel (csrc/ops/attention_prefill_paged.hip) skips a sequence whose length is outside [q_len, max_pages *
+    page_size] and a row whose page id is outside the pool, as :func:`kv_cache_append` does; ``check=True`` costs one
+    sync and raises ``ValueError`` for either.  On CPU tensors the call is :func:`kv_cache_append_prefill_ref`."""
+    who = "kv_cache_append_prefill"
+    _check_paged(who, k_new, k_pool, v_pool, block_table, kv_len)
+    if v_new.shape != k_new.shape or v_new.dtype != torch.bfloat16 or v_new.device != k_new.device:
+        raise ValueError(f"{who}: k_new and v_new must be bf16 tensors of one shape on one device")
+    if k_new.size(1) != k_pool.size(1):
+        raise ValueError(f"{who}: the new rows have {k_new.size(1)} KV heads, the pools {k_pool.size(1)}")
+    if torch.is_grad_enabled() and any(x.requires_grad for x in (k_new, v_new, k_pool, v_pool)):
+        raise ValueError(f"{who}: forward only, an input requires grad")
+    ql = _chunk_lengths(who, k_new, k_pool, block_table, kv_len, q_len, check)
+    if k_new.is_cuda:
+        hip().kv_append_paged_chunk(k_new.contiguous(), v_new.contiguous(), k_pool, v_pool, block_table.contiguous(),
+                                    kv_len.contiguous(), ql.contiguous())
+    else:
+        kv_cache_append_prefill_ref(k_new, v_new, k_pool, v_pool, block_table, kv_len, ql)
 
 
 # ------------------------------------------------------------------------------------ the paged KV cache in fp8
