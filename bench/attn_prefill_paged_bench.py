@@ -13,7 +13,17 @@ warm-up first, the contestants interleaved round by round with the order alterna
 as two series (even and odd rounds) and the spread between the two medians is reported beside the median of all.
 Prints one JSON line and a markdown table (profiles/attn_prefill_paged/SUMMARY.md keeps a run's output).
 
-    python bench/attn_prefill_paged_bench.py [--iters 10] [--rounds 6]
+With ``--kv-fp8`` every shape also gets the pools quantised by ``fused.kv_quantize_ref`` and two more contestants in
+the same interleaved rounds:
+
+    fp8      fused.attention_prefill_paged_fp8 straight over the four fp8 pools;
+    deq      ``fused.kv_dequantize_ref`` of the four pools in torch, then ``paged`` on the result: what a user of the fp8
+             cache had to do, at twice the cache's memory.
+
+and ``fused.kv_cache_append_prefill_fp8`` is timed next to the bf16 chunk append at the same 4 x 4096 rows
+(profiles/attn_prefill_paged_fp8/SUMMARY.md keeps a run's output).
+
+    python bench/attn_prefill_paged_bench.py [--iters 10] [--rounds 6] [--kv-fp8]
 """
 import argparse
 import json
@@ -51,6 +61,7 @@ def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=6)
+    ap.add_argument("--kv-fp8", action="store_true", help="also time the fp8 cache: the fp8 kernel, and dequantise + paged")
     a = ap.parse_args()
     g = torch.Generator(device="cuda").manual_seed(0)
     sc = D ** -0.5
@@ -69,6 +80,15 @@ def main() -> int:
                 fns[f"slab {key}"] = lambda q=q, k=k, v=v, prefix=prefix: fused.attention(q, k, v, sc, q_offset=prefix or None)
                 fns[f"gather {key}"] = lambda q=q, kp=kp, vp=vp, table=table, prefix=prefix: fused.attention(
                     q, fused._gather_pages(kp, table).contiguous(), fused._gather_pages(vp, table).contiguous(), sc, q_offset=prefix or None)
+                if a.kv_fp8:
+                    (kc, ke), (vc, ve) = fused.kv_quantize_ref(kp), fused.kv_quantize_ref(vp)
+                    o8 = fused.attention_prefill_paged_fp8(q, kc, vc, ke, ve, table, kv_len, scale=sc)
+                    want = fused.attention_prefill_paged(q, fused.kv_dequantize_ref(kc, ke), fused.kv_dequantize_ref(vc, ve), table, kv_len, scale=sc)
+                    assert torch.equal(o8, want), (B, prefix, P)
+                    fns[f"fp8 {key}"] = lambda q=q, kc=kc, vc=vc, ke=ke, ve=ve, table=table, kv_len=kv_len: fused.attention_prefill_paged_fp8(
+                        q, kc, vc, ke, ve, table, kv_len, scale=sc)
+                    fns[f"deq {key}"] = lambda q=q, kc=kc, vc=vc, ke=ke, ve=ve, table=table, kv_len=kv_len: fused.attention_prefill_paged(
+                        q, fused.kv_dequantize_ref(kc, ke), fused.kv_dequantize_ref(vc, ve), table, kv_len, scale=sc)
     qls, pre = [2048, 1500, 333, 0], [0, 1000, 8192, 77]
     kp, vp, table, kv_len = cache(4, [p + n for p, n in zip(pre, qls)], 64, g)
     q_len = torch.tensor(qls, dtype=torch.int32, device="cuda")
@@ -79,6 +99,10 @@ def main() -> int:
     dst = torch.empty_like(new)
     fns["append 4x4096"] = lambda: fused.kv_cache_append_prefill(new, new, ak, av, atab, alen)
     fns["copy 4x4096"] = lambda: (dst.copy_(new), dst.copy_(new))
+    if a.kv_fp8:
+        codes = [torch.zeros(ak.shape, dtype=torch.uint8, device="cuda") for _ in range(2)]
+        exps = [torch.zeros(ak.shape[:3], dtype=torch.uint8, device="cuda") for _ in range(2)]
+        fns["append8 4x4096"] = lambda: fused.kv_cache_append_prefill_fp8(new, new, *codes, *exps, atab, alen)
     names = list(fns)
     for fn in fns.values():
         timed(fn, 2)
@@ -101,6 +125,19 @@ def main() -> int:
     nbytes = 2 * 2 * new.numel() * 2  # K and V, read and written
     print(f"append of 4 x 4096 rows: {med['append 4x4096']:.0f} us = {nbytes / med['append 4x4096'] / 1e3:.0f} GB/s; "
           f"copy_ of the same bytes {med['copy 4x4096']:.0f} us = {nbytes / med['copy 4x4096'] / 1e3:.0f} GB/s")
+    if a.kv_fp8:
+        print("| B | prefix | page | fp8 us | deq + paged us | paged (bf16 pools) us | fp8 / (deq + paged) | fp8 / paged | spread fp8 | spread deq | beats deq by more than the spreads |\n"
+              "|---|---|---|---|---|---|---|---|---|---|---|")
+        for B in (1, 4):
+            for prefix in (0, 2048, 8192):
+                for P in (64, 256):
+                    key = f"B{B} prefix{prefix} P{P}"
+                    f8, dq, pa = med[f"fp8 {key}"], med[f"deq {key}"], med[f"paged {key}"]
+                    s8, sd = spread["fp8 " + key], spread["deq " + key]
+                    print(f"| {B} | {prefix} | {P} | {f8:.0f} | {dq:.0f} | {pa:.0f} | {f8 / dq:.3f} | {f8 / pa:.3f} | {100 * s8:.1f} % | "
+                          f"{100 * sd:.1f} % | {f8 / dq < 1 - max(s8, sd)} |")
+        print(f"fp8 append of 4 x 4096 rows: {med['append8 4x4096']:.0f} us, spread {100 * spread['append8 4x4096']:.1f} %; "
+              f"the bf16 append {med['append 4x4096']:.0f} us")
     return 0
 
 

@@ -8,7 +8,8 @@
 // over a ragged KV cache (attn_decode) goes to the kernel of attention_decode.hip through gtk_decode::launch, and
 // over a paged cache (attn_decode_paged, kv_append_paged) to those of attention_decode_paged.hip, over a paged
 // cache of e4m3 codes (attn_decode_paged_fp8, kv_append_paged_fp8) to those of attention_decode_paged_fp8.hip.  Prefill
-// over the paged cache (attn_prefill_paged, kv_append_paged_chunk) goes to the kernels of attention_prefill_paged.hip.
+// over the paged cache (attn_prefill_paged, kv_append_paged_chunk) goes to the kernels of attention_prefill_paged.hip, over
+// the fp8 cache (attn_prefill_paged_fp8, kv_append_paged_chunk_fp8) to those of attention_prefill_paged_fp8.hip.
 #include "attention_kernels.h"
 #include "attention_splitkv.h"
 
@@ -63,6 +64,14 @@ void launch_prefill_paged(hipStream_t st, const u16* q, const u16* kp, const u16
                           int num_pages, float c);
 void launch_append_chunk(hipStream_t st, const u16* k_new, const u16* v_new, u16* kp, u16* vp, const int* block_table,
                          const int* kv_len, const int* q_len, int B, int Hkv, int Sq, int page_size, int max_pages, int num_pages);
+
+// csrc/ops/attention_prefill_paged_fp8.hip: the same two over the cache of e4m3 codes; the append quantises
+void launch_prefill_paged_fp8(hipStream_t st, const u16* q, const uint8_t* kc, const uint8_t* vc, const uint8_t* kx, const uint8_t* vx,
+                              const int* block_table, const int* kv_len, const int* q_len, u16* o, float* lse2, int B, int H, int Hkv,
+                              int Sq, int page_size, int max_pages, int num_pages, float c);
+void launch_append_chunk_fp8(hipStream_t st, const u16* k_new, const u16* v_new, uint8_t* kc, uint8_t* vc, uint8_t* kx, uint8_t* vx,
+                             const int* block_table, const int* kv_len, const int* q_len, int B, int Hkv, int Sq, int page_size,
+                             int max_pages, int num_pages);
 
 }  // namespace gtk_decode
 
@@ -561,6 +570,43 @@ void kv_append_paged_fp8(const at::Tensor& k_new, const at::Tensor& v_new, at::T
                                 k_exp.data_ptr<uint8_t>(), v_exp.data_ptr<uint8_t>(), block_table.data_ptr<int>(),
                                 kv_len.data_ptr<int>(), (int)B, (int)Hkv, (int)Sq, (int)k_codes.size(2), (int)block_table.size(1),
                                 (int)k_codes.size(0));
+}
+
+// attn_prefill_paged over the fp8 cache -> (o, lse2), bit for bit attn_prefill_paged's on the dequantised pools
+std::vector<at::Tensor> attn_prefill_paged_fp8(const at::Tensor& q, const at::Tensor& k_codes, const at::Tensor& v_codes,
+                                               const at::Tensor& k_exp, const at::Tensor& v_exp, const at::Tensor& block_table,
+                                               const at::Tensor& kv_len, const at::Tensor& q_len, double scale) {
+  check_paged_fp8("attention prefill paged fp8", q, k_codes, v_codes, k_exp, v_exp, block_table, kv_len);
+  check_chunk("attention prefill paged fp8", q, k_codes, block_table, q_len);
+  const int64_t B = q.size(0), H = q.size(1), Sq = q.size(2), Hkv = k_codes.size(1), P = k_codes.size(2), MP = block_table.size(1);
+  TORCH_CHECK(Hkv > 0 && H > 0 && H % Hkv == 0, "attention prefill paged fp8: q heads must be a multiple of kv heads");
+  TORCH_CHECK(B * H * Sq < (int64_t(1) << 31), "attention prefill paged fp8: B * H * Sq must be below 2^31");
+  check_scale(scale);
+  auto o = at::empty({B, Sq, H, D}, q.options());
+  auto lse = at::empty({B, H, Sq}, q.options().dtype(at::kFloat));
+  gtk_decode::launch_prefill_paged_fp8(cur_stream(), bp(q), k_codes.data_ptr<uint8_t>(), v_codes.data_ptr<uint8_t>(),
+                                       k_exp.data_ptr<uint8_t>(), v_exp.data_ptr<uint8_t>(), block_table.data_ptr<int>(),
+                                       kv_len.data_ptr<int>(), q_len.data_ptr<int>(), bpm(o), lse.data_ptr<float>(), (int)B, (int)H,
+                                       (int)Hkv, (int)Sq, (int)P, (int)MP, (int)k_codes.size(0), (float)(scale * 1.4426950408889634));
+  return {o, lse};
+}
+
+// kv_append_paged_chunk into the fp8 cache: every row i < q_len[b] is quantised by the row rule on its way in
+void kv_append_paged_chunk_fp8(const at::Tensor& k_new, const at::Tensor& v_new, at::Tensor& k_codes, at::Tensor& v_codes,
+                               at::Tensor& k_exp, at::Tensor& v_exp, const at::Tensor& block_table, const at::Tensor& kv_len,
+                               const at::Tensor& q_len) {
+  check_paged_fp8("kv append paged chunk fp8", k_new, k_codes, v_codes, k_exp, v_exp, block_table, kv_len);
+  check_chunk("kv append paged chunk fp8", k_new, k_codes, block_table, q_len);
+  TORCH_CHECK(v_new.is_cuda() && v_new.scalar_type() == at::kBFloat16 && v_new.is_contiguous() && v_new.sizes() == k_new.sizes() &&
+                  v_new.device() == k_new.device(),
+              "kv append paged chunk fp8: k_new and v_new must be contiguous bf16 GPU tensors of one shape on one device");
+  const int64_t B = k_new.size(0), Hkv = k_new.size(1), Sq = k_new.size(2);
+  TORCH_CHECK(Hkv == k_codes.size(1), "kv append paged chunk fp8: the new rows and the pools must have the same KV heads");
+  TORCH_CHECK(B * Hkv * Sq < (int64_t(1) << 31), "kv append paged chunk fp8: B * Hkv * Sq must be below 2^31");
+  gtk_decode::launch_append_chunk_fp8(cur_stream(), bp(k_new), bp(v_new), k_codes.data_ptr<uint8_t>(), v_codes.data_ptr<uint8_t>(),
+                                      k_exp.data_ptr<uint8_t>(), v_exp.data_ptr<uint8_t>(), block_table.data_ptr<int>(),
+                                      kv_len.data_ptr<int>(), q_len.data_ptr<int>(), (int)B, (int)Hkv, (int)Sq, (int)k_codes.size(2),
+                                      (int)block_table.size(1), (int)k_codes.size(0));
 }
 
 // the document-masked backward, from the outputs of attn_fwd_doc

@@ -63,15 +63,9 @@
 //                        Quantising a new row reads nothing of the cache.
 //
 // Built with attention_decode_paged.hip's flags (packed fp32 VALU off, the MFMA VGPR form).
-#include "../common/q8_block.h"
-#include "attention_decode_body.h"
+#include "attention_fp8.h"  // widen8, exp_scale, quantize_row8 and their typedefs
 
 namespace gtk_decode {
-
-typedef unsigned char u8;
-typedef int i32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kVTile8 = BK * D;                  // one 64-key V image of codes
 constexpr int kExpTile = 512;                    // a tile's exponent bytes as the two DMAs leave them: K at 0, V at 256
@@ -79,21 +73,6 @@ constexpr int kStage8 = kVTile8 + kExpTile;
 constexpr int kWaveLds8 = 2 * kStage8;           // a wave's double buffer
 constexpr int kSmem8 = 4 * kWaveLds8;
 static_assert(kSmem8 >= kMergeO + 4 * 32 * 2 * 4, "the merge area must fit the V buffers");
-
-// 8 codes (two dwords, element j in byte j) to the 8 bf16 of an MFMA operand, exactly
-__device__ __forceinline__ bf16x8 widen8(uint32_t a, uint32_t b) {
-  const f32x2 a0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)a, false), a1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)a, true);
-  const f32x2 b0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)b, false), b1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)b, true);
-  u32x4 u;
-  u[0] = (__float_as_uint(a0[0]) >> 16) | (__float_as_uint(a0[1]) & 0xffff0000u);
-  u[1] = (__float_as_uint(a1[0]) >> 16) | (__float_as_uint(a1[1]) & 0xffff0000u);
-  u[2] = (__float_as_uint(b0[0]) >> 16) | (__float_as_uint(b0[1]) & 0xffff0000u);
-  u[3] = (__float_as_uint(b1[0]) >> 16) | (__float_as_uint(b1[1]) & 0xffff0000u);
-  return __builtin_bit_cast(bf16x8, u);
-}
-
-// 2^e of byte b of an exponent dword
-__device__ __forceinline__ float exp_scale(uint32_t w, int b) { return __uint_as_float(((w >> (8 * b)) & 0xffu) << 23); }
 
 // the lane's byte offset into a 64-key tile of K codes: key r (and r + 32), dims 64 hh ..
 __device__ __forceinline__ uint32_t k8_lane_offset(int r, int hh) { return (uint32_t)(r * D + 64 * hh); }
@@ -305,26 +284,6 @@ __global__ __launch_bounds__(256) void attn_decode_paged_fp8_kernel(const u16* _
   for (; kt < t1; kt += 4, ++j) tile(kt, j, true);
 
   decode_merge_store(smem, oacc, m, l, t, w, real, n, z, rows, li, ocol, o, lse2, o_part, lse_part);
-}
-
-// one lane's 8 elements of a row held by 16 lanes: the row's exponent, and the lane's 8 codes
-__device__ __forceinline__ u32x2 quantize_row8(const uint4& x, int& e) {
-  using namespace gtk_q8;
-  const uint32_t xs[4] = {x.x, x.y, x.z, x.w};
-  float f[8];
-#pragma unroll
-  for (int d = 0; d < 4; ++d) f[2 * d] = __uint_as_float(xs[d] << 16), f[2 * d + 1] = __uint_as_float(xs[d] & 0xffff0000u);
-  float amax = 0.f;  // over the elements that are not NaN: fmaxf drops a quieted one
-#pragma unroll
-  for (int jj = 0; jj < 8; ++jj) amax = fmaxf(amax, fabsf(__builtin_canonicalizef(f[jj])));
-#pragma unroll
-  for (int d = 1; d < 16; d <<= 1) amax = fmaxf(amax, __shfl_xor(amax, d));
-  e = q8_block_exp(amax);
-  const float down = q8_pow2(-e);
-  u32x2 cw;
-  cw[0] = q8_codes2(f[0] * down, f[1] * down) | (q8_codes2(f[2] * down, f[3] * down) << 16);
-  cw[1] = q8_codes2(f[4] * down, f[5] * down) | (q8_codes2(f[6] * down, f[7] * down) << 16);
-  return cw;
 }
 
 __global__ __launch_bounds__(256) void kv_append_paged_fp8_kernel(const u16* __restrict__ k_new, const u16* __restrict__ v_new,

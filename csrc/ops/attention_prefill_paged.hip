@@ -61,7 +61,8 @@
 //                        kv_len[b] is outside [ql, max_pages * page_size] and a row whose page id is outside [0,
 //                        num_pages) are left out, nothing is clamped onto another page.
 //
-// Not here: split-KV for a short chunk against a very long prefix, the fp8 pools, a backward, head dim 64.
+// Not here: split-KV for a short chunk against a very long prefix, a backward, head dim 64.  The fp8 pools are served
+// by attention_prefill_paged_fp8.hip.
 // Built with attention_decode.hip's flags (packed fp32 VALU off, the MFMA VGPR form).
 #include "attention_decode_body.h"
 

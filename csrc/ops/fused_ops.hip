@@ -1000,6 +1000,12 @@ std::vector<at::Tensor> attn_prefill_paged(const at::Tensor& q, const at::Tensor
                                            double scale);
 void kv_append_paged_chunk(const at::Tensor& k_new, const at::Tensor& v_new, at::Tensor& k_pool, at::Tensor& v_pool,
                            const at::Tensor& block_table, const at::Tensor& kv_len, const at::Tensor& q_len);
+std::vector<at::Tensor> attn_prefill_paged_fp8(const at::Tensor& q, const at::Tensor& k_codes, const at::Tensor& v_codes,
+                                               const at::Tensor& k_exp, const at::Tensor& v_exp, const at::Tensor& block_table,
+                                               const at::Tensor& kv_len, const at::Tensor& q_len, double scale);
+void kv_append_paged_chunk_fp8(const at::Tensor& k_new, const at::Tensor& v_new, at::Tensor& k_codes, at::Tensor& v_codes,
+                               at::Tensor& k_exp, at::Tensor& v_exp, const at::Tensor& block_table, const at::Tensor& kv_len,
+                               const at::Tensor& q_len);
 }  // namespace gtk_attn
 
 namespace gtk_xpose {  // csrc/ops/transpose.hip
@@ -1058,6 +1064,11 @@ PYBIND11_MODULE(_fused, m) {
         "(o [B,Sq,H,D], lse2 [B,H,Sq]); padded rows give 0 and -inf");
   m.def("kv_append_paged_chunk", &gtk_attn::kv_append_paged_chunk,
         "k_new, v_new [B,Hkv,Sq,D] (any Sq, q_len[b] real rows) into the pages at positions kv_len[b] - q_len[b] .., in place");
+  m.def("attn_prefill_paged_fp8", &gtk_attn::attn_prefill_paged_fp8,
+        "attn_prefill_paged over the fp8 cache (codes uint8 [num_pages,Hkv,page_size,D], exponent bytes uint8 "
+        "[num_pages,Hkv,page_size] for K and for V): -> (o, lse2), attn_prefill_paged's on the dequantised pools");
+  m.def("kv_append_paged_chunk_fp8", &gtk_attn::kv_append_paged_chunk_fp8,
+        "kv_append_paged_chunk into the fp8 cache: every real row quantised to e4m3 codes under its own power-of-two scale, in place");
   m.doc() = "gfx950 fused kernels for the Llama-3 DP validation workload";
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
   m.def("rmsnorm_bwd", &rmsnorm_bwd);

@@ -199,7 +199,10 @@ def targets() -> List[Target]:
                                                              "-Xclang", "-packed-fp32-ops"],
                           # prefill over the paged cache (the forward's work split and tile body) and the chunk append
                           "attention_prefill_paged.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-Xclang", "-target-feature",
-                                                          "-Xclang", "-packed-fp32-ops"]}),
+                                                          "-Xclang", "-packed-fp32-ops"],
+                          # and the same two over the cache of e4m3 codes
+                          "attention_prefill_paged_fp8.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-Xclang", "-target-feature",
+                                                              "-Xclang", "-packed-fp32-ops"]}),
     ]
 
 

@@ -21,6 +21,8 @@ __all__ = [
     "kv_quantize_ref", "kv_dequantize_ref", "attention_decode_paged_fp8", "attention_decode_paged_fp8_ref",
     "kv_cache_append_fp8", "kv_cache_append_fp8_ref",
     "attention_prefill_paged", "attention_prefill_paged_ref", "kv_cache_append_prefill", "kv_cache_append_prefill_ref",
+    "attention_prefill_paged_fp8", "attention_prefill_paged_fp8_ref", "kv_cache_append_prefill_fp8",
+    "kv_cache_append_prefill_fp8_ref",
 ]
 
 
@@ -808,7 +810,7 @@ def attention_prefill_paged(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch
     outside the pool.  On CPU tensors the call is :func:`attention_prefill_paged_ref`.
 
     Not served: split-KV for a short chunk against a very long prefix (one workgroup walks a query block's whole
-    prefix), the fp8 pools, a backward, head dim 64."""
+    prefix), a backward, head dim 64.  The fp8 pools: :func:`attention_prefill_paged_fp8`."""
     who = "attention_prefill_paged"
     _check_paged(who, q, k_pool, v_pool, block_table, kv_len)
     H, Hkv = q.size(1), k_pool.size(1)
@@ -925,9 +927,9 @@ def kv_dequantize_ref(codes: torch.Tensor, exp: torch.Tensor) -> torch.Tensor:
 
 
 def _check_paged_fp8(who, x, k_codes, v_codes, k_exp, v_exp, block_table, kv_len):
-    """What :func:`attention_decode_paged_fp8` and :func:`kv_cache_append_fp8` ask of the four pools, the table and
-    the lengths; ``x`` is q or k_new."""
-    name = "q" if who == "attention_decode_paged_fp8" else "k_new"
+    """What the calls over the fp8 cache ask of the four pools, the table and the lengths; ``x`` is q (the attention
+    calls) or k_new (the appends)."""
+    name = "q" if who.startswith("attention_") else "k_new"
     if x.dim() != 4 or x.dtype != torch.bfloat16 or x.size(-1) != 128:
         raise ValueError(f"{who}: {name} must be a bf16 4-d tensor with head dim 128, got {x.dtype} {tuple(x.shape)}")
     pools = (("k_codes", k_codes), ("v_codes", v_codes), ("k_exp", k_exp), ("v_exp", v_exp))
@@ -1046,3 +1048,90 @@ def kv_cache_append_fp8(k_new: torch.Tensor, v_new: torch.Tensor, k_codes: torch
                                   kv_len.contiguous())
     else:
         kv_cache_append_fp8_ref(k_new, v_new, k_codes, v_codes, k_exp, v_exp, block_table, kv_len)
+
+
+# ------------------------------------------------------------------------------------ prefill over the fp8 paged KV cache
+def attention_prefill_paged_fp8_ref(q: torch.Tensor, k_codes: torch.Tensor, v_codes: torch.Tensor, k_exp: torch.Tensor,
+                                    v_exp: torch.Tensor, block_table: torch.Tensor, kv_len: torch.Tensor,
+                                    q_len: Optional[torch.Tensor] = None, scale: float | None = None):
+    """:func:`attention_prefill_paged_ref` on the dequantised pools -> (o, lse2)."""
+    return attention_prefill_paged_ref(q, kv_dequantize_ref(k_codes, k_exp), kv_dequantize_ref(v_codes, v_exp), block_table, kv_len,
+                                       q_len, scale)
+
+
+def attention_prefill_paged_fp8(q: torch.Tensor, k_codes: torch.Tensor, v_codes: torch.Tensor, k_exp: torch.Tensor,
+                                v_exp: torch.Tensor, block_table: torch.Tensor, kv_len: torch.Tensor,
+                                q_len: Optional[torch.Tensor] = None, scale: float | None = None, return_lse: bool = False,
+                                check: bool = False):
+    """:func:`attention_prefill_paged` over a KV cache kept in 8 bits -> o [B, Sq, H, 128] bf16 (with ``return_lse``
+    also lse2 [B, H, Sq] fp32, log2 units).  Forward only.
+
+    The four pools are :func:`attention_decode_paged_fp8`'s (write them with :func:`kv_cache_append_prefill_fp8`);
+    ``q``, ``q_len``, ``kv_len``, ``block_table``, the clamps, the padded rows (``o = 0``, ``lse2 = -inf``) and
+    ``check`` are :func:`attention_prefill_paged`'s.  The kernel (csrc/ops/attention_prefill_paged_fp8.hip) stages a
+    tile as codes and turns it, once per workgroup, into the bf16 tile the bf16 kernel works on, so the result is
+    :func:`attention_prefill_paged`'s on the dequantised pools (:func:`kv_dequantize_ref`) bit for bit.  It does not
+    depend on the bytes of unused pages or of rows at or past ``kv_len[b]``, NaN codes and ``0xff`` exponent bytes
+    included, and no content of the table, the lengths or the exponent bytes moves an access outside the four pools,
+    the table row or ``q``.  On CPU tensors the call is :func:`attention_prefill_paged_fp8_ref`.
+
+    Not served: split-KV for a short chunk against a very long prefix, a backward, head dim 64."""
+    who = "attention_prefill_paged_fp8"
+    _check_paged_fp8(who, q, k_codes, v_codes, k_exp, v_exp, block_table, kv_len)
+    H, Hkv = q.size(1), k_codes.size(1)
+    if Hkv == 0 or H == 0 or H % Hkv:
+        raise ValueError(f"{who}: q heads ({H}) must be a multiple of kv heads ({Hkv})")
+    if torch.is_grad_enabled() and q.requires_grad:
+        raise ValueError(f"{who}: forward only, an input requires grad")
+    ql = _chunk_lengths(who, q, k_codes, block_table, kv_len, q_len, check)
+    sc = scale if scale is not None else q.size(-1) ** -0.5
+    if q.is_cuda:
+        o, lse2 = hip().attn_prefill_paged_fp8(q.contiguous(), k_codes, v_codes, k_exp, v_exp, block_table.contiguous(),
+                                               kv_len.contiguous(), ql.contiguous(), float(sc))
+    else:
+        o, lse2 = attention_prefill_paged_fp8_ref(q, k_codes, v_codes, k_exp, v_exp, block_table, kv_len, ql, sc)
+    return (o, lse2) if return_lse else o
+
+
+def kv_cache_append_prefill_fp8_ref(k_new: torch.Tensor, v_new: torch.Tensor, k_codes: torch.Tensor, v_codes: torch.Tensor,
+                                    k_exp: torch.Tensor, v_exp: torch.Tensor, block_table: torch.Tensor, kv_len: torch.Tensor,
+                                    q_len: Optional[torch.Tensor] = None) -> None:
+    """:func:`kv_cache_append_prefill_ref`'s positions and skips applied to the new rows' quantised form
+    (:func:`kv_quantize_ref`), in place; rows at or past ``ql`` are not read."""
+    B, _, Sq, _ = k_new.shape
+    P, MP = k_codes.size(2), block_table.size(1)
+    n = kv_len.long().view(B, 1)
+    ql = torch.full_like(n, Sq) if q_len is None else q_len.long().clamp(0, Sq).view(B, 1)
+    i = torch.arange(Sq, device=k_new.device).view(1, Sq)
+    pos = n - ql + i
+    page = block_table.long().gather(1, (pos // P).clamp(0, MP - 1))
+    ok = (i < ql) & (n >= ql) & (n <= MP * P) & (page >= 0) & (page < k_codes.size(0))
+    b, i = ok.nonzero(as_tuple=True)
+    for new, codes, exp in ((k_new, k_codes, k_exp), (v_new, v_codes, v_exp)):
+        c, e = kv_quantize_ref(new[b, :, i])
+        codes[page[b, i], :, pos[b, i] % P] = c
+        exp[page[b, i], :, pos[b, i] % P] = e
+
+
+def kv_cache_append_prefill_fp8(k_new: torch.Tensor, v_new: torch.Tensor, k_codes: torch.Tensor, v_codes: torch.Tensor,
+                                k_exp: torch.Tensor, v_exp: torch.Tensor, block_table: torch.Tensor, kv_len: torch.Tensor,
+                                q_len: Optional[torch.Tensor] = None, check: bool = False) -> None:
+    """:func:`kv_cache_append_prefill` into the fp8 cache: a ragged chunk's rows ``k_new``, ``v_new`` [B, Hkv, Sq, 128]
+    bf16, any Sq, are quantised by the row rule on their way into the pages, 128 code bytes and one exponent byte a
+    row, in place and on the current stream, in one launch that reads nothing of the cache
+    (csrc/ops/attention_prefill_paged_fp8.hip).  Positions, skips, ``q_len`` and ``check`` are
+    :func:`kv_cache_append_prefill`'s.  On CPU tensors the call is :func:`kv_cache_append_prefill_fp8_ref`."""
+    who = "kv_cache_append_prefill_fp8"
+    _check_paged_fp8(who, k_new, k_codes, v_codes, k_exp, v_exp, block_table, kv_len)
+    if v_new.shape != k_new.shape or v_new.dtype != torch.bfloat16 or v_new.device != k_new.device:
+        raise ValueError(f"{who}: k_new and v_new must be bf16 tensors of one shape on one device")
+    if k_new.size(1) != k_codes.size(1):
+        raise ValueError(f"{who}: the new rows have {k_new.size(1)} KV heads, the pools {k_codes.size(1)}")
+    if torch.is_grad_enabled() and (k_new.requires_grad or v_new.requires_grad):
+        raise ValueError(f"{who}: forward only, an input requires grad")
+    ql = _chunk_lengths(who, k_new, k_codes, block_table, kv_len, q_len, check)
+    if k_new.is_cuda:
+        hip().kv_append_paged_chunk_fp8(k_new.contiguous(), v_new.contiguous(), k_codes, v_codes, k_exp, v_exp,
+                                        block_table.contiguous(), kv_len.contiguous(), ql.contiguous())
+    else:
+        kv_cache_append_prefill_fp8_ref(k_new, v_new, k_codes, v_codes, k_exp, v_exp, block_table, kv_len, ql)
